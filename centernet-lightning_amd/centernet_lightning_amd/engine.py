@@ -636,7 +636,9 @@ class Plan:
                 key = (id(x), L.args.x, L.args.Cin, L.args.ldx) if (id(x) not in unsafe and len(ws) <= 1) else ("solo", id(L))
                 own_pass.setdefault(key, []).append(L)
             elif L.args.KH == 3:
-                passes.append((L, slot_of.setdefault(id(L), len(slot_of))))
+                # (keyed apart from id(L): L may also be the producer of a later pair, whose y_absmax slot is slot_of[id(L)] — one slot for both would
+                # fold L's max |y| into the max |x| its explicit pass left there)
+                passes.append((L, slot_of.setdefault(("pass", id(L)), len(slot_of))))
                 reports.add(id(L))
         # a tensor read by several such launches (the per-head first blocks behind an fp32-kernel neck layer): ONE explicit pass, shared
         for key, group in own_pass.items():

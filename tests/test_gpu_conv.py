@@ -1212,3 +1212,37 @@ def test_small_out_conv_folded_into_the_row_winograd_epilogue(case):
     p.N, p.H_in, p.W_in, p.Cin, p.Cout, p.KH, p.KW, p.stride, p.pad, p.ldx, p.ldy, p.algo = 1, 8, 8, 24, 64, 3, 3, 1, 1, 24, 64, CNL_ALGO_AUTO
     p.x = p.w = p.bias = p.y = p.fuse_w = p.fuse_part = 1 << 20
     assert lib.cnl_conv3x3_winograd_f32(ctypes.byref(p), _stream()) == _lib.CNL_E_UNSUPPORTED
+
+
+def test_a_conv_with_its_own_absmax_pass_reports_max_y_into_a_slot_of_its_own():
+    """Regression (tests/test_gpu_plan_replay.py): a 3x3 direct conv whose input has no reporting producer gets an explicit cnl_absmax_per_image_f32
+    pass into slot s (its x_absmax); when that conv is in turn the producer of a fp16-split consumer, its y_absmax must be ANOTHER slot — sharing s
+    folded max |y| into the max |x| already there, and the consumer scaled its input by up to max |x| / max |y| (here layer4's first conv at 96 x 128:
+    a slot of 451 for a maximum of 285).  Every reported slot must equal max |y| of its producer's output, image by image."""
+    import os
+    import centernet_lightning_amd as cl
+    import recipes
+    import ref_cpu
+    torch.manual_seed(0)
+    model = cl.build_centernet(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "centernet-lightning_amd", "configs",
+                                            "resnet34_simple.yaml"))
+    model.load_state_dict(ref_cpu.synth_state_dict(model.state_dict(), seed=1, calib_shape=(2, 3, 128, 128)))
+    model.set_kernel_options(reuse_buffers=False)
+    model = model.cuda()
+    x = recipes.images(4321, (2, 3, 96, 128)).cuda()
+    model.get_encoded_outputs(x)
+    torch.cuda.synchronize()
+    plan = next(iter(model._engine.plans.values()))
+    both = [L for L in plan.launches if isinstance(L.args, ConvParams) and L.args.x_absmax and L.args.y_absmax]
+    passed = {L.args[5] for L in plan.launches if L.fn is _lib.load().cnl_absmax_per_image_f32}
+    assert any(L.args.x_absmax in passed for L in both)                  # the shape of the defect is present in this plan
+    n = 0
+    for L in plan.launches:
+        if isinstance(L.args, ConvParams) and L.args.y_absmax:
+            assert L.args.y_absmax != L.args.x_absmax, L.what
+            y = plan.tensor(L.keep[1])
+            off = (L.args.y_absmax - plan.absmax.data_ptr()) // 4
+            got = plan.absmax.view(-1)[off::_lib.absmax_stride()][:plan.N].cpu()
+            assert torch.equal(got, y.abs().reshape(plan.N, -1).amax(dim=1).cpu()), L.what
+            n += 1
+    assert n >= 10

@@ -241,20 +241,7 @@ def test_feature_level_error_against_float64(cfg, shape):
             assert e[a][key] <= 1e-4, (a, key, e)
 
 
-def _trained_checkpoint_like(sd):
-    """BatchNorm scales as a trained checkpoint has them: every BN gamma times 10^U(-2, 0.5) per channel, 5 % of the channels dead
-    (gamma = beta = 0: the folded filter and its bias are exactly zero) — the FOLDED conv weights then spread over 2.5 decades per output
-    channel and so do the activations the next layer reads; running statistics re-calibrated so that the network stays O(1)."""
-    g = torch.Generator().manual_seed(77)
-    for k in list(sd):
-        if k.endswith("running_var"):
-            base = k[: -len("running_var")]
-            c = sd[k].numel()
-            s = torch.pow(10.0, torch.rand(c, generator=g) * 2.5 - 2.0)
-            s[torch.randperm(c, generator=g)[: max(1, c // 20)]] = 0.0
-            sd[base + "weight"].mul_(s)
-            sd[base + "bias"].mul_((s > 0).float())
-    ref_cpu.forward(sd, torch.rand(2, 3, 128, 128, generator=torch.Generator().manual_seed(99)) * 4.2 - 2.1, stats=True)
+_trained_checkpoint_like = recipes._trained_checkpoint_like       # (oracle/recipes.py: shared with tests/test_gpu_plan_replay.py)
 
 
 def test_feature_level_error_with_trained_checkpoint_like_scales():
