@@ -11,6 +11,7 @@ Fusions relative to the reference's op-per-layer graph (results identical up to 
   * Fuse: project(top) -> upsample -> + skip              -> CNL_UPSAMPLE_OUT_ADD epilogue of the 1x1 conv
   * first 3x3 block of every head (same input, meta.py:46) -> one conv with concatenated Cout
   * heatmap .sigmoid() (centernet.py:205)                 -> epilogue of the heatmap out_conv
+  * ResNet-50/101 bottleneck: conv3 + downsample (+ sum, ReLU) -> one two-source 1x1 launch (cnl_pointwise_nhwc_f32)
 """
 import bisect
 import ctypes
@@ -21,7 +22,7 @@ from dataclasses import dataclass
 import torch
 
 from . import _lib
-from ._lib import (CNL_ALGO_AUTO, CNL_ALGO_F2, CNL_ALGO_F32, CNL_ALGO_F43, CNL_ALGO_LATENCY, CNL_RELU, CNL_RELU6, CNL_SIGMOID, CNL_UPSAMPLE_IN, CNL_UPSAMPLE_OUT_ADD, CNL_W_SPLIT,
+from ._lib import (CNL_ALGO_AUTO, CNL_ALGO_F2, CNL_ALGO_F32, CNL_ALGO_F43, CNL_ALGO_FORCE, CNL_ALGO_LATENCY, CNL_RELU, CNL_RELU6, CNL_SIGMOID, CNL_UPSAMPLE_IN, CNL_UPSAMPLE_OUT_ADD, CNL_W_SPLIT,
                    CNL_WINO_F16X2, ConvParams, DeconvParams)
 
 BN_EPS_DEFAULT = 1e-5
@@ -188,6 +189,18 @@ _Layer.wants_up2 = _layer_wants_up2
 _Layer.up2 = _layer_up2
 
 
+class _Bottleneck:
+    """A packed torchvision v1.5 bottleneck (params.Bottleneck): conv1 / conv2 / conv3 / downsample as _Layers, and — where the block has a
+    downsample — `cat`, the 1x1 layer of the two-source launch: [W3 | Wds] concatenated along K (cat.k1 = conv3's Cin) with b3 + bds."""
+
+    def __init__(self, c1, c2, c3, down, li):
+        self.c1, self.c2, self.c3, self.down, self.li = c1, c2, c3, down, li
+        self.cat = None
+        if down is not None:
+            self.cat = _Layer(torch.cat([c3.w, down.w], dim=3).contiguous(), (c3.b + down.b).contiguous())
+            self.cat.k1 = c3.cin
+
+
 class _SepLayer:
     """make_conv(conv_type="separable") (layers.py:56-69) packed: depthwise weight [3][3][C] (tap-major) + bias with BN folded,
     and the pointwise half as a 1x1 _Layer."""
@@ -309,10 +322,14 @@ class PackedWeights:
                                                      ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)),
                        "cnl_stem_pack_weights_f32")
         self.blocks = []
+        self.bottleneck = bool(getattr(bb, "bottleneck", False))
         for li in range(4):
             for blk in getattr(bb, f"layer{li + 1}"):
                 d = L(blk.downsample[0], blk.downsample[1]) if blk.downsample is not None else None
-                self.blocks.append((L(blk.conv1, blk.bn1), L(blk.conv2, blk.bn2), d, li))
+                if self.bottleneck:
+                    self.blocks.append(_Bottleneck(L(blk.conv1, blk.bn1), L(blk.conv2, blk.bn2), L(blk.conv3, blk.bn3), d, li))
+                else:
+                    self.blocks.append((L(blk.conv1, blk.bn1), L(blk.conv2, blk.bn2), d, li))
         self.neck_kind = type(neck).__name__
         def C(m):
             kind = type(m).__name__
@@ -393,6 +410,23 @@ class PackedWeights:
         return False
 
 
+# The stop rule of DESIGN.md §11: the single-source bottleneck 1x1 shapes (Cin, Cout) on which cnl_pointwise_nhwc_f32 beats the generic kernel in its
+# split form.  Measured with tools/backbone_profile.py (plans (p) / (b), ResNet-50 at N = 32, 512^2) in three sessions: no shape wins beyond the
+# run-to-run spread (+-2 %; most per-shape verdicts flip between sessions) and 64 -> 64 loses in all of them, so every single-source 1x1 conv stays on the
+# generic kernel (CNL_ALGO_FORCE + 5) and the new kernel runs the two-source launches.  A function of the layer shape, never of N.
+_POINTWISE_WINS = frozenset()
+
+
+def _pointwise_route(cin, cout, pixels):
+    return (cin, cout) in _POINTWISE_WINS
+
+
+# tools/backbone_profile.py's A/B plans (not an option of the product): None = the default plan; "pointwise_all" = every stride-1 bottleneck 1x1 conv on
+# cnl_pointwise_nhwc_f32 (the stop rule's measurement); "generic_split" = every bottleneck 1x1 conv on the generic kernel in its split form
+# (CNL_ALGO_FORCE + 5), conv3 and downsample apart; "generic_auto" = the generic kernel under its own rule.
+_POINTWISE_AB = None
+
+
 class BufferTooLarge(ValueError):
     """A plan buffer would cross the kernels' 32-bit buffer addressing (< 4 GiB per tensor): the engine retries with a smaller sub-batch."""
 
@@ -438,10 +472,11 @@ def split_range_ratio(x_nhwc):
 
 class _Launch:
     """One C-ABI call of the plan: `args` is a params struct (passed by reference) or a tuple of scalar / pointer arguments."""
-    __slots__ = ("fn", "args", "what", "flops", "keep")
+    __slots__ = ("fn", "args", "what", "flops", "keep", "aux")
 
-    def __init__(self, fn, args, what, flops=0, keep=()):
+    def __init__(self, fn, args, what, flops=0, keep=(), aux=None):
         self.fn, self.args, self.what, self.flops, self.keep = fn, args, what, flops, keep
+        self.aux = aux          # cnl_pointwise_nhwc_f32: [x2, H2, W2, C2, ldx2, stride2, x2_absmax] after the params struct
 
 
 class _ListSlot:
@@ -496,7 +531,8 @@ class Plan:
 
         def pointers(L):
             if isinstance(L.args, (ConvParams, DeconvParams)):
-                return [(L.args, f) for f in (("x", "y", "residual", "splitk_scratch", "fuse_part") if isinstance(L.args, ConvParams) else ("x", "y", "residual"))]
+                ptrs = [(L.args, f) for f in (("x", "y", "residual", "splitk_scratch", "fuse_part") if isinstance(L.args, ConvParams) else ("x", "y", "residual"))]
+                return ptrs + [(L.aux, 0)] if L.aux is not None else ptrs
             if isinstance(L.args, list):
                 return [(L.args, i) for i in range(len(L.args))]
             return []
@@ -583,6 +619,7 @@ class Plan:
         ones that report max |y|) and it writes every channel of the buffer.  A 3x3 direct conv without such a producer (the
         stride-2 conv after layer1) gets an explicit cnl_absmax_per_image_f32 pass: cheaper than what the split kernel saves."""
         lib, wino, direct, up2 = self.lib, self.lib.cnl_conv3x3_winograd_f32, self.lib.cnl_conv2d_nhwc_f32, self.lib.cnl_conv3x3_up2_nhwc_f32
+        pw = lib.cnl_pointwise_nhwc_f32
         self.absmax = None
         if not self.options.absmax_handover or self.algo == CNL_ALGO_F32:   # every fp16-split Winograd launch makes its own pass,
             return                                                        # every direct conv stays on the fp32 matrix cores
@@ -607,8 +644,24 @@ class Plan:
         shared = []                                               # launches that take the slot of their group's explicit pass
         own_pass = {}                                             # input buffer -> fp16-split Winograd launches without a reporting producer
         stem_group = []                                           # fp16-split Winograd launches that read the stem's (pooled) output
+        pairs2, stem2, passes2 = [], [], []                       # the second source of two-source pointwise launches (L.aux)
         for L in self.launches:         # plan order: a direct conv only reports max |y| if it got its own hint
             if not isinstance(L.args, ConvParams):
+                continue
+            if L.fn is pw:
+                # cnl_pointwise_nhwc_f32 always runs the split arithmetic and reports max |y|: each of its sources takes the slot of its reporting
+                # producer, the stem's, or an explicit pass
+                for src, x in enumerate((L.keep[0], L.keep[4]) if L.aux is not None else (L.keep[0],)):
+                    ws = writers.get(id(x), [])
+                    P = ws[0] if len(ws) == 1 else None
+                    if (P is not None and P is not L and id(x) not in unsafe and id(P) in reports and P.args.y == x.data_ptr()
+                            and P.args.Cout == P.args.ldy):
+                        (pairs2 if src else pairs).append((P, L, slot_of.setdefault(id(P), len(slot_of))))
+                    elif x is self.backbone_in:
+                        (stem2 if src else stem_group).append(L)
+                    else:
+                        (passes2 if src else passes).append((L, slot_of.setdefault(("pass2" if src else "pass", id(L)), len(slot_of))))
+                reports.add(id(L))
                 continue
             is_wino5 = L.fn is wino and lib.cnl_conv3x3_winograd_kernel(ctypes.byref(L.args)) == CNL_WINO_F16X2
             if L.fn is direct and (L.args.flags & CNL_UPSAMPLE_OUT_ADD):
@@ -635,7 +688,7 @@ class Plan:
                 reports.add(id(L))
                 key = (id(x), L.args.x, L.args.Cin, L.args.ldx) if (id(x) not in unsafe and len(ws) <= 1) else ("solo", id(L))
                 own_pass.setdefault(key, []).append(L)
-            elif L.args.KH == 3:
+            elif L.args.KH == 3 or L.args.algo == CNL_ALGO_FORCE + 5:      # (+ the bottleneck 1x1 convs pinned to the split form: _conv1x1)
                 # (keyed apart from id(L): L may also be the producer of a later pair, whose y_absmax slot is slot_of[id(L)] — one slot for both would
                 # fold L's max |y| into the max |x| its explicit pass left there)
                 passes.append((L, slot_of.setdefault(("pass", id(L)), len(slot_of))))
@@ -644,7 +697,7 @@ class Plan:
         for key, group in own_pass.items():
             passes.append((group[0], slot_of.setdefault(("shared", key), len(slot_of))))
             shared.extend((L, key) for L in group[1:])
-        if stem_group:
+        if stem_group or stem2:
             slot_of[("stem",)] = len(slot_of)
         # one float per (tensor, image): an image's scale must not depend on its batch neighbours
         ams = _lib.absmax_stride()             # floats between the per-image slots: one cache line per image
@@ -653,18 +706,28 @@ class Plan:
         for P, L, i in pairs:
             P.args.y_absmax = self.absmax.data_ptr() + i * row
             L.args.x_absmax = self.absmax.data_ptr() + i * row
+        for P, L, i in pairs2:
+            P.args.y_absmax = self.absmax.data_ptr() + i * row
+            L.aux[6] = self.absmax.data_ptr() + i * row
         for L, key in shared:
             L.args.x_absmax = self.absmax.data_ptr() + slot_of[("shared", key)] * row
-        if stem_group:
+        if stem_group or stem2:
             self.stem_absmax = self.absmax.data_ptr() + slot_of[("stem",)] * row
             for L in stem_group:
                 L.args.x_absmax = self.stem_absmax
+            for L in stem2:
+                L.aux[6] = self.stem_absmax
         for L, i in passes:
             a = L.args
             L.args.x_absmax = self.absmax.data_ptr() + i * row
             self.launches.insert(self.launches.index(L), _Launch(
                 lib.cnl_absmax_per_image_f32, [a.x, self.N, a.H_in * a.W_in, a.Cin, a.ldx, L.args.x_absmax], L.what + ".absmax",
                 0, keep=(self.absmax, L.keep[0])))
+        for L, i in passes2:
+            x2, h2, w2, c2, ldx2 = L.aux[:5]
+            L.aux[6] = self.absmax.data_ptr() + i * row
+            self.launches.insert(self.launches.index(L), _Launch(
+                lib.cnl_absmax_per_image_f32, [x2, self.N, h2 * w2, c2, ldx2, L.aux[6]], L.what + ".absmax (x2)", 0, keep=(self.absmax, L.keep[4])))
 
     # -- helpers --
     def _buf(self, n, h, w, c):
@@ -675,7 +738,7 @@ class Plan:
         self.buffers.append(t)
         return t
 
-    def _conv(self, layer, x, xh, xw, ldx, y, ldy, flags=0, residual=None, ldr=0, what="conv", x_off=0, y_off=0):
+    def _conv(self, layer, x, xh, xw, ldx, y, ldy, flags=0, residual=None, ldr=0, what="conv", x_off=0, y_off=0, algo=None):
         """Append one cnl_conv2d_nhwc_f32 launch. x / y / residual are NHWC buffer tensors (or views sharing
         storage, addressed by element offsets x_off / y_off inside the pixel)."""
         p = ConvParams()
@@ -688,7 +751,7 @@ class Plan:
         p.KH, p.KW, p.stride, p.pad = layer.kh, layer.kw, layer.stride, layer.pad
         p.ldx, p.ldy, p.ldr = ldx, ldy, ldr
         p.flags = flags
-        p.algo = self.algo
+        p.algo = self.algo if algo is None else algo
         p.w_absmax = layer.wmax.data_ptr()
         ho, wo = ctypes.c_int32(), ctypes.c_int32()
         _lib.check(self.lib.cnl_conv2d_out_hw(ctypes.byref(p), ctypes.byref(ho), ctypes.byref(wo)), what)
@@ -735,6 +798,73 @@ class Plan:
                 p.flags |= CNL_W_SPLIT
         self.launches.append(_Launch(fn, p, what, flops, keep=(x, y, residual, layer)))
         return p, ho.value, wo.value
+
+    def _bottlenecks(self, Wt, cur, ch, cw, cc, feats):
+        """ResNet-50/101 stages (torchvision v1.5: stride on conv2).  conv1: 1x1 on cnl_pointwise_nhwc_f32 or the generic kernel (_pointwise_route);
+        conv2: the 3x3 path of _conv (row-Winograd at stride 1, the fp16-split direct kernel at stride 2); conv3: ONE two-source launch with the
+        stage's downsample where the block has one, else a single-source launch with the residual.  Without the split arithmetic (algo "f32") or
+        without the max |x| hand-over every 1x1 conv is an ordinary _conv launch (conv3 and downsample apart)."""
+        N = self.N
+        pw_ok = self.algo in (CNL_ALGO_AUTO, CNL_ALGO_F2) and self.options.absmax_handover and _POINTWISE_AB != "generic_auto"
+        for j, blk in enumerate(Wt.blocks):
+            c1, c2, c3, down, li = blk.c1, blk.c2, blk.c3, blk.down, blk.li
+            bi = j - next(i for i, b in enumerate(Wt.blocks) if b.li == li)      # index inside the stage: the state dict's layer{i}.{b}
+            name = f"layer{li + 1}.{bi}"
+            t1 = self._buf(N, ch, cw, c1.cout)
+            self._conv1x1(c1, cur, ch, cw, cc, t1, CNL_RELU, pw_ok, what=f"{name}.conv1")
+            oh, ow = (ch + 2 - 3) // c2.stride + 1, (cw + 2 - 3) // c2.stride + 1
+            t2 = self._buf(N, oh, ow, c2.cout)
+            self._conv(c2, t1, ch, cw, c1.cout, t2, c2.cout, CNL_RELU, what=f"{name}.conv2")
+            out = self._buf(N, oh, ow, c3.cout)
+            if down is not None and pw_ok and _POINTWISE_AB in (None, "pointwise_all"):
+                self._pointwise(blk.cat, t2, oh, ow, c2.cout, out, CNL_RELU, x2=(cur, ch, cw, cc, down.stride), what=f"{name}.conv3+downsample")
+            else:
+                idn = cur
+                if down is not None:
+                    idn = self._buf(N, oh, ow, down.cout)
+                    self._conv1x1(down, cur, ch, cw, cc, idn, 0, pw_ok, what=f"{name}.downsample")
+                self._conv1x1(c3, t2, oh, ow, c2.cout, out, CNL_RELU, pw_ok, residual=idn, what=f"{name}.conv3")
+            cur, ch, cw, cc = out, oh, ow, c3.cout
+            feats[li] = (cur, ch, cw, cc)
+        return cur, ch, cw, cc
+
+    def _conv1x1(self, layer, x, h, w, ldx, y, flags, pw_ok, residual=None, what="conv1x1"):
+        """A 1x1 conv of a bottleneck block: the pointwise kernel where the stop rule keeps the shape there (_pointwise_route), else the generic
+        direct kernel in its split form (CNL_ALGO_FORCE + 5: the form the rule was measured against); without pw_ok the generic kernel under its
+        own rule.  The A/B plans of tools/backbone_profile.py replace the choice (_POINTWISE_AB)."""
+        ldr = layer.cout if residual is not None else 0
+        if pw_ok and layer.stride == 1 and (_POINTWISE_AB == "pointwise_all" or (_POINTWISE_AB is None and _pointwise_route(layer.cin, layer.cout, h * w))):
+            return self._pointwise(layer, x, h, w, ldx, y, flags, residual=residual, what=what)
+        algo = CNL_ALGO_FORCE + 5 if (pw_ok and _POINTWISE_AB != "generic_auto") else None
+        return self._conv(layer, x, h, w, ldx, y, layer.cout, flags, residual=residual, ldr=ldr, what=what, algo=algo)
+
+    def _pointwise(self, layer, x, h, w, ldx, y, flags, residual=None, x2=None, what="pointwise"):
+        """Append one cnl_pointwise_nhwc_f32 launch: y = act(x W (+ x2[::s, ::s] W2) + b (+ residual)).  `layer` is a 1x1 _Layer (two-source: the
+        [W3 | Wds] layer of _Bottleneck.cat, layer.k1 = the channels of x); x2 = (buffer, H2, W2, C2, stride) or None."""
+        k1 = getattr(layer, "k1", layer.cin) if x2 is not None else layer.cin
+        p = ConvParams()
+        p.x = x.data_ptr()
+        p.w = layer.split_w().data_ptr()
+        p.bias = layer.b.data_ptr()
+        p.residual = residual.data_ptr() if residual is not None else None
+        p.y = y.data_ptr()
+        p.N, p.H_in, p.W_in, p.Cin, p.Cout = self.N, h, w, k1, layer.cout
+        p.KH, p.KW, p.stride, p.pad = 1, 1, 1, 0
+        p.ldx, p.ldy, p.ldr = ldx, layer.cout, layer.cout if residual is not None else 0
+        p.flags = flags | CNL_W_SPLIT
+        p.algo = self.algo
+        p.w_absmax = layer.wmax.data_ptr()
+        aux, x2b = None, None
+        if x2 is not None:
+            x2b, h2, w2, c2, s2 = x2
+            assert k1 + c2 == layer.cin, what
+            aux = [x2b.data_ptr(), h2, w2, c2, c2, s2, None]
+            what += f" [pointwise, two-source, x2 stride {s2}]"
+        else:
+            what += " [pointwise]"
+        flops = 2 * self.N * h * w * layer.cout * layer.cin
+        self.launches.append(_Launch(self.lib.cnl_pointwise_nhwc_f32, p, what, flops, keep=(x, y, residual, layer, x2b), aux=aux))
+        return p, h, w
 
     def _split_slices(self, layer, flags, ho, wo):
         """KernelOptions.split_small: slices of the reduction for a launch with at most 32 output tiles of 64 x 128 (an eighth of the CUs).  Only
@@ -878,7 +1008,9 @@ class Plan:
             self.launches.append(_Launch("maxpool", (s1, cur, N, h2, w2, 64), "maxpool3x3s2", keep=(s1, cur)))
         ch, cw, cc = h4, w4, 64
         feats = {}
-        for bi, (c1, c2, down, li) in enumerate(Wt.blocks):
+        if Wt.bottleneck:
+            cur, ch, cw, cc = self._bottlenecks(Wt, cur, ch, cw, cc, feats)
+        for bi, (c1, c2, down, li) in enumerate(() if Wt.bottleneck else Wt.blocks):
             oh, ow = (ch + 2 - 3) // c1.stride + 1, (cw + 2 - 3) // c1.stride + 1
             t = self._buf(N, oh, ow, c1.cout)
             self._conv(c1, cur, ch, cw, cc, t, c1.cout, CNL_RELU, what=f"layer{li + 1}.{bi}.conv1")
@@ -1110,6 +1242,21 @@ class Plan:
         if not isinstance(p, ConvParams) or not p.x_absmax:
             return
         lib = self.lib
+        if L.fn is lib.cnl_pointwise_nhwc_f32:
+            views = [self.input_view(p)]
+            if L.aux is not None:
+                x2, h2, w2, c2, ldx2 = L.aux[:5]
+                off = (x2 - self.arena.data_ptr()) // 4
+                views.append(self.arena.as_strided((p.N, h2, w2, c2), (h2 * w2 * ldx2, w2 * ldx2, ldx2, 1), self.arena.storage_offset() + off))
+            # both sources share one scale per image: the weakest tile of either against the larger of the two maxima
+            top = torch.stack([v.abs().amax(dim=(1, 2, 3)) for v in views]).amax(0)
+            rs = []
+            for v in views:
+                vmax = v.abs().amax(dim=(1, 2, 3))
+                rs.append(torch.where(vmax > 0, split_range_ratio(v) * top / torch.where(vmax > 0, vmax, torch.ones_like(vmax)), torch.ones_like(vmax)))
+            ratio = torch.stack(rs).amax(0)
+            self._raise_range(L, ratio)
+            return
         if L.fn is lib.cnl_conv3x3_winograd_f32:
             split = lib.cnl_conv3x3_winograd_kernel(ctypes.byref(p)) == CNL_WINO_F16X2
         elif L.fn is lib.cnl_conv2d_nhwc_f32:
@@ -1118,7 +1265,9 @@ class Plan:
             split = L.fn is lib.cnl_conv3x3_up2_nhwc_f32
         if not split:
             return
-        ratio = split_range_ratio(self.input_view(p))
+        self._raise_range(L, split_range_ratio(self.input_view(p)))
+
+    def _raise_range(self, L, ratio):
         worst = float(ratio.max())
         if worst > SPLIT_RANGE_LIMIT:
             n = int(ratio.argmax())
@@ -1145,6 +1294,8 @@ class Plan:
             return lib.cnl_maxpool3x3s2_nhwc_f32(src.data_ptr(), dst.data_ptr(), n, h, w, c, stream)
         if isinstance(L.args, list):
             return L.fn(*L.args, stream)
+        if L.fn is lib.cnl_pointwise_nhwc_f32:                   # (aux: the second source; None for a single-source launch)
+            return L.fn(ctypes.byref(L.args), *(L.aux if L.aux is not None else (None, 0, 0, 0, 0, 1, None)), stream)
         return L.fn(ctypes.byref(L.args), stream)
 
     def total_flops(self):
@@ -1236,6 +1387,8 @@ class Engine:
         """Largest batch whose biggest activation tensor stays below the 4 GiB buffer-addressing limit of the kernels."""
         widest = max(64, max((l.cout for b in self.weights.head_blocks.values() for l in b), default=64))      # (the fused first head
                                                                                                           # blocks fall back to per-head launches)
+        if self.weights.bottleneck:
+            widest = max(widest, 256)             # layer1's output of a bottleneck ResNet: stride 4 x 256 channels, whatever the heads
         per_image = max((H // 2) * (W // 2) * 64, (H // 4) * (W // 4) * widest) * 4
         return max(1, ADDRESS_LIMIT // per_image)
 

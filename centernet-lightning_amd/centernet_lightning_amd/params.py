@@ -1,4 +1,4 @@
-"""Parameter containers for the CenterNet hot path: ResNet-34 backbone, simple / FPN neck, GenericHead.
+"""Parameter containers for the CenterNet hot path: ResNet-18/34/50/101 backbone, simple / FPN neck, GenericHead.
 
 These nn.Modules only HOLD parameters (so `state_dict()` / `load_state_dict()` / `.to()` behave like the
 reference's modules and torchvision ResNet checkpoints load by key name); they are never *called* — the
@@ -15,8 +15,10 @@ from collections import OrderedDict
 import torch
 from torch import nn
 
-RESNET_LAYERS = {"resnet18": [2, 2, 2, 2], "resnet34": [3, 4, 6, 3]}
+RESNET_LAYERS = {"resnet18": [2, 2, 2, 2], "resnet34": [3, 4, 6, 3], "resnet50": [3, 4, 6, 3], "resnet101": [3, 4, 23, 3]}
+BOTTLENECK_RESNETS = ("resnet50", "resnet101")
 BACKBONE_CHANNELS = [64, 64, 128, 256, 512]          # strides 2, 4, 8, 16, 32 (tests/test_necks.py:7-8)
+BOTTLENECK_CHANNELS = [64, 256, 512, 1024, 2048]     # the same strides, expansion 4
 
 
 class ConvBn(nn.Module):
@@ -155,15 +157,39 @@ class BasicBlock(nn.Module):
             nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity="relu")
 
 
+class Bottleneck(nn.Module):
+    """torchvision v1.5 bottleneck: 1x1 reduce (conv1) -> 3x3 carrying the stride (conv2) -> 1x1 expand x4 (conv3); a 1x1 downsample
+    (conv + BN) where the stride or the channel count changes — the first block of every stage."""
+    expansion = 4
+
+    def __init__(self, cin, width, stride):
+        super().__init__()
+        cout = width * self.expansion
+        self.conv1 = nn.Conv2d(cin, width, 1, bias=False)
+        self.bn1 = nn.BatchNorm2d(width)
+        self.conv2 = nn.Conv2d(width, width, 3, stride=stride, padding=1, bias=False)
+        self.bn2 = nn.BatchNorm2d(width)
+        self.conv3 = nn.Conv2d(width, cout, 1, bias=False)
+        self.bn3 = nn.BatchNorm2d(cout)
+        self.stride = stride
+        self.downsample = None
+        if stride != 1 or cin != cout:
+            self.downsample = nn.Sequential(nn.Conv2d(cin, cout, 1, stride=stride, bias=False), nn.BatchNorm2d(cout))
+        for m in (self.conv1, self.conv2, self.conv3) + ((self.downsample[0],) if self.downsample is not None else ()):
+            nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity="relu")
+
+
 class ResNetBackbone(nn.Module):
-    """Parameter layout of torchvision `resnet34` (keys conv1, bn1, layer{1..4}.{i}.conv{1,2}, bn{1,2}, downsample.{0,1})."""
+    """Parameter layout of torchvision `resnet18/34` (keys conv1, bn1, layer{1..4}.{i}.conv{1,2}, bn{1,2}, downsample.{0,1}) and of
+    `resnet50/101` (Bottleneck: conv{1,2,3}, bn{1,2,3}, stride on conv2 — torchvision's v1.5)."""
 
     def __init__(self, name="resnet34", pretrained=False, frozen_stages=0, **ignored):
         super().__init__()
         if name not in RESNET_LAYERS:
             raise ValueError(f"backbone '{name}' is outside the MI355X hot-path scope (supported: {sorted(RESNET_LAYERS)})")
         self.name = name
-        self.out_channels = list(BACKBONE_CHANNELS)
+        self.bottleneck = name in BOTTLENECK_RESNETS
+        self.out_channels = list(BOTTLENECK_CHANNELS if self.bottleneck else BACKBONE_CHANNELS)
         self.output_stride = 32
         self.conv1 = nn.Conv2d(3, 64, 7, stride=2, padding=3, bias=False)
         self.bn1 = nn.BatchNorm2d(64)
@@ -172,8 +198,13 @@ class ResNetBackbone(nn.Module):
         for li, (n_blocks, cout) in enumerate(zip(RESNET_LAYERS[name], [64, 128, 256, 512])):
             blocks = []
             for b in range(n_blocks):
-                blocks.append(BasicBlock(cin, cout, stride=2 if (b == 0 and li > 0) else 1))
-                cin = cout
+                stride = 2 if (b == 0 and li > 0) else 1
+                if self.bottleneck:
+                    blocks.append(Bottleneck(cin, cout, stride))
+                    cin = cout * Bottleneck.expansion
+                else:
+                    blocks.append(BasicBlock(cin, cout, stride))
+                    cin = cout
             setattr(self, f"layer{li + 1}", nn.Sequential(*blocks))
         # `pretrained: True` (configs/base_resnet34.yaml:5) cannot be honoured offline; weights arrive through
         # load_state_dict().  Recorded so callers can see the request.

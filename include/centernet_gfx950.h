@@ -197,6 +197,20 @@ int cnl_conv2d_kernel(const cnl_conv_params* p);
  */
 size_t cnl_conv_split_weight_floats(int32_t Cin, int32_t Cout, int32_t KH, int32_t KW);
 int cnl_conv_split_weights_f32(const float* w_ohwi, float* w_buf, int32_t Cin, int32_t Cout, int32_t KH, int32_t KW, void* stream);
+/*
+ * 1x1 convolution over NHWC rows as one GEMM [N*H*W, K] x [K, Cout] (torchvision Bottleneck.conv1 / conv3 / downsample of ResNet-50 / 101)
+ * on the fp16-split arithmetic (csrc/pointwise.hip), with a TWO-SOURCE form for a stage's conv3 and its downsample in one launch:
+ *     y = act(x1 W1 + x2[:, ::stride2, ::stride2, :] W2 + bias (+ residual))
+ * p: KH = KW = 1, stride 1, pad 0; x = x1 [N, H_in, W_in, ldx] with Cin channels; y [N, H_in, W_in, ldy]; flags = CNL_W_SPLIT (| CNL_RELU);
+ * p->w is a cnl_conv_split_weights_f32 buffer of the [Cout][Cin + C2] weights ([W1 | W2] concatenated along K, KH = KW = 1), p->bias holds
+ * the summed biases; x_absmax (required) / y_absmax as in cnl_conv_params; residual / ldr optional; algo AUTO / F2, or CNL_ALGO_FORCE + t to
+ * pin tile shape t (1: 64 x 128, 2: 128 x 128, 3: 256 x 64; same bits); CNL_ALGO_F32 is CNL_E_UNSUPPORTED.  x2 = NULL: single source (H2, W2,
+ * C2, ldx2, stride2, x2_absmax ignored).  Otherwise x2 [N, H2, W2, ldx2] with C2 channels, (H2 - 1) / stride2 + 1 == H_in (likewise W),
+ * stride2 1 or 2, x2_absmax its per-image maxima.  Both sources share ONE power-of-two scale per image, from the larger of the two maxima
+ * (error bound: DESIGN.md §11).  Cin, C2: multiples of 32, Cin + C2 <= 4096; Cout <= 4096; any N*H*W.  Batch-invariant, deterministic.
+ */
+int cnl_pointwise_nhwc_f32(const cnl_conv_params* p, const float* x2, int32_t H2, int32_t W2, int32_t C2, int32_t ldx2, int32_t stride2,
+                           const float* x2_absmax, void* stream);
 size_t cnl_up2_weight_floats(int32_t Cin, int32_t Cout);
 int cnl_up2_pack_weights_f32(const float* w_ohwi, float* w_packed, int32_t Cin, int32_t Cout, void* stream);
 int cnl_conv3x3_up2_nhwc_f32(const cnl_conv_params* p, void* stream);
