@@ -52,6 +52,12 @@ class DecodeParams(Structure):
                 ("workspace", c_void_p), ("workspace_bytes", c_size_t)]
 
 
+class LetterboxFrame(Structure):
+    """cnl_letterbox_frame: one record of the table cnl_letterbox_bilinear_u8 / cnl_unletterbox_boxes_f32 read (40 bytes)."""
+    _fields_ = [("src", c_void_p), ("h", c_int32), ("w", c_int32), ("row_stride", c_int32), ("new_h", c_int32), ("new_w", c_int32),
+                ("pad_top", c_int32), ("pad_left", c_int32), ("reserved", c_int32)]
+
+
 _SIGNATURES = {
     "cnl_version": (ctypes.c_int, []),
     "cnl_sizeof_params": (c_size_t, [ctypes.c_int32]),
@@ -89,6 +95,8 @@ _SIGNATURES = {
                                                   c_int32, c_int32, c_void_p]),
     "cnl_normalize_u8_nhwc_f32": (ctypes.c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, POINTER(c_float), POINTER(c_float), c_void_p]),
     "cnl_resize_bilinear_u8": (ctypes.c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p]),
+    "cnl_letterbox_bilinear_u8": (ctypes.c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_uint32, c_void_p]),
+    "cnl_unletterbox_boxes_f32": (ctypes.c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
     "cnl_stem_conv7x7_u8": (ctypes.c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, POINTER(c_float), POINTER(c_float), c_void_p, c_void_p,
                                            c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "cnl_stem_packed_weight_floats": (c_size_t, []),

@@ -1,0 +1,132 @@
+"""Letterboxing: frames of different sizes -> one canvas batch, and decoded boxes back into each frame's own pixels.
+
+The reference validates with keep-aspect resize + pad (configs/centernet.yaml val_data.transforms; datasets/inference.py carries
+original_height / original_width) one image at a time on the host.  Here the geometry is host arithmetic on tensor SHAPES (no device
+sync), the pixels are one launch of cnl_letterbox_bilinear_u8 and the boxes one launch of cnl_unletterbox_boxes_f32.
+"""
+import ctypes
+from typing import List, Sequence, Tuple
+
+import torch
+
+from . import _lib
+
+
+def letterbox_geometry(h: int, w: int, height: int, width: int) -> Tuple[int, int, int, int]:
+    """(new_h, new_w, pad_top, pad_left) of an h x w frame inside a height x width canvas.
+
+    r = min(height / h, width / w) in float64; new_h = min(height, max(1, round(h * r))) and new_w likewise, with Python's round
+    (half to even) — what albumentations' LongestMaxSize uses (py3round); for a square target this IS LongestMaxSize(max_size=height).
+    pad_top = (height - new_h) // 2, pad_left = (width - new_w) // 2, the rest goes to the bottom / right: albumentations'
+    PadIfNeeded(position="center").  The border is a CONSTANT colour, not albumentations' default reflected border: a reflected border
+    shows the network real objects twice.  albumentations is restated from its published behaviour ("parity unpinned", as
+    oracle/decode_ref.resize_bilinear_u8 states for cv2.resize).
+
+    height and width must be positive multiples of 32 (the model's requirement), h and w at least 1; otherwise ValueError."""
+    for name, v in (("h", h), ("w", w), ("height", height), ("width", width)):
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise ValueError(f"letterbox_geometry: {name} must be an int, got {v!r}")
+    if h < 1 or w < 1:
+        raise ValueError(f"letterbox_geometry: frame size {h} x {w} must be at least 1 x 1")
+    if height < 32 or width < 32 or height % 32 or width % 32:
+        raise ValueError(f"letterbox_geometry: target {height} x {width} must be positive multiples of 32")
+    r = min(height / h, width / w)
+    new_h = min(height, max(1, round(h * r)))
+    new_w = min(width, max(1, round(w * r)))
+    return new_h, new_w, (height - new_h) // 2, (width - new_w) // 2
+
+
+class LetterboxGeometry:
+    """What letterbox_uint8 did to each frame: `table` is the device array of cnl_letterbox_frame records the kernels read,
+    `frames` the host-side list of (h, w, new_h, new_w, pad_top, pad_left), `height` / `width` the canvas size."""
+
+    def __init__(self, table: torch.Tensor, frames: List[Tuple[int, int, int, int, int, int]], height: int, width: int, keep=()):
+        self.table = table
+        self.frames = frames
+        self.height = height
+        self.width = width
+        self._keep = keep          # the (possibly copied) source frames: the table holds their addresses
+
+    def __len__(self):
+        return len(self.frames)
+
+    def __repr__(self):
+        return f"LetterboxGeometry(n={len(self.frames)}, canvas={self.height}x{self.width})"
+
+
+def _fill_word(fill, C: int) -> int:
+    vals = [fill] * 4 if isinstance(fill, int) else list(fill)
+    if len(vals) < C or any((not isinstance(v, int)) or v < 0 or v > 255 for v in vals):
+        raise ValueError(f"fill must be one uint8 value or at least {C} of them, got {fill!r}")
+    word = 0
+    for c, v in enumerate(vals[:4]):
+        word |= v << (8 * c)
+    return word
+
+
+def letterbox_uint8(frames, height: int, width: int, fill=(0, 0, 0)):
+    """frames: a sequence of uint8 [h_i, w_i, C] tensors on one HIP device (C in 1..4, the same for all), or one [N, h, w, C] tensor
+    -> (canvas [N, height, width, C] uint8, LetterboxGeometry).  One launch; one pinned-memory upload (the table); no device sync."""
+    import numpy as np
+    if isinstance(frames, torch.Tensor):
+        if frames.dim() != 4:
+            raise ValueError(f"expected a sequence of uint8 [h,w,C] frames or one [N,h,w,C] tensor, got {tuple(frames.shape)}")
+        if not frames.is_cuda:
+            raise RuntimeError("letterbox_uint8 runs on HIP devices only (no CPU fallback)")
+        if frames.dtype != torch.uint8:
+            raise ValueError(f"expected uint8 frames, got {frames.dtype}")
+        frames = list(frames.contiguous().unbind(0))
+    frames = list(frames)
+    if not frames:
+        raise ValueError("letterbox_uint8: no frames")
+    for f in frames:
+        if not (isinstance(f, torch.Tensor) and f.is_cuda):
+            raise RuntimeError("letterbox_uint8 runs on HIP devices only (no CPU fallback)")
+    dev, C = frames[0].device, frames[0].shape[-1] if frames[0].dim() == 3 else -1
+    for f in frames:
+        if f.dtype != torch.uint8 or f.dim() != 3 or f.shape[-1] != C or not 1 <= C <= 4:
+            raise ValueError(f"expected uint8 [h,w,C<=4] frames with one C, got {f.dtype} {tuple(f.shape)}")
+        if f.device != dev:
+            raise ValueError(f"frames live on different devices ({dev}, {f.device})")
+    height, width = int(height), int(width)
+    geo = [(f.shape[0], f.shape[1]) + letterbox_geometry(f.shape[0], f.shape[1], height, width) for f in frames]
+    word = _fill_word(fill, C)
+    frames = [f.contiguous() for f in frames]
+    N = len(frames)
+    rec = np.zeros((N, 5), dtype=np.int64)                       # cnl_letterbox_frame: 8-byte pointer + 8 int32
+    rec[:, 0] = [f.data_ptr() for f in frames]
+    i32 = rec.view(np.int32).reshape(N, 10)
+    i32[:, 2:9] = [(h, w, w * C, nh, nw, pt, pl) for (h, w, nh, nw, pt, pl) in geo]
+    assert rec.nbytes == N * ctypes.sizeof(_lib.LetterboxFrame)
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        host = torch.empty((N, 5), dtype=torch.int64, pin_memory=True)
+        host.copy_(torch.from_numpy(rec))
+        table = host.to(dev, non_blocking=True)
+        canvas = torch.empty((N, height, width, C), device=dev, dtype=torch.uint8)
+        _lib.check(lib.cnl_letterbox_bilinear_u8(table.data_ptr(), canvas.data_ptr(), N, height, width, C, word,
+                                                 ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "cnl_letterbox_bilinear_u8")
+    return canvas, LetterboxGeometry(table, geo, height, width, keep=frames)
+
+
+def unletterbox_(bboxes: torch.Tensor, geom: LetterboxGeometry, clip: bool = True) -> torch.Tensor:
+    """In place: [N, k, 4] x1 y1 x2 y2 in canvas pixels -> each frame's own pixels."""
+    if not (isinstance(bboxes, torch.Tensor) and bboxes.is_cuda):
+        raise RuntimeError("unletterbox runs on HIP devices only (no CPU fallback)")
+    if bboxes.dtype != torch.float32 or bboxes.dim() != 3 or bboxes.shape[-1] != 4 or not bboxes.is_contiguous():
+        raise ValueError(f"expected contiguous float32 [N,k,4] boxes, got {bboxes.dtype} {tuple(bboxes.shape)}")
+    if bboxes.shape[0] != len(geom) or bboxes.device != geom.table.device:
+        raise ValueError(f"boxes of {bboxes.shape[0]} frames on {bboxes.device} against a geometry of {len(geom)} frames on {geom.table.device}")
+    lib = _lib.load()
+    with torch.cuda.device(bboxes.device):
+        _lib.check(lib.cnl_unletterbox_boxes_f32(bboxes.data_ptr(), geom.table.data_ptr(), bboxes.shape[0], bboxes.shape[1], int(bool(clip)),
+                                                 ctypes.c_void_p(torch.cuda.current_stream(bboxes.device).cuda_stream)), "cnl_unletterbox_boxes_f32")
+    return bboxes
+
+
+def unletterbox(bboxes: torch.Tensor, geom: LetterboxGeometry, clip: bool = True) -> torch.Tensor:
+    """A new tensor: the boxes gather_detection2d / gather_tracking2d return for normalize_bbox=False, in each frame's own pixel
+    coordinates; clip=True clamps them to [0, w] x [0, h]."""
+    if not (isinstance(bboxes, torch.Tensor) and bboxes.is_cuda):
+        raise RuntimeError("unletterbox runs on HIP devices only (no CPU fallback)")
+    return unletterbox_(bboxes.clone(memory_format=torch.contiguous_format), geom, clip)

@@ -20,6 +20,7 @@ import torch
 from torch import nn
 
 from . import decode as _decode
+from . import letterbox as _letterbox
 from .collate import collate_detections
 from .config import model_section
 from .engine import Engine
@@ -207,6 +208,32 @@ class CenterNet(nn.Module):
         if "reid" in out:
             return TrackingOutput(out["heatmap"], out["box_2d"], out["reid"])
         return DetectionOutput(out["heatmap"], out["box_2d"])
+
+    # ------------------------------------------------------------------ frames of different sizes
+    def letterbox_uint8(self, frames, height: int, width: int, fill=(0, 0, 0)):
+        """uint8 frames of DIFFERENT sizes (a sequence of [h_i, w_i, 3] tensors on the GPU, or one [N,h,w,3] tensor) -> (canvas
+        [N,height,width,3] uint8, geom): keep-aspect cv2 INTER_LINEAR resize (albumentations LongestMaxSize) centred on a constant `fill`
+        border (PadIfNeeded(position="center")), one launch of cnl_letterbox_bilinear_u8 for the whole batch.  `geom` holds the device
+        table and the host-side list of (h, w, new_h, new_w, pad_top, pad_left); see letterbox_geometry for the rule."""
+        return _letterbox.letterbox_uint8(frames, height, width, fill)
+
+    def unletterbox(self, bboxes: torch.Tensor, geom, clip: bool = True) -> torch.Tensor:
+        """Boxes [N,k,4] in canvas pixels (gather_* with normalize_bbox=False) -> each frame's own pixels (cnl_unletterbox_boxes_f32)."""
+        return _letterbox.unletterbox(bboxes, geom, clip)
+
+    def detect_frames(self, frames, height: int = 512, width: int = 512, fill=(0, 0, 0), mean=IMAGENET_MEAN, std=IMAGENET_STD,
+                      num_detections: int = 100, nms_kernel: int = 3):
+        """Frames of different sizes -> {"bboxes" (each frame's own pixels, clipped to it), "labels", "scores"[, "embeddings"]}:
+        letterbox_uint8 -> forward_uint8 on the canvas (the stem normalises: still no fp32 image in memory) -> the decode ->
+        unletterbox.  Nothing between the frames and the result touches the host except the table upload."""
+        canvas, geom = _letterbox.letterbox_uint8(frames, height, width, fill)
+        if canvas.shape[-1] != 3:
+            raise ValueError(f"detect_frames expects 3-channel frames, got {canvas.shape[-1]} channels")
+        out = self.forward_uint8(canvas, mean=mean, std=std)
+        gather = self.gather_tracking2d if len(out) == 3 else self.gather_detection2d
+        dets = gather(out, num_detections=num_detections, nms_kernel=nms_kernel, normalize_bbox=False)
+        _letterbox.unletterbox_(dets["bboxes"], geom, True)
+        return dets
 
     # ------------------------------------------------------------------ decode (Gen-A names)
     def gather_detection2d(self, heatmap, box_2d=None, num_detections=100, nms_kernel=3, normalize_bbox=False):

@@ -279,6 +279,47 @@ int cnl_resize_bilinear_u8(const uint8_t* x, uint8_t* y, int32_t N, int32_t H_in
                            int32_t C, void* stream);
 
 /*
+ * Batch entry for frames of DIFFERENT sizes: keep-aspect resize + centred constant border, the reference's validation transforms
+ * (configs/centernet.yaml val_data.transforms; albumentations LongestMaxSize for a square target, then
+ * PadIfNeeded(position="center") with a CONSTANT border) for N frames in ONE launch, and the way back for the decoded boxes
+ * (datasets/inference.py carries original_height / original_width for that).
+ *
+ * `table` is a device array of N records, one per frame, 40 bytes each, 8-byte aligned:
+ *     offset  0  const void* src    the frame's first pixel (uint8, HWC, C channels; device memory)
+ *     offset  8  int32 h, w         frame size, >= 1
+ *     offset 16  int32 row_stride   bytes from one source row to the next (>= w * C)
+ *     offset 20  int32 new_h, new_w size of the resized frame inside the canvas, 1..height / 1..width
+ *     offset 28  int32 pad_top, pad_left   where the resized frame starts: pad_top + new_h <= height, pad_left + new_w <= width
+ *     offset 36  int32 reserved     0
+ * Geometry rule of the Python host (letterbox_geometry): r = min(height / h, width / w) in double, new_h = min(height,
+ * max(1, round_half_even(h * r))), new_w alike, pad_top = (height - new_h) / 2, pad_left = (width - new_w) / 2 (the remainder goes
+ * to the bottom / right).  The kernel takes whatever window the record names.
+ *
+ * out: [N, height, width, C] u8, height and width positive multiples of 32, C in 1..4, 4-byte aligned.  Inside a frame's window the
+ * bytes are those of the 8-bit resize entry point above for that frame resized to (new_h, new_w); outside it, byte c of every pixel
+ * is bits 8c..8c+7 of fill_rgba.  Every byte of `out` is written exactly once (no memset needed before it); a frame's result depends
+ * on that frame's record only.  N = 0 is a no-op.
+ */
+typedef struct cnl_letterbox_frame {
+    const void* src;
+    int32_t h, w;
+    int32_t row_stride;
+    int32_t new_h, new_w;
+    int32_t pad_top, pad_left;
+    int32_t reserved;
+} cnl_letterbox_frame;
+int cnl_letterbox_bilinear_u8(const void* table, uint8_t* out, int32_t N, int32_t height, int32_t width, int32_t C,
+                              uint32_t fill_rgba, void* stream);
+
+/*
+ * Canvas pixels -> each frame's own pixels, in place.  boxes: [N, k, 4] (x1 y1 x2 y2) f32, 16-byte aligned, as the decode writes them
+ * with normalize_boxes = 0; `table` as above.  With sx = float(new_w) / float(w) and sy = float(new_h) / float(h):
+ * x' = (x - pad_left) / sx, y' = (y - pad_top) / sy, one rounding per operation; clip != 0 clamps to [0, w] / [0, h].
+ * The axes have their own ratio because rounding new_h and new_w makes them differ slightly.
+ */
+int cnl_unletterbox_boxes_f32(float* boxes, const void* table, int32_t N, int32_t k, int32_t clip, void* stream);
+
+/*
  * ResNet stem: Conv2d(3,64,7,stride=2,padding=3,bias=False)+BN+ReLU (torchvision resnet.conv1/bn1/relu).
  * x is read through explicit element strides (sn,sc,sh,sw) so NCHW-contiguous and channels_last
  * callers are both zero-copy (models/meta.py:97-98 precedent); y is NHWC [N, H/2, W/2, 64].
