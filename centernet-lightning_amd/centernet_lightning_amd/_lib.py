@@ -126,6 +126,12 @@ _SIGNATURES = {
     "cnl_track_frame_bytes": (ctypes.c_int64, [c_int32, c_int32, c_int32]),
     "cnl_track_frame_f32": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_float, c_void_p, c_void_p,
                                            c_int32, c_int32, c_int32, c_int32, c_void_p, ctypes.c_int64, c_void_p]),
+    "cnl_lsap_batch_f64": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "cnl_track_streams_workspace_bytes": (ctypes.c_int64, [c_int32, c_int32, c_int32]),
+    "cnl_track_streams_record_bytes": (ctypes.c_int64, [c_int32, c_int32, c_int32]),
+    "cnl_track_streams_f32": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int32, c_int32, c_float,
+                                             c_double, c_float, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p,
+                                             ctypes.c_int64, c_void_p, ctypes.c_int64, c_void_p]),
     "cnl_host_alloc": (ctypes.c_int, [ctypes.c_size_t, ctypes.POINTER(c_void_p)]),
     "cnl_host_free": (ctypes.c_int, [c_void_p]),
 }

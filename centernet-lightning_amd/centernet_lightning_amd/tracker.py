@@ -445,8 +445,354 @@ class Tracker:
         return self._emb[:len(self.tracks)] if self._emb is not None else None
 
 
-def build_tracker(config, model=None):
-    """tracker.py:349-353."""
+class _StreamState:
+    """What `TrackerBank[s]` returns: the per-stream state, named as Tracker's (`tracks` are Track objects)."""
+    __slots__ = ("tracks", "frame", "next_track_id")
+
+    def __init__(self):
+        self.tracks: List[Track] = []
+        self.frame = 0
+        self.next_track_id = 0
+
+
+class TrackerBank:
+    """S independent trackers whose unit of work is ONE FRAME FROM EACH STREAM (csrc/track_streams.hip): `step_batch(images)` takes frame i
+    as the next frame of stream i — what a live deployment with S cameras has in hand — where `Tracker.step_batch` takes the batch as
+    consecutive frames of one video.  Per step: one association pass on the device for all streams (threshold mask, cost matrices, BOTH
+    assignment stages — the Hungarian step runs on the GPU, one workgroup per stream, with scipy's exact result), ONE stream
+    synchronisation, the track life cycle per stream on the host from the match lists, one pooled table update.  No cost matrix crosses
+    PCIe.  Same constructor arguments, defaults and results as `Tracker`, one setting for all streams; host-side costs
+    (`allow_host_cost` metrics, callables) are refused: the bank exists to keep the matrices on the device.
+
+    A stream whose costs are not finite (e.g. a zero embedding under "cosine") is redone through the single-stream host path, so the
+    caller sees what `Tracker` raises there (scipy's ValueError); the exception leaves EVERY stream of the bank as it was before the step."""
+
+    def __init__(self, num_streams, model=None, nms_kernel=3, num_detections=300, detection_threshold=0.3, reid_cost="cosine",
+                 reid_threshold=0.2, box_cost="iou", box_threshold=0.5, smoothing_factor=0.5, use_kalman=False,
+                 max_inactive_age=30, min_birth_age=2, device=None, allow_host_cost=False):
+        if isinstance(num_streams, bool) or not isinstance(num_streams, (int, np.integer)) or num_streams < 1:
+            raise ValueError(f"num_streams={num_streams!r}: expected an integer >= 1")
+        if callable(reid_cost) or callable(box_cost) or reid_cost not in _REID_METRICS:
+            raise ValueError(f"reid_cost={reid_cost!r} / box_cost={box_cost!r}: a TrackerBank keeps the cost matrices on the device; only "
+                             f"{sorted(_REID_METRICS)} and 'iou' / 'giou' / None have gfx950 kernels (allow_host_cost does not apply: use one "
+                             "Tracker per stream for host-side costs)")
+        if box_cost not in _BOX_MODES:
+            raise ValueError(f"box_cost={box_cost!r}: expected 'iou', 'giou' or None")
+        self.model = model
+        if model is None:
+            warnings.warn("A model was not provided. Only `.update_batch()` will work")
+        self.num_streams = int(num_streams)
+        self.nms_kernel = nms_kernel
+        self.num_detections = num_detections
+        self.detection_threshold = detection_threshold
+        self.reid_cost = reid_cost
+        self.reid_threshold = reid_threshold
+        self.box_cost = box_cost
+        self.box_threshold = box_threshold
+        self.smoothing_factor = smoothing_factor
+        self.use_kalman = bool(use_kalman)
+        self.max_inactive_age = max_inactive_age
+        self.min_birth_age = min_birth_age
+        self._device = torch.device(device) if device is not None else None
+        self._streams = [_StreamState() for _ in range(self.num_streams)]
+        self._emb = self._box = self._spare = None      # pooled device table: stream s owns rows _off[s] .. _off[s + 1]
+        self._off = np.zeros(self.num_streams + 1, np.int64)
+        self._rec = self._ctl = self._src = self._ws = None     # mapped records / live list + trk_off / apply index lists; device workspace
+        self._apply_stream = None
+        self.d2h_bytes = 0
+        self.last_matches = [None] * self.num_streams
+
+    device = Tracker.device
+    _tables = Tracker._tables
+
+    def __len__(self):
+        return self.num_streams
+
+    def __getitem__(self, s):
+        return self._streams[s]
+
+    def track_embeddings(self, s):
+        """Device view [T_s, E] of stream s's rows of the pooled table (row order = self[s].tracks)."""
+        return self._emb[int(self._off[s]):int(self._off[s + 1])] if self._emb is not None else None
+
+    # ------------------------------------------------------------------ state
+    def reset(self, stream=None):
+        """Forget every stream (None) or one stream; the other streams keep tracks, counters and table rows."""
+        if stream is None:
+            if self._apply_stream is not None:
+                self._apply_stream.synchronize()
+            self._streams = [_StreamState() for _ in range(self.num_streams)]
+            self._emb = self._box = self._spare = None
+            self._off[:] = 0
+            self.last_matches = [None] * self.num_streams
+            return
+        s = self._check_streams([stream])[0]
+        self._streams[s] = _StreamState()
+        self.last_matches[s] = None
+        if self._off[s + 1] == self._off[s]:
+            return
+        # repack the pooled table without stream s's rows: the pooled apply launch with every kept row copied through (src_det = -1)
+        E = self._emb.shape[1]
+        rows = np.concatenate([np.arange(self._off[t], self._off[t + 1]) for t in range(self.num_streams) if t != s] + [np.zeros(0, np.int64)])
+        dev = self.device
+        with _on(dev):
+            cur = torch.cuda.current_stream(dev)
+            if self._apply_stream is not None:
+                self._apply_stream.synchronize()      # its reads of the index lists come before this overwrite
+            self._apply(rows.astype(np.int32), np.full(len(rows), -1, np.int32), E, self._emb, self._box, cur)
+        self._set_offsets()
+
+    def _set_offsets(self):
+        r = 0
+        for s, st in enumerate(self._streams):
+            self._off[s] = r
+            for t in st.tracks:
+                t._row = r
+                r += 1
+        self._off[self.num_streams] = r
+
+    def _check_streams(self, streams):
+        S = self.num_streams
+        live = list(range(S)) if streams is None else [int(x) for x in streams]
+        if not live or any(x < 0 or x >= S for x in live) or len(set(live)) != len(live):
+            raise ValueError(f"streams={streams!r}: expected distinct stream indices in 0..{S - 1}, at least one")
+        return live
+
+    def _apply(self, src_trk, src_det, E, d_emb, d_box, cur):
+        """The pooled table update: one cnl_track_apply_f32 launch over the rows of all streams, index lists in mapped host memory."""
+        lib = _lib.load()
+        R_new = len(src_trk)
+        if R_new == 0:
+            return
+        if self._src is None or self._src.nbytes < 8 * R_new:
+            self._src = _Mapped(8 * max(1024, 1 << (R_new - 1).bit_length()))
+        cap = self._src.nbytes // 8
+        lists = self._src.np.view(np.int32).reshape(2, cap)
+        lists[0, :R_new] = src_trk
+        lists[1, :R_new] = src_det
+        new_emb, new_box = self._tables(R_new, E)
+        has_old = self._emb is not None
+        _lib.check(lib.cnl_track_apply_f32(self._emb.data_ptr() if has_old else None, self._box.data_ptr() if has_old else None,
+                                           d_emb.data_ptr(), d_box.data_ptr(), self._src.ptr, self._src.ptr + 4 * cap, R_new, E,
+                                           float(self.smoothing_factor), new_emb.data_ptr(), new_box.data_ptr(),
+                                           ctypes.c_void_p(cur.cuda_stream)), "cnl_track_apply_f32")
+        self._apply_stream = cur
+        self._spare, (self._emb, self._box) = ((self._emb, self._box) if has_old else None), (new_emb, new_box)
+
+    # ------------------------------------------------------------------ inference
+    @torch.no_grad()
+    def step_batch(self, images: torch.Tensor, streams=None, **kwargs):
+        """Run the model on one frame from each participating stream (images[i] is the next frame of stream streams[i]; default: stream i)
+        and advance those streams.  Returns {"bboxes": [...], "track_ids": [...]} with one list per image (active tracks only)."""
+        live = self._check_streams(streams)
+        if images.dim() != 4 or images.shape[0] != len(live):
+            raise ValueError(f"images {tuple(images.shape)}: expected [{len(live)}, 3, H, W], one frame per participating stream")
+        nms_kernel = kwargs.get("nms_kernel", self.nms_kernel)
+        num_detections = kwargs.get("num_detections", self.num_detections)
+        self.model.eval()
+        images = images.to(self.device)
+        heatmap, box_2d, reid = self.model(images)
+        det = self.model.gather_tracking2d(heatmap, box_2d, reid, nms_kernel=nms_kernel, num_detections=num_detections,
+                                           normalize_bbox=True)
+        self._step(det["bboxes"], det["scores"], det["embeddings"], det["labels"], None, live, **kwargs)
+        out = {"bboxes": [], "track_ids": []}
+        for s in live:
+            st = self._streams[s]
+            st.frame += 1
+            out["bboxes"].append([x.bbox for x in st.tracks if x.active])
+            out["track_ids"].append([x.track_id for x in st.tracks if x.active])
+        return out
+
+    def update_batch(self, bboxes, labels, scores, embeddings, streams=None, **kwargs):
+        """One frame's detections for each participating stream: [L, k, 4], [L, k], [L, k], [L, k, E] (numpy arrays or torch tensors; L =
+        len(streams), default every stream).  As `Tracker.update`, it does not advance `frame`."""
+        live = self._check_streams(streams)
+        dev = self.device
+        for name, a, nd in (("bboxes", bboxes, 3), ("labels", labels, 2), ("scores", scores, 2), ("embeddings", embeddings, 3)):
+            if a.ndim != nd or a.shape[0] != len(live):
+                raise ValueError(f"{name} {tuple(a.shape)}: expected {nd} dimensions with {len(live)} streams in front")
+
+        def to_dev(a):
+            if isinstance(a, torch.Tensor) and a.device == dev and a.dtype == torch.float32 and a.is_contiguous():
+                return a
+            return torch.as_tensor(a).to(device=dev, dtype=torch.float32).contiguous()
+        host = lambda a: a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+        if all(isinstance(a, torch.Tensor) and a.is_cuda for a in (bboxes, labels, scores)):
+            self._step(to_dev(bboxes), to_dev(scores), to_dev(embeddings), labels.to(dev), None, live, **kwargs)
+        else:
+            self._step(to_dev(bboxes), to_dev(scores), to_dev(embeddings), None, (host(bboxes), host(labels), host(scores)), live, **kwargs)
+
+    # ------------------------------------------------------------------ one step
+    def _host_association(self, i, s, d_box, d_score, d_emb, detection_threshold, reid_threshold, box_threshold):
+        """Stream s's association through the single-stream path (cnl_track_frame_f32 + scipy on the host) on its slice of the operands:
+        what a stream with non-finite costs is redone with, so that the caller sees what Tracker raises (scipy: ValueError)."""
+        lib = _lib.load()
+        dev = self.device
+        k, E = d_emb.shape[1], d_emb.shape[2]
+        t0, T = int(self._off[s]), int(self._off[s + 1] - self._off[s])
+        box_mode, metric = _BOX_MODES[self.box_cost], _REID_METRICS[self.reid_cost]
+        rec = _Mapped(int(lib.cnl_track_frame_bytes(k, T, 0)))
+        with _on(dev):
+            cur = torch.cuda.current_stream(dev)
+            _lib.check(lib.cnl_track_frame_f32(d_emb[i].data_ptr(), d_box[i].data_ptr(), d_score[i].data_ptr(), None, 0, k, E,
+                                               float(detection_threshold), self._emb[t0:].data_ptr() if T else None,
+                                               self._box[t0:].data_ptr() if T else None, T, box_mode, metric, 0, rec.ptr, rec.nbytes,
+                                               ctypes.c_void_p(cur.cuda_stream)), "cnl_track_frame_f32")
+            cur.synchronize()
+        h = rec.np
+        hdr = h[:32].view(np.int32)
+        n, off_reid, off_box = int(hdr[0]), int(hdr[6]), int(hdr[7])
+        if T == 0:
+            return [], list(range(n)), []
+        reid = h[off_reid:off_reid + 8 * n * T].view(np.float64).reshape(n, T)
+        matches, ud, ut = match_with_threshold(reid, reid_threshold)
+        if box_mode:
+            box = h[off_box:off_box + 4 * n * T].view(np.float32).reshape(n, T)
+            new_matches, ud2, ut2 = match_with_threshold(box[np.ix_(ud, ut)], box_threshold)
+            matches.extend((ud[x], ut[y]) for x, y in new_matches)
+            ud, ut = [ud[x] for x in ud2], [ut[y] for y in ut2]
+        return matches, ud, ut
+
+    def _step(self, d_box, d_score, d_emb, d_label, host, live, **kwargs):
+        detection_threshold = kwargs.get("detection_threshold", self.detection_threshold)
+        reid_threshold = kwargs.get("reid_threshold", self.reid_threshold)
+        box_threshold = kwargs.get("box_threshold", self.box_threshold)
+        lib = _lib.load()
+        dev = self.device
+        S, L = self.num_streams, len(live)
+        if d_emb.dim() != 3 or d_emb.shape[0] != L:
+            raise ValueError(f"detections: embeddings {tuple(d_emb.shape)}, expected [{L}, k, E]")
+        k, E = int(d_emb.shape[1]), int(d_emb.shape[2])
+        if d_box.shape != (L, k, 4) or d_score.shape != (L, k):
+            raise ValueError(f"detections: boxes {tuple(d_box.shape)}, scores {tuple(d_score.shape)}, embeddings {tuple(d_emb.shape)}")
+        d_box, d_score, d_emb = d_box.contiguous(), d_score.contiguous(), d_emb.contiguous()
+        with_dets = host is None
+        label_kind = 0
+        if with_dets and d_label is not None:
+            if d_label.shape != (L, k):
+                raise ValueError(f"detections: labels {tuple(d_label.shape)}, expected ({L}, {k})")
+            label_kind = _LABEL_KINDS.get(d_label.dtype, 0)
+            if not label_kind:
+                d_label, label_kind = d_label.to(torch.int64), 1
+            d_label = d_label.contiguous()
+        elif not with_dets and any(a.shape[:2] != (L, k) for a in host):
+            raise ValueError(f"detections: boxes {host[0].shape}, labels {host[1].shape}, scores {host[2].shape}, expected [{L}, {k}, ...]")
+        off = self._off
+        R = int(off[S])
+        T_max = max(int(off[s + 1] - off[s]) for s in live)
+        box_mode, metric = _BOX_MODES[self.box_cost], _REID_METRICS[self.reid_cost]
+        # cnl_track_streams_record_bytes / cnl_track_streams_workspace_bytes, in Python (a ctypes call costs ~2 us)
+        off_dets = (64 + 4 * k + 7) & ~7
+        off_match = off_dets + (24 * k if with_dets else 0)
+        off_udet, off_utrk = off_match + 8 * k, off_match + 12 * k
+        stride = (off_utrk + 4 * T_max + 7) & ~7
+        ws_need = 20 * k * R + 4 * (S + 2 * S * k + 2 * R)
+        with _on(dev):
+            cur = torch.cuda.current_stream(dev)
+            stream = ctypes.c_void_p(cur.cuda_stream)
+            if self._apply_stream is not None and self._apply_stream != cur:
+                self._apply_stream.synchronize()        # the previous step's table update ran on another stream: finish it first
+            if self._rec is None or self._rec.nbytes < S * stride:
+                self._rec = _Mapped(max(2 * S * stride, 1 << 16))
+            if self._ws is None or self._ws.numel() < ws_need:
+                self._ws = torch.empty(max(2 * ws_need, 1 << 20), device=dev, dtype=torch.uint8)
+            if self._ctl is None:
+                self._ctl = _Mapped(4 * (2 * S + 1))
+            # live list and trk_off sit in mapped memory of their own: the association kernels that read them have finished at this step's
+            # synchronisation, whereas the apply launch still reads ITS lists (self._src) after the host has moved on — those are
+            # overwritten only behind the next step's synchronisation, which follows that launch in stream order
+            ctl = self._ctl.np.view(np.int32)
+            ctl[:L] = live
+            ctl[S:2 * S + 1] = off
+            rec = self._rec
+            _lib.check(lib.cnl_track_streams_f32(d_emb.data_ptr(), d_box.data_ptr(), d_score.data_ptr(), d_label.data_ptr() if label_kind else None,
+                                                 label_kind, S, L, self._ctl.ptr, k, E, float(detection_threshold), float(reid_threshold),
+                                                 float(box_threshold), self._emb.data_ptr() if R else None, self._box.data_ptr() if R else None,
+                                                 self._ctl.ptr + 4 * S, R, T_max, box_mode, metric, int(with_dets), self._ws.data_ptr(),
+                                                 self._ws.numel(), rec.ptr, stride, stream), "cnl_track_streams_f32")
+            cur.synchronize()
+        h = rec.np
+        # ---- read every stream's lists first: an exception leaves all streams untouched ----
+        assoc, d2h = [], 0
+        for i, s in enumerate(live):
+            r = h[s * stride:(s + 1) * stride]
+            hdr = r[:64].view(np.int32)
+            n, T, status, m, nu, nt = int(hdr[0]), int(hdr[2]), int(hdr[3]), int(hdr[9]), int(hdr[11]), int(hdr[12])
+            det_index = r[64:64 + 4 * n].view(np.int32).copy()
+            if status in (3, 4, 19):
+                raise ValueError(f"stream {s}: association status {status} (k = {k}, T = {T}: beyond the supported sizes)")
+            if status:
+                matches, ud, ut = self._host_association(i, s, d_box, d_score, d_emb, detection_threshold, reid_threshold, box_threshold)
+            else:
+                matches = r[off_match:off_match + 8 * m].view(np.int32).reshape(m, 2).tolist()
+                matches = [tuple(p) for p in matches]
+                ud = r[off_udet:off_udet + 4 * nu].view(np.int32).tolist()
+                ut = r[off_utrk:off_utrk + 4 * nt].view(np.int32).tolist()
+            if with_dets:
+                f = r[off_dets:off_dets + 20 * k].view(np.float32)
+                h_box, h_score = f[:4 * k].reshape(k, 4).copy(), None
+                h_label = r[off_dets + 20 * k:off_dets + 24 * k].view(np.int32).astype(np.int64)
+            else:
+                h_box, h_label, h_score = host[0][i], host[1][i], host[2][i]
+                n_host = int(np.count_nonzero(np.asarray(h_score, dtype=np.float32) >= np.float32(detection_threshold)))
+                if n_host != n:
+                    raise RuntimeError(f"stream {s}: detection count mismatch between host ({n_host}) and device ({n})")
+            d2h += 64 + 4 * n + (24 * k if with_dets else 0) + 8 * m + 4 * nu + 4 * nt
+            assoc.append((matches, ud, ut, det_index, h_box, h_label))
+        self.d2h_bytes = d2h
+
+        # ---- track life cycle per stream (host) + the rows of the new pooled table ----
+        slot = {s: i for i, s in enumerate(live)}
+        src_trk, src_det = [], []
+        for s, st in enumerate(self._streams):
+            base = int(off[s])
+            if s not in slot:
+                src_trk.extend(range(base, base + len(st.tracks)))
+                src_det.extend([-1] * len(st.tracks))
+                continue
+            i = slot[s]
+            matches, unmatched_dets, unmatched_tracks, det_index, h_box, h_label = assoc[i]
+            self.last_matches[s] = matches
+            tracks = st.tracks
+            T = len(tracks)
+            row_det = {}
+            for det_idx, track_idx in matches:
+                # reference quirk kept (tracker.py:171), as in Tracker._update_device: the match indexes the thresholded arrays, the update
+                # reads the unfiltered ones at the same position
+                tracks[track_idx].update_matched(h_box[det_idx])
+                row_det[track_idx] = det_idx
+            for track_idx in unmatched_tracks:
+                tracks[track_idx].update_unmatched()
+            old_rows = list(range(T))
+            for det_idx in unmatched_dets:
+                src = int(det_index[det_idx])
+                tracks.append(Track(self, st.next_track_id, h_box[src], h_label[src], min_birth_age=self.min_birth_age,
+                                    max_inactive_age=self.max_inactive_age, smoothing_factor=self.smoothing_factor, use_kalman=self.use_kalman))
+                st.next_track_id += 1
+                old_rows.append(-1)
+                row_det[len(tracks) - 1] = src
+            keep = [j for j, t in enumerate(tracks) if not t.to_delete]
+            st.tracks = [tracks[j] for j in keep]
+            src_trk.extend(base + old_rows[j] if old_rows[j] >= 0 else -1 for j in keep)
+            src_det.extend(i * k + row_det[j] if j in row_det else -1 for j in keep)
+        with _on(dev):
+            self._apply(src_trk, src_det, E, d_emb, d_box, cur)
+        self._set_offsets()
+        R_new = int(off[S])
+        if self.use_kalman and R_new:
+            # a Kalman track's box is its filtered state, computed on the host with the life cycle: the boxes of all streams go up in ONE copy
+            boxes = np.asarray([np.asarray(t.bbox, np.float64) for st in self._streams for t in st.tracks], np.float32).reshape(R_new, 4)
+            with torch.cuda.device(dev):
+                self._box[:R_new].copy_(torch.from_numpy(boxes), non_blocking=False)
+            for s in live:
+                for t in self._streams[s].tracks:
+                    t.kalman_predict()
+
+
+def build_tracker(config, model=None, num_streams=None):
+    """tracker.py:349-353; with `num_streams`, a TrackerBank of that many streams with the same settings."""
     if isinstance(config, str):
         config = load_config(config)["tracker"]
+    if num_streams is not None:
+        return TrackerBank(num_streams, model=model, **config)
     return Tracker(model=model, **config)

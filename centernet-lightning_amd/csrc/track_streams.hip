@@ -1,0 +1,420 @@
+// track_streams.hip — one association pass for S independent video streams (one frame from each), assignment included.
+//
+// track.hip leaves the Hungarian step to scipy on the host: per frame the n x T cost matrices cross PCIe and the host thread solves
+// them one stream after the other.  Here the matrices stay in a device workspace and the assignment runs on the device, one
+// single-wave workgroup per stream, so that S streams are solved on S CUs at once and only the match lists reach the host:
+//
+//   streams_costs_kernel    compaction + cost matrices of every live stream (the device code of track.hip's frame_kernel, shared
+//                           through track_costs.h: bit-identical matrices), written to the workspace; frame record header / detections
+//   streams_assign_kernel   per stream: stage 1 (re-ID matrix, cost < reid_threshold), stage 2 (box-cost sub-matrix of what is still
+//                           unmatched, cost < box_threshold), match / unmatched lists into the stream's record (mapped host memory)
+//   lsap_batch_kernel       the solver alone on B caller-supplied matrices (cnl_lsap_batch_f64)
+//
+// The solver is scipy.optimize.linear_sum_assignment's algorithm (rectangular shortest augmenting path, Crouse 2016) in scipy's
+// order and in float64, because the RESULT must be scipy's, ties included: box-cost matrices are full of ties (every non-overlapping
+// pair costs exactly 1.0) and a different optimal assignment changes which pairs survive the threshold.  What is parallel is the scan
+// over the remaining columns (64 lanes) and the dual updates; the augmentations and the steps of a scan are sequential, as there.
+#include "track_costs.h"
+
+#pragma clang fp contract(off)   // one rounding per operation: the reduced costs decide ties exactly as scipy's do
+
+namespace cnl_track {
+
+constexpr int LSAP_MAX_SHORT = 1024;     // min(n, T): rows of the (possibly transposed) problem
+constexpr int LSAP_MAX_LONG = 4096;      // max(n, T): its columns
+// status words (cnl_lsap_batch_f64; cnl_track_streams_f32 adds 16 for the box stage)
+constexpr int LSAP_OK = 0, LSAP_INVALID = 1, LSAP_INFEASIBLE = 2, LSAP_TOO_LARGE = 3, STREAM_BAD_TABLE = 4;
+
+// The solver's state, carved from dynamic LDS: 12 bytes per row + 28 bytes per column.
+struct LsapLds {
+    double *u, *v, *spc;
+    int *path, *row4col, *remaining, *col4row;
+};
+__host__ __device__ inline size_t lsap_lds_bytes(int nr_cap, int nc_cap) { return 12ul * nr_cap + 28ul * nc_cap; }
+__device__ __forceinline__ LsapLds lsap_carve(double* base, int nr_cap, int nc_cap) {
+    LsapLds L;
+    L.u = base;
+    L.v = L.u + nr_cap;
+    L.spc = L.v + nc_cap;
+    L.path = reinterpret_cast<int*>(L.spc + nc_cap);
+    L.row4col = L.path + nc_cap;
+    L.remaining = L.row4col + nc_cap;
+    L.col4row = L.remaining + nc_cap;
+    return L;
+}
+
+// nr <= nc; C(i, j) = cost[i * rs + j * cs].  Called by the 64 lanes of a single-wave workgroup; every branch on the solver's state is
+// uniform.  On LSAP_OK, L.col4row[i] is row i's column and L.row4col[j] column j's row (or -1).
+__device__ int lsap_wave(const double* __restrict__ cost, const long rs, const long cs, const int nr, const int nc, const LsapLds L) {
+    const int lane = threadIdx.x;
+    const double INF = __builtin_inf();
+    for (int i = lane; i < nr; i += 64) { L.u[i] = 0.0; L.col4row[i] = -1; }
+    for (int j = lane; j < nc; j += 64) { L.v[j] = 0.0; L.row4col[j] = -1; L.path[j] = -1; }
+    __syncthreads();
+    for (int cur = 0; cur < nr; ++cur) {
+        for (int it = lane; it < nc; it += 64) { L.remaining[it] = nc - it - 1; L.spc[it] = INF; }
+        __syncthreads();
+        double min_val = 0.0;
+        int num_remaining = nc, sink = -1, i = cur;
+        while (sink == -1) {
+            // scipy's scan `for it in 0..num_remaining: ... if (spc[j] < lowest || (spc[j] == lowest && row4col[j] == -1)) { lowest = spc[j]; index = it; }`
+            // picks, among the columns holding the minimum, the LAST unassigned one if any is unassigned, else the FIRST: the key of this
+            // reduction (a lane walks its own positions in ascending order with scipy's very condition, the lanes are merged by the same order).
+            double best = INF;
+            int best_it = -1, best_free = 0;
+            const double ui = L.u[i];
+            const double* row = cost + (long)i * rs;
+            for (int it = lane; it < num_remaining; it += 64) {
+                const int j = L.remaining[it];
+                const double r = ((min_val + row[(long)j * cs]) - ui) - L.v[j];
+                double sp = L.spc[j];
+                if (r < sp) { L.path[j] = i; L.spc[j] = r; sp = r; }
+                const int fr = L.row4col[j] == -1;
+                if (sp < best || (sp == best && fr)) { best = sp; best_it = it; best_free = fr; }
+            }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                const double ob = __shfl_xor(best, o, 64);
+                const int oi = __shfl_xor(best_it, o, 64), of = __shfl_xor(best_free, o, 64);
+                const bool take = ob < best || (ob == best && (of != best_free ? of : (of ? oi > best_it : oi < best_it)));
+                if (take) { best = ob; best_it = oi; best_free = of; }
+            }
+            min_val = best;
+            if (min_val == INF) return LSAP_INFEASIBLE;
+            const int j = L.remaining[best_it], last = L.remaining[num_remaining - 1], r4c = L.row4col[j];
+            if (r4c == -1) sink = j; else i = r4c;
+            --num_remaining;
+            __syncthreads();
+            // removal is scipy's swap-with-last; the removed column is parked behind the live part, which lists the scanned columns (SC)
+            if (lane == 0) { L.remaining[best_it] = last; L.remaining[num_remaining] = j; }
+            __syncthreads();
+        }
+        // dual updates: u[cur] += minVal; u[i] += minVal - spc[col4row[i]] for the other visited rows (the rows of the scanned, assigned
+        // columns); v[j] -= minVal - spc[j] for the scanned columns.  Same operands and operations as scipy, distinct addresses per lane.
+        if (lane == 0) L.u[cur] = L.u[cur] + min_val;
+        for (int idx = num_remaining + lane; idx < nc; idx += 64) {
+            const int j = L.remaining[idx];
+            const double d = min_val - L.spc[j];
+            const int r = L.row4col[j];
+            if (r != -1) L.u[r] = L.u[r] + d;
+            L.v[j] = L.v[j] - d;
+        }
+        __syncthreads();
+        if (lane == 0) {      // augment along the path (sequential by nature; at most cur + 1 steps)
+            int j = sink;
+            while (true) {
+                const int pi = L.path[j];
+                L.row4col[j] = pi;
+                const int t = L.col4row[pi];
+                L.col4row[pi] = j;
+                j = t;
+                if (pi == cur) break;
+            }
+        }
+        __syncthreads();
+    }
+    return LSAP_OK;
+}
+
+// One n x T problem (row stride ld) as scipy treats it: invalid entries refused, transposed when n > T, result per ORIGINAL row:
+// out[r] = assigned column or -1 (out: global memory or LDS outside L).  Nothing is written unless the status is LSAP_OK.
+__device__ int lsap_problem(const double* __restrict__ cost, const long ld, const int n, const int T, const int nr_cap, const int nc_cap,
+                            const LsapLds L, int* out) {
+    const int lane = threadIdx.x;
+    if (n <= 0 || T <= 0) return LSAP_OK;
+    const bool transposed = n > T;
+    const int nr = transposed ? T : n, nc = transposed ? n : T;
+    if (nr > nr_cap || nc > nc_cap) return LSAP_TOO_LARGE;
+    int bad = 0;
+    for (long p = lane; p < (long)n * T; p += 64) {
+        const long r = p / T;
+        const double c = cost[r * ld + (p - r * T)];
+        bad |= (c != c) || (c == -__builtin_inf());
+    }
+    if (__ballot(bad) != 0ull) return LSAP_INVALID;
+    const int st = transposed ? lsap_wave(cost, 1, ld, nr, nc, L) : lsap_wave(cost, ld, 1, nr, nc, L);
+    if (st != LSAP_OK) return st;
+    const int* src = transposed ? L.row4col : L.col4row;
+    for (int r = lane; r < n; r += 64) out[r] = src[r];
+    __syncthreads();
+    return LSAP_OK;
+}
+
+__global__ __launch_bounds__(64) void lsap_batch_kernel(const double* __restrict__ cost, const long long* __restrict__ cost_offset,
+                                                        const int* __restrict__ row_stride, const int* __restrict__ n_rows,
+                                                        const int* __restrict__ n_cols, int* __restrict__ col4row,
+                                                        const long long* __restrict__ col4row_offset, int* __restrict__ status,
+                                                        int nr_cap, int nc_cap) {
+    extern __shared__ double lsap_lds[];
+    const int b = blockIdx.x;
+    const int n = n_rows[b], T = n_cols[b], ld = row_stride[b];
+    int st;
+    if (n < 0 || T < 0 || ld < T) st = LSAP_TOO_LARGE;
+    else st = lsap_problem(cost + cost_offset[b], ld, n, T, nr_cap, nc_cap, lsap_carve(lsap_lds, nr_cap, nc_cap), col4row + col4row_offset[b]);
+    if (threadIdx.x == 0) status[b] = st;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- S streams
+// Workspace (P = k * R pairs, R = rows of the pooled track table): f64 reid[P] | f64 sub[P] | f32 box[P] | int32 n[S] | col[S][k] |
+// ud[S][k] | ut[R] | tflag[R].  Stream s owns pairs k * trk_off[s] ... and rows trk_off[s] ... of ut / tflag.
+struct StreamWs {
+    double *reid, *sub;
+    float* box;
+    int *n, *col, *ud, *ut, *tflag;
+};
+__host__ __device__ inline size_t streams_ws_bytes(long S, long k, long R) { return 20ul * k * R + 4ul * (S + 2 * S * k + 2 * R); }
+__device__ __forceinline__ StreamWs streams_ws(char* ws, int S, int k, int R, int s, int t0) {
+    const long P = (long)k * R;
+    StreamWs w;
+    w.reid = reinterpret_cast<double*>(ws) + (long)k * t0;
+    w.sub = reinterpret_cast<double*>(ws) + P + (long)k * t0;
+    w.box = reinterpret_cast<float*>(ws + 16 * P) + (long)k * t0;
+    int* ints = reinterpret_cast<int*>(ws + 20 * P);
+    w.n = ints + s;
+    w.col = ints + S + (long)s * k;
+    w.ud = ints + S + (long)S * k + (long)s * k;
+    w.ut = ints + S + 2l * S * k + t0;
+    w.tflag = w.ut + R;
+    return w;
+}
+// Record of one stream: int32 header[16] | det_index[k] | (boxes[k][4] scores[k] labels[k]) | matches[k][2] | unmatched dets[k] | unmatched tracks[T]
+struct StreamRec {
+    int off_index, off_dets, off_match, off_udet, off_utrk;
+    long bytes;
+};
+__host__ __device__ inline StreamRec stream_rec(int k, int T, int with_dets) {
+    StreamRec r;
+    r.off_index = 64;
+    r.off_dets = (64 + 4 * k + 7) & ~7;
+    r.off_match = r.off_dets + (with_dets ? 24 * k : 0);
+    r.off_udet = r.off_match + 8 * k;
+    r.off_utrk = r.off_udet + 4 * k;
+    r.bytes = ((long)r.off_utrk + 4l * T + 7) & ~7l;
+    return r;
+}
+
+// grid (pair blocks of the largest stream, S_live): blockIdx.y = slot i of this step's detections, stream live[i].
+__global__ __launch_bounds__(256) void streams_costs_kernel(const float* __restrict__ det_emb, const float* __restrict__ det_box,
+                                                            const float* __restrict__ det_score, const void* __restrict__ det_label, int label_kind,
+                                                            const int* __restrict__ live, const int* __restrict__ trk_off, int S, int k, int E, float thr,
+                                                            const float* __restrict__ trk_emb, const float* __restrict__ trk_box, int R, int T_max,
+                                                            int box_mode, int reid_metric, int with_dets, char* __restrict__ ws,
+                                                            char* __restrict__ record, long record_stride) {
+    __shared__ int sel[MAXK];
+    __shared__ int wave_sum[4];
+    const int i = blockIdx.y, s = live[i];
+    if (s < 0 || s >= S) return;                                   // (refused on the host; never index with it)
+    const int t0 = trk_off[s], T = trk_off[s + 1] - t0;
+    const bool table_ok = t0 >= 0 && T >= 0 && t0 + T <= R && T <= T_max;
+    const float* de = det_emb + (long)i * k * E;
+    const float* db = det_box + (long)i * k * 4;
+    const float* dsc = det_score + (long)i * k;
+    const int n = compact_scores(dsc, k, thr, sel, wave_sum);
+    if (blockIdx.x == 0) {
+        const int tid = threadIdx.x;
+        char* rec = record + (long)s * record_stride;
+        const StreamRec ro = stream_rec(k, T_max, with_dets);
+        int* hdr = reinterpret_cast<int*>(rec);
+        if (tid == 0) {
+            hdr[0] = n; hdr[1] = k; hdr[2] = T; hdr[4] = ro.off_index; hdr[5] = ro.off_dets; hdr[6] = ro.off_match; hdr[7] = ro.off_udet;
+            hdr[8] = ro.off_utrk; hdr[13] = with_dets; hdr[14] = i; hdr[15] = s;
+            if (table_ok) *streams_ws(ws, S, k, R, s, t0).n = n;
+        }
+        int* det_index = reinterpret_cast<int*>(rec + ro.off_index);
+        for (int q = tid; q < n; q += 256) det_index[q] = sel[q];
+        if (with_dets) {
+            float* o = reinterpret_cast<float*>(rec + ro.off_dets);
+            for (int q = tid; q < 4 * k; q += 256) o[q] = db[q];
+            for (int q = tid; q < k; q += 256) o[4 * k + q] = dsc[q];
+            int* ol = reinterpret_cast<int*>(o + 5 * k);
+            for (int q = tid; q < k; q += 256)
+                ol[q] = label_kind == 1 ? (int)(reinterpret_cast<const long long*>(det_label) + (long)i * k)[q]
+                      : label_kind == 2 ? (reinterpret_cast<const int*>(det_label) + (long)i * k)[q]
+                      : label_kind == 3 ? (int)(reinterpret_cast<const float*>(det_label) + (long)i * k)[q] : 0;
+        }
+    }
+    if (!table_ok) return;
+    const StreamWs w = streams_ws(ws, S, k, R, s, t0);
+    pair_costs_at((long)blockIdx.x * 256 + threadIdx.x, sel, n, de, db, E, trk_emb + (long)t0 * E, trk_box + (long)t0 * 4, T, box_mode, reid_metric,
+                  w.reid, w.box);
+}
+
+// lanes with `flag` take consecutive positions from `count` on, in lane order (count: uniform, advanced)
+__device__ __forceinline__ int wave_pos(const bool flag, int& count) {
+    const unsigned long long m = __ballot(flag);
+    const int pos = count + __popcll(m & ((1ull << threadIdx.x) - 1ull));
+    count += __popcll(m);
+    return pos;
+}
+
+// One single-wave workgroup per live stream: both assignment stages and the lists of the stream's record.
+__global__ __launch_bounds__(64) void streams_assign_kernel(const int* __restrict__ live, const int* __restrict__ trk_off, int S, int k, int R, int T_max,
+                                                            double reid_thr, float box_thr, int box_mode, int with_dets, char* __restrict__ ws,
+                                                            char* __restrict__ record, long record_stride, int nr_cap, int nc_cap) {
+    extern __shared__ double lsap_lds[];
+    const int lane = threadIdx.x, s = live[blockIdx.x];
+    if (s < 0 || s >= S) return;
+    char* rec = record + (long)s * record_stride;
+    int* hdr = reinterpret_cast<int*>(rec);
+    const int t0 = trk_off[s], T = trk_off[s + 1] - t0;
+    int status = (t0 >= 0 && T >= 0 && t0 + T <= R) ? (T <= T_max ? LSAP_OK : LSAP_TOO_LARGE) : STREAM_BAD_TABLE;
+    const StreamRec ro = stream_rec(k, T_max, with_dets);
+    int* omatch = reinterpret_cast<int*>(rec + ro.off_match);
+    int* oud = reinterpret_cast<int*>(rec + ro.off_udet);
+    int* out = reinterpret_cast<int*>(rec + ro.off_utrk);
+    int m = 0, m1 = 0, nu = 0, tu = 0;
+    if (status == LSAP_OK) {
+        const StreamWs w = streams_ws(ws, S, k, R, s, t0);
+        const LsapLds L = lsap_carve(lsap_lds, nr_cap, nc_cap);
+        const int n = *w.n;
+        for (int t = lane; t < T; t += 64) w.tflag[t] = 0;
+        status = lsap_problem(w.reid, T, n, T, nr_cap, nc_cap, L, w.col);       // stage 1: the re-ID matrix
+        __syncthreads();
+        if (status == LSAP_OK) {
+            // matches in row order (cost < threshold: float64 against the double, as numpy compares a float64 array with a Python float)
+            for (int r0 = 0; r0 < n; r0 += 64) {
+                const int r = r0 + lane;
+                const bool in = r < n;
+                int c = -1;
+                bool keep = false;
+                if (in && T > 0) {
+                    c = w.col[r];
+                    keep = c >= 0 && w.reid[(long)r * T + c] < reid_thr;
+                }
+                const int pos = wave_pos(keep, m);
+                if (keep) { omatch[2 * pos] = r; omatch[2 * pos + 1] = c; w.tflag[c] = 1; }
+                const int pu = wave_pos(in && !keep, nu);
+                if (in && !keep) w.ud[pu] = r;
+            }
+            m1 = m;
+            __syncthreads();
+            for (int q0 = 0; q0 < T; q0 += 64) {
+                const int t = q0 + lane;
+                const bool fr = t < T && !w.tflag[t];
+                const int pos = wave_pos(fr, tu);
+                if (fr) w.ut[pos] = t;
+            }
+            __syncthreads();
+            bool stage2 = box_mode != 0 && nu > 0 && tu > 0;
+            if (stage2) {
+                // stage 2: box[np.ix_(unmatched_dets, unmatched_tracks)], which scipy converts to float64
+                for (long p = lane; p < (long)nu * tu; p += 64) {
+                    const int x = (int)(p / tu), y = (int)(p - (long)x * tu);
+                    w.sub[p] = (double)w.box[(long)w.ud[x] * T + w.ut[y]];
+                }
+                __syncthreads();
+                const int st2 = lsap_problem(w.sub, tu, nu, tu, nr_cap, nc_cap, L, w.col);
+                __syncthreads();
+                if (st2 != LSAP_OK) status = 16 + st2;
+                else {
+                    int nu2 = 0;
+                    for (int x0 = 0; x0 < nu; x0 += 64) {      // float32 cost against the threshold as float32 (numpy's weak-scalar rule)
+                        const int x = x0 + lane;
+                        const bool in = x < nu;
+                        int d = -1, t = -1;
+                        bool keep = false;
+                        if (in) {
+                            d = w.ud[x];
+                            const int c = w.col[x];
+                            if (c >= 0) { t = w.ut[c]; keep = w.box[(long)d * T + t] < box_thr; }
+                        }
+                        const int pos = wave_pos(keep, m);
+                        if (keep) { omatch[2 * pos] = d; omatch[2 * pos + 1] = t; w.tflag[t] = 1; }
+                        const int pu = wave_pos(in && !keep, nu2);
+                        if (in && !keep) oud[pu] = d;
+                    }
+                    nu = nu2;
+                }
+            } else {
+                for (int x = lane; x < nu; x += 64) oud[x] = w.ud[x];
+            }
+            __syncthreads();
+            tu = 0;
+            if (status == LSAP_OK)
+                for (int q0 = 0; q0 < T; q0 += 64) {
+                    const int t = q0 + lane;
+                    const bool fr = t < T && !w.tflag[t];
+                    const int pos = wave_pos(fr, tu);
+                    if (fr) out[pos] = t;
+                }
+        }
+    }
+    if (lane == 0) {
+        const bool ok = status == LSAP_OK;
+        hdr[3] = status; hdr[9] = ok ? m : 0; hdr[10] = ok ? m1 : 0; hdr[11] = ok ? nu : 0; hdr[12] = ok ? tu : 0;
+    }
+}
+
+static cnl::DeviceOnce lsap_once, assign_once;
+constexpr int LSAP_LDS_MAX = 12 * LSAP_MAX_SHORT + 28 * LSAP_MAX_LONG;      // 126976 of the CU's 160 KiB
+
+}  // namespace cnl_track
+using namespace cnl_track;
+
+extern "C" int cnl_lsap_batch_f64(const double* cost, const int64_t* cost_offset, const int32_t* row_stride, const int32_t* n_rows,
+                                  const int32_t* n_cols, int32_t B, int32_t max_rows, int32_t max_cols, int32_t* col4row,
+                                  const int64_t* col4row_offset, int32_t* status, void* stream) {
+    CNL_REQUIRE(B >= 0 && max_rows >= 0 && max_cols >= 0, CNL_E_BAD_ARG, "cnl_lsap_batch_f64: negative B / max_rows / max_cols");
+    if (B == 0) return CNL_OK;
+    CNL_REQUIRE(cost && cost_offset && row_stride && n_rows && n_cols && col4row && col4row_offset && status, CNL_E_BAD_ARG,
+                "cnl_lsap_batch_f64: null pointer");
+    const int lo = max_rows < max_cols ? max_rows : max_cols, hi = max_rows < max_cols ? max_cols : max_rows;
+    CNL_REQUIRE(lo <= LSAP_MAX_SHORT && hi <= LSAP_MAX_LONG, CNL_E_UNSUPPORTED,
+                "cnl_lsap_batch_f64: problems of up to %d x %d: min(rows, cols) <= %d and max(rows, cols) <= %d are supported", max_rows, max_cols,
+                LSAP_MAX_SHORT, LSAP_MAX_LONG);
+    const int nr_cap = lo > 0 ? lo : 1, nc_cap = hi > 0 ? hi : 1;
+    if (int rc = cnl::kernel_setup(lsap_once, (const void*)lsap_batch_kernel, LSAP_LDS_MAX)) return rc;
+    hipLaunchKernelGGL(lsap_batch_kernel, dim3((unsigned)B), dim3(64), lsap_lds_bytes(nr_cap, nc_cap), (hipStream_t)stream, cost,
+                       (const long long*)cost_offset, row_stride, n_rows, n_cols, col4row, (const long long*)col4row_offset, status, nr_cap, nc_cap);
+    return cnl::check_launch("lsap_batch_kernel");
+}
+
+extern "C" int64_t cnl_track_streams_workspace_bytes(int32_t S, int32_t k, int32_t T_max) {
+    if (S <= 0 || k <= 0 || T_max < 0) return 0;
+    return (int64_t)streams_ws_bytes(S, k, (long)S * T_max);
+}
+
+extern "C" int64_t cnl_track_streams_record_bytes(int32_t k, int32_t T_max, int32_t with_detections) {
+    if (k <= 0 || T_max < 0) return 0;
+    return stream_rec(k, T_max, with_detections ? 1 : 0).bytes;
+}
+
+extern "C" int cnl_track_streams_f32(const float* det_emb, const float* det_box, const float* det_score, const void* det_label, int32_t label_kind,
+                                     int32_t S, int32_t S_live, const int32_t* live, int32_t k, int32_t E, float detection_threshold,
+                                     double reid_threshold, float box_threshold, const float* trk_emb, const float* trk_box,
+                                     const int32_t* trk_off, int32_t R, int32_t T_max, int32_t box_cost, int32_t reid_metric,
+                                     int32_t with_detections, void* workspace, int64_t workspace_bytes, void* record, int64_t record_stride,
+                                     void* stream) {
+    CNL_REQUIRE(det_emb && det_box && det_score && live && trk_off && workspace && record, CNL_E_BAD_ARG, "cnl_track_streams_f32: null pointer");
+    CNL_REQUIRE(S > 0 && S_live > 0 && S_live <= S && k > 0 && E > 0 && R >= 0 && T_max >= 0, CNL_E_BAD_ARG,
+                "cnl_track_streams_f32: bad S / S_live / k / E / R / T_max (%d / %d / %d / %d / %d / %d)", S, S_live, k, E, R, T_max);
+    CNL_REQUIRE(k <= MAXK, CNL_E_UNSUPPORTED, "cnl_track_streams_f32: k = %d > %d detections per frame", k, MAXK);
+    CNL_REQUIRE(T_max <= LSAP_MAX_LONG, CNL_E_UNSUPPORTED, "cnl_track_streams_f32: T_max = %d > %d tracks per stream", T_max, LSAP_MAX_LONG);
+    CNL_REQUIRE(S_live <= 65535, CNL_E_UNSUPPORTED, "cnl_track_streams_f32: S_live = %d > 65535 streams per step", S_live);
+    CNL_REQUIRE(box_cost >= 0 && box_cost <= 2, CNL_E_BAD_ARG, "cnl_track_streams_f32: box_cost must be 0 (none), 1 (iou), 2 (giou)");
+    CNL_REQUIRE(reid_metric >= 0 && reid_metric <= 7, CNL_E_BAD_ARG, "cnl_track_streams_f32: reid_metric must be 0 (cosine) .. 7 (correlation)");
+    CNL_REQUIRE(label_kind >= 0 && label_kind <= 3 && (label_kind == 0 || det_label), CNL_E_BAD_ARG,
+                "cnl_track_streams_f32: label_kind must be 0 (none), 1 (int64), 2 (int32), 3 (float32) with det_label set");
+    CNL_REQUIRE(R == 0 || trk_emb, CNL_E_BAD_ARG, "cnl_track_streams_f32: R > 0 without track table");
+    CNL_REQUIRE(R == 0 || box_cost == 0 || trk_box, CNL_E_BAD_ARG, "cnl_track_streams_f32: box cost requested without track boxes");
+    CNL_REQUIRE(((uintptr_t)record & 7) == 0 && ((uintptr_t)workspace & 7) == 0 && (record_stride & 7) == 0, CNL_E_BAD_ARG,
+                "cnl_track_streams_f32: record, record_stride and workspace must be 8-byte aligned");
+    const int wd = with_detections ? 1 : 0;
+    const int64_t rec_need = stream_rec(k, T_max, wd).bytes, ws_need = (int64_t)streams_ws_bytes(S, k, R);
+    CNL_REQUIRE(record_stride >= rec_need, CNL_E_BAD_ARG, "cnl_track_streams_f32: record_stride %ld, k = %d, T_max = %d needs %ld (cnl_track_streams_record_bytes)",
+                (long)record_stride, k, T_max, (long)rec_need);
+    CNL_REQUIRE(workspace_bytes >= ws_need, CNL_E_BAD_ARG, "cnl_track_streams_f32: workspace holds %ld bytes, S = %d, k = %d, R = %d needs %ld",
+                (long)workspace_bytes, S, k, R, (long)ws_need);
+    const int lo = k < T_max ? k : T_max, hi = k < T_max ? T_max : k;
+    const int nr_cap = lo > 0 ? lo : 1, nc_cap = hi;
+    if (int rc = cnl::kernel_setup(assign_once, (const void*)streams_assign_kernel, LSAP_LDS_MAX)) return rc;
+    const long pairs = (long)k * T_max;
+    const unsigned gx = (unsigned)(pairs > 0 ? (pairs + 255) / 256 : 1);
+    hipLaunchKernelGGL(streams_costs_kernel, dim3(gx, (unsigned)S_live), dim3(256), 0, (hipStream_t)stream, det_emb, det_box, det_score, det_label,
+                       label_kind, live, trk_off, S, k, E, detection_threshold, trk_emb, trk_box, R, T_max, box_cost, reid_metric, wd, (char*)workspace,
+                       (char*)record, (long)record_stride);
+    if (int rc = cnl::check_launch("track streams_costs_kernel")) return rc;
+    hipLaunchKernelGGL(streams_assign_kernel, dim3((unsigned)S_live), dim3(64), lsap_lds_bytes(nr_cap, nc_cap), (hipStream_t)stream, live, trk_off, S, k, R,
+                       T_max, reid_threshold, box_threshold, box_cost, wd, (char*)workspace, (char*)record, (long)record_stride, nr_cap, nc_cap);
+    return cnl::check_launch("track streams_assign_kernel");
+}

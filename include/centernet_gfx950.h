@@ -528,6 +528,60 @@ int cnl_track_apply_f32(const float* trk_emb, const float* trk_box, const float*
                         float* new_emb, float* new_box, void* stream);
 
 /*
+ * Many video streams per step, assignment on the device (csrc/track_streams.hip).  The unit of work is ONE FRAME FROM EACH of S_live
+ * streams: the association of every stream, Hungarian step included, in one pass of two back-to-back launches on `stream`; the host
+ * synchronises once and reads the match lists.  No cost matrix crosses PCIe.
+ *
+ * Batched rectangular assignment: B independent problems in one launch, one single-wave workgroup each.  Problem b is the n_rows[b] x n_cols[b]
+ * float64 matrix at cost + cost_offset[b] (elements) with row stride row_stride[b] >= n_cols[b]; all five arrays are device memory.
+ * col4row + col4row_offset[b] receives n_rows[b] int32: the column assigned to each row, or -1 (rows > cols).  The result is EXACTLY
+ * scipy.optimize.linear_sum_assignment's, ties included (same algorithm, order and float64 arithmetic: rectangular shortest augmenting
+ * path, transposed when rows > cols).  status[b]: 0 ok; 1 a NaN or -inf entry; 2 infeasible (scipy raises ValueError in both cases);
+ * 3 larger than max_rows x max_cols (or a negative size / row_stride < cols) — nothing is written to col4row unless the status is 0.
+ * max_rows / max_cols bound every problem of the launch and size the workgroup's LDS (12 B per min-side row + 28 B per max-side column):
+ * min(max_rows, max_cols) <= 1024 and max(max_rows, max_cols) <= 4096, else CNL_E_UNSUPPORTED.
+ */
+int cnl_lsap_batch_f64(const double* cost, const int64_t* cost_offset, const int32_t* row_stride, const int32_t* n_rows, const int32_t* n_cols,
+                       int32_t B, int32_t max_rows, int32_t max_cols, int32_t* col4row, const int64_t* col4row_offset, int32_t* status,
+                       void* stream);
+/*
+ * One association pass for S streams.  This step's detections of the S_live <= S participating streams are det_emb [S_live,k,E],
+ * det_box [S_live,k,4], det_score [S_live,k], det_label [S_live,k] (label_kind as cnl_track_frame_f32): slot i belongs to stream live[i]
+ * (int32, distinct, 0 <= live[i] < S).  ONE pooled track table trk_emb [R,E], trk_box [R,4]: stream s owns rows trk_off[s] .. trk_off[s+1]
+ * (int32 [S+1], ascending, trk_off[S] <= R; no stream has more than T_max <= 4096 rows).  live and trk_off may be cnl_host_alloc memory.
+ * Per live stream, what the single-stream path does between cnl_track_frame_f32 and cnl_track_apply_f32:
+ *   1. compaction score >= detection_threshold and the n x T cost matrices (re-ID float64, box float32) by the device code of
+ *      cnl_track_frame_f32 (bit-identical matrices), into the workspace;
+ *   2. stage 1: assignment on the re-ID matrix, pairs with cost < reid_threshold kept (float64 compare);
+ *   3. stage 2 (box_cost != 0): assignment on the box-cost sub-matrix of the still-unmatched detections x still-unmatched tracks (both
+ *      ascending; converted to float64 as scipy does), pairs with cost < box_threshold kept (float32 compare);
+ *   4. the stream's record at record + live[i] * record_stride (8-byte aligned; cnl_host_alloc memory or device memory):
+ *        int32 header[16] = { n, k, T, status, off_index, off_dets, off_match, off_udet, off_utrk, n_match, n_match_stage1, n_udet,
+ *                             n_utrk, with_detections, slot i, stream }        (byte offsets into the record)
+ *        int32 det_index[k]                                at off_index  (first n valid: original indices of the kept detections)
+ *        f32 boxes[k][4], f32 scores[k], int32 labels[k]   at off_dets   (with_detections != 0 only)
+ *        int32 matches[n_match][2] = (detection row, track)   at off_match: stage 1 in row order, then stage 2 in row order — the order
+ *                                                             tracker.py's match_with_threshold yields; rows index det_index, tracks the stream's rows
+ *        int32 unmatched detection rows[n_udet], ascending  at off_udet;   int32 unmatched tracks[n_utrk], ascending  at off_utrk
+ *      status: 0 ok; 1 / 2 / 3 as cnl_lsap_batch_f64 for stage 1, 17 / 18 / 19 for stage 2; 4 trk_off inconsistent with R.  With a status
+ *      set the lists are not valid (a non-finite cost, e.g. a zero embedding under "cosine": scipy raises there — the caller redoes that
+ *      stream through the single-stream path).
+ * cnl_track_streams_record_bytes(k, T_max, with_detections) is the smallest record_stride; cnl_track_streams_workspace_bytes(S, k, T_max)
+ * bounds the device workspace (20 bytes per pair of the pooled table, k * R pairs, R <= S * T_max, plus the index lists); the sections of
+ * stream s start at k * trk_off[s] pairs.
+ * The table update needs no new kernel: cnl_track_apply_f32 does the pooled update when the index lists are global — src_trk[r] = row of
+ * the OLD pooled table, src_det[r] = i * k + d for detection d of slot i, T_new = total rows of all streams; a stream that takes no part in
+ * the step keeps its rows (src_det = -1).
+ */
+int64_t cnl_track_streams_workspace_bytes(int32_t S, int32_t k, int32_t T_max);
+int64_t cnl_track_streams_record_bytes(int32_t k, int32_t T_max, int32_t with_detections);
+int cnl_track_streams_f32(const float* det_emb, const float* det_box, const float* det_score, const void* det_label, int32_t label_kind,
+                          int32_t S, int32_t S_live, const int32_t* live, int32_t k, int32_t E, float detection_threshold,
+                          double reid_threshold, float box_threshold, const float* trk_emb, const float* trk_box, const int32_t* trk_off,
+                          int32_t R, int32_t T_max, int32_t box_cost, int32_t reid_metric, int32_t with_detections, void* workspace,
+                          int64_t workspace_bytes, void* record, int64_t record_stride, void* stream);
+
+/*
  * Wire formats: COCO boxes are xywh — torchvision box_convert(boxes, "xyxy", "xywh") of
  * CenterNet.validation_step (models/centernet.py:207): out[i] = (x1, y1, x2 - x1, y2 - y1); n boxes of 4 floats, may be in place.
  */
