@@ -1,12 +1,11 @@
 // Shared by conv_mfma.hip (fp32 matrix cores) and conv_f16x2.hip (fp16 matrix cores, split operands): launch arguments, tile
 // configuration and the buffer / LDS-DMA helpers of the direct implicit-GEMM convolution.
 #pragma once
-#include "cnl_common.h"
+#include "cnl_device.h"
 
 namespace cnl_conv {
+using namespace cnl_dev;
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 struct ConvArgs {
     const float* x;
@@ -40,7 +39,6 @@ struct ConvArgs {
 };
 
 constexpr unsigned CNL_I_SUBPIXEL = 1u << 16;   // internal: y[n, 2oy+sub_dy, 2ox+sub_dx, :] = act(conv + bias) (+ residual there)
-constexpr unsigned OOB = 0xFFFFFFF0u;   // voffset that is always >= num_records -> DMA writes zeros / store dropped
 
 template <int WM, int WN, int TM, int TN>
 struct Cfg {
@@ -56,22 +54,7 @@ struct Cfg {
     static_assert(BM % (NW * 8) == 0 && BN % (NW * 8) == 0, "tile rows must split evenly over waves");
 };
 
-typedef __attribute__((address_space(3))) void lds_void;
 
-// amdgcn builtins are wrapped in NON-template device functions: called with template-dependent arguments
-// directly inside the kernel template they make hipcc's host pass silently drop the kernel's host stub.
-__device__ __forceinline__ void dma16(const float* base, unsigned bytes, char* lds_dst, unsigned voffset, unsigned soffset) {
-    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)bytes, 0x00020000);
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void*)lds_dst, 16, voffset, soffset, 0, 0);
-}
-__device__ __forceinline__ float buf_load(const float* base, unsigned bytes, unsigned voffset, unsigned soffset) {
-    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)bytes, 0x00020000);
-    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc, voffset, soffset, 0));
-}
-__device__ __forceinline__ void buf_store(float v, float* base, unsigned bytes, unsigned voffset, unsigned soffset) {
-    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)bytes, 0x00020000);
-    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rsrc, voffset, soffset, CNL_NT_STORES);
-}
 __device__ __forceinline__ f32x4 buf_load4(const float* base, unsigned bytes, unsigned voffset, unsigned soffset) {
     const auto rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)bytes, 0x00020000);
     return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, voffset, soffset, 0));

@@ -20,48 +20,7 @@
 
 namespace cnl_conv {
 
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
-__device__ __forceinline__ f32x16 mfma16(u32x4 a, u32x4 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
-__device__ __forceinline__ f32x16 mfma16_zero() {
-    const f32x16 z = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    const u32x4 zz = {0u, 0u, 0u, 0u};
-    return mfma16(zz, zz, z);
-}
-// (v0, v1) S -> hi pair (RN16, packed) and lo pair (RZ16 of the exact residuals, packed).  Plain C on purpose: the compiler folds it
-// into v_fma_mixlo/mixhi_f16, v_fma_mix_f32 and v_cvt_pkrtz_f16_f32, and — unlike with inline asm — its hazard recognizer then sees
-// VALU instructions and keeps the two wait states gfx950 needs between a VALU write and an MFMA reading that register.
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void split2(float v0, float v1, float S, unsigned& hi, unsigned& lo) {
-    const _Float16 h0 = (_Float16)__builtin_fmaf(v0, S, 0.f), h1 = (_Float16)__builtin_fmaf(v1, S, 0.f);
-    const float r0 = __builtin_fmaf(v0, S, -(float)h0), r1 = __builtin_fmaf(v1, S, -(float)h1);
-    const f16x2 hv = {h0, h1};
-    hi = __builtin_bit_cast(unsigned, hv);
-    lo = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(r0, r1));
-}
-__device__ __forceinline__ void split8(const f32x4& v0, const f32x4& v1, float S, u32x4& hi, u32x4& lo) {
-    unsigned h[4], l[4];
-    split2(v0[0], v0[1], S, h[0], l[0]);
-    split2(v0[2], v0[3], S, h[1], l[1]);
-    split2(v1[0], v1[1], S, h[2], l[2]);
-    split2(v1[2], v1[3], S, h[3], l[3]);
-    hi = u32x4{h[0], h[1], h[2], h[3]};
-    lo = u32x4{l[0], l[1], l[2], l[3]};
-}
-// the power of two that puts a tensor of maximum magnitude mx into [2^13, 2^14)  (1 for 0 / Inf / NaN maxima)
-__device__ __forceinline__ float pow2_scale(float mx) {
-    float S = 1.f;
-    if (mx > 0.f && mx < __builtin_inff()) {
-        int e;
-        (void)__builtin_frexpf(mx, &e);            // 2^(e-1) <= mx < 2^e
-        e = 14 - e;
-        S = __builtin_ldexpf(1.f, e < -60 ? -60 : (e > 60 ? 60 : e));
-    }
-    return S;
-}
 
 // KS: compile-time square kernel size (1, 2 or 3).  SUB: the launch is one sub-pixel phase of a conv on the nearest-2x upsampled input
 // (cnl_conv3x3_up2_nhwc_f32): row m = (n, oy, ox) is stored at pixel (2 oy + sub_dy, 2 ox + sub_dx) of the 2x output grid; pad (rows)
@@ -178,7 +137,7 @@ __global__ __launch_bounds__(256, 2) void conv_f16x2_kernel(const ConvArgs a) {
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
-        for (int j = 0; j < TN; ++j) acc[i][j] = mfma16_zero();
+        for (int j = 0; j < TN; ++j) acc[i][j] = mfma_zero();
 
     // fragment read addresses (bytes inside a stage): row * 128 + ((2*jj + hi) ^ swz) * 16
     const int swz = (lane >> 1) & 7;

@@ -17,13 +17,12 @@
 // image (row stride 65 keeps both the transposing write and the fragment reads bank-conflict-free); the first
 // version read it with a 147-float stride per lane and spent 3/4 of its time there.
 // The input is read through explicit element strides, so NCHW and channels_last callers are zero-copy.
-#include "cnl_common.h"
+#include "cnl_device.h"
 #include <cstdlib>
 
 namespace cnl_stem {
+using namespace cnl_dev;
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int ST_TH = 16, ST_TW = 32;                 // output tile (4 rows per wave)
 constexpr int ST_PR = 2 * ST_TH + 5;                  // patch rows
@@ -35,14 +34,9 @@ constexpr int ST_W_BYTES = ST_KP * 64 * 4;            // 39424 = 38.5 x 1 KB (th
 constexpr int ST_LDS_BYTES = ST_PR * ST_RS * 4 + 39 * 1024;    // 77824 -> 2 workgroups / CU
 constexpr unsigned ST_OOB = 0xFFFFFFF0u;
 
-typedef __attribute__((address_space(3))) void lds_void;
 __device__ __forceinline__ void dma4(const float* base, unsigned bytes, float* lds_dst, unsigned voffset) {
     const auto rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)bytes, 0x00020000);
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void*)lds_dst, 4, voffset, 0, 0, 0);
-}
-__device__ __forceinline__ void dma16(const float* base, unsigned bytes, char* lds_dst, unsigned voffset) {
-    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)bytes, 0x00020000);
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void*)lds_dst, 16, voffset, 0, 0, 0);
 }
 
 __global__ __launch_bounds__(256, 2) void stem_conv_kernel(const float* __restrict__ x, long sn, int sc, int sh, int sw,
@@ -66,7 +60,7 @@ __global__ __launch_bounds__(256, 2) void stem_conv_kernel(const float* __restri
     // ---- staging by LDS-DMA: no VGPR round trip and almost no VALU (this runs beside the co-resident group's MFMA stream) ----
     // weights: 39 pieces of 1 KB, lane-linear
     for (int q = wave; q < (ST_W_BYTES + 1023) / 1024; q += 4)
-        dma16(w, (unsigned)ST_W_BYTES, reinterpret_cast<char*>(wl) + q * 1024, (unsigned)(q * 1024 + lane * 16));
+        dma16(w, (unsigned)ST_W_BYTES, reinterpret_cast<char*>(wl) + q * 1024, (unsigned)(q * 1024 + lane * 16), 0);
     // input patch -> LDS [row][col*3 + c]: 4-byte DMA, lane f of a row fetches pixel col = f/3, channel c = f%3 from wherever
     // the caller's strides put it (NCHW planes or channels_last alike); out-of-image lanes get zeros from the bounds check
     const float* xn = x + (long)n * sn;

@@ -16,14 +16,11 @@
 // MFMA in registers: each patch element ~8 times, 10.6 VALU per MFMA — the loop was VALU-bound, 120 of the kernel's 216 us.)  The split
 // weights sit in LDS as [piece][group][cout][8] so a lane's operand is one ds_read_b128.  Per step and wave: 4 rows x 2 cout groups x 3
 // MFMAs of 32 cycles.
-#include "cnl_common.h"
+#include "cnl_device.h"
 
 namespace cnl_stem5 {
+using namespace cnl_dev;
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 #ifndef S5_NW
 #define S5_NW 4       /* waves per workgroup (A/B build: make variant TAG=s5nw8 EXTRA=-DS5_NW=8) */
@@ -45,9 +42,7 @@ constexpr int PLANE_BYTES = PR * RS * 2;              // 18944
 constexpr int NT = 64 * NW;                           // threads per workgroup
 constexpr int SCAN_IT = (PR * (RS / 4) + NT - 1) / NT; // float4 per thread (5; NW = 4: 10)
 constexpr int LDS_BYTES = PATCH_BYTES + W_BYTES + 64; // 80960 -> 2 workgroups / CU
-constexpr unsigned OOB = 0xFFFFFFF0u;
 
-typedef __attribute__((address_space(3))) void lds_void;
 __device__ __forceinline__ void dma4(const float* base, unsigned bytes, float* lds_dst, unsigned voffset) {
     const auto rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)bytes, 0x00020000);
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void*)lds_dst, 4, voffset, 0, 0, 0);
@@ -56,35 +51,6 @@ __device__ __forceinline__ void dma4(const float* base, unsigned bytes, float* l
 __device__ __forceinline__ void dma1(const void* base, unsigned bytes, float* lds_dst, unsigned voffset) {
     const auto rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)bytes, 0x00020000);
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void*)lds_dst, 1, voffset, 0, 0, 0);
-}
-__device__ __forceinline__ void dma16(const void* base, unsigned bytes, char* lds_dst, unsigned voffset) {
-    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)bytes, 0x00020000);
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void*)lds_dst, 16, voffset, 0, 0, 0);
-}
-__device__ __forceinline__ f32x16 mfma16(u32x4 a, u32x4 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
-// (v0, v1) S -> hi pair (RN16, packed) and lo pair (RZ16 of the exact residuals, packed).  Plain C on purpose (the compiler folds it
-// into v_fma_mixlo/mixhi_f16, v_fma_mix_f32, v_cvt_pkrtz): with inline asm the hazard recognizer does not see VALU instructions,
-// and this kernel reuses an MFMA's operand registers for the next row's split a few instructions after the MFMA issues.
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void split2(float v0, float v1, float S, unsigned& hi, unsigned& lo) {
-    const _Float16 h0 = (_Float16)__builtin_fmaf(v0, S, 0.f), h1 = (_Float16)__builtin_fmaf(v1, S, 0.f);
-    const float r0 = __builtin_fmaf(v0, S, -(float)h0), r1 = __builtin_fmaf(v1, S, -(float)h1);
-    const f16x2 hv = {h0, h1};
-    hi = __builtin_bit_cast(unsigned, hv);
-    lo = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(r0, r1));
-}
-// the power of two that puts a tensor of maximum magnitude mx into [2^13, 2^14)  (1 for 0 / Inf / NaN maxima)
-__device__ __forceinline__ float pow2_scale(float mx) {
-    float S = 1.f;
-    if (mx > 0.f && mx < __builtin_inff()) {
-        int e;
-        (void)__builtin_frexpf(mx, &e);
-        e = 14 - e;
-        S = __builtin_ldexpf(1.f, e < -60 ? -60 : (e > 60 ? 60 : e));
-    }
-    return S;
 }
 
 // w_split: [piece][group][cout][8] fp16 (W_BYTES), scal[0] = S_w.
@@ -137,7 +103,7 @@ __global__ __launch_bounds__(NT, NW / 2) void stem_f16x2_kernel(const void* __re
 #define S5_EXP 0        // timing builds (results wrong): 1 no patch DMA, 2 no weight DMA, 3 one K step, 4 no stores, 5 no patch scan, 6 / 7 border cells of the pooled map stored plainly / not at all
 #endif
     if (S5_EXP != 2)
-    for (int q = wave; q < W_BYTES / 1024; q += NW) dma16(w_split, (unsigned)W_BYTES, wl + q * 1024, (unsigned)(q * 1024 + lane * 16));
+    for (int q = wave; q < W_BYTES / 1024; q += NW) dma16(w_split, (unsigned)W_BYTES, wl + q * 1024, (unsigned)(q * 1024 + lane * 16), 0);
     constexpr int ES = U8 ? 1 : 4;                                             // bytes per input element
     const char* xn = reinterpret_cast<const char*>(x) + (long)n * sn * ES;
     unsigned lane_off[4];

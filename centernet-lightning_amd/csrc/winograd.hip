@@ -17,6 +17,7 @@
 // The 16x16-pixel-block fp32 kernel this file used to hold, the exact three-way bf16 split (winograd3/4) and the two-waves-per-SIMD
 // form of 5 (winograd7) are measured-and-superseded variants: tools/experiments/ (`make -C csrc experiments`, algo = CNL_ALGO_FORCE + variant).
 #include "cnl_common.h"
+#include "winograd_internal.h"
 #ifdef CNL_W9_VGPR_SPILLS_OVERRIDE      /* `make variant`: the spill count of THAT build's winograd9.hip */
 #define CNL_W9_VGPR_SPILLS CNL_W9_VGPR_SPILLS_OVERRIDE
 #elif __has_include("build/w9_usage.h")
@@ -57,41 +58,6 @@ __global__ __launch_bounds__(256) void winograd_weights_kernel(const float* __re
 
 }  // namespace cnl_wino
 using namespace cnl_wino;
-
-int cnl_wino2_launch(const cnl_conv_params* p, size_t u_floats, void* stream);     // winograd2.hip
-size_t cnl_wino5_weight_bytes(int Cin, int Cout);                                  // winograd5.hip
-size_t cnl_wino5_scalar_floats();
-int cnl_wino5_transform_weights(const float* w_ohwi, const float* u_f32, size_t u_f32_floats, void* u5, float* scal, int Cin, int Cout, void* stream);
-int cnl_wino5_own_absmax(const cnl_conv_params* p, float* scal, void* stream);
-int cnl_wino5_launch(const cnl_conv_params* p, const void* u5, float* scal, void* stream);
-int cnl_wino6_launch(const cnl_conv_params* p, const void* u5, float* scal, void* stream);        // winograd6.hip
-size_t cnl_wino9_weight_bytes(int Cin, int Cout);                                  // winograd9.hip
-size_t cnl_wino9_scalar_floats(int Cin, int Cout);
-int cnl_wino9_transform_weights(const float* w_ohwi, void* u9, float* isu, int Cin, int Cout, void* stream);
-bool cnl_wino9_eligible(const cnl_conv_params* p);
-size_t cnl_wino9_up_weight_bytes(int Cin, int Cout);                               // the row-pair weight sets of a conv behind a folded upsample (cnl_conv_params.w_up)
-int cnl_wino9_up_transform_weights(const float* w_ohwi, void* u9, float* isu, int Cin, int Cout, void* stream);
-int cnl_wino9_launch(const cnl_conv_params* p, const void* u9, const float* isu, const float* xmax, void* stream);
-int cnl_wino_packed_stride(const cnl_conv_params* p);                               // packed rows of the row kernels (winograd9.hip)
-bool cnl_wino10_eligible(const cnl_conv_params* p);                                // winograd10.hip (reads winograd9.hip's weights)
-size_t cnl_wino13_weight_bytes(int Cin, int Cout);                                 // winograd13.hip: F(4,3) along x (weights of its own: six transform positions)
-size_t cnl_wino13_scalar_floats(int Cin, int Cout);
-int cnl_wino13_transform_weights(const float* w_ohwi, void* u13, float* isu, int Cin, int Cout, void* stream);
-bool cnl_wino13_eligible(const cnl_conv_params* p);
-int cnl_wino13_launch(const cnl_conv_params* p, const void* u13, const float* isu, const float* xmax, void* stream);
-int cnl_wino10_launch(const cnl_conv_params* p, const void* u9, const float* isu, const float* xmax, bool cout32, void* stream);
-#ifdef CNL_EXPERIMENTS
-bool cnl_wino12_eligible(const cnl_conv_params* p);                                // tools/experiments/winograd12.hip (round 5: Cin = 64, the epilogue rides in the next item's chunks)
-int cnl_wino12_launch(const cnl_conv_params* p, const void* u9, const float* isu, const float* xmax, void* stream);
-int cnl_wino1_launch(const cnl_conv_params* p, void* stream);                       // tools/experiments/winograd1.hip
-size_t cnl_wino3_weight_bytes(int Cin, int Cout);                                  // tools/experiments/winograd3.hip
-int cnl_wino3_transform_weights(const float* w_ohwi, void* u3, int Cin, int Cout, void* stream);
-int cnl_wino3_launch(const cnl_conv_params* p, const void* u3, void* stream);
-int cnl_wino4_launch(const cnl_conv_params* p, const void* u3, void* stream);        // tools/experiments/winograd4.hip
-int cnl_wino7_launch(const cnl_conv_params* p, const void* u5, float* scal, void* stream);        // tools/experiments/winograd7.hip
-#else
-static size_t cnl_wino3_weight_bytes(int, int) { return 0; }
-#endif
 
 // Layout of the transformed-weight buffer (floats): [fp32 U = [ci/8][16][CoutP][8]] [experiment builds: bf16 x 3 pieces]
 // [fp16 x 2 pieces of F(2x2)] [its scalars] [fp16 x 2 pieces of the row-Winograd kernel] [its per-cout scales] [fp16 x 2 pieces of the F(4,3) row

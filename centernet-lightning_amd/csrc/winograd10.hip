@@ -28,18 +28,15 @@
 //   THIS chunk is loaded in slices 0..3 (first use: slice 30);
 //   the patch of chunk n + 2 travels global -> 4 staging registers -> LDS in two halves (rows 0..2 + the two last pixel columns, rows
 //   3..5); one barrier per chunk (slice 40).
-#include "cnl_common.h"
+#include "cnl_device.h"
+#include "winograd_internal.h"
 #include <utility>
 
 #pragma clang fp contract(off)
 
 namespace cnl_wino10 {
+using namespace cnl_dev;
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 struct Args {
     const float* x;
@@ -73,7 +70,6 @@ struct Args {
 #define W10_STAMP(i_) do {} while (0)
 #endif
 
-constexpr unsigned OOB = 0xFFFFFFF0u;
 constexpr int R = 4;                        // output rows per work item
 constexpr int PR = R + 2;                   // patch rows
 constexpr int TW = 32;                      // tiles (pixel pairs) per row of a work item: 64 output pixels
@@ -92,44 +88,6 @@ constexpr int JOB0 = 6, JOB_SLICES = 12;    // job j: slices [JOB0 + 12 j, JOB0 
 constexpr int BARRIER_SLICE = 40;
 constexpr int NSTG = 4;
 
-__device__ __forceinline__ u32x4 buf_load16(const void* base, unsigned bytes, unsigned voffset, unsigned soffset) {
-    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)bytes, 0x00020000);
-    return (u32x4)__builtin_amdgcn_raw_buffer_load_b128(rsrc, voffset, soffset, 0);
-}
-__device__ __forceinline__ void buf_store16(f32x4 v, float* base, unsigned bytes, unsigned voffset, unsigned soffset) {
-    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)bytes, 0x00020000);
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rsrc, voffset, soffset, CNL_NT_STORES);
-}
-__device__ __forceinline__ f32x16 mfma16(u32x4 a, u32x4 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
-// the split of a channel pair (v0, v1), scaled by the power of two S:  hi = RN16(v S) packed, r = v S - hi exactly (winograd5.hip)
-__device__ __forceinline__ unsigned split_hi_lo(float v0, float S) {
-    unsigned pk;
-    asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(pk) : "v"(v0), "v"(S));
-    return pk;
-}
-__device__ __forceinline__ unsigned split_hi_hi(unsigned pk, float v1, float S) {
-    asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(pk) : "v"(v1), "v"(S));
-    return pk;
-}
-__device__ __forceinline__ float split_res_lo(float v, float S, unsigned pk) {
-    float r;
-    asm("v_fma_mix_f32 %0, %1, %2, -%3 op_sel_hi:[0,0,1]" : "=v"(r) : "v"(v), "v"(S), "v"(pk));
-    return r;
-}
-__device__ __forceinline__ float split_res_hi(float v, float S, unsigned pk) {
-    float r;
-    asm("v_fma_mix_f32 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "=v"(r) : "v"(v), "v"(S), "v"(pk));
-    return r;
-}
-__device__ __forceinline__ int lane_now() {
-    unsigned z = 0;
-    asm volatile("" : "+v"(z));
-    return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, z));
-}
-__device__ __forceinline__ f32x4 lds_f4(const char* p) { return *reinterpret_cast<const f32x4*>(p); }
-#define W10_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 
 // ---- the static schedule of a chunk -----------------------------------------------------------------------------------------
 constexpr int NSEG = 12;
@@ -234,7 +192,7 @@ __device__ __forceinline__ void slice(State<NBH>& st, const Args& a, const int c
     constexpr int vbuf = r % 3;
     if constexpr (S == BARRIER_SLICE) {
         // every wave is done reading this chunk's patch, and the next chunk's (written since the previous barrier) is complete
-        W10_BARRIER();
+        CNL_BARRIER();
         __builtin_amdgcn_sched_barrier(0);
     }
     if constexpr (nbh < NBH) {       // (32-cout items: the odd slices carry no MFMA — the chunk keeps its 72 issue slots for the V jobs, loads and staging)
@@ -478,7 +436,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 W10_SCALE_EXP(es_cur, xmax_cur);
                 st.cur.S = __builtin_ldexpf(1.f, es_cur);
             }
-            W10_BARRIER();                  // the previous item's last exchange pass has been read by every wave: the region is free
+            CNL_BARRIER();                  // the previous item's last exchange pass has been read by every wave: the region is free
             W10_STAMP(2);
 #pragma unroll
             for (int i = 0; i < NSTG; ++i) st.stg[i] = keep[0][i];
@@ -493,7 +451,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             for (int i = 0; i < 3; ++i) st.stg[i] = keep[3][i];
             pwrite<1, 0>(st, 1); pwrite<1, 1>(st, 1); pwrite<1, 2>(st, 1);
         }
-        W10_BARRIER();
+        CNL_BARRIER();
         W10_STAMP(3);
         rread<0>(st, 0, 0); rread<1>(st, 0, 0); rread<2>(st, 0, 0); rread<3>(st, 0, 0);
         job_all(st, 0, std::make_integer_sequence<int, 28>{});
@@ -511,7 +469,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             chunk<1, false, NBH>(st, a, cn + 1, up, u_plane, u_wave);
         }
         W10_STAMP(5);
-        W10_BARRIER();                      // every wave is done with the patch buffers: the exchange region may overwrite them
+        CNL_BARRIER();                      // every wave is done with the patch buffers: the exchange region may overwrite them
         W10_STAMP(6);
 
         // ---- epilogue (winograd9.hip's, four passes): out0 = Y0 + Y1 + Y2, out1 = Y1 - Y2 - Y3; the four positions (waves) meet through LDS.
@@ -578,7 +536,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         for (int i = 0; i < NI; ++i) { iql[i] = f32x2{iq[i][0], iq[i][1]}; iqh[i] = f32x2{iq[i][2], iq[i][3]}; }
         const f32x2 bql = {bq[0], bq[1]}, bqh = {bq[2], bq[3]};
         W10_XWRITE(0);
-        W10_BARRIER();
+        CNL_BARRIER();
 #pragma unroll
         for (int j = 0; j < R; ++j) {
             const char* X = sX + (j & 1) * (X_BYTES / 2);
@@ -639,7 +597,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 buf_store16(o0, a.y, a.y_bytes, ok[i][0] ? yv[i] : OOB, 0);
                 buf_store16(o1, a.y, a.y_bytes, ok[i][1] ? yv[i] : OOB, (unsigned)(a.ldy * 4));
             }
-            if (j + 1 < R) { W10_BARRIER(); }
+            if (j + 1 < R) { CNL_BARRIER(); }
             __builtin_amdgcn_sched_barrier(0);
             if (j == 1) {
                 // three of the four accumulator rows are dead (row 3 went into the exchange region during this pass... row 2 during pass 0): the
@@ -703,79 +661,41 @@ static unsigned long long* g_w10_trace = nullptr;
 extern "C" __attribute__((visibility("default"))) void cnl_w10_set_trace(void* p) { g_w10_trace = (unsigned long long*)p; }
 #endif
 // can this kernel run the layer at all?  (the conditions of winograd9.hip: it reads that kernel's weights)
-bool cnl_wino9_eligible(const cnl_conv_params* p);
-size_t cnl_wino9_weight_bytes(int Cin, int Cout);
 bool cnl_wino10_eligible(const cnl_conv_params* p) { return cnl_wino9_eligible(p); }
-int cnl_wino_packed_stride(const cnl_conv_params* p);
 
 // Launch (arguments already validated by cnl_conv3x3_winograd_f32); u9 / isu: the weight pieces and per-cout scales of winograd9.hip;
 // xmax = N per-image maxima of the input.
 template <int NBH>
 static int wino10_launch(const cnl_conv_params* p, const void* u9, const float* isu, const float* xmax, void* stream) {
     using namespace cnl_wino10;
-    constexpr int BN = 32 * NBH;
     Args a;
-    a.x = p->x; a.u9 = u9; a.xmax = xmax; a.isu = isu; a.ymax = reinterpret_cast<unsigned*>(p->y_absmax);
-    a.bias = p->bias; a.res = p->residual; a.y = p->y;
-    const int upf = (p->flags & CNL_UPSAMPLE_IN) ? 2 : 1;
-    a.Nimg = p->N; a.Hs = p->H_in; a.Ws = p->W_in; a.H = p->H_in * upf; a.W = p->W_in * upf; a.Cin = p->Cin; a.Cout = p->Cout;
+    a.u9 = u9;
+    const int upf = (p->flags & CNL_UPSAMPLE_IN) ? 2 : 1, W = p->W_in * upf;
+    a.Hs = p->H_in; a.Ws = p->W_in;
     // narrow maps: 2 (W = 32) or 4 (W = 16) images side by side in one 64-pixel block row (no folded upsample there)
-    a.ipb = (upf == 1 && (a.W == 32 || a.W == 16)) ? 64 / a.W : 1;
-    a.lw = a.W == 32 ? 5 : 4;
-    a.N = (p->N + a.ipb - 1) / a.ipb;
-    // other widths that 64-pixel blocks pad: packed rows (cnl_wino_packed_stride, winograd9.hip) — same arithmetic chain per output, same bits
-    a.pk = cnl_wino_packed_stride(p);
-    a.m_pk = a.pk ? (unsigned)(0x100000000ull / (unsigned)a.pk) : 0u;
-    if (a.pk) a.N = 1;
-    a.CoutP = (p->Cout + 63) / 64 * 64;
-    a.ldx = p->ldx; a.ldy = p->ldy; a.ldr = p->ldr;
+    a.ipb = (upf == 1 && (W == 32 || W == 16)) ? 64 / W : 1;
+    a.lw = W == 32 ? 5 : 4;
     a.CC = p->Cin / 16;
-    a.nb = a.CoutP / BN; a.bx = a.pk ? (int)(((long long)p->N * a.pk + 2 * TW - 1) / (2 * TW)) : (a.W + 2 * TW - 1) / (2 * TW); a.by = (a.H + R - 1) / R;
-    const auto magic = [](int d) { return d == 1 ? 0xFFFFFFFFu : (unsigned)(0x100000000ull / (unsigned)d); };
-    a.m_nb = magic(a.nb); a.m_bx = magic(a.bx); a.m_by = magic(a.by);
-    const long long blocks = (long long)a.N * a.by * a.bx * a.nb;
-    CNL_REQUIRE(blocks < (1ll << 31), CNL_E_UNSUPPORTED, "cnl_conv3x3_winograd_f32: grid too large");
-    a.blocks = (int)blocks;
-    const unsigned long long xb = (((unsigned long long)p->N * p->H_in * p->W_in - 1) * p->ldx + p->Cin) * 4ull;
-    const unsigned long long ub = (unsigned long long)cnl_wino9_weight_bytes(p->Cin, p->Cout);
-    const unsigned long long Mo = (unsigned long long)p->N * a.H * a.W;
-    const unsigned long long yb = ((Mo - 1) * p->ldy + p->Cout) * 4ull;
-    const unsigned long long rb = p->residual ? ((Mo - 1) * p->ldr + p->Cout) * 4ull : 0ull;
-    CNL_REQUIRE(xb < 0xFFFFFF00ull && ub < 0xFFFFFF00ull && yb + 4ull * p->ldy < 0xFFFFFF00ull && rb + 4ull * (p->residual ? p->ldr : 0) < 0xFFFFFF00ull,
-                CNL_E_UNSUPPORTED, "cnl_conv3x3_winograd_f32: tensor spans >= 4 GiB; split the batch");
-    a.x_bytes = (unsigned)xb; a.u_bytes = (unsigned)ub; a.y_bytes = (unsigned)yb; a.r_bytes = (unsigned)rb; a.b_bytes = (unsigned)p->Cout * 4u;
-    a.flags = p->flags;
+    // other widths that 64-pixel blocks pad: packed rows (cnl_wino_packed_stride, winograd9.hip) — same arithmetic chain per output, same bits
+    int rc = cnl_wino_row_setup(a, p, isu, xmax, {R, 2 * TW, 32 * NBH, 4}, a.ipb, cnl_wino_packed_stride(p), cnl_wino9_weight_bytes(p->Cin, p->Cout));
+    if (rc != CNL_OK) return rc;
 #ifdef W10_TRACE
     a.trace = g_w10_trace;
 #endif
-    static cnl::DeviceOnce once, once_res;
+    // the four instantiations: (packed rows | plain grid) x (residual | plain), listed in the order the code object has always had them
+    static cnl::DeviceOnce once[4];
+    void (*const fns[4])(const Args) = {winograd10_kernel<true, NBH, true>, winograd10_kernel<false, NBH, true>, winograd10_kernel<true, NBH>, winograd10_kernel<false, NBH>};
+    const int which = (a.pk ? 0 : 2) + (p->residual ? 0 : 1);
     int n_cu = 0;                          // persistent workgroups: two per CU, walking the work items with stride gridDim.x
-    static cnl::DeviceOnce once_pk, once_res_pk;
-    int rc = a.pk ? (p->residual ? cnl::kernel_setup(once_res_pk, reinterpret_cast<const void*>(&winograd10_kernel<true, NBH, true>), LDS_BYTES, &n_cu)
-                                 : cnl::kernel_setup(once_pk, reinterpret_cast<const void*>(&winograd10_kernel<false, NBH, true>), LDS_BYTES, &n_cu))
-                  : (p->residual ? cnl::kernel_setup(once_res, reinterpret_cast<const void*>(&winograd10_kernel<true, NBH>), LDS_BYTES, &n_cu)
-                                 : cnl::kernel_setup(once, reinterpret_cast<const void*>(&winograd10_kernel<false, NBH>), LDS_BYTES, &n_cu));
+    rc = cnl::kernel_setup(once[which], reinterpret_cast<const void*>(fns[which]), LDS_BYTES, &n_cu);
     if (rc != CNL_OK) return rc;
-    const unsigned grid = (unsigned)(blocks < 2ll * n_cu ? blocks : 2ll * n_cu);
-    if (a.pk) {
-        if (p->residual) hipLaunchKernelGGL((winograd10_kernel<true, NBH, true>), dim3(grid), dim3(256), LDS_BYTES, (hipStream_t)stream, a);
-        else hipLaunchKernelGGL((winograd10_kernel<false, NBH, true>), dim3(grid), dim3(256), LDS_BYTES, (hipStream_t)stream, a);
-    } else if (p->residual) hipLaunchKernelGGL((winograd10_kernel<true, NBH>), dim3(grid), dim3(256), LDS_BYTES, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL((winograd10_kernel<false, NBH>), dim3(grid), dim3(256), LDS_BYTES, (hipStream_t)stream, a);
+    const unsigned grid = (unsigned)(a.blocks < 2ll * n_cu ? a.blocks : 2ll * n_cu);
+    hipLaunchKernelGGL(fns[which], dim3(grid), dim3(256), LDS_BYTES, (hipStream_t)stream, a);
     return cnl::check_launch("winograd10_kernel");
 }
 // cout32: 4-row x 64-pixel x 32-cout work items (twice the items of half the size: 16-pixel maps, one-image batches) instead of 64-cout ones
-int cnl_wino_images_per_launch(const cnl_conv_params* p);                                      // winograd9.hip: tensors of >= 4 GiB run in groups of images
-void cnl_wino_sub_batch(const cnl_conv_params* p, int n0, int n, cnl_conv_params* q, const float** xmax);
 int cnl_wino10_launch(const cnl_conv_params* p, const void* u9, const float* isu, const float* xmax, bool cout32, void* stream) {
-    const int per = cnl_wino_images_per_launch(p);
-    CNL_REQUIRE(per > 0, CNL_E_UNSUPPORTED, "cnl_conv3x3_winograd_f32: one image of a tensor spans >= 4 GiB");
-    for (int n0 = 0; n0 < p->N; n0 += per) {
-        cnl_conv_params q;
-        const float* xm = xmax;
-        cnl_wino_sub_batch(p, n0, p->N - n0 < per ? p->N - n0 : per, &q, &xm);
-        const int rc = cout32 ? wino10_launch<1>(&q, u9, isu, xm, stream) : wino10_launch<2>(&q, u9, isu, xm, stream);
-        if (rc != CNL_OK) return rc;
-    }
-    return CNL_OK;
+    return cnl_wino_image_groups(p, xmax, [&](const cnl_conv_params* q, const float* xm) {
+        return cout32 ? wino10_launch<1>(q, u9, isu, xm, stream) : wino10_launch<2>(q, u9, isu, xm, stream);
+    });
 }

@@ -23,18 +23,15 @@
 // 96 transform + split operations per patch row and wave (winograd10.hip: 28), i.e. 5.3 VALU beside each MFMA (1.9 there), and six patch rows per
 // four output rows.  Scaling rules as in winograd9.hip: weights per OUTPUT CHANNEL, activations per image (|V| <= 7 max |x|) — batch-invariant.
 // Structure (prologue requested inside the previous item's epilogue, one barrier per chunk, exchange region aliasing the patch buffers): winograd10.hip.
-#include "cnl_common.h"
+#include "cnl_device.h"
+#include "winograd_internal.h"
 #include <utility>
 
 #pragma clang fp contract(off)
 
 namespace cnl_wino13 {
+using namespace cnl_dev;
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 struct Args {
     const float* x;
@@ -66,7 +63,6 @@ struct Args {
 #define W13_STAMP(i_) do {} while (0)
 #endif
 
-constexpr unsigned OOB = 0xFFFFFFF0u;
 constexpr int R = 4;                        // output rows per work item
 constexpr int PR = R + 2;                   // patch rows
 constexpr int TW = 32;                      // tiles (four pixels) per row of a work item: 128 output pixels
@@ -97,44 +93,6 @@ constexpr float OWN_C[4][3] = {{1.f, -2.5f, 0.5f}, {-1.f, 0.5f, 2.5f}, {-2.f, -1
 constexpr float SH_C[2][4] = {{-1.5f, -2.f, 1.5f, 1.f}, {1.f, -1.5f, -2.f, 1.5f}};
 constexpr float V_BOUND = 7.f;                      // max over the rows of B^T of the sum of |coefficients|: |V| <= 7 max |x|
 
-__device__ __forceinline__ u32x4 buf_load16(const void* base, unsigned bytes, unsigned voffset, unsigned soffset) {
-    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)bytes, 0x00020000);
-    return (u32x4)__builtin_amdgcn_raw_buffer_load_b128(rsrc, voffset, soffset, 0);
-}
-__device__ __forceinline__ void buf_store16(f32x4 v, float* base, unsigned bytes, unsigned voffset, unsigned soffset) {
-    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)bytes, 0x00020000);
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rsrc, voffset, soffset, CNL_NT_STORES);
-}
-__device__ __forceinline__ f32x16 mfma16(u32x4 a, u32x4 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
-// the split of a channel pair (v0, v1), scaled by the power of two S:  hi = RN16(v S) packed, r = v S - hi exactly (winograd5.hip)
-__device__ __forceinline__ unsigned split_hi_lo(float v0, float S) {
-    unsigned pk;
-    asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(pk) : "v"(v0), "v"(S));
-    return pk;
-}
-__device__ __forceinline__ unsigned split_hi_hi(unsigned pk, float v1, float S) {
-    asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(pk) : "v"(v1), "v"(S));
-    return pk;
-}
-__device__ __forceinline__ float split_res_lo(float v, float S, unsigned pk) {
-    float r;
-    asm("v_fma_mix_f32 %0, %1, %2, -%3 op_sel_hi:[0,0,1]" : "=v"(r) : "v"(v), "v"(S), "v"(pk));
-    return r;
-}
-__device__ __forceinline__ float split_res_hi(float v, float S, unsigned pk) {
-    float r;
-    asm("v_fma_mix_f32 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "=v"(r) : "v"(v), "v"(S), "v"(pk));
-    return r;
-}
-__device__ __forceinline__ int lane_now() {
-    unsigned z = 0;
-    asm volatile("" : "+v"(z));
-    return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, z));
-}
-__device__ __forceinline__ f32x4 lds_f4(const char* p) { return *reinterpret_cast<const f32x4*>(p); }
-#define W13_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 
 struct Item {               // per-work-item addressing state
     unsigned vcol[2], vext;  // source offsets: column part of the row pieces (pixel x0 - 1 + tid / 4 and 64 further; the row is a scalar offset), full offset of the column piece
@@ -262,7 +220,7 @@ __device__ __forceinline__ void slice(State& st, const Args& a, const int cn, co
     const f32x16 Z = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     if constexpr (S == BARRIER_SLICE) {
         // every wave is done reading this chunk's patch, and the next chunk's (written since the previous barrier) is complete
-        W13_BARRIER();
+        CNL_BARRIER();
         __builtin_amdgcn_sched_barrier(0);
     }
     if constexpr (unit < 2) {
@@ -511,7 +469,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             W13_SCALE_EXP(es_cur, xmax_cur);
             st.cur.S = __builtin_ldexpf(1.f, es_cur);
         }
-        W13_BARRIER();                      // the previous item's last exchange pass has been read by every wave: the region is free
+        CNL_BARRIER();                      // the previous item's last exchange pass has been read by every wave: the region is free
         W13_STAMP(1);
 #define W13_PWRITE_HALF(src_, half_, pbuf_)                                                                      \
         do {                                                                                                     \
@@ -525,7 +483,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         W13_PWRITE_HALF(2, 0, 1);
         W13_PWRITE_HALF(3, 1, 1);
 #undef W13_PWRITE_HALF
-        W13_BARRIER();
+        CNL_BARRIER();
         W13_STAMP(2);
         typedef std::make_integer_sequence<int, 10> Reads;
         typedef std::make_integer_sequence<int, JOB_OPS> Ops;
@@ -544,7 +502,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             chunk<1, false>(st, a, cn + 1, u_plane, u_own, u_sh);
         }
         W13_STAMP(6);
-        W13_BARRIER();                      // every wave is done with the patch buffers: the exchange region may overwrite them
+        CNL_BARRIER();                      // every wave is done with the patch buffers: the exchange region may overwrite them
         W13_STAMP(7);
 
         // ---- epilogue, four passes (pass j = output row j): the six positions meet through LDS.  Every wave writes its three blocks of that row (own
@@ -623,7 +581,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         for (int i = 0; i < 2; ++i) { iql[i] = f32x2{iq[i][0], iq[i][1]}; iqh[i] = f32x2{iq[i][2], iq[i][3]}; }
         const f32x2 bql = {bq[0], bq[1]}, bqh = {bq[2], bq[3]};
         W13_XWRITE3(0, 0); W13_XWRITE3(0, 1); W13_XWRITE3(0, 2); W13_XWRITE3(0, 3);
-        W13_BARRIER();
+        CNL_BARRIER();
 #pragma unroll
         for (int j = 0; j < R; ++j) {
             const char* X = sX + (j & 1) * X_HALF;
@@ -683,7 +641,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                 asm volatile("" :: "v"(o[3]));
 #undef W13_Y2
             }
-            if (j + 1 < R) { W13_BARRIER(); }
+            if (j + 1 < R) { CNL_BARRIER(); }
             __builtin_amdgcn_sched_barrier(0);
             if (j == 0) {
                 if constexpr (RES) res_rows(2);
@@ -820,65 +778,28 @@ int cnl_wino13_packed_stride(const cnl_conv_params* p) {
     return packed < plain ? (int)pk : 0;
 }
 
-int cnl_wino_images_per_launch(const cnl_conv_params* p);                                      // winograd9.hip: tensors of >= 4 GiB run in groups of images
-void cnl_wino_sub_batch(const cnl_conv_params* p, int n0, int n, cnl_conv_params* q, const float** xmax);
 static int wino13_launch_one(const cnl_conv_params* p, const void* u13, const float* isu, const float* xmax, void* stream) {
     using namespace cnl_wino13;
     Args a;
-    a.x = p->x; a.u13 = u13; a.xmax = xmax; a.isu = isu; a.ymax = reinterpret_cast<unsigned*>(p->y_absmax);
-    a.bias = p->bias; a.res = p->residual; a.y = p->y;
-    a.Nimg = p->N; a.H = p->H_in; a.W = p->W_in; a.Cin = p->Cin; a.Cout = p->Cout;
-    a.N = p->N;
-    a.pk = cnl_wino13_packed_stride(p);
-    a.m_pk = a.pk ? (unsigned)(0x100000000ull / (unsigned)a.pk) : 0u;
-    if (a.pk) a.N = 1;
-    a.CoutP = (p->Cout + 63) / 64 * 64;
-    a.ldx = p->ldx; a.ldy = p->ldy; a.ldr = p->ldr;
+    a.u13 = u13;
     a.CC = p->Cin / 16;
-    a.nb = a.CoutP / BN; a.bx = a.pk ? (int)(((long long)p->N * a.pk + PXW - 1) / PXW) : (a.W + PXW - 1) / PXW; a.by = (a.H + R - 1) / R;
-    const auto magic = [](int d) { return d == 1 ? 0xFFFFFFFFu : (unsigned)(0x100000000ull / (unsigned)d); };
-    a.m_nb = magic(a.nb); a.m_bx = magic(a.bx); a.m_by = magic(a.by);
-    const long long blocks = (long long)a.N * a.by * a.bx * a.nb;
-    CNL_REQUIRE(blocks < (1ll << 31), CNL_E_UNSUPPORTED, "cnl_conv3x3_winograd_f32: grid too large");
-    a.blocks = (int)blocks;
-    const unsigned long long xb = (((unsigned long long)p->N * p->H_in * p->W_in - 1) * p->ldx + p->Cin) * 4ull;
-    const unsigned long long ub = (unsigned long long)cnl_wino13_weight_bytes(p->Cin, p->Cout);
-    const unsigned long long Mo = (unsigned long long)p->N * a.H * a.W;
-    const unsigned long long yb = ((Mo - 1) * p->ldy + p->Cout) * 4ull;
-    const unsigned long long rb = p->residual ? ((Mo - 1) * p->ldr + p->Cout) * 4ull : 0ull;
-    CNL_REQUIRE(xb < 0xFFFFFF00ull && ub < 0xFFFFFF00ull && yb + 16ull * p->ldy < 0xFFFFFF00ull && rb + 16ull * (p->residual ? p->ldr : 0) < 0xFFFFFF00ull,
-                CNL_E_UNSUPPORTED, "cnl_conv3x3_winograd_f32: tensor spans >= 4 GiB; split the batch");
-    a.x_bytes = (unsigned)xb; a.u_bytes = (unsigned)ub; a.y_bytes = (unsigned)yb; a.r_bytes = (unsigned)rb; a.b_bytes = (unsigned)p->Cout * 4u;
-    a.flags = p->flags;
+    int rc = cnl_wino_row_setup(a, p, isu, xmax, {R, PXW, BN, 16}, 1, cnl_wino13_packed_stride(p), cnl_wino13_weight_bytes(p->Cin, p->Cout));
+    if (rc != CNL_OK) return rc;
 #ifdef W13_TRACE
     a.trace = g_w13_trace;
 #endif
+    // the four instantiations: (plain | residual) x (plain grid | packed rows)
     static cnl::DeviceOnce once[4];
-    const void* const fns[4] = {reinterpret_cast<const void*>(&winograd13_kernel<false, false>), reinterpret_cast<const void*>(&winograd13_kernel<true, false>),
-                                reinterpret_cast<const void*>(&winograd13_kernel<false, true>), reinterpret_cast<const void*>(&winograd13_kernel<true, true>)};
+    void (*const fns[4])(const Args) = {winograd13_kernel<false, false>, winograd13_kernel<true, false>, winograd13_kernel<false, true>, winograd13_kernel<true, true>};
     const int which = (p->residual ? 1 : 0) + (a.pk ? 2 : 0);
     int n_cu = 0;                          // persistent workgroups: one per CU, walking the work items with stride gridDim.x
-    const int rc = cnl::kernel_setup(once[which], fns[which], LDS_BYTES, &n_cu);
+    rc = cnl::kernel_setup(once[which], reinterpret_cast<const void*>(fns[which]), LDS_BYTES, &n_cu);
     if (rc != CNL_OK) return rc;
-    const unsigned grid = (unsigned)(blocks < (long long)n_cu ? blocks : (long long)n_cu);
-    switch (which) {
-    case 0: hipLaunchKernelGGL((winograd13_kernel<false, false>), dim3(grid), dim3(256), LDS_BYTES, (hipStream_t)stream, a); break;
-    case 1: hipLaunchKernelGGL((winograd13_kernel<true, false>), dim3(grid), dim3(256), LDS_BYTES, (hipStream_t)stream, a); break;
-    case 2: hipLaunchKernelGGL((winograd13_kernel<false, true>), dim3(grid), dim3(256), LDS_BYTES, (hipStream_t)stream, a); break;
-    default: hipLaunchKernelGGL((winograd13_kernel<true, true>), dim3(grid), dim3(256), LDS_BYTES, (hipStream_t)stream, a); break;
-    }
+    const unsigned grid = (unsigned)(a.blocks < n_cu ? a.blocks : n_cu);
+    hipLaunchKernelGGL(fns[which], dim3(grid), dim3(256), LDS_BYTES, (hipStream_t)stream, a);
     return cnl::check_launch("winograd13_kernel");
 }
 // Launch (arguments already validated by cnl_conv3x3_winograd_f32); u13 / isu: this kernel's weight pieces and per-cout scales; xmax = N per-image maxima of the input.
 int cnl_wino13_launch(const cnl_conv_params* p, const void* u13, const float* isu, const float* xmax, void* stream) {
-    const int per = cnl_wino_images_per_launch(p);
-    CNL_REQUIRE(per > 0, CNL_E_UNSUPPORTED, "cnl_conv3x3_winograd_f32: one image of a tensor spans >= 4 GiB");
-    for (int n0 = 0; n0 < p->N; n0 += per) {
-        cnl_conv_params q;
-        const float* xm = xmax;
-        cnl_wino_sub_batch(p, n0, p->N - n0 < per ? p->N - n0 : per, &q, &xm);
-        const int rc = wino13_launch_one(&q, u13, isu, xm, stream);
-        if (rc != CNL_OK) return rc;
-    }
-    return CNL_OK;
+    return cnl_wino_image_groups(p, xmax, [&](const cnl_conv_params* q, const float* xm) { return wino13_launch_one(q, u13, isu, xm, stream); });
 }

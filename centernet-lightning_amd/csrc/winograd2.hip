@@ -15,15 +15,13 @@
 //   B (weight) fragments go global -> registers (every U element is used by exactly one wave), refilled for chunk cc+1 right
 //   after position j's last MFMA of chunk cc; the compiler orders their uses with counted vmcnt waits.
 //   Only the input patch (10x18 px x 8 ch, double-buffered, fetched two chunks ahead by LDS-DMA) is shared: ONE barrier per chunk.
-#include "cnl_common.h"
+#include "cnl_device.h"
+#include "winograd_internal.h"
 #include <cstdlib>
 
 namespace cnl_wino2 {
+using namespace cnl_dev;
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(3))) void lds_void;
 
 struct Args {
     const float* x;
@@ -41,7 +39,6 @@ struct Args {
     unsigned flags;
 };
 
-constexpr unsigned OOB = 0xFFFFFFF0u;
 constexpr int T = 32;                       // tiles per workgroup: 4 tile rows x 8 tile columns
 constexpr int BN = 64;
 constexpr int PH = 10, PW = 18;             // patch height / width in pixels
@@ -51,10 +48,6 @@ constexpr int P_SLOTS = 384;                // 380 used; 256 (all waves) + 128 (
 constexpr int P_BYTES = P_SLOTS * 16;       // 6144 per buffer (two buffers)
 constexpr int LDS_BYTES = 2 * V_BYTES + 2 * P_BYTES;             // 45056 -> two workgroups per CU (the VGPR budget allows no more)
 
-__device__ __forceinline__ void dma16(const float* base, unsigned bytes, char* lds_dst, unsigned voffset, unsigned soffset) {
-    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)bytes, 0x00020000);
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void*)lds_dst, 16, voffset, soffset, 0, 0);
-}
 __device__ __forceinline__ void dma16_plus1k(const float* base, unsigned bytes, char* lds_dst, unsigned voffset, unsigned soffset) {
     const auto rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)bytes, 0x00020000);
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void*)lds_dst, 16, voffset, soffset, 1024, 0);
@@ -64,20 +57,11 @@ __device__ __forceinline__ f32x4 buf_load16(const float* base, unsigned bytes, u
     typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
     return __builtin_bit_cast(f32x4, (u32x4)__builtin_amdgcn_raw_buffer_load_b128(rsrc, voffset, soffset, 0));
 }
-__device__ __forceinline__ float buf_load(const float* base, unsigned bytes, unsigned voffset, unsigned soffset) {
-    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)bytes, 0x00020000);
-    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc, voffset, soffset, 0));
-}
-__device__ __forceinline__ void buf_store(float v, float* base, unsigned bytes, unsigned voffset, unsigned soffset) {
-    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)bytes, 0x00020000);
-    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rsrc, voffset, soffset, CNL_NT_STORES);
-}
 __device__ __forceinline__ f32x16 mfma32(float a, float b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
 __device__ __forceinline__ f32x16 mfma_zero() {
     const f32x16 z = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     return __builtin_amdgcn_mfma_f32_32x32x2f32(0.f, 0.f, z, 0, 0, 0);
 }
-__device__ __forceinline__ f32x4 lds_f4(const char* p) { return *reinterpret_cast<const f32x4*>(p); }
 __device__ __forceinline__ f32x2 lds_f2(const char* p) { return *reinterpret_cast<const f32x2*>(p); }
 __device__ __forceinline__ f32x2 pk_add(f32x2 a, f32x2 b) {
     f32x2 r;
@@ -196,7 +180,6 @@ __global__ __launch_bounds__(256, 2) void winograd2_kernel(const Args a) {
     _Pragma("unroll") for (int jj = 0; jj < 4; ++jj) *reinterpret_cast<f32x2*>((vbase_) + dst_v[q_] + jj * (T * 32)) = vv[q_][jj];
 
     // workgroup barrier WITHOUT the vmcnt(0) that __syncthreads() adds when LDS-DMA is in flight (own LDS accesses drained)
-#define W2_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 
     unsigned item = blockIdx.x;
     W2_SETUP(item);
@@ -221,7 +204,7 @@ __global__ __launch_bounds__(256, 2) void winograd2_kernel(const Args a) {
         else if (a.res) asm volatile("s_waitcnt vmcnt(63)" ::: "memory");      /* 64 newer ops: at most one of them is waited for too */
         else asm volatile("s_waitcnt vmcnt(32)" ::: "memory");
         first = false;
-        W2_BARRIER();                                         // ... and everybody's
+        CNL_BARRIER();                                         // ... and everybody's
         {   // input transform of chunk 0 (not overlapped with this workgroup's MFMAs — the other workgroup of the CU has some)
             W2_T_READ(0, sP);
             W2_T_READ(1, sP);
@@ -230,7 +213,7 @@ __global__ __launch_bounds__(256, 2) void winograd2_kernel(const Args a) {
             W2_T_WRITE(0, sV);
             W2_T_WRITE(1, sV);
         }
-        W2_BARRIER();                                         // patch 0 consumed everywhere: its buffer may be refilled (chunk 0, slice 2)
+        CNL_BARRIER();                                         // patch 0 consumed everywhere: its buffer may be refilled (chunk 0, slice 2)
         W2_READ_FRAGS(0, sV, 0);
 
         // One chunk = 32 MFMAs in 32 slices fenced by sched_barrier(0).  The vmcnt waits are COUNTED: LDS-DMAs complete in issue
@@ -271,7 +254,7 @@ __global__ __launch_bounds__(256, 2) void winograd2_kernel(const Args a) {
                 __builtin_amdgcn_sched_barrier(0);                                                               \
             }                                                                                                    \
             asm volatile("s_waitcnt vmcnt(8)" ::: "memory");    /* this wave's part of patch cc+2 landed (8 newer fragment loads) */ \
-            W2_BARRIER();                                     /* everybody's; and patch cc+1 consumed everywhere */ \
+            CNL_BARRIER();                                     /* everybody's; and patch cc+1 consumed everywhere */ \
         } while (0)
 
         int cc = 0;
@@ -309,7 +292,7 @@ __global__ __launch_bounds__(256, 2) void winograd2_kernel(const Args a) {
         const bool more = next < (unsigned)a.blocks;
 #pragma unroll
         for (int g = 0; g < 2; ++g) {
-            W2_BARRIER();                                      // everyone is done reading V / the patches (g = 0) or sQ (g = 1)
+            CNL_BARRIER();                                      // everyone is done reading V / the patches (g = 0) or sQ (g = 1)
             if (g == 0 && more) {                              // patch buffers and fragment registers are idle from here on
                 W2_SETUP(next);
                 W2_ISSUE_P(0);
@@ -324,7 +307,7 @@ __global__ __launch_bounds__(256, 2) void winograd2_kernel(const Args a) {
                 sQ[((wave * 2 + 0) * 32 + tl) * 32 + (lane & 31)] = m0 + m1 + m2;
                 sQ[((wave * 2 + 1) * 32 + tl) * 32 + (lane & 31)] = m1 - m2 - m3;
             }
-            W2_BARRIER();
+            CNL_BARRIER();
             // Stage 2: thread = (tile, co): Y[a][c] = sum_i A^T[a][i] q[i][c]; 4 tiles per thread and pass
             const int col = en0 + g * 32 + co;
             const bool col_ok = col < a.Cout;

@@ -2,18 +2,14 @@
 //
 // winograd3.hip showed that the matrix core fed with exact bf16 pieces reproduces fp32 products, and that the kernel around it is
 // bound by power and instruction issue, i.e. by the amount of work per output.  fp16 pieces carry 11 significand bits instead
-// of 8: with a power-of-two scale S per tensor (max |x S| in [2^13, 2^14), exact), x S = hi + lo with hi = RN16(x S),
-// lo = RZ16(x S - hi) represents x to 2^-22 relative (down to 2^-17 of the tensor's maximum; below that the ABSOLUTE error stays
-// <= 2^-25 / S, i.e. 2^-38 of the maximum), and the three terms  hi lo' + lo hi' + hi hi'  leave out lo lo' <= 2^-22 |x y|.
-// Measured on MI355X (tools/bf16x3_probe.hip, K = 2304): max |err| 7.7e-6 / rms 9.2e-7 against 1.27e-5 / 1.36e-6 for the fp32
-// MFMA and 8.0e-6 / 1.33e-6 for the six-term bf16 split; fp16 subnormals run at full MFMA rate and are not flushed.
+// of 8; the split, its error and its measured accuracy: cnl_device.h (the one place that states the contract).
 // Against winograd3.hip: 3 instead of 6 MFMAs per product, 4 instead of 6 bytes per operand element through LDS / from L2, and
-// 2.5 instead of 5.5 VALU operations per V element for the split — the mixed-precision fma does the scaling, the rounding and
-// the exact residual:  hi = v_fma_mixlo/hi_f16(v, S, 0),  r = v_fma_mix_f32(v, S, -hi),  lo = v_cvt_pkrtz_f16_f32(r0, r1).
+// 2.5 instead of 5.5 VALU operations per V element for the split.
 // The scale of the activations comes from the tensor's maximum magnitude (absmax_kernel, one pass over the input before the
 // launch, result left in the layer's weight buffer); the weights carry their own scale, fixed when they are transformed.
 // Structure (work item, wave roles, wave-private single-buffered V, patch DMA, one barrier per chunk): winograd3.hip.
-#include "cnl_common.h"
+#include "cnl_device.h"
+#include "winograd_internal.h"
 
 #pragma clang fp contract(off)
 
@@ -24,13 +20,8 @@
 #define W5_NT_Y 2     /* cache policy (aux) of the output stores: nt — a layer's output is far larger than the L2 and would only evict the input patches and weights that ARE re-read (fused first head blocks -9 %) */
 #endif
 namespace cnl_wino5 {
+using namespace cnl_dev;
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) void lds_void;
 
 struct Args {
     const float* x;
@@ -52,7 +43,6 @@ struct Args {
     int order;                        // work-item order (see W5_SETUP)
 };
 
-constexpr unsigned OOB = 0xFFFFFFF0u;
 constexpr int T = 64;                       // tiles per workgroup: 8 x 8
 constexpr int BN = 64;
 constexpr int PH = 18, PW = 18;             // patch height / width in pixels
@@ -66,52 +56,6 @@ constexpr int P_SLOTS = 1408;               // 1368 used; 5 x 256 (all waves) + 
 constexpr int P_BYTES = P_SLOTS * 16;       // 22528 per buffer (two buffers)
 constexpr int LDS_BYTES = V_BYTES + 2 * P_BYTES;                 // 110592: one workgroup per CU (the accumulators allow no more)
 
-__device__ __forceinline__ void dma16(const float* base, unsigned bytes, char* lds_dst, unsigned voffset, unsigned soffset) {
-    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)bytes, 0x00020000);
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void*)lds_dst, 16, voffset, soffset, 0, W5_NT_X);
-}
-__device__ __forceinline__ u32x4 buf_load16(const void* base, unsigned bytes, unsigned voffset, unsigned soffset) {
-    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)bytes, 0x00020000);
-    return (u32x4)__builtin_amdgcn_raw_buffer_load_b128(rsrc, voffset, soffset, 0);
-}
-__device__ __forceinline__ float buf_load(const float* base, unsigned bytes, unsigned voffset, unsigned soffset) {
-    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)bytes, 0x00020000);
-    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc, voffset, soffset, 0));
-}
-__device__ __forceinline__ void buf_store(float v, float* base, unsigned bytes, unsigned voffset, unsigned soffset) {
-    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)bytes, 0x00020000);
-    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rsrc, voffset, soffset, W5_NT_Y);
-}
-__device__ __forceinline__ f32x16 mfma16(u32x4 a, u32x4 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
-// the split of a channel pair (v0, v1), scaled by the power of two S:  hi = RN16(v S) packed, r = v S - hi exactly
-__device__ __forceinline__ unsigned split_hi_lo(float v0, float S) {            // RN16(v0 S) in the low half
-    unsigned pk;
-    asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(pk) : "v"(v0), "v"(S));
-    return pk;
-}
-__device__ __forceinline__ unsigned split_hi_hi(unsigned pk, float v1, float S) {   // ... and RN16(v1 S) in the high half
-    asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(pk) : "v"(v1), "v"(S));
-    return pk;
-}
-__device__ __forceinline__ float split_res_lo(float v, float S, unsigned pk) {
-    float r;
-    asm("v_fma_mix_f32 %0, %1, %2, -%3 op_sel_hi:[0,0,1]" : "=v"(r) : "v"(v), "v"(S), "v"(pk));
-    return r;
-}
-__device__ __forceinline__ float split_res_hi(float v, float S, unsigned pk) {
-    float r;
-    asm("v_fma_mix_f32 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "=v"(r) : "v"(v), "v"(S), "v"(pk));
-    return r;
-}
-__device__ __forceinline__ f32x16 mfma_zero() {
-    const f32x16 z = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    const u32x4 zz = {0u, 0u, 0u, 0u};
-    return mfma16(zz, zz, z);
-}
-__device__ __forceinline__ f32x4 lds_f4(const char* p) { return *reinterpret_cast<const f32x4*>(p); }
-__device__ __forceinline__ u32x4 lds_u4(const char* p) { return *reinterpret_cast<const u32x4*>(p); }
 
 // Registers of one wave's input-transform pipeline.  A "pass-item" = (item: tile, 4 channels) x (pass P: position pair {2P, 2P+1}
 // of the wave's row).  Its VALU operations are indexed 0..39 so that the main loop can place them per MFMA slice:
@@ -244,8 +188,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         if ((cc_) < a.CC) {                                                                                      \
             char* d_ = sP + ((cc_) & 1) * P_BYTES;                                                               \
             _Pragma("unroll") for (int i = 0; i < 5; ++i)                                                        \
-                dma16(a.x, a.x_bytes, d_ + (i * 256 + wave * 64) * 16, p_off[i], (unsigned)((cc_) * 64));        \
-            if (wave < 2) dma16(a.x, a.x_bytes, d_ + (1280 + wave * 64) * 16, p_off[5], (unsigned)((cc_) * 64)); \
+                dma16<W5_NT_X>(a.x, a.x_bytes, d_ + (i * 256 + wave * 64) * 16, p_off[i], (unsigned)((cc_) * 64));        \
+            if (wave < 2) dma16<W5_NT_X>(a.x, a.x_bytes, d_ + (1280 + wave * 64) * 16, p_off[5], (unsigned)((cc_) * 64)); \
         }                                                                                                        \
     } while (0)
     // B fragments of position xi0 + j_ of chunk cc_, cout group g_ (three pieces): global -> registers
@@ -285,7 +229,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             *reinterpret_cast<u32x2*>(sV + dstv + (it_) * 512 + ((2 * (P_) + jj_) * NP + kk_) * VPIECE) =        \
                 u32x2{xf.pk[jj_][kk_][0], xf.pk[jj_][kk_][1]};
     // workgroup barrier WITHOUT the vmcnt(0) that __syncthreads() adds when LDS-DMA is in flight (own LDS accesses drained)
-#define W5_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 
     // One position slot = 12 MFMAs in 12 slices fenced by sched_barrier(0).
     //   j_ / buf_    position multiplied in this slot and its fragment buffer
@@ -302,7 +245,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             const int pi = k / 6, ks = k % 6;                                                                    \
             if ((MID_) && k == 6) {                                                                              \
                 asm volatile("s_waitcnt vmcnt(4)" ::: "memory");   /* all but the newest 4 B loads: the patch DMA is older */ \
-                W5_BARRIER();                                                                   \
+                CNL_BARRIER();                                                                   \
                 __builtin_amdgcn_sched_barrier(0);                                                               \
             }                                                                                                    \
             W5_MFMA(j_, buf_, k);                                                                                \
@@ -349,7 +292,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         if (first) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(38)" ::: "memory");
         first = false;
-        W5_BARRIER();                                         // ... and everybody's
+        CNL_BARRIER();                                         // ... and everybody's
         {   // input transform of chunk 0, all four positions (not overlapped with MFMAs): eight pass-items, each read one ahead
             const char* pa = sP + src_a;
             const char* pb = sP + src_b;
@@ -435,7 +378,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                     }
                 }
             }
-            W5_BARRIER();                                      // everyone is done reading V / the patches (tg = 0) or sQ
+            CNL_BARRIER();                                      // everyone is done reading V / the patches (tg = 0) or sQ
             if (tg == 1 && more) {                             // patch buffers and fragment registers are idle
                 W5_SETUP(next);
                 W5_ISSUE_P(0);
@@ -453,7 +396,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                     sQ[(((wave * 2 + 0) * 2 + g) * 32 + tl) * 32 + (lane & 31)] = m0 + m1 + m2;
                     sQ[(((wave * 2 + 1) * 2 + g) * 32 + tl) * 32 + (lane & 31)] = m1 - m2 - m3;
                 }
-            W5_BARRIER();
+            CNL_BARRIER();
             // Stage 2: thread = (tile, co): Y[a][c] = sum_i A^T[a][i] q[i][c]; 4 tiles x 2 cout groups per thread and pass
 #pragma unroll
             for (int g = 0; g < 2; ++g) {
@@ -478,8 +421,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                         const float yb = (q[1][c] - q[2][c] - q[3][c]) * inv;
                         const float oa = fmaxf(ya + bv[g] + rv[g][it][0][c], lo), ob = fmaxf(yb + bv[g] + rv[g][it][1][c], lo);
                         omax = fmaxf(omax, fmaxf(ok[g][it][0][c] ? fabsf(oa) : 0.f, ok[g][it][1][c] ? fabsf(ob) : 0.f));
-                        buf_store(oa, a.y, a.y_bytes, ok[g][it][0][c] ? y_voff[g][it] : OOB, (unsigned)(c * a.ldy * 4));
-                        buf_store(ob, a.y, a.y_bytes, ok[g][it][1][c] ? y_voff[g][it] : OOB, (unsigned)((a.W + c) * a.ldy * 4));
+                        buf_store<W5_NT_Y>(oa, a.y, a.y_bytes, ok[g][it][0][c] ? y_voff[g][it] : OOB, (unsigned)(c * a.ldy * 4));
+                        buf_store<W5_NT_Y>(ob, a.y, a.y_bytes, ok[g][it][1][c] ? y_voff[g][it] : OOB, (unsigned)((a.W + c) * a.ldy * 4));
                     }
                 }
             }

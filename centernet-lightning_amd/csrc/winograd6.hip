@@ -9,7 +9,8 @@
 //   refilled for the position after next as soon as its six MFMAs are issued); ONE pass-item (tile, 4 channels, position pair) of
 //   transform work per position slot; V wave-private and single-buffered as in winograd5; LDS 88 KB.
 // Used where Cout is a multiple of 128 (cnl_conv3x3_winograd_f32's dispatch); everything else as winograd5.hip.
-#include "cnl_common.h"
+#include "cnl_device.h"
+#include "winograd_internal.h"
 
 #pragma clang fp contract(off)
 
@@ -23,13 +24,8 @@
 #define W6_EXP 0     /* timing experiments (wrong results): 1 no B loads, 2 no A reads, 3 no patch reads, 4 no barrier in the loop */
 #endif
 namespace cnl_wino6 {
+using namespace cnl_dev;
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) void lds_void;
 
 struct Args {
     const float* x;
@@ -53,7 +49,6 @@ struct Args {
     unsigned mg_sw, sh_sw;            // STACK: magic division by SW (n < 2^31)
 };
 
-constexpr unsigned OOB = 0xFFFFFFF0u;
 constexpr int T = 32;                       // tiles per workgroup: 4 x 8 (8 x 16 output pixels)
 constexpr int BN = 128;                     // output channels per workgroup: four 32-cout groups
 constexpr int PH = 10, PW = 18;             // patch height / width in pixels
@@ -68,52 +63,6 @@ constexpr int P_BYTES = P_SLOTS * 16;       // 12288 per buffer (two buffers)
 constexpr int OFF_BYTES = 3 * 256 * 4;          // per-thread patch offsets of the current item (see W6_SETUP)
 constexpr int LDS_BYTES = V_BYTES + 2 * P_BYTES + OFF_BYTES;     // 93184
 
-__device__ __forceinline__ void dma16(const float* base, unsigned bytes, char* lds_dst, unsigned voffset, unsigned soffset) {
-    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)bytes, 0x00020000);
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void*)lds_dst, 16, voffset, soffset, 0, W6_NT_X);
-}
-__device__ __forceinline__ u32x4 buf_load16(const void* base, unsigned bytes, unsigned voffset, unsigned soffset) {
-    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)bytes, 0x00020000);
-    return (u32x4)__builtin_amdgcn_raw_buffer_load_b128(rsrc, voffset, soffset, 0);
-}
-__device__ __forceinline__ float buf_load(const float* base, unsigned bytes, unsigned voffset, unsigned soffset) {
-    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)bytes, 0x00020000);
-    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc, voffset, soffset, 0));
-}
-__device__ __forceinline__ void buf_store(float v, float* base, unsigned bytes, unsigned voffset, unsigned soffset) {
-    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)bytes, 0x00020000);
-    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rsrc, voffset, soffset, W6_NT_Y);
-}
-__device__ __forceinline__ f32x16 mfma16(u32x4 a, u32x4 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
-// the split of a channel pair (v0, v1), scaled by the power of two S:  hi = RN16(v S) packed, r = v S - hi exactly
-__device__ __forceinline__ unsigned split_hi_lo(float v0, float S) {            // RN16(v0 S) in the low half
-    unsigned pk;
-    asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(pk) : "v"(v0), "v"(S));
-    return pk;
-}
-__device__ __forceinline__ unsigned split_hi_hi(unsigned pk, float v1, float S) {   // ... and RN16(v1 S) in the high half
-    asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(pk) : "v"(v1), "v"(S));
-    return pk;
-}
-__device__ __forceinline__ float split_res_lo(float v, float S, unsigned pk) {
-    float r;
-    asm("v_fma_mix_f32 %0, %1, %2, -%3 op_sel_hi:[0,0,1]" : "=v"(r) : "v"(v), "v"(S), "v"(pk));
-    return r;
-}
-__device__ __forceinline__ float split_res_hi(float v, float S, unsigned pk) {
-    float r;
-    asm("v_fma_mix_f32 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "=v"(r) : "v"(v), "v"(S), "v"(pk));
-    return r;
-}
-__device__ __forceinline__ f32x16 mfma_zero() {
-    const f32x16 z = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    const u32x4 zz = {0u, 0u, 0u, 0u};
-    return mfma16(zz, zz, z);
-}
-__device__ __forceinline__ f32x4 lds_f4(const char* p) { return *reinterpret_cast<const f32x4*>(p); }
-__device__ __forceinline__ u32x4 lds_u4(const char* p) { return *reinterpret_cast<const u32x4*>(p); }
 
 // Registers of one wave's input-transform pipeline.  A "pass-item" = (item: tile, 4 channels) x (pass P: position pair {2P, 2P+1}
 // of the wave's row).  Its VALU operations are indexed 0..39 so that the main loop can place them per MFMA slice:
@@ -270,7 +219,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         if ((cc_) < a.CC) {                                                                                      \
             char* d_ = sP + ((cc_) & 1) * P_BYTES;                                                               \
             _Pragma("unroll") for (int i = 0; i < 3; ++i)                                                        \
-                dma16(a.x, a.x_bytes, d_ + (i * 256 + wave * 64) * 16, sOff[i * 256], (unsigned)((cc_) * 64));   \
+                dma16<W6_NT_X>(a.x, a.x_bytes, d_ + (i * 256 + wave * 64) * 16, sOff[i * 256], (unsigned)((cc_) * 64));   \
         }                                                                                                        \
     } while (0)
     // B fragments of position xi0 + j_ of chunk cc_, cout group g_ (three pieces): global -> registers
@@ -310,7 +259,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             *reinterpret_cast<u32x2*>(sV + dstv + (it_) * 512 + ((2 * (P_) + jj_) * NP + kk_) * VPIECE) =        \
                 u32x2{xf.pk[jj_][kk_][0], xf.pk[jj_][kk_][1]};
     // workgroup barrier WITHOUT the vmcnt(0) that __syncthreads() adds when LDS-DMA is in flight (own LDS accesses drained)
-#define W6_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 
     // One position slot = 12 MFMAs in 12 slices fenced by sched_barrier(0).
     //   j_ / buf_    position multiplied in this slot and its fragment buffer
@@ -326,7 +274,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         _Pragma("unroll") for (int k = 0; k < 12; ++k) {                                                         \
             if ((MID_) && k == 6) {                                                                              \
                 asm volatile("s_waitcnt vmcnt(8)" ::: "memory");   /* all but the newest 8 B loads: the patch DMA is older */ \
-                W6_BARRIER();                                                                                    \
+                CNL_BARRIER();                                                                                    \
                 __builtin_amdgcn_sched_barrier(0);                                                               \
             }                                                                                                    \
             W6_MFMA(j_, buf_, k);                                                                                \
@@ -368,7 +316,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         if (first) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(44)" ::: "memory");
         first = false;
-        W6_BARRIER();                                         // ... and everybody's
+        CNL_BARRIER();                                         // ... and everybody's
         {   // input transform of chunk 0, all four positions (not overlapped with MFMAs): four pass-items, each read one ahead
             const char* pa = sP + src_a;
             const char* pb = sP + src_b;
@@ -462,7 +410,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                     }
                 }
             }
-            W6_BARRIER();                                      // everyone is done reading V / the patches (tg = 0) or sQ
+            CNL_BARRIER();                                      // everyone is done reading V / the patches (tg = 0) or sQ
             if (tg == 1 && more) {                             // patch buffers and fragment registers are idle
                 W6_SETUP(next);
                 W6_ISSUE_P(0);
@@ -478,7 +426,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                     sQ[(((wave * 2 + 0) * 2 + g) * 32 + tl) * 32 + (lane & 31)] = m0 + m1 + m2;
                     sQ[(((wave * 2 + 1) * 2 + g) * 32 + tl) * 32 + (lane & 31)] = m1 - m2 - m3;
                 }
-            W6_BARRIER();
+            CNL_BARRIER();
             // Stage 2: thread = (tile, co): Y[a][c] = sum_i A^T[a][i] q[i][c]; 4 tiles x 2 cout groups per thread and pass
 #pragma unroll
             for (int g = 0; g < 2; ++g) {
@@ -503,8 +451,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                         const float yb = (q[1][c] - q[2][c] - q[3][c]) * inv;
                         const float oa = fmaxf(ya + bv[tg * 2 + g] + rv[g][it][0][c], lo), ob = fmaxf(yb + bv[tg * 2 + g] + rv[g][it][1][c], lo);
                         omax = fmaxf(omax, fmaxf(ok[g][it][0][c] ? fabsf(oa) : 0.f, ok[g][it][1][c] ? fabsf(ob) : 0.f));
-                        buf_store(oa, a.y, a.y_bytes, ok[g][it][0][c] ? y_voff[g][it] : OOB, (unsigned)(c * a.ldy * 4));
-                        buf_store(ob, a.y, a.y_bytes, ok[g][it][1][c] ? y_voff[g][it] : OOB, (unsigned)((a.W + c) * a.ldy * 4));
+                        buf_store<W6_NT_Y>(oa, a.y, a.y_bytes, ok[g][it][0][c] ? y_voff[g][it] : OOB, (unsigned)(c * a.ldy * 4));
+                        buf_store<W6_NT_Y>(ob, a.y, a.y_bytes, ok[g][it][1][c] ? y_voff[g][it] : OOB, (unsigned)((a.W + c) * a.ldy * 4));
                     }
                 }
             }
@@ -559,8 +507,6 @@ __global__ __launch_bounds__(256) void absmax_kernel(const float* __restrict__ x
 
 }  // namespace cnl_wino6
 
-size_t cnl_wino5_weight_bytes(int Cin, int Cout);      // winograd5.hip: the weight layout, scales and scalars are shared
-int cnl_wino5_own_absmax(const cnl_conv_params* p, float* scal, void* stream);
 
 // Launch (arguments already validated by cnl_conv3x3_winograd_f32); u5 = the fp16-split weights, scal = the layer's scalars.
 int cnl_wino6_launch(const cnl_conv_params* p, const void* u5, float* scal, void* stream) {

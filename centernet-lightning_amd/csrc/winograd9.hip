@@ -26,7 +26,8 @@
 // first use (L2 hits).
 // Weights: U_p[ky] = (G g[ky])_p, scaled PER OUTPUT CHANNEL by a power of two (max |U S_u[co]| in [2^12, 2^13)) and split into two
 // fp16 pieces, [ci/16][p][ky][piece][CoutP][16 ci]; the epilogue multiplies by 1/(S_v S_u[co]).
-#include "cnl_common.h"
+#include "cnl_device.h"
+#include "winograd_internal.h"
 #include <utility>
 
 #pragma clang fp contract(off)
@@ -34,13 +35,9 @@
 #ifndef W9_NT_Y
 #define W9_NT_Y 2     /* cache policy (aux) of the output stores: nt (see winograd5.hip) */
 #endif
-int cnl_wino_packed_stride(const cnl_conv_params* p);
 namespace cnl_wino9 {
+using namespace cnl_dev;
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 struct Args {
     const float* x;
@@ -87,7 +84,6 @@ struct Args {
 #define W9_STAMP(i_) do {} while (0)
 #endif
 
-constexpr unsigned OOB = 0xFFFFFFF0u;
 constexpr int R = 8;                        // output rows per work item
 constexpr int PR = R + 2;                   // patch rows
 constexpr int TW = 32;                      // tiles (pixel pairs) per row of a work item: 64 output pixels
@@ -113,47 +109,6 @@ constexpr int NSTG = 6;                     // staging registers per thread: a p
 #ifndef W9_AUX_U
 #define W9_AUX_U 0
 #endif
-template <int AUX = 0>
-__device__ __forceinline__ u32x4 buf_load16(const void* base, unsigned bytes, unsigned voffset, unsigned soffset) {
-    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)bytes, 0x00020000);
-    return (u32x4)__builtin_amdgcn_raw_buffer_load_b128(rsrc, voffset, soffset, AUX);
-}
-__device__ __forceinline__ void buf_store16(f32x4 v, float* base, unsigned bytes, unsigned voffset, unsigned soffset) {
-    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)bytes, 0x00020000);
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rsrc, voffset, soffset, W9_NT_Y);
-}
-__device__ __forceinline__ f32x16 mfma16(u32x4 a, u32x4 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
-// the split of a channel pair (v0, v1), scaled by the power of two S:  hi = RN16(v S) packed, r = v S - hi exactly (winograd5.hip)
-__device__ __forceinline__ unsigned split_hi_lo(float v0, float S) {
-    unsigned pk;
-    asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(pk) : "v"(v0), "v"(S));
-    return pk;
-}
-__device__ __forceinline__ unsigned split_hi_hi(unsigned pk, float v1, float S) {
-    asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(pk) : "v"(v1), "v"(S));
-    return pk;
-}
-__device__ __forceinline__ float split_res_lo(float v, float S, unsigned pk) {
-    float r;
-    asm("v_fma_mix_f32 %0, %1, %2, -%3 op_sel_hi:[0,0,1]" : "=v"(r) : "v"(v), "v"(S), "v"(pk));
-    return r;
-}
-__device__ __forceinline__ float split_res_hi(float v, float S, unsigned pk) {
-    float r;
-    asm("v_fma_mix_f32 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "=v"(r) : "v"(v), "v"(S), "v"(pk));
-    return r;
-}
-// the lane id from the hardware (2 VALU) on an opaque input: per-lane values derived from it are computed where they are used instead
-// of at kernel entry, from where they would stay live across the chunk loop
-__device__ __forceinline__ int lane_now() {
-    unsigned z = 0;
-    asm volatile("" : "+v"(z));
-    return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, z));
-}
-__device__ __forceinline__ f32x4 lds_f4(const char* p) { return *reinterpret_cast<const f32x4*>(p); }
-#define W9_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 
 // ---- the static schedule of a chunk -----------------------------------------------------------------------------------------
 // 24 segments of 6 MFMAs (3 terms x 2 cout halves), each one (input row r, kernel row ky) -> output row r - ky.  Rows in order,
@@ -298,7 +253,7 @@ __device__ __forceinline__ void slice(State& st, const Args& a, const int cn, co
 #endif
     if constexpr (S == BARRIER_SLICE) {
         // every wave is done reading this chunk's patch, and the next chunk's (written a chunk ago) is complete
-        W9_BARRIER();
+        CNL_BARRIER();
         __builtin_amdgcn_sched_barrier(0);
     }
 #ifdef W9_SKIP4     // timing build (wrong results): every fourth MFMA is left out — what 25 % fewer matrix instructions buy under the chip's power limit
@@ -411,7 +366,7 @@ __device__ __forceinline__ void slice_ur(State& st, const Args& a, const int cn,
     constexpr int ku = term == 1 ? 1 : 0, kv = term == 0 ? 1 : 0;         // terms: hi lo', lo hi', hi hi'
     constexpr int vbuf = (urs_frag(seg) + 2 * PAR) & 3, wset = urs_set(seg);
     if constexpr (S == UR_BARRIER) {
-        W9_BARRIER();
+        CNL_BARRIER();
         __builtin_amdgcn_sched_barrier(0);
     }
     if constexpr (FIRST && urs_first_use(S)) st.acc[r - ky][nbh] = mfma16(st.fb[wset][nbh][ku], st.vf[vbuf][kv], f32x16{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f});
@@ -671,7 +626,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 #pragma unroll
         for (int i = 0; i < 4; ++i) load_b<2, 4>(st, a, st.cur.u_voff, 0, i, u_plane, u_wave);
     }
-    W9_BARRIER();
+    CNL_BARRIER();
     W9_STAMP(4);
     rread<0>(st, 0, 0); rread<1>(st, 0, 0); rread<2>(st, 0, 0); rread<3>(st, 0, 0);
     job_all(st, 0, st.cur.S, std::make_integer_sequence<int, 28>{});
@@ -812,7 +767,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             }
         }
         W9_XWRITE(0);
-        W9_BARRIER();
+        CNL_BARRIER();
 #pragma unroll
         for (int j = 0; j < R; ++j) {
             const char* X = sX + (j & 1) * (X_BYTES / 2);
@@ -877,8 +832,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                 }
                 if (ok[i][0]) omax2[i] = fmaxf(omax2[i], fmaxf(fmaxf(fabsf(o0[0]), fabsf(o0[1])), fmaxf(fabsf(o0[2]), fabsf(o0[3]))));
                 if (ok[i][1]) omax2[i] = fmaxf(omax2[i], fmaxf(fmaxf(fabsf(o1[0]), fabsf(o1[1])), fmaxf(fabsf(o1[2]), fabsf(o1[3]))));
-                buf_store16(o0, a.y, a.y_bytes, ok[i][0] ? yv[i] : OOB, 0);
-                buf_store16(o1, a.y, a.y_bytes, ok[i][1] ? yv[i] : OOB, (unsigned)(a.ldy * 4));
+                buf_store16<W9_NT_Y>(o0, a.y, a.y_bytes, ok[i][0] ? yv[i] : OOB, 0);
+                buf_store16<W9_NT_Y>(o1, a.y, a.y_bytes, ok[i][1] ? yv[i] : OOB, (unsigned)(a.ldy * 4));
                 if constexpr (FUSE) {
                     // d[c] = sum over this thread's four couts of out[co] * fw[co][c], then over the 8 lanes (pieces) of the tile: quad
                     // neighbours, quad pairs, the two quads of the half row — a fixed tree, the same in every lane; lane piece 0 stores the
@@ -908,7 +863,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                     }
                 }
             }
-            if (j + 1 < R) { W9_BARRIER(); }
+            if (j + 1 < R) { CNL_BARRIER(); }
             __builtin_amdgcn_sched_barrier(0);
         }
 #undef W9_XWRITE
@@ -1145,25 +1100,9 @@ void cnl_wino_sub_batch(const cnl_conv_params* p, int n0, int n, cnl_conv_params
     *xmax += (size_t)n0 * AMS;
 }
 
-static int wino9_launch_one(const cnl_conv_params* p, const void* u9, const float* isu, const float* xmax, void* stream);
 // can this launch take the row-pair form (UR)?  A folded upsample, the row-pair weights given, nothing the UR instantiations lack (residual, folded 1x1)
 bool cnl_wino9_up_rows(const cnl_conv_params* p) {
     return (p->flags & CNL_UPSAMPLE_IN) && p->w_up && !p->residual && !p->fuse_w && ((uintptr_t)p->w_up & 15) == 0;
-}
-// Launch (arguments already validated by cnl_conv3x3_winograd_f32); xmax = N per-image maxima of the input.
-int cnl_wino9_launch(const cnl_conv_params* p, const void* u9, const float* isu, const float* xmax, void* stream) {
-    const int per = cnl_wino_images_per_launch(p);
-    CNL_REQUIRE(per > 0, CNL_E_UNSUPPORTED, "cnl_conv3x3_winograd_f32: one image of a tensor spans >= 4 GiB");
-    if (per >= p->N) return wino9_launch_one(p, u9, isu, xmax, stream);
-    CNL_REQUIRE(!p->fuse_w, CNL_E_UNSUPPORTED, "cnl_conv3x3_winograd_f32: fuse_w on a launch whose tensors span >= 4 GiB; split the batch");
-    for (int n0 = 0; n0 < p->N; n0 += per) {
-        cnl_conv_params q;
-        const float* xm = xmax;
-        cnl_wino_sub_batch(p, n0, p->N - n0 < per ? p->N - n0 : per, &q, &xm);
-        const int rc = wino9_launch_one(&q, u9, isu, xm, stream);
-        if (rc != CNL_OK) return rc;
-    }
-    return CNL_OK;
 }
 static int wino9_launch_one(const cnl_conv_params* p, const void* u9, const float* isu, const float* xmax, void* stream) {
     using namespace cnl_wino9;
@@ -1173,39 +1112,20 @@ static int wino9_launch_one(const cnl_conv_params* p, const void* u9, const floa
         u9 = p->w_up;
         isu = p->w_up + cnl_wino9_up_weight_bytes(p->Cin, p->Cout) / 4;
     }
-    a.x = p->x; a.u9 = u9; a.xmax = xmax; a.isu = isu; a.ymax = reinterpret_cast<unsigned*>(p->y_absmax);
-    a.bias = p->bias; a.res = p->residual; a.y = p->y;
-    const int upf = (p->flags & CNL_UPSAMPLE_IN) ? 2 : 1;
-    a.Nimg = p->N; a.Hs = p->H_in; a.Ws = p->W_in; a.H = p->H_in * upf; a.W = p->W_in * upf; a.Cin = p->Cin; a.Cout = p->Cout;
+    a.u9 = u9;
+    const int upf = (p->flags & CNL_UPSAMPLE_IN) ? 2 : 1, W = p->W_in * upf;
+    a.Hs = p->H_in; a.Ws = p->W_in;
     // narrow maps: 2 (W = 32) or 4 (W = 16) images side by side in one 64-pixel block row (no folded upsample there)
-    a.ipb = (upf == 1 && (a.W == 32 || a.W == 16)) ? 64 / a.W : 1;
-    a.lw = a.W == 32 ? 5 : 4;
-    a.N = (p->N + a.ipb - 1) / a.ipb;
-    // other widths that 64-pixel blocks pad: packed rows (cnl_wino_packed_stride) — same arithmetic chain per output, same bits
-    a.pk = cnl_wino_packed_stride(p);
-    a.m_pk = a.pk ? (unsigned)(0x100000000ull / (unsigned)a.pk) : 0u;
-    if (a.pk) a.N = 1;
-    a.CoutP = (p->Cout + 63) / 64 * 64;
-    a.ldx = p->ldx; a.ldy = p->ldy; a.ldr = p->ldr;
+    a.ipb = (upf == 1 && (W == 32 || W == 16)) ? 64 / W : 1;
+    a.lw = W == 32 ? 5 : 4;
     a.CC = p->Cin / 16;
-    a.nb = a.CoutP / BN; a.bx = a.pk ? (int)(((long long)p->N * a.pk + 2 * TW - 1) / (2 * TW)) : (a.W + 2 * TW - 1) / (2 * TW); a.by = (a.H + R - 1) / R;
-    const auto magic = [](int d) { return d == 1 ? 0xFFFFFFFFu : (unsigned)(0x100000000ull / (unsigned)d); };
-    a.m_nb = magic(a.nb); a.m_bx = magic(a.bx); a.m_by = magic(a.by);
-    const long long blocks = (long long)a.N * a.by * a.bx * a.nb;
-    CNL_REQUIRE(blocks < (1ll << 31), CNL_E_UNSUPPORTED, "cnl_conv3x3_winograd_f32: grid too large");
-    a.blocks = (int)blocks;
-    const unsigned long long xb = (((unsigned long long)p->N * p->H_in * p->W_in - 1) * p->ldx + p->Cin) * 4ull;
-    const unsigned long long ub = (unsigned long long)(ur ? cnl_wino9_up_weight_bytes(p->Cin, p->Cout) : cnl_wino9_weight_bytes(p->Cin, p->Cout));
-    const unsigned long long Mo = (unsigned long long)p->N * a.H * a.W;
-    const unsigned long long yb = ((Mo - 1) * p->ldy + p->Cout) * 4ull;
-    const unsigned long long rb = p->residual ? ((Mo - 1) * p->ldr + p->Cout) * 4ull : 0ull;
-    CNL_REQUIRE(xb < 0xFFFFFF00ull && ub < 0xFFFFFF00ull && yb + 4ull * p->ldy < 0xFFFFFF00ull && rb + 4ull * (p->residual ? p->ldr : 0) < 0xFFFFFF00ull,
-                CNL_E_UNSUPPORTED, "cnl_conv3x3_winograd_f32: tensor spans >= 4 GiB; split the batch");
-    a.x_bytes = (unsigned)xb; a.u_bytes = (unsigned)ub; a.y_bytes = (unsigned)yb; a.r_bytes = (unsigned)rb; a.b_bytes = (unsigned)p->Cout * 4u;
-    a.flags = p->flags;
+    // other widths that 64-pixel blocks pad: packed rows (cnl_wino_packed_stride) — same arithmetic chain per output, same bits
+    int rc = cnl_wino_row_setup(a, p, isu, xmax, {R, 2 * TW, BN, 4}, a.ipb, cnl_wino_packed_stride(p),
+                                ur ? cnl_wino9_up_weight_bytes(p->Cin, p->Cout) : cnl_wino9_weight_bytes(p->Cin, p->Cout));
+    if (rc != CNL_OK) return rc;
     a.fw = p->fuse_w; a.fpart = p->fuse_w ? p->fuse_part : nullptr; a.fp_bytes = a.fp_block = 0;
     if (a.fpart) {
-        const unsigned long long blk = Mo * 16ull, all = blk * (unsigned long long)(a.CoutP / 32);
+        const unsigned long long blk = (unsigned long long)p->N * a.H * a.W * 16ull, all = blk * (unsigned long long)(a.CoutP / 32);
         CNL_REQUIRE(all < 0xFFFFFF00ull, CNL_E_UNSUPPORTED, "cnl_conv3x3_winograd_f32: fuse_part spans >= 4 GiB; split the batch");
         a.fp_bytes = (unsigned)all; a.fp_block = (unsigned)blk;
     }
@@ -1215,27 +1135,24 @@ static int wino9_launch_one(const cnl_conv_params* p, const void* u9, const floa
     CNL_REQUIRE(!(a.fpart && p->residual), CNL_E_UNSUPPORTED, "cnl_conv3x3_winograd_f32: fuse_w with a residual");
     // the eight instantiations: (plain | residual | folded 1x1) x (plain grid | packed rows) + the row-pair form behind a folded upsample x (plain grid | packed rows)
     static cnl::DeviceOnce once[8];
-    const void* const fns[8] = {reinterpret_cast<const void*>(&winograd9_kernel<false, false, false>), reinterpret_cast<const void*>(&winograd9_kernel<true, false, false>),
-                                reinterpret_cast<const void*>(&winograd9_kernel<false, true, false>), reinterpret_cast<const void*>(&winograd9_kernel<false, false, true>),
-                                reinterpret_cast<const void*>(&winograd9_kernel<true, false, true>), reinterpret_cast<const void*>(&winograd9_kernel<false, true, true>),
-                                reinterpret_cast<const void*>(&winograd9_kernel<false, false, false, true>), reinterpret_cast<const void*>(&winograd9_kernel<false, false, true, true>)};
+    void (*const fns[8])(const Args) = {winograd9_kernel<false, false, false>, winograd9_kernel<true, false, false>, winograd9_kernel<false, true, false>,
+                                        winograd9_kernel<false, false, true>,  winograd9_kernel<true, false, true>,  winograd9_kernel<false, true, true>,
+                                        winograd9_kernel<false, false, false, true>, winograd9_kernel<false, false, true, true>};
     const int which = ur ? (a.pk ? 7 : 6) : (a.fpart ? 2 : (p->residual ? 1 : 0)) + (a.pk ? 3 : 0);
     int n_cu = 0;                          // persistent workgroups: one per CU, walking the work items with stride gridDim.x
-    int rc = cnl::kernel_setup(once[which], fns[which], LDS_BYTES, &n_cu);
+    rc = cnl::kernel_setup(once[which], reinterpret_cast<const void*>(fns[which]), LDS_BYTES, &n_cu);
     if (rc != CNL_OK) return rc;
 #ifdef W9_MAX_CUS      // experiment builds: the persistent grid on fewer CUs (is a power-bound launch any slower on 240 of 256?)
     if (n_cu > W9_MAX_CUS) n_cu = W9_MAX_CUS;
 #endif
-    const unsigned grid = (unsigned)(blocks < (long long)n_cu ? blocks : (long long)n_cu);
-    switch (which) {
-    case 0: hipLaunchKernelGGL((winograd9_kernel<false, false, false>), dim3(grid), dim3(256), LDS_BYTES, (hipStream_t)stream, a); break;
-    case 1: hipLaunchKernelGGL((winograd9_kernel<true, false, false>), dim3(grid), dim3(256), LDS_BYTES, (hipStream_t)stream, a); break;
-    case 2: hipLaunchKernelGGL((winograd9_kernel<false, true, false>), dim3(grid), dim3(256), LDS_BYTES, (hipStream_t)stream, a); break;
-    case 3: hipLaunchKernelGGL((winograd9_kernel<false, false, true>), dim3(grid), dim3(256), LDS_BYTES, (hipStream_t)stream, a); break;
-    case 4: hipLaunchKernelGGL((winograd9_kernel<true, false, true>), dim3(grid), dim3(256), LDS_BYTES, (hipStream_t)stream, a); break;
-    case 5: hipLaunchKernelGGL((winograd9_kernel<false, true, true>), dim3(grid), dim3(256), LDS_BYTES, (hipStream_t)stream, a); break;
-    case 6: hipLaunchKernelGGL((winograd9_kernel<false, false, false, true>), dim3(grid), dim3(256), LDS_BYTES, (hipStream_t)stream, a); break;
-    default: hipLaunchKernelGGL((winograd9_kernel<false, false, true, true>), dim3(grid), dim3(256), LDS_BYTES, (hipStream_t)stream, a); break;
-    }
+    const unsigned grid = (unsigned)(a.blocks < n_cu ? a.blocks : n_cu);
+    hipLaunchKernelGGL(fns[which], dim3(grid), dim3(256), LDS_BYTES, (hipStream_t)stream, a);
     return cnl::check_launch("winograd9_kernel");
+}
+// Launch (arguments already validated by cnl_conv3x3_winograd_f32); xmax = N per-image maxima of the input.
+int cnl_wino9_launch(const cnl_conv_params* p, const void* u9, const float* isu, const float* xmax, void* stream) {
+    const int per = cnl_wino_images_per_launch(p);
+    if (per >= p->N) return wino9_launch_one(p, u9, isu, xmax, stream);
+    CNL_REQUIRE(per == 0 || !p->fuse_w, CNL_E_UNSUPPORTED, "cnl_conv3x3_winograd_f32: fuse_w on a launch whose tensors span >= 4 GiB; split the batch");
+    return cnl_wino_image_groups(p, xmax, [&](const cnl_conv_params* q, const float* xm) { return wino9_launch_one(q, u9, isu, xm, stream); });
 }

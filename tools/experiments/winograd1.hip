@@ -36,15 +36,13 @@
 // (+ residual) (+ ReLU) and stores the 2x2 outputs NHWC with buffer stores (uniform part of the address in the SGPR
 // offset, 64 consecutive channels per 256 bytes).
 // (round 2: kept under experiments/ — superseded by winograd2.hip, bit-identical to it; built only by `make experiments`)
-#include "cnl_common.h"
+#include "cnl_device.h"
+#include "winograd_internal.h"
 #include <cstdlib>
 
 namespace cnl_wino {
+using namespace cnl_dev;
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(3))) void lds_void;
 
 struct WinoArgs {
     const float* x;
@@ -63,7 +61,6 @@ struct WinoArgs {
     long long* trace;                 // CNL_WTRACE builds only: per-wave barrier-wait / chunk-body cycle sums
 };
 
-constexpr unsigned OOB = 0xFFFFFFF0u;
 constexpr int T = 64;                       // tiles per workgroup (8 x 8 -> 16 x 16 output pixels)
 constexpr int BN = 64;                      // output channels per workgroup
 constexpr int PW = 18;                      // patch width / height in pixels
@@ -74,10 +71,6 @@ constexpr int P_SLOTS = 704;                // 684 used; 512 (all waves) + 192 (
 constexpr int P_BYTES = P_SLOTS * 16;       // 11264 per buffer
 constexpr int LDS_BYTES = 2 * V_BYTES + 2 * P_BYTES;                 // 88064: V and the patch; U never touches LDS (see the kernel)
 
-__device__ __forceinline__ void dma16(const float* base, unsigned bytes, char* lds_dst, unsigned voffset, unsigned soffset) {
-    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)bytes, 0x00020000);
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void*)lds_dst, 16, voffset, soffset, 0, 0);
-}
 // same, 1024 bytes further on in BOTH the global source and the LDS destination (the instruction's immediate offset applies to
 // both addresses): saves the VALU add of a second per-lane offset
 __device__ __forceinline__ void dma16_plus1k(const float* base, unsigned bytes, char* lds_dst, unsigned voffset, unsigned soffset) {
@@ -89,14 +82,6 @@ __device__ __forceinline__ f32x4 buf_load16(const float* base, unsigned bytes, u
     typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
     return __builtin_bit_cast(f32x4, (u32x4)__builtin_amdgcn_raw_buffer_load_b128(rsrc, voffset, soffset, 0));
 }
-__device__ __forceinline__ float buf_load(const float* base, unsigned bytes, unsigned voffset, unsigned soffset) {
-    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)bytes, 0x00020000);
-    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc, voffset, soffset, 0));
-}
-__device__ __forceinline__ void buf_store(float v, float* base, unsigned bytes, unsigned voffset, unsigned soffset) {
-    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)bytes, 0x00020000);
-    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rsrc, voffset, soffset, 0);
-}
 __device__ __forceinline__ f32x16 mfma32(float a, float b, f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
 }
@@ -105,7 +90,6 @@ __device__ __forceinline__ f32x16 mfma_zero() {
     return __builtin_amdgcn_mfma_f32_32x32x2f32(0.f, 0.f, z, 0, 0, 0);
 }
 __device__ __forceinline__ float lds_f(const char* p) { return *reinterpret_cast<const float*>(p); }
-__device__ __forceinline__ f32x4 lds_f4(const char* p) { return *reinterpret_cast<const f32x4*>(p); }
 __device__ __forceinline__ f32x2 lds_f2(const char* p) { return *reinterpret_cast<const f32x2*>(p); }
 // packed fp32 add / subtract on a channel pair (the compiler scalarises <2 x float> arithmetic in this kernel)
 __device__ __forceinline__ f32x2 pk_add(f32x2 a, f32x2 b) {
@@ -212,7 +196,6 @@ __global__ __launch_bounds__(512, 2) void winograd_conv_kernel(const WinoArgs a)
     // the 8 MFMAs of one position: k = 0..7 -> c = k >> 1, g = k & 1
 #define WINO_MFMA8(j_, fa_, k_) acc[j_][(k_) & 1] = mfma32((fa_)[(k_) & 1][(k_) >> 1], fbU[j_][(k_) >> 1], acc[j_][(k_) & 1])
     // workgroup barrier WITHOUT the vmcnt(0) that __syncthreads() adds while VMEM -> LDS transfers are in flight
-#define WINO_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 
     // Persistent workgroups (grid = one per CU): the first chunk of the NEXT work item is fetched while the epilogue of the
     // current one runs, so only the very first item of a launch waits for HBM latency with an idle matrix pipe.
@@ -248,7 +231,7 @@ __global__ __launch_bounds__(512, 2) void winograd_conv_kernel(const WinoArgs a)
         else if (a.res) asm volatile("s_waitcnt vmcnt(32)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
         first = false;
-        WINO_BARRIER();
+        CNL_BARRIER();
         {   // input transform of chunk 0 (not overlapped with MFMAs)
             const char* src_ = sP + p_src;
             float d_[4][4], t_[4][4];
@@ -341,7 +324,7 @@ __global__ __launch_bounds__(512, 2) void winograd_conv_kernel(const WinoArgs a)
             WTRACE_PRE();                                                           \
             if (cc > 0) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");            \
             WTRACE_MID();                                                           \
-            WINO_BARRIER();                                                         \
+            CNL_BARRIER();                                                         \
             WTRACE_POST();                                                          \
         } while (0)
         int cc = 0;
@@ -351,7 +334,7 @@ __global__ __launch_bounds__(512, 2) void winograd_conv_kernel(const WinoArgs a)
         }
 #undef WINO_CHUNK
         {   // last chunk: MFMAs only; its B fragments were requested during the previous chunk
-            WINO_BARRIER();
+            CNL_BARRIER();
             const char* vB = sV + (cc & 1) * V_BYTES + fragA;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
@@ -373,7 +356,7 @@ __global__ __launch_bounds__(512, 2) void winograd_conv_kernel(const WinoArgs a)
         const unsigned next = item + gridDim.x;
 #pragma unroll
         for (int g = 0; g < 2; ++g) {
-            WINO_BARRIER();                                    // done reading V (g = 0) or sQ of the previous pass
+            CNL_BARRIER();                                    // done reading V (g = 0) or sQ of the previous pass
             if (g == 1 && next < (unsigned)a.blocks) {         // fetch the next item's first two patches and first B fragments
                 WINO_SETUP(next);
                 WINO_ISSUE_P(0);
@@ -388,7 +371,7 @@ __global__ __launch_bounds__(512, 2) void winograd_conv_kernel(const WinoArgs a)
                 sQ[((wi * 2 + 0) * 32 + tl) * 64 + wh * 32 + (lane & 31)] = m0 + m1 + m2;
                 sQ[((wi * 2 + 1) * 32 + tl) * 64 + wh * 32 + (lane & 31)] = m1 - m2 - m3;
             }
-            WINO_BARRIER();
+            CNL_BARRIER();
             // Stage 2: thread = (tile, co): Y[a][c] = sum_i A^T[a][i] q[i][c]; 4 items per thread
 #pragma unroll
             for (int it = 0; it < 4; ++it) {
@@ -420,8 +403,8 @@ __global__ __launch_bounds__(512, 2) void winograd_conv_kernel(const WinoArgs a)
                 for (int c = 0; c < 2; ++c) {
                     const float ya = q[0][c] + q[1][c] + q[2][c];
                     const float yb = q[1][c] - q[2][c] - q[3][c];
-                    buf_store(fmaxf(ya + bv + rv[0][c], lo), a.y, a.y_bytes, ok[0][c] ? y_voff : OOB, (unsigned)(c * a.ldy * 4));
-                    buf_store(fmaxf(yb + bv + rv[1][c], lo), a.y, a.y_bytes, ok[1][c] ? y_voff : OOB, (unsigned)((a.W + c) * a.ldy * 4));
+                    buf_store<0>(fmaxf(ya + bv + rv[0][c], lo), a.y, a.y_bytes, ok[0][c] ? y_voff : OOB, (unsigned)(c * a.ldy * 4));
+                    buf_store<0>(fmaxf(yb + bv + rv[1][c], lo), a.y, a.y_bytes, ok[1][c] ? y_voff : OOB, (unsigned)((a.W + c) * a.ldy * 4));
                 }
             }
         }

@@ -22,19 +22,15 @@
 // head blocks 64->512 behind the upsample 682-693 (624-637), 152 x 272 x 64 -> 64 + residual 140 (148-150), 64 -> 256 there 457 (430-435)
 // (profiles/r05_experiments.txt r5f).  Three designs — one workgroup with an exposed epilogue (9), two workgroups sharing a CU (10), one
 // workgroup with two accumulator sets (this) — land within 10 % of each other on the 64-channel layers.
-#include "cnl_common.h"
+#include "cnl_device.h"
+#include "winograd_internal.h"
 #include <utility>
 
 #pragma clang fp contract(off)
 
-int cnl_wino_packed_stride(const cnl_conv_params* p);
 namespace cnl_wino12 {
+using namespace cnl_dev;
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 struct Args {
     const float* x;
@@ -59,7 +55,6 @@ struct Args {
     unsigned flags;
 };
 
-constexpr unsigned OOB = 0xFFFFFFF0u;
 constexpr int R = 4;                        // output rows per work item
 constexpr int PR = R + 2;                   // patch rows
 constexpr int TW = 32;                      // tiles (pixel pairs) per row of a work item: 64 output pixels
@@ -81,43 +76,6 @@ constexpr int JOB0 = 6, JOB_SLICES = 12;
 constexpr int BARRIER_SLICE = 40;
 constexpr int NSTG = 4;
 
-__device__ __forceinline__ u32x4 buf_load16(const void* base, unsigned bytes, unsigned voffset, unsigned soffset) {
-    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)bytes, 0x00020000);
-    return (u32x4)__builtin_amdgcn_raw_buffer_load_b128(rsrc, voffset, soffset, 0);
-}
-__device__ __forceinline__ void buf_store16(f32x4 v, float* base, unsigned bytes, unsigned voffset, unsigned soffset) {
-    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)bytes, 0x00020000);
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rsrc, voffset, soffset, CNL_NT_STORES);
-}
-__device__ __forceinline__ f32x16 mfma16(u32x4 a, u32x4 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
-__device__ __forceinline__ unsigned split_hi_lo(float v0, float S) {
-    unsigned pk;
-    asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(pk) : "v"(v0), "v"(S));
-    return pk;
-}
-__device__ __forceinline__ unsigned split_hi_hi(unsigned pk, float v1, float S) {
-    asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(pk) : "v"(v1), "v"(S));
-    return pk;
-}
-__device__ __forceinline__ float split_res_lo(float v, float S, unsigned pk) {
-    float r;
-    asm("v_fma_mix_f32 %0, %1, %2, -%3 op_sel_hi:[0,0,1]" : "=v"(r) : "v"(v), "v"(S), "v"(pk));
-    return r;
-}
-__device__ __forceinline__ float split_res_hi(float v, float S, unsigned pk) {
-    float r;
-    asm("v_fma_mix_f32 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "=v"(r) : "v"(v), "v"(S), "v"(pk));
-    return r;
-}
-__device__ __forceinline__ int lane_now() {
-    unsigned z = 0;
-    asm volatile("" : "+v"(z));
-    return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, z));
-}
-__device__ __forceinline__ f32x4 lds_f4(const char* p) { return *reinterpret_cast<const f32x4*>(p); }
-#define W12_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 
 // ---- the static schedule of a chunk (winograd10.hip's) ----
 constexpr int NSEG = 12;
@@ -300,7 +258,7 @@ __device__ __forceinline__ void slice(State& st, Epi& ep, const EpiLane& el, con
     constexpr int ku = term == 1 ? 1 : 0, kv = term == 0 ? 1 : 0;
     constexpr int vbuf = r % 3;
     if constexpr (S == BARRIER_SLICE || (EPI >= 0 && S == 11)) {      // (11: the exchange writes of the riding epilogue pass are complete)
-        W12_BARRIER();
+        CNL_BARRIER();
         __builtin_amdgcn_sched_barrier(0);
     }
     if constexpr (FIRST && first_use(S)) st.acc[SET][r - ky][nbh] = mfma16(st.fb[ky][nbh][ku], st.vf[vbuf][kv], f32x16{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f});
@@ -603,7 +561,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         for (int i = 0; i < 3; ++i) st.stg[i] = keep[3][i];
         pwrite<1, 0>(st, 1); pwrite<1, 1>(st, 1); pwrite<1, 2>(st, 1);
     }
-    W12_BARRIER();
+    CNL_BARRIER();
     rread<0>(st, 0, 0); rread<1>(st, 0, 0); rread<2>(st, 0, 0); rread<3>(st, 0, 0);
     job_all(st, 0, st.cur.S, std::make_integer_sequence<int, 28>{});
     rread<0>(st, 0, 1); rread<1>(st, 0, 1); rread<2>(st, 0, 1); rread<3>(st, 0, 1);
@@ -653,7 +611,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     {                                                                                                            \
         epi_xwrite<ES_, 0, 0, 0>(st, el, wave); epi_xwrite<ES_, 0, 0, 1>(st, el, wave); epi_xwrite<ES_, 0, 0, 2>(st, el, wave); epi_xwrite<ES_, 0, 0, 3>(st, el, wave); \
         epi_xwrite<ES_, 0, 1, 0>(st, el, wave); epi_xwrite<ES_, 0, 1, 1>(st, el, wave); epi_xwrite<ES_, 0, 1, 2>(st, el, wave); epi_xwrite<ES_, 0, 1, 3>(st, el, wave); \
-        W12_BARRIER();                                                                                           \
+        CNL_BARRIER();                                                                                           \
         W12_LAST_PASS(ES_, 0) W12_LAST_PASS(ES_, 1) W12_LAST_PASS(ES_, 2) W12_LAST_PASS(ES_, 3)                  \
     }
 #define W12_LAST_PASS(ES_, J_)                                                                                   \
@@ -672,7 +630,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         epi_step<RES, 1, 0>(st, ep, lo); epi_step<RES, 1, 1>(st, ep, lo); epi_step<RES, 1, 2>(st, ep, lo); epi_step<RES, 1, 3>(st, ep, lo); \
         epi_step<RES, 1, 4>(st, ep, lo); epi_step<RES, 1, 5>(st, ep, lo); epi_step<RES, 1, 6>(st, ep, lo); epi_step<RES, 1, 7>(st, ep, lo); \
         epi_store<1, 0>(st, a); epi_store<1, 1>(st, a);                                                          \
-        if constexpr (J_ + 1 < R) { W12_BARRIER(); }                                                             \
+        if constexpr (J_ + 1 < R) { CNL_BARRIER(); }                                                             \
     }
     if (last_set == 0) W12_LAST_EPILOGUE(0) else W12_LAST_EPILOGUE(1)
     report(ep);
@@ -686,68 +644,29 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 
 }  // namespace cnl_wino12
 
-bool cnl_wino9_eligible(const cnl_conv_params* p);
-size_t cnl_wino9_weight_bytes(int Cin, int Cout);
-int cnl_wino_images_per_launch(const cnl_conv_params* p);
-void cnl_wino_sub_batch(const cnl_conv_params* p, int n0, int n, cnl_conv_params* q, const float** xmax);
 // this kernel runs exactly four chunks per work item
 bool cnl_wino12_eligible(const cnl_conv_params* p) { return cnl_wino9_eligible(p) && p->Cin == 16 * cnl_wino12::CC && !p->fuse_w; }
 
 static int wino12_launch_one(const cnl_conv_params* p, const void* u9, const float* isu, const float* xmax, void* stream) {
     using namespace cnl_wino12;
     Args a;
-    a.x = p->x; a.u9 = u9; a.xmax = xmax; a.isu = isu; a.ymax = reinterpret_cast<unsigned*>(p->y_absmax);
-    a.bias = p->bias; a.res = p->residual; a.y = p->y;
-    const int upf = (p->flags & CNL_UPSAMPLE_IN) ? 2 : 1;
-    a.Nimg = p->N; a.Hs = p->H_in; a.Ws = p->W_in; a.H = p->H_in * upf; a.W = p->W_in * upf; a.Cin = p->Cin; a.Cout = p->Cout;
-    a.ipb = (upf == 1 && (a.W == 32 || a.W == 16)) ? 64 / a.W : 1;
-    a.lw = a.W == 32 ? 5 : 4;
-    a.N = (p->N + a.ipb - 1) / a.ipb;
-    a.pk = cnl_wino_packed_stride(p);
-    a.m_pk = a.pk ? (unsigned)(0x100000000ull / (unsigned)a.pk) : 0u;
-    if (a.pk) a.N = 1;
-    a.CoutP = (p->Cout + 63) / 64 * 64;
-    a.ldx = p->ldx; a.ldy = p->ldy; a.ldr = p->ldr;
-    a.nb = a.CoutP / BN; a.bx = a.pk ? (int)(((long long)p->N * a.pk + 2 * TW - 1) / (2 * TW)) : (a.W + 2 * TW - 1) / (2 * TW); a.by = (a.H + R - 1) / R;
-    const auto magic = [](int d) { return d == 1 ? 0xFFFFFFFFu : (unsigned)(0x100000000ull / (unsigned)d); };
-    a.m_nb = magic(a.nb); a.m_bx = magic(a.bx); a.m_by = magic(a.by);
-    const long long blocks = (long long)a.N * a.by * a.bx * a.nb;
-    CNL_REQUIRE(blocks < (1ll << 31), CNL_E_UNSUPPORTED, "cnl_conv3x3_winograd_f32: grid too large");
-    a.blocks = (int)blocks;
-    const unsigned long long xb = (((unsigned long long)p->N * p->H_in * p->W_in - 1) * p->ldx + p->Cin) * 4ull;
-    const unsigned long long ub = (unsigned long long)cnl_wino9_weight_bytes(p->Cin, p->Cout);
-    const unsigned long long Mo = (unsigned long long)p->N * a.H * a.W;
-    const unsigned long long yb = ((Mo - 1) * p->ldy + p->Cout) * 4ull;
-    const unsigned long long rb = p->residual ? ((Mo - 1) * p->ldr + p->Cout) * 4ull : 0ull;
-    CNL_REQUIRE(xb < 0xFFFFFF00ull && ub < 0xFFFFFF00ull && yb + 4ull * p->ldy < 0xFFFFFF00ull && rb + 4ull * (p->residual ? p->ldr : 0) < 0xFFFFFF00ull,
-                CNL_E_UNSUPPORTED, "cnl_conv3x3_winograd_f32: tensor spans >= 4 GiB; split the batch");
-    a.x_bytes = (unsigned)xb; a.u_bytes = (unsigned)ub; a.y_bytes = (unsigned)yb; a.r_bytes = (unsigned)rb; a.b_bytes = (unsigned)p->Cout * 4u;
-    a.flags = p->flags;
+    a.u9 = u9;
+    const int upf = (p->flags & CNL_UPSAMPLE_IN) ? 2 : 1, W = p->W_in * upf;
+    a.Hs = p->H_in; a.Ws = p->W_in;
+    a.ipb = (upf == 1 && (W == 32 || W == 16)) ? 64 / W : 1;
+    a.lw = W == 32 ? 5 : 4;
+    int rc = cnl_wino_row_setup(a, p, isu, xmax, {R, 2 * TW, BN, 4}, a.ipb, cnl_wino_packed_stride(p), cnl_wino9_weight_bytes(p->Cin, p->Cout));
+    if (rc != CNL_OK) return rc;
     static cnl::DeviceOnce once[4];
-    const void* const fns[4] = {reinterpret_cast<const void*>(&winograd12_kernel<false, false>), reinterpret_cast<const void*>(&winograd12_kernel<true, false>),
-                                reinterpret_cast<const void*>(&winograd12_kernel<false, true>), reinterpret_cast<const void*>(&winograd12_kernel<true, true>)};
+    void (*const fns[4])(const Args) = {winograd12_kernel<false, false>, winograd12_kernel<true, false>, winograd12_kernel<false, true>, winograd12_kernel<true, true>};
     const int which = (p->residual ? 1 : 0) + (a.pk ? 2 : 0);
     int n_cu = 0;
-    const int rc = cnl::kernel_setup(once[which], fns[which], LDS_BYTES, &n_cu);
+    rc = cnl::kernel_setup(once[which], reinterpret_cast<const void*>(fns[which]), LDS_BYTES, &n_cu);
     if (rc != CNL_OK) return rc;
-    const unsigned grid = (unsigned)(blocks < (long long)n_cu ? blocks : (long long)n_cu);
-    switch (which) {
-    case 0: hipLaunchKernelGGL((winograd12_kernel<false, false>), dim3(grid), dim3(256), LDS_BYTES, (hipStream_t)stream, a); break;
-    case 1: hipLaunchKernelGGL((winograd12_kernel<true, false>), dim3(grid), dim3(256), LDS_BYTES, (hipStream_t)stream, a); break;
-    case 2: hipLaunchKernelGGL((winograd12_kernel<false, true>), dim3(grid), dim3(256), LDS_BYTES, (hipStream_t)stream, a); break;
-    default: hipLaunchKernelGGL((winograd12_kernel<true, true>), dim3(grid), dim3(256), LDS_BYTES, (hipStream_t)stream, a); break;
-    }
+    const unsigned grid = (unsigned)(a.blocks < n_cu ? a.blocks : n_cu);
+    hipLaunchKernelGGL(fns[which], dim3(grid), dim3(256), LDS_BYTES, (hipStream_t)stream, a);
     return cnl::check_launch("winograd12_kernel");
 }
 int cnl_wino12_launch(const cnl_conv_params* p, const void* u9, const float* isu, const float* xmax, void* stream) {
-    const int per = cnl_wino_images_per_launch(p);
-    CNL_REQUIRE(per > 0, CNL_E_UNSUPPORTED, "cnl_conv3x3_winograd_f32: one image of a tensor spans >= 4 GiB");
-    for (int n0 = 0; n0 < p->N; n0 += per) {
-        cnl_conv_params q;
-        const float* xm = xmax;
-        cnl_wino_sub_batch(p, n0, p->N - n0 < per ? p->N - n0 : per, &q, &xm);
-        const int rc = wino12_launch_one(&q, u9, isu, xm, stream);
-        if (rc != CNL_OK) return rc;
-    }
-    return CNL_OK;
+    return cnl_wino_image_groups(p, xmax, [&](const cnl_conv_params* q, const float* xm) { return wino12_launch_one(q, u9, isu, xm, stream); });
 }

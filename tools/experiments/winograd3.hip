@@ -25,7 +25,8 @@
 //     ds_write_b64 per (item, position pair); hand-placed 6 VALU per MFMA slice.
 //   * only the input patch (18x18 px x 16 ch, double-buffered, LDS-DMA two chunks ahead) is shared: ONE barrier per chunk.
 //   * U is pre-split once per weight load (cnl_winograd_transform_weights_f32): [ci/16][position][piece][cout][16 ci] bf16.
-#include "cnl_common.h"
+#include "cnl_device.h"
+#include "winograd_internal.h"
 #include <cstdlib>
 
 #pragma clang fp contract(off)
@@ -54,13 +55,9 @@
 #endif
 
 namespace cnl_wino3 {
+using namespace cnl_dev;
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) void lds_void;
 
 struct Args {
     const float* x;
@@ -79,7 +76,6 @@ struct Args {
     long long* trace;                 // CNL_W3TRACE builds only: per-wave cycle sums of the phases of a work item
 };
 
-constexpr unsigned OOB = 0xFFFFFFF0u;
 constexpr int T = 64;                       // tiles per workgroup: 8 x 8
 constexpr int BN = 64;
 constexpr int PH = 18, PW = 18;             // patch height / width in pixels
@@ -92,22 +88,6 @@ constexpr int P_SLOTS = 1408;               // 1368 used; 5 x 256 (all waves) + 
 constexpr int P_BYTES = P_SLOTS * 16;       // 22528 per buffer (two buffers)
 constexpr int LDS_BYTES = V_BYTES + 2 * P_BYTES;                 // 143360: one workgroup per CU
 
-__device__ __forceinline__ void dma16(const float* base, unsigned bytes, char* lds_dst, unsigned voffset, unsigned soffset) {
-    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)bytes, 0x00020000);
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void*)lds_dst, 16, voffset, soffset, 0, 0);
-}
-__device__ __forceinline__ u32x4 buf_load16(const void* base, unsigned bytes, unsigned voffset, unsigned soffset) {
-    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)bytes, 0x00020000);
-    return (u32x4)__builtin_amdgcn_raw_buffer_load_b128(rsrc, voffset, soffset, 0);
-}
-__device__ __forceinline__ float buf_load(const float* base, unsigned bytes, unsigned voffset, unsigned soffset) {
-    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)bytes, 0x00020000);
-    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc, voffset, soffset, 0));
-}
-__device__ __forceinline__ void buf_store(float v, float* base, unsigned bytes, unsigned voffset, unsigned soffset) {
-    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)bytes, 0x00020000);
-    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rsrc, voffset, soffset, 0);
-}
 __device__ __forceinline__ f32x16 mfma16(u32x4 a, u32x4 b, f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
 }
@@ -116,8 +96,6 @@ __device__ __forceinline__ f32x16 mfma_zero() {
     const u32x4 zz = {0u, 0u, 0u, 0u};
     return mfma16(zz, zz, z);
 }
-__device__ __forceinline__ f32x4 lds_f4(const char* p) { return *reinterpret_cast<const f32x4*>(p); }
-__device__ __forceinline__ u32x4 lds_u4(const char* p) { return *reinterpret_cast<const u32x4*>(p); }
 
 // Registers of one wave's input-transform pipeline.  A "pass-item" = (item: tile, 4 channels) x (pass P: position pair {2P, 2P+1}
 // of the wave's row).  Its 64 VALU operations are indexed 0..63 so that the main loop can place them six per MFMA slice:
@@ -277,7 +255,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             *reinterpret_cast<u32x2*>(sV + dstv + (it_) * 512 + ((2 * (P_) + jj_) * 3 + kk_) * VPIECE) =         \
                 u32x2{xf.pk[jj_][kk_][0], xf.pk[jj_][kk_][1]};
     // workgroup barrier WITHOUT the vmcnt(0) that __syncthreads() adds when LDS-DMA is in flight (own LDS accesses drained)
-#define W3_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 
     // One position slot = 24 MFMAs in 24 slices fenced by sched_barrier(0); every slice carries at most ~6 other instructions.
     //   j_ / buf_    position multiplied in this slot and its fragment buffer
@@ -295,7 +272,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             if ((MID_) && k == 12) {                                                                             \
                 W3T_MID0();                                                                                      \
                 asm volatile("s_waitcnt vmcnt(6)" ::: "memory");   /* all but the newest 6 B loads: the patch DMA is older */ \
-                W3_BARRIER();                                                                                    \
+                CNL_BARRIER();                                                                                    \
                 W3T_MID1();                                                                                      \
                 __builtin_amdgcn_sched_barrier(0);                                                               \
             }                                                                                                    \
@@ -358,7 +335,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         if (first) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(41)" ::: "memory");
         first = false;
-        W3_BARRIER();                                         // ... and everybody's
+        CNL_BARRIER();                                         // ... and everybody's
         W3T(1);
         {   // input transform of chunk 0, all four positions (not overlapped with MFMAs): eight pass-items, each read one ahead
             const char* pa = sP + src_a;
@@ -448,7 +425,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                 }
             }
             W3T(8);
-            W3_BARRIER();                                      // everyone is done reading V / the patches (tg = 0) or sQ
+            CNL_BARRIER();                                      // everyone is done reading V / the patches (tg = 0) or sQ
             W3T(9);
             if (tg == 1 && more) {                             // patch buffers and fragment registers are idle
                 W3_SETUP(next);
@@ -467,7 +444,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                     sQ[(((wave * 2 + 0) * 2 + g) * 32 + tl) * 32 + (lane & 31)] = m0 + m1 + m2;
                     sQ[(((wave * 2 + 1) * 2 + g) * 32 + tl) * 32 + (lane & 31)] = m1 - m2 - m3;
                 }
-            W3_BARRIER();
+            CNL_BARRIER();
             W3T(10);
             // Stage 2: thread = (tile, co): Y[a][c] = sum_i A^T[a][i] q[i][c]; 4 tiles x 2 cout groups per thread and pass
 #pragma unroll
@@ -491,8 +468,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                     for (int c = 0; c < 2; ++c) {
                         const float ya = q[0][c] + q[1][c] + q[2][c];
                         const float yb = q[1][c] - q[2][c] - q[3][c];
-                        buf_store(fmaxf(ya + bv[g] + rv[g][it][0][c], lo), a.y, a.y_bytes, ok[g][it][0][c] ? y_voff[g][it] : OOB, (unsigned)(c * a.ldy * 4));
-                        buf_store(fmaxf(yb + bv[g] + rv[g][it][1][c], lo), a.y, a.y_bytes, ok[g][it][1][c] ? y_voff[g][it] : OOB, (unsigned)((a.W + c) * a.ldy * 4));
+                        buf_store<0>(fmaxf(ya + bv[g] + rv[g][it][0][c], lo), a.y, a.y_bytes, ok[g][it][0][c] ? y_voff[g][it] : OOB, (unsigned)(c * a.ldy * 4));
+                        buf_store<0>(fmaxf(yb + bv[g] + rv[g][it][1][c], lo), a.y, a.y_bytes, ok[g][it][1][c] ? y_voff[g][it] : OOB, (unsigned)((a.W + c) * a.ldy * 4));
                     }
                 }
             }

@@ -15,19 +15,16 @@
 //   every U and V element is still loaded / produced by exactly one wave (no duplicated streams); the only shared data is the
 //   input patch (double-buffered LDS-DMA, ONE barrier per chunk).
 // Weights: the pre-split layout of winograd3.hip.  Same call sites (reference models/meta.py:24-26, models/layers.py:72-77).
-#include "cnl_common.h"
+#include "cnl_device.h"
+#include "winograd_internal.h"
 #include <cstdlib>
 
 #pragma clang fp contract(off)
 
 namespace cnl_wino4 {
+using namespace cnl_dev;
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) void lds_void;
 
 struct Args {
     const float* x;
@@ -45,7 +42,6 @@ struct Args {
     unsigned flags;
 };
 
-constexpr unsigned OOB = 0xFFFFFFF0u;
 constexpr int T = 64;                       // tiles per workgroup: 8 x 8
 constexpr int BN = 64;
 constexpr int PH = 18, PW = 18;             // patch height / width in pixels
@@ -58,22 +54,6 @@ constexpr int P_SLOTS = 1408;               // 1368 used; 2 x 512 (all waves) + 
 constexpr int P_BYTES = P_SLOTS * 16;       // 22528 per buffer (two buffers)
 constexpr int LDS_BYTES = V_BYTES + 2 * P_BYTES;                 // 143360: one workgroup per CU
 
-__device__ __forceinline__ void dma16(const float* base, unsigned bytes, char* lds_dst, unsigned voffset, unsigned soffset) {
-    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)bytes, 0x00020000);
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void*)lds_dst, 16, voffset, soffset, 0, 0);
-}
-__device__ __forceinline__ u32x4 buf_load16(const void* base, unsigned bytes, unsigned voffset, unsigned soffset) {
-    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)bytes, 0x00020000);
-    return (u32x4)__builtin_amdgcn_raw_buffer_load_b128(rsrc, voffset, soffset, 0);
-}
-__device__ __forceinline__ float buf_load(const float* base, unsigned bytes, unsigned voffset, unsigned soffset) {
-    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)bytes, 0x00020000);
-    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc, voffset, soffset, 0));
-}
-__device__ __forceinline__ void buf_store(float v, float* base, unsigned bytes, unsigned voffset, unsigned soffset) {
-    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)bytes, 0x00020000);
-    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rsrc, voffset, soffset, 0);
-}
 __device__ __forceinline__ f32x16 mfma16(u32x4 a, u32x4 b, f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
 }
@@ -82,8 +62,6 @@ __device__ __forceinline__ f32x16 mfma_zero() {
     const u32x4 zz = {0u, 0u, 0u, 0u};
     return mfma16(zz, zz, z);
 }
-__device__ __forceinline__ f32x4 lds_f4(const char* p) { return *reinterpret_cast<const f32x4*>(p); }
-__device__ __forceinline__ u32x4 lds_u4(const char* p) { return *reinterpret_cast<const u32x4*>(p); }
 
 // Registers of the input transform of ONE (item: tile, 4 channels) x (position j of the wave's row).  V[i][j] = t[A] +- t[B] with
 // (A, B) = columns (0,2), (1,2), (2,1), (1,3) of t = (B^T d)[i] for j = 0..3.  The 34 VALU operations are indexed so that the main
@@ -208,7 +186,6 @@ __device__ __forceinline__ void run(const Args& a, char* smem) {
 #define W4_X_WRITE(pl_, it_)                                                                                     \
     _Pragma("unroll") for (int kk_ = 0; kk_ < 3; ++kk_)                                                          \
         *reinterpret_cast<u32x2*>(sV + dstv + (it_) * 512 + ((pl_) * 3 + kk_) * VPIECE) = u32x2{xf.pk[kk_][0], xf.pk[kk_][1]};
-#define W4_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 
     // One position slot = 24 MFMAs of local position pl_ (fragment buffer pl_) in 24 slices fenced by sched_barrier(0).
     //   (cN_, plN_)  the next position: its A fragments go into buffer plN_ (slices 6-11), its cout-group-0 B fragments into the
@@ -262,7 +239,7 @@ __device__ __forceinline__ void run(const Args& a, char* smem) {
         if (first) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(13)" ::: "memory");
         first = false;
-        W4_BARRIER();
+        CNL_BARRIER();
         {   // input transform of chunk 0 for this wave's two positions (the other wave of the SIMD covers the latencies)
             const char* pa = sP + src_a;
             const char* pb = sP + src_b;
@@ -283,7 +260,7 @@ __device__ __forceinline__ void run(const Args& a, char* smem) {
             // patch cn + 1 landed everywhere, patch cn consumed everywhere (its buffer receives patch cn + 2)
             // (cn = 0: the chunk-0 transform above read patch 0)
             asm volatile("s_waitcnt vmcnt(6)" ::: "memory");       /* all but the newest 6 B loads: the patch DMA is older */
-            W4_BARRIER();
+            CNL_BARRIER();
             W4_ISSUE_P(cn + 2);
             const char* pa = sP + ((cn + 1) & 1) * P_BYTES + src_a;
             const char* pb = sP + ((cn + 1) & 1) * P_BYTES + src_b;
@@ -339,7 +316,7 @@ __device__ __forceinline__ void run(const Args& a, char* smem) {
                             rv[it][dy][dx] = buf_load(a.res, a.r_bytes, ok[it][dy][dx] ? r_voff : OOB, (unsigned)((dy * a.W + dx) * a.ldr * 4));
                 }
             }
-            W4_BARRIER();                                      // everyone is done reading V / the patches (ps = 0) or sQ
+            CNL_BARRIER();                                      // everyone is done reading V / the patches (ps = 0) or sQ
             if (ps == 3 && more) {                             // patch buffers and fragment registers are idle
                 W4_SETUP(next);
                 W4_ISSUE_P(0);
@@ -354,7 +331,7 @@ __device__ __forceinline__ void run(const Args& a, char* smem) {
                 sQ[(((wi * 2 + JP) * 2 + 0) * 32 + tl) * 32 + (lane & 31)] = JP == 0 ? ma + mb : ma;
                 sQ[(((wi * 2 + JP) * 2 + 1) * 32 + tl) * 32 + (lane & 31)] = JP == 0 ? mb : -ma - mb;
             }
-            W4_BARRIER();
+            CNL_BARRIER();
             // Stage 2: thread = (tile, co): Y[a][c] = sum_i A^T[a][i] (q[i][0][c] + q[i][1][c]); 2 tiles per thread and pass
 #pragma unroll
             for (int it = 0; it < 2; ++it) {
@@ -369,8 +346,8 @@ __device__ __forceinline__ void run(const Args& a, char* smem) {
                 for (int c = 0; c < 2; ++c) {
                     const float ya = q[0][c] + q[1][c] + q[2][c];
                     const float yb = q[1][c] - q[2][c] - q[3][c];
-                    buf_store(fmaxf(ya + bv[g] + rv[it][0][c], lo), a.y, a.y_bytes, ok[it][0][c] ? y_voff[it] : OOB, (unsigned)(c * a.ldy * 4));
-                    buf_store(fmaxf(yb + bv[g] + rv[it][1][c], lo), a.y, a.y_bytes, ok[it][1][c] ? y_voff[it] : OOB, (unsigned)((a.W + c) * a.ldy * 4));
+                    buf_store<0>(fmaxf(ya + bv[g] + rv[it][0][c], lo), a.y, a.y_bytes, ok[it][0][c] ? y_voff[it] : OOB, (unsigned)(c * a.ldy * 4));
+                    buf_store<0>(fmaxf(yb + bv[g] + rv[it][1][c], lo), a.y, a.y_bytes, ok[it][1][c] ? y_voff[it] : OOB, (unsigned)((a.W + c) * a.ldy * 4));
                 }
             }
         }
@@ -392,7 +369,6 @@ __global__ __launch_bounds__(512) void winograd4_kernel(const Args a) {
 
 }  // namespace cnl_wino4
 
-size_t cnl_wino3_weight_bytes(int Cin, int Cout);      // winograd3.hip
 
 // Launch (arguments already validated by cnl_conv3x3_winograd_f32); u3 = the pre-split weights.
 int cnl_wino4_launch(const cnl_conv_params* p, const void* u3, void* stream) {

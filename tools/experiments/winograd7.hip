@@ -10,19 +10,15 @@
 //   V of a position is produced and consumed by the same wave (private, single-buffered, program order), one (item, position) at
 //   a time: 4 patch reads, 8 fma + 4 add + 10 split operations, one ds_write2st64_b64; the patch is the only shared data (one
 //   barrier per chunk); the eight partial inverse-transform sums of a tile meet through LDS in the epilogue.
-#include "cnl_common.h"
+#include "cnl_device.h"
+#include "winograd_internal.h"
 #include <cstdlib>
 
 #pragma clang fp contract(off)
 
 namespace cnl_wino7 {
+using namespace cnl_dev;
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) void lds_void;
 
 struct Args {
     const float* x;
@@ -44,7 +40,6 @@ struct Args {
     int order;                        // work-item order (see W7_SETUP)
 };
 
-constexpr unsigned OOB = 0xFFFFFFF0u;
 constexpr int T = 64;                       // tiles per workgroup: 8 x 8
 constexpr int BN = 64;
 constexpr int PH = 18, PW = 18;             // patch height / width in pixels
@@ -58,52 +53,6 @@ constexpr int P_SLOTS = 1408;               // 1368 used; 2 x 512 (all waves) + 
 constexpr int P_BYTES = P_SLOTS * 16;       // 22528 per buffer (two buffers)
 constexpr int LDS_BYTES = V_BYTES + 2 * P_BYTES;                 // 110592: one workgroup per CU
 
-__device__ __forceinline__ void dma16(const float* base, unsigned bytes, char* lds_dst, unsigned voffset, unsigned soffset) {
-    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)bytes, 0x00020000);
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void*)lds_dst, 16, voffset, soffset, 0, 0);
-}
-__device__ __forceinline__ u32x4 buf_load16(const void* base, unsigned bytes, unsigned voffset, unsigned soffset) {
-    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)bytes, 0x00020000);
-    return (u32x4)__builtin_amdgcn_raw_buffer_load_b128(rsrc, voffset, soffset, 0);
-}
-__device__ __forceinline__ float buf_load(const float* base, unsigned bytes, unsigned voffset, unsigned soffset) {
-    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)bytes, 0x00020000);
-    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc, voffset, soffset, 0));
-}
-__device__ __forceinline__ void buf_store(float v, float* base, unsigned bytes, unsigned voffset, unsigned soffset) {
-    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)bytes, 0x00020000);
-    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rsrc, voffset, soffset, CNL_NT_STORES);
-}
-__device__ __forceinline__ f32x16 mfma16(u32x4 a, u32x4 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
-// the split of a channel pair (v0, v1), scaled by the power of two S (see winograd5.hip): hi = RN16(v S) packed, r = v S - hi exactly
-__device__ __forceinline__ unsigned split_hi_lo(float v0, float S) {
-    unsigned pk;
-    asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(pk) : "v"(v0), "v"(S));
-    return pk;
-}
-__device__ __forceinline__ unsigned split_hi_hi(unsigned pk, float v1, float S) {
-    asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(pk) : "v"(v1), "v"(S));
-    return pk;
-}
-__device__ __forceinline__ float split_res_lo(float v, float S, unsigned pk) {
-    float r;
-    asm("v_fma_mix_f32 %0, %1, %2, -%3 op_sel_hi:[0,0,1]" : "=v"(r) : "v"(v), "v"(S), "v"(pk));
-    return r;
-}
-__device__ __forceinline__ float split_res_hi(float v, float S, unsigned pk) {
-    float r;
-    asm("v_fma_mix_f32 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "=v"(r) : "v"(v), "v"(S), "v"(pk));
-    return r;
-}
-__device__ __forceinline__ f32x16 mfma_zero() {
-    const f32x16 z = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    const u32x4 zz = {0u, 0u, 0u, 0u};
-    return mfma16(zz, zz, z);
-}
-__device__ __forceinline__ f32x4 lds_f4(const char* p) { return *reinterpret_cast<const f32x4*>(p); }
-__device__ __forceinline__ u32x4 lds_u4(const char* p) { return *reinterpret_cast<const u32x4*>(p); }
 
 // Registers of the input transform of ONE (item: tile, 4 channels) x (position j of the wave's row).  V[i][j] = t[A] +- t[B] with
 // (A, B) = columns (0,2), (1,2), (2,1), (1,3) of t = (B^T d)[i] for j = 0..3.  The 22 VALU operations are indexed so that the main
@@ -242,7 +191,6 @@ __device__ __forceinline__ void run(const Args& a, char* smem) {
 #define W7_X_WRITE(pl_, it_)                                                                                     \
     _Pragma("unroll") for (int kk_ = 0; kk_ < NP; ++kk_)                                                         \
         *reinterpret_cast<u32x2*>(sV + dstv + (it_) * 512 + ((pl_) * NP + kk_) * VPIECE) = u32x2{xf.pk[kk_][0], xf.pk[kk_][1]};
-#define W7_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 
     // One position slot = 12 MFMAs of local position pl_ (fragment buffers pl_) in 12 slices fenced by sched_barrier(0).
     //   (cN_, plN_)  the next position (the wave's other one): its A fragments go into buffer plN_ (slices 2-5) and the B fragments of
@@ -298,7 +246,7 @@ __device__ __forceinline__ void run(const Args& a, char* smem) {
         if (first) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
         first = false;
-        W7_BARRIER();
+        CNL_BARRIER();
         {   // input transform of chunk 0 for this wave's two positions (the other wave of the SIMD covers the latencies)
             const char* pa = sP + src_a;
             const char* pb = sP + src_b;
@@ -319,7 +267,7 @@ __device__ __forceinline__ void run(const Args& a, char* smem) {
             // patch cn + 1 landed everywhere, patch cn consumed everywhere (its buffer receives patch cn + 2)
             // (cn = 0: the chunk-0 transform above read patch 0)
             asm volatile("s_waitcnt vmcnt(4)" ::: "memory");       /* all but the newest 4 B loads: the patch DMA is older */
-            W7_BARRIER();
+            CNL_BARRIER();
             W7_ISSUE_P(cn + 2);
             const char* pa = sP + ((cn + 1) & 1) * P_BYTES + src_a;
             const char* pb = sP + ((cn + 1) & 1) * P_BYTES + src_b;
@@ -376,7 +324,7 @@ __device__ __forceinline__ void run(const Args& a, char* smem) {
                             rv[it][dy][dx] = buf_load(a.res, a.r_bytes, ok[it][dy][dx] ? r_voff : OOB, (unsigned)((dy * a.W + dx) * a.ldr * 4));
                 }
             }
-            W7_BARRIER();                                      // everyone is done reading V / the patches (ps = 0) or sQ
+            CNL_BARRIER();                                      // everyone is done reading V / the patches (ps = 0) or sQ
             if (ps == 3 && more) {                             // patch buffers and fragment registers are idle
                 W7_SETUP(next);
                 W7_ISSUE_P(0);
@@ -391,7 +339,7 @@ __device__ __forceinline__ void run(const Args& a, char* smem) {
                 sQ[(((wi * 2 + JP) * 2 + 0) * 32 + tl) * 32 + (lane & 31)] = JP == 0 ? ma + mb : ma;
                 sQ[(((wi * 2 + JP) * 2 + 1) * 32 + tl) * 32 + (lane & 31)] = JP == 0 ? mb : -ma - mb;
             }
-            W7_BARRIER();
+            CNL_BARRIER();
             // Stage 2: thread = (tile, co): Y[a][c] = sum_i A^T[a][i] (q[i][0][c] + q[i][1][c]); 2 tiles per thread and pass
 #pragma unroll
             for (int it = 0; it < 2; ++it) {
@@ -437,7 +385,6 @@ __global__ __launch_bounds__(512) void winograd7_kernel(const Args a) {
 
 }  // namespace cnl_wino7
 
-size_t cnl_wino5_weight_bytes(int Cin, int Cout);      // winograd5.hip: the weight layout, scales and scalars are shared
 
 namespace cnl_wino7 {
 // per-image max |x| (see winograd5.hip): blockIdx.y = image
