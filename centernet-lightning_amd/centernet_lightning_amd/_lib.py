@@ -58,6 +58,12 @@ class LetterboxFrame(Structure):
                 ("pad_top", c_int32), ("pad_left", c_int32), ("reserved", c_int32)]
 
 
+class MergeView(Structure):
+    """One record of cnl_merge_tiles_f32's `views` table (32 bytes)."""
+    _fields_ = [("frame_w", c_int32), ("frame_h", c_int32), ("x0", c_int32), ("y0", c_int32), ("pad_left", c_int32), ("pad_top", c_int32),
+                ("sx", c_float), ("sy", c_float)]
+
+
 _SIGNATURES = {
     "cnl_version": (ctypes.c_int, []),
     "cnl_sizeof_params": (c_size_t, [ctypes.c_int32]),
@@ -97,6 +103,10 @@ _SIGNATURES = {
     "cnl_resize_bilinear_u8": (ctypes.c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "cnl_letterbox_bilinear_u8": (ctypes.c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_uint32, c_void_p]),
     "cnl_unletterbox_boxes_f32": (ctypes.c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
+    "cnl_merge_tiles_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32]),
+    "cnl_merge_tiles_f32": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                           c_float, c_float, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                           c_size_t, c_void_p]),
     "cnl_stem_conv7x7_u8": (ctypes.c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, POINTER(c_float), POINTER(c_float), c_void_p, c_void_p,
                                            c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "cnl_stem_packed_weight_floats": (c_size_t, []),

@@ -21,6 +21,7 @@ from torch import nn
 
 from . import decode as _decode
 from . import letterbox as _letterbox
+from . import tiles as _tiles
 from .collate import collate_detections
 from .config import model_section
 from .engine import Engine
@@ -234,6 +235,49 @@ class CenterNet(nn.Module):
         dets = gather(out, num_detections=num_detections, nms_kernel=nms_kernel, normalize_bbox=False)
         _letterbox.unletterbox_(dets["bboxes"], geom, True)
         return dets
+
+    # ------------------------------------------------------------------ frames larger than the network input
+    def tile_uint8(self, frames, tile_h: int = 512, tile_w: int = 512, overlap: float = 0.2, full_frame: bool = True, fill=(0, 0, 0)):
+        """uint8 frames -> (views [V,tile_h,tile_w,C] uint8, geom): each frame's overlapping tiles (tile_grid) and, with full_frame, the
+        whole frame letterboxed, gathered by one launch of cnl_letterbox_bilinear_u8; see tiles.tile_uint8."""
+        return _tiles.tile_uint8(frames, tile_h, tile_w, overlap, full_frame, fill)
+
+    def merge_tiles(self, bboxes, scores, labels, geom, **kwargs):
+        """The detections of all views -> per frame, in its own pixels, duplicates removed (cnl_merge_tiles_f32); see tiles.merge_tiles."""
+        return _tiles.merge_tiles(bboxes, scores, labels, geom, **kwargs)
+
+    def detect_tiled(self, frames, tile=(512, 512), overlap: float = 0.2, full_frame: bool = True, batch: int = 32, fill=(0, 0, 0),
+                     mean=IMAGENET_MEAN, std=IMAGENET_STD, num_detections: int = 100, nms_kernel: int = 3, max_detections: int = 300,
+                     score_threshold: float = 0.1, match_threshold: float = 0.5, match_metric: str = "iou", class_aware: bool = True,
+                     max_candidates: int = 4096):
+        """Sliced inference for frames larger than the network input -> {"bboxes" [N,max_detections,4] (each frame's own pixels),
+        "labels", "scores", "count" [N] int32[, "embeddings"]}; rows past a frame's count are zero.
+        tile_uint8 (one launch) -> forward_uint8 + the decode on chunks of at most `batch` views -> one merge over all frames
+        (class-aware greedy NMS, IoU or intersection-over-smaller) -> for tracking models the embeddings of the survivors.
+        Nothing between the frames and the result touches the host except the table upload."""
+        if isinstance(batch, bool) or not isinstance(batch, int) or batch < 1:
+            raise ValueError(f"detect_tiled: batch must be a positive int, got {batch!r}")
+        views, geom = _tiles.tile_uint8(frames, int(tile[0]), int(tile[1]), overlap, full_frame, fill)
+        if views.shape[-1] != 3:
+            raise ValueError(f"detect_tiled expects 3-channel frames, got {views.shape[-1]} channels")
+        parts = []
+        for i in range(0, views.shape[0], batch):
+            out = self.forward_uint8(views[i:i + batch], mean=mean, std=std)
+            gather = self.gather_tracking2d if len(out) == 3 else self.gather_detection2d
+            parts.append(gather(out, num_detections=num_detections, nms_kernel=nms_kernel, normalize_bbox=False))
+        dets = {key: (torch.cat([p[key] for p in parts]) if len(parts) > 1 else parts[0][key]) for key in parts[0]}
+        m = _tiles.merge_tiles(dets["bboxes"], dets["scores"], dets["labels"], geom, max_detections=max_detections,
+                               score_threshold=score_threshold, match_threshold=match_threshold, match_metric=match_metric,
+                               class_aware=class_aware, max_candidates=max_candidates)
+        result = {"bboxes": m["bboxes"], "labels": m["labels"], "scores": m["scores"], "count": m["count"]}
+        if "embeddings" in dets:
+            emb = dets["embeddings"]
+            k, E, N = emb.shape[1], emb.shape[2], m["source"].shape[0]
+            src = m["source"].long()
+            index = (src.clamp_min(0) + geom.first_view[:N].long()[:, None] * k).reshape(-1, 1).expand(-1, E)
+            picked = torch.gather(emb.reshape(-1, E), 0, index).view(N, -1, E)
+            result["embeddings"] = picked.masked_fill((src < 0).unsqueeze(-1), 0.0)          # (not a product: -x * 0 is -0)
+        return result
 
     # ------------------------------------------------------------------ decode (Gen-A names)
     def gather_detection2d(self, heatmap, box_2d=None, num_detections=100, nms_kernel=3, normalize_bbox=False):

@@ -1,0 +1,216 @@
+"""Sliced inference: frames larger than the network input are cut into overlapping network-sized tiles, the tiles run as one batch,
+and the boxes of all views of a frame are merged in the frame's own pixels (duplicates from the overlaps removed on the GPU).
+
+The geometry is host arithmetic on tensor SHAPES (no device sync).  The tile gather is ONE launch of cnl_letterbox_bilinear_u8: a tile
+is a record whose src points inside a frame and whose resize is 1:1 (the kernel then returns the source bytes); the optional full-frame
+view is the plain letterbox record.  The merge is cnl_merge_tiles_f32 (csrc/tile_merge.hip; the rule: include/centernet_gfx950.h).
+"""
+import ctypes
+from typing import List, Tuple
+
+import torch
+
+from . import _lib
+from .letterbox import _fill_word, letterbox_geometry
+
+METRICS = {"iou": 0, "ios": 1}
+
+
+def _axis(size: int, tile: int, overlap: float) -> List[Tuple[int, int]]:
+    """[(start, length)] of the tiles along one axis."""
+    if size <= tile:
+        return [(0, size)]
+    step = tile - round(tile * overlap)
+    n = -(-(size - tile) // step) + 1
+    return [(min(i * step, size - tile), tile) for i in range(n)]
+
+
+def tile_grid(h: int, w: int, tile_h: int = 512, tile_w: int = 512, overlap: float = 0.2) -> List[Tuple[int, int, int, int]]:
+    """[(y0, x0, th, tw)], row-major, of the tiles of an h x w frame.
+
+    Per axis (x shown): ov = round(tile_w * overlap) with Python's round, step = tile_w - ov.  w <= tile_w gives one tile x0 = 0, tw = w
+    (the gather pads it to tile_w on the right).  Otherwise n = ceil((w - tile_w) / step) + 1 tiles of width tile_w at
+    x0_i = min(i * step, w - tile_w): the last tile is shifted back so that every tile lies inside the frame.
+
+    tile_h and tile_w must be positive multiples of 32, overlap in [0, 0.5], h and w at least 1; otherwise ValueError."""
+    for name, v in (("h", h), ("w", w), ("tile_h", tile_h), ("tile_w", tile_w)):
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise ValueError(f"tile_grid: {name} must be an int, got {v!r}")
+    if isinstance(overlap, bool) or not isinstance(overlap, (int, float)) or not 0.0 <= overlap <= 0.5:       # (NaN fails the comparison)
+        raise ValueError(f"tile_grid: overlap must be a number in [0, 0.5], got {overlap!r}")
+    if h < 1 or w < 1:
+        raise ValueError(f"tile_grid: frame size {h} x {w} must be at least 1 x 1")
+    if tile_h < 32 or tile_w < 32 or tile_h % 32 or tile_w % 32:
+        raise ValueError(f"tile_grid: tile {tile_h} x {tile_w} must be positive multiples of 32")
+    return [(y0, x0, th, tw) for (y0, th) in _axis(h, tile_h, overlap) for (x0, tw) in _axis(w, tile_w, overlap)]
+
+
+class TileGeometry:
+    """What tile_uint8 did.  `table`: the device array of cnl_letterbox_frame records, one per view; `merge_table`: the device array of
+    the merge's view records ([V, 8] int32 words: frame_w, frame_h, x0, y0, pad_left, pad_top, and the bits of the floats sx, sy);
+    `first_view`: device int32 [N + 1], frame n owns views first_view[n] .. first_view[n + 1] - 1 (`frame_first_view` is the same list
+    on the host); `views`: the host list of (frame, y0, x0, th, tw) — the full-frame view is (frame, 0, 0, h, w); `sizes`: (h, w) per frame.
+    tile_uint8 is the constructor users need; from_records (below) builds a merge-only geometry for tests and tools."""
+
+    def __init__(self, table, merge_table, first_view, views, frame_first_view, sizes, tile_h, tile_w, keep=()):
+        self.table = table
+        self.merge_table = merge_table
+        self.first_view = first_view
+        self.views = views
+        self.frame_first_view = frame_first_view
+        self.sizes = sizes
+        self.tile_h = tile_h
+        self.tile_w = tile_w
+        self._keep = keep          # the source frames: the table holds their addresses
+
+    @property
+    def num_frames(self):
+        return len(self.frame_first_view) - 1
+
+    def __len__(self):
+        return len(self.views)
+
+    def __repr__(self):
+        return f"TileGeometry(frames={self.num_frames}, views={len(self.views)}, tile={self.tile_h}x{self.tile_w})"
+
+    @classmethod
+    def from_records(cls, records, frame_first_view, device):
+        """Advanced / testing constructor: a geometry for merge_tiles ALONE, from merge records [(frame_w, frame_h, x0, y0, pad_left,
+        pad_top, sx, sy)] and the list frame_first_view (N + 1 entries), for detections that did not come from tile_uint8.  There are no
+        pixels behind it: `table` is None, `sizes` is empty and the `views` entries carry th = tw = 0.  One blocking upload."""
+        import numpy as np
+        V = len(records)
+        ffv = [int(v) for v in frame_first_view]
+        if len(ffv) < 1 or ffv[0] != 0 or ffv[-1] != V or any(b < a for a, b in zip(ffv, ffv[1:])):
+            raise ValueError(f"frame_first_view must run from 0 to {V} without decreasing, got {ffv!r}")
+        rec = np.zeros((V, 8), dtype=np.int32)
+        if V:
+            rec[:, :6] = [[int(x) for x in r[:6]] for r in records]
+            rec[:, 6:] = np.array([[r[6], r[7]] for r in records], dtype=np.float32).view(np.int32)
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("the tile merge runs on HIP devices only (no CPU fallback)")
+        with torch.cuda.device(device):
+            merge_table = torch.from_numpy(rec).to(device)
+            first_view = torch.tensor(ffv, dtype=torch.int32).to(device)
+        views = [(n, int(r[3]), int(r[2]), 0, 0) for n in range(len(ffv) - 1) for r in records[ffv[n]:ffv[n + 1]]]
+        return cls(None, merge_table, first_view, views, ffv, [], 0, 0)
+
+
+def _row_strided(f: torch.Tensor) -> bool:
+    """Can the kernel read this [h, w, C] frame in place?  Pixels and channels packed, rows any positive stride."""
+    h, w, C = f.shape
+    return f.stride(2) == 1 and f.stride(1) == C and (h == 1 or (f.stride(0) >= w * C and f.stride(0) < 2 ** 31))
+
+
+def tile_uint8(frames, tile_h: int = 512, tile_w: int = 512, overlap: float = 0.2, full_frame: bool = True, fill=(0, 0, 0)):
+    """frames: a sequence of uint8 [h_i, w_i, C] tensors on one HIP device (C in 1..4, the same for all; rows may be strided), or one
+    [N, h, w, C] tensor -> (views [V, tile_h, tile_w, C] uint8, TileGeometry).  The views of a frame are its tile_grid tiles, row-major
+    (a frame smaller than a tile is padded with `fill` on the right / bottom), then with full_frame=True the whole frame letterboxed to
+    the tile size.  One launch for all views of all frames; one pinned-memory upload (the tables); no device sync."""
+    import numpy as np
+    if isinstance(frames, torch.Tensor):
+        if frames.dim() != 4:
+            raise ValueError(f"expected a sequence of uint8 [h,w,C] frames or one [N,h,w,C] tensor, got {tuple(frames.shape)}")
+        if not frames.is_cuda:
+            raise RuntimeError("tile_uint8 runs on HIP devices only (no CPU fallback)")
+        frames = list(frames.unbind(0))
+    frames = list(frames)
+    if not frames:
+        raise ValueError("tile_uint8: no frames")
+    for f in frames:
+        if not (isinstance(f, torch.Tensor) and f.is_cuda):
+            raise RuntimeError("tile_uint8 runs on HIP devices only (no CPU fallback)")
+    dev, C = frames[0].device, frames[0].shape[-1] if frames[0].dim() == 3 else -1
+    for f in frames:
+        if f.dtype != torch.uint8 or f.dim() != 3 or f.shape[-1] != C or not 1 <= C <= 4:
+            raise ValueError(f"expected uint8 [h,w,C<=4] frames with one C, got {f.dtype} {tuple(f.shape)}")
+        if f.device != dev:
+            raise ValueError(f"frames live on different devices ({dev}, {f.device})")
+    word = _fill_word(fill, C)
+    frames = [f if _row_strided(f) else f.contiguous() for f in frames]
+    lb, mg, views, ffv, sizes = [], [], [], [0], []
+    one = np.float32(1.0).view(np.int32)
+    for n, f in enumerate(frames):
+        h, w = int(f.shape[0]), int(f.shape[1])
+        stride = int(f.stride(0)) if h > 1 else w * C
+        sizes.append((h, w))
+        for (y0, x0, th, tw) in tile_grid(h, w, tile_h, tile_w, overlap):
+            lb.append((f.data_ptr() + y0 * stride + x0 * C, th, tw, stride, th, tw, 0, 0))
+            mg.append((w, h, x0, y0, 0, 0, one, one))
+            views.append((n, y0, x0, th, tw))
+        if full_frame:
+            nh, nw, pt, pl = letterbox_geometry(h, w, tile_h, tile_w)
+            lb.append((f.data_ptr(), h, w, stride, nh, nw, pt, pl))
+            sx, sy = np.float32(nw) / np.float32(w), np.float32(nh) / np.float32(h)       # as cnl_unletterbox_boxes_f32 forms them
+            mg.append((w, h, 0, 0, pl, pt, sx.view(np.int32), sy.view(np.int32)))
+            views.append((n, 0, 0, h, w))
+        ffv.append(len(views))
+    V, N = len(views), len(frames)
+    # one upload: [V x 5] int64 letterbox records | [V x 4] int64 = [V x 8] int32 merge records | N + 1 int32 (padded to int64)
+    n_ffv = (N + 2) // 2
+    buf = np.zeros(V * 9 + n_ffv, dtype=np.int64)
+    rec = buf[:V * 5].reshape(V, 5)
+    rec[:, 0] = [r[0] for r in lb]
+    rec.view(np.int32).reshape(V, 10)[:, 2:9] = [r[1:] for r in lb]
+    assert rec.nbytes == V * ctypes.sizeof(_lib.LetterboxFrame) and ctypes.sizeof(_lib.MergeView) == 32
+    buf[V * 5:V * 9].view(np.int32).reshape(V, 8)[:] = np.array(mg, dtype=np.int32)
+    buf[V * 9:].view(np.int32)[:N + 1] = ffv
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        host = torch.empty((buf.size,), dtype=torch.int64, pin_memory=True)
+        host.copy_(torch.from_numpy(buf))
+        d = host.to(dev, non_blocking=True)
+        table = d[:V * 5].view(V, 5)
+        merge_table = d[V * 5:V * 9].view(torch.int32).view(V, 8)
+        first_view = d[V * 9:].view(torch.int32)[:N + 1]
+        out = torch.empty((V, tile_h, tile_w, C), device=dev, dtype=torch.uint8)
+        _lib.check(lib.cnl_letterbox_bilinear_u8(table.data_ptr(), out.data_ptr(), V, tile_h, tile_w, C, word,
+                                                 ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "cnl_letterbox_bilinear_u8")
+    return out, TileGeometry(table, merge_table, first_view, views, ffv, sizes, tile_h, tile_w, keep=(frames, d))
+
+
+def merge_tiles(bboxes: torch.Tensor, scores: torch.Tensor, labels: torch.Tensor, geom: TileGeometry, max_detections: int = 300,
+                score_threshold: float = 0.1, match_threshold: float = 0.5, match_metric: str = "iou", class_aware: bool = True,
+                max_candidates: int = 4096):
+    """The decoded detections of all views ([V, k, 4] boxes in view pixels, [V, k] scores, [V, k] int64 labels: gather_* with
+    normalize_bbox=False) -> per frame, in the frame's own pixels and with the duplicates removed:
+    {"bboxes" [N, max_detections, 4], "scores", "labels" (int64), "source" (int32: the candidate number v * k + r relative to the frame's
+    first view, -1 past the count), "count" [N] int32}.  Three launches for the whole batch, no device sync."""
+    for name, t in (("bboxes", bboxes), ("scores", scores), ("labels", labels)):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda):
+            raise RuntimeError(f"merge_tiles: {name} must live on a HIP device (no CPU fallback)")
+    if match_metric not in METRICS:
+        raise ValueError(f"match_metric must be one of {sorted(METRICS)}, got {match_metric!r}")
+    if bboxes.dtype != torch.float32 or bboxes.dim() != 3 or bboxes.shape[-1] != 4 or scores.dtype != torch.float32 or labels.dtype != torch.int64:
+        raise ValueError(f"expected float32 [V,k,4] boxes, float32 [V,k] scores and int64 [V,k] labels, got {bboxes.dtype} {tuple(bboxes.shape)}, "
+                         f"{scores.dtype} {tuple(scores.shape)}, {labels.dtype} {tuple(labels.shape)}")
+    V, k = int(bboxes.shape[0]), int(bboxes.shape[1])
+    if tuple(scores.shape) != (V, k) or tuple(labels.shape) != (V, k):
+        raise ValueError(f"scores {tuple(scores.shape)} and labels {tuple(labels.shape)} must both be [{V}, {k}]")
+    if V != len(geom) or bboxes.device != geom.merge_table.device:
+        raise ValueError(f"detections of {V} views on {bboxes.device} against a geometry of {len(geom)} views on {geom.merge_table.device}")
+    for name, v in (("max_detections", max_detections), ("max_candidates", max_candidates)):
+        if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+            raise ValueError(f"merge_tiles: {name} must be a positive int, got {v!r}")
+    bboxes, scores, labels = bboxes.contiguous(), scores.contiguous(), labels.contiguous()
+    N, dev = geom.num_frames, bboxes.device
+    lib = _lib.load()
+    ws_bytes = int(lib.cnl_merge_tiles_workspace_bytes(N, V, k, max_candidates))
+    if ws_bytes == 0:
+        _lib.check(_lib.CNL_E_BAD_ARG, "cnl_merge_tiles_workspace_bytes")
+    with torch.cuda.device(dev):
+        ws = torch.empty((ws_bytes + 256,), device=dev, dtype=torch.uint8)
+        ws_ptr = (ws.data_ptr() + 255) & ~255
+        out_boxes = torch.empty((N, max_detections, 4), device=dev, dtype=torch.float32)
+        out_scores = torch.empty((N, max_detections), device=dev, dtype=torch.float32)
+        out_labels = torch.empty((N, max_detections), device=dev, dtype=torch.int64)
+        out_source = torch.empty((N, max_detections), device=dev, dtype=torch.int32)
+        out_count = torch.empty((N,), device=dev, dtype=torch.int32)
+        _lib.check(lib.cnl_merge_tiles_f32(bboxes.data_ptr(), scores.data_ptr(), labels.data_ptr(), geom.merge_table.data_ptr(),
+                                           geom.first_view.data_ptr(), N, V, k, max_detections, max_candidates, float(score_threshold),
+                                           float(match_threshold), METRICS[match_metric], int(bool(class_aware)), out_boxes.data_ptr(),
+                                           out_scores.data_ptr(), out_labels.data_ptr(), out_source.data_ptr(), out_count.data_ptr(),
+                                           ws_ptr, ws_bytes, ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
+                   "cnl_merge_tiles_f32")
+    return {"bboxes": out_boxes, "scores": out_scores, "labels": out_labels, "source": out_source, "count": out_count}

@@ -320,6 +320,53 @@ int cnl_letterbox_bilinear_u8(const void* table, uint8_t* out, int32_t N, int32_
 int cnl_unletterbox_boxes_f32(float* boxes, const void* table, int32_t N, int32_t k, int32_t clip, void* stream);
 
 /*
+ * Sliced inference, the merge: the decoded boxes of the V views (network-sized tiles cut out of a frame, plus optionally the whole
+ * frame letterboxed) of N frames go back into each frame's own pixels, and the duplicates the tile overlaps create are removed by a
+ * greedy non-maximum suppression per frame.  Three launches for the whole batch, no device synchronisation, no float atomics.  (The
+ * tiles themselves are cnl_letterbox_bilinear_u8 records whose src points inside a frame, with new_h = h, new_w = w and no pads: a
+ * 1:1 resize returns the source bytes.)
+ *
+ * boxes [V, k, 4] (x1 y1 x2 y2 in view pixels, 16-byte aligned), scores [V, k], labels [V, k] i64: what the decode writes for the V
+ * views with normalize_boxes = 0.  frame_first_view: N + 1 int32 in device memory, non-decreasing, [0] = 0, [N] = V: frame n owns the
+ * views frame_first_view[n] .. frame_first_view[n + 1] - 1.  `views` is a device array of V records, 32 bytes each, 4-byte aligned:
+ *     offset  0  int32 frame_w, frame_h   the size of the frame the view was cut from
+ *     offset  8  int32 x0, y0             where the view's window starts in the frame (0 for the full-frame view)
+ *     offset 16  int32 pad_left, pad_top  the letterbox pads of the view (0 for a tile)
+ *     offset 24  float sx, sy             view pixels per frame pixel: float(new_w) / float(w), float(new_h) / float(h) (1 for a tile)
+ *
+ * The rule, one rounding per operation (a numpy restatement reproduces it bit for bit):
+ *   1. candidate c = v * k + r of a frame (v counted from the frame's first view) takes part if scores[c] > score_threshold (a NaN
+ *      score never does; -0 and +0 are the same score);
+ *   2. its box goes to the frame: x' = (x - pad_left) / sx + float(x0), y' = (y - pad_top) / sy + float(y0), then clamped to
+ *      [0, frame_w] x [0, frame_h] as fminf(fmaxf(v, 0), limit): a NaN coordinate becomes 0 (no NaN reaches the match test);
+ *   3. the frame's candidates are ordered by score descending, equal scores by c ascending;
+ *   4. only the first max_candidates of that order take part (max_candidates in 1..16384);
+ *   5. walking in order, candidate i is kept unless an already kept j matches it: (class_aware == 0 or label_j == label_i) and
+ *      inter > match_threshold * denom, with iw = max(min(x2i, x2j) - max(x1i, x1j), 0), ih alike, inter = iw * ih,
+ *      area = (x2 - x1) * (y2 - y1), denom = (area_i + area_j) - inter for metric 0 (IoU), min(area_i, area_j) for metric 1 (IoS: a
+ *      box cut by a tile edge has a small IoU with the whole box from the neighbouring tile);
+ *   6. the first K_out kept candidates of frame n, in order, are written to out_boxes [N, K_out, 4] (16-byte aligned), out_scores,
+ *      out_labels (i64) and out_source [N, K_out] (the candidate number c, for gathering embeddings); out_count[n] says how many.
+ *      Rows past the count hold score 0, label 0, box 0 and source -1: every output element is written.
+ * A frame's output depends on that frame's views only, not on N or on the launch geometry.
+ *
+ * Limits (CNL_E_BAD_ARG otherwise): N in 0..65535, V >= 0, k >= 1, V * k <= 2^30, K_out >= 1, max_candidates in 1..16384, metric 0 or 1,
+ * thresholds not NaN.  frame_first_view is read on the device and cannot be validated by the call: entries are forced into 0..V and a
+ * decreasing pair gives an empty frame, so nothing is read or written out of bounds; but a table whose frames SHARE views is outside
+ * the contract — the workspace is sized for disjoint frames, and a frame whose bit matrix would not fit in it is written as empty
+ * (out_count 0, all padding).
+ *
+ * ws: cnl_merge_tiles_workspace_bytes(N, V, k, max_candidates) bytes of device memory, 256-byte aligned (0 is returned for sizes the
+ * merge rejects).  N = 0 is a no-op; V = 0 writes N empty frames.
+ */
+size_t cnl_merge_tiles_workspace_bytes(int32_t N, int32_t V, int32_t k, int32_t max_candidates);
+int cnl_merge_tiles_f32(const float* boxes, const float* scores, const int64_t* labels, const void* views,
+                        const int32_t* frame_first_view, int32_t N, int32_t V, int32_t k, int32_t K_out, int32_t max_candidates,
+                        float score_threshold, float match_threshold, int32_t metric, int32_t class_aware, float* out_boxes,
+                        float* out_scores, int64_t* out_labels, int32_t* out_source, int32_t* out_count, void* ws, size_t ws_bytes,
+                        void* stream);
+
+/*
  * ResNet stem: Conv2d(3,64,7,stride=2,padding=3,bias=False)+BN+ReLU (torchvision resnet.conv1/bn1/relu).
  * x is read through explicit element strides (sn,sc,sh,sw) so NCHW-contiguous and channels_last
  * callers are both zero-copy (models/meta.py:97-98 precedent); y is NHWC [N, H/2, W/2, 64].
