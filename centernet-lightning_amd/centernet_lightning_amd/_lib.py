@@ -58,6 +58,13 @@ class LetterboxFrame(Structure):
                 ("pad_top", c_int32), ("pad_left", c_int32), ("reserved", c_int32)]
 
 
+class Yuv420Frame(Structure):
+    """cnl_yuv420_frame: one record of the table cnl_letterbox_yuv420_u8 reads (72 bytes)."""
+    _fields_ = [("y", c_void_p), ("u", c_void_p), ("v", c_void_p), ("y_pitch", c_int32), ("c_pitch", c_int32), ("c_step", c_int32),
+                ("x0", c_int32), ("y0", c_int32), ("h", c_int32), ("w", c_int32), ("new_h", c_int32), ("new_w", c_int32),
+                ("pad_top", c_int32), ("pad_left", c_int32), ("reserved", c_int32)]
+
+
 class MergeView(Structure):
     """One record of cnl_merge_tiles_f32's `views` table (32 bytes)."""
     _fields_ = [("frame_w", c_int32), ("frame_h", c_int32), ("x0", c_int32), ("y0", c_int32), ("pad_left", c_int32), ("pad_top", c_int32),
@@ -102,6 +109,7 @@ _SIGNATURES = {
     "cnl_normalize_u8_nhwc_f32": (ctypes.c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, POINTER(c_float), POINTER(c_float), c_void_p]),
     "cnl_resize_bilinear_u8": (ctypes.c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "cnl_letterbox_bilinear_u8": (ctypes.c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_uint32, c_void_p]),
+    "cnl_letterbox_yuv420_u8": (ctypes.c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, POINTER(c_int32), c_uint32, c_void_p]),
     "cnl_unletterbox_boxes_f32": (ctypes.c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
     "cnl_merge_tiles_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32]),
     "cnl_merge_tiles_f32": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32,

@@ -103,6 +103,28 @@ def _row_strided(f: torch.Tensor) -> bool:
     return f.stride(2) == 1 and f.stride(1) == C and (h == 1 or (f.stride(0) >= w * C and f.stride(0) < 2 ** 31))
 
 
+def _view_records(sizes, tile_h: int, tile_w: int, overlap: float, full_frame: bool):
+    """The views of frames of the given (h, w) sizes -> (windows [(frame, y0, x0, h, w, new_h, new_w, pad_top, pad_left)]: what the
+    gather kernel needs per view, the merge records, TileGeometry.views, frame_first_view).  A tile is a 1:1 window at the canvas'
+    top left; the full-frame view is the whole frame letterboxed."""
+    import numpy as np
+    windows, mg, views, ffv = [], [], [], [0]
+    one = np.float32(1.0).view(np.int32)
+    for n, (h, w) in enumerate(sizes):
+        for (y0, x0, th, tw) in tile_grid(h, w, tile_h, tile_w, overlap):
+            windows.append((n, y0, x0, th, tw, th, tw, 0, 0))
+            mg.append((w, h, x0, y0, 0, 0, one, one))
+            views.append((n, y0, x0, th, tw))
+        if full_frame:
+            nh, nw, pt, pl = letterbox_geometry(h, w, tile_h, tile_w)
+            windows.append((n, 0, 0, h, w, nh, nw, pt, pl))
+            sx, sy = np.float32(nw) / np.float32(w), np.float32(nh) / np.float32(h)       # as cnl_unletterbox_boxes_f32 forms them
+            mg.append((w, h, 0, 0, pl, pt, sx.view(np.int32), sy.view(np.int32)))
+            views.append((n, 0, 0, h, w))
+        ffv.append(len(views))
+    return windows, mg, views, ffv
+
+
 def tile_uint8(frames, tile_h: int = 512, tile_w: int = 512, overlap: float = 0.2, full_frame: bool = True, fill=(0, 0, 0)):
     """frames: a sequence of uint8 [h_i, w_i, C] tensors on one HIP device (C in 1..4, the same for all; rows may be strided), or one
     [N, h, w, C] tensor -> (views [V, tile_h, tile_w, C] uint8, TileGeometry).  The views of a frame are its tile_grid tiles, row-major
@@ -129,23 +151,13 @@ def tile_uint8(frames, tile_h: int = 512, tile_w: int = 512, overlap: float = 0.
             raise ValueError(f"frames live on different devices ({dev}, {f.device})")
     word = _fill_word(fill, C)
     frames = [f if _row_strided(f) else f.contiguous() for f in frames]
-    lb, mg, views, ffv, sizes = [], [], [], [0], []
-    one = np.float32(1.0).view(np.int32)
-    for n, f in enumerate(frames):
-        h, w = int(f.shape[0]), int(f.shape[1])
-        stride = int(f.stride(0)) if h > 1 else w * C
-        sizes.append((h, w))
-        for (y0, x0, th, tw) in tile_grid(h, w, tile_h, tile_w, overlap):
-            lb.append((f.data_ptr() + y0 * stride + x0 * C, th, tw, stride, th, tw, 0, 0))
-            mg.append((w, h, x0, y0, 0, 0, one, one))
-            views.append((n, y0, x0, th, tw))
-        if full_frame:
-            nh, nw, pt, pl = letterbox_geometry(h, w, tile_h, tile_w)
-            lb.append((f.data_ptr(), h, w, stride, nh, nw, pt, pl))
-            sx, sy = np.float32(nw) / np.float32(w), np.float32(nh) / np.float32(h)       # as cnl_unletterbox_boxes_f32 forms them
-            mg.append((w, h, 0, 0, pl, pt, sx.view(np.int32), sy.view(np.int32)))
-            views.append((n, 0, 0, h, w))
-        ffv.append(len(views))
+    sizes = [(int(f.shape[0]), int(f.shape[1])) for f in frames]
+    windows, mg, views, ffv = _view_records(sizes, tile_h, tile_w, overlap, full_frame)
+    lb = []
+    for (n, y0, x0, h, w, nh, nw, pt, pl) in windows:
+        f = frames[n]
+        stride = int(f.stride(0)) if f.shape[0] > 1 else f.shape[1] * C
+        lb.append((f.data_ptr() + y0 * stride + x0 * C, h, w, stride, nh, nw, pt, pl))
     V, N = len(views), len(frames)
     # one upload: [V x 5] int64 letterbox records | [V x 4] int64 = [V x 8] int32 merge records | N + 1 int32 (padded to int64)
     n_ffv = (N + 2) // 2

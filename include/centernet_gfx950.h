@@ -320,6 +320,49 @@ int cnl_letterbox_bilinear_u8(const void* table, uint8_t* out, int32_t N, int32_
 int cnl_unletterbox_boxes_f32(float* boxes, const void* table, int32_t N, int32_t k, int32_t clip, void* stream);
 
 /*
+ * The same canvas from YUV 4:2:0 video surfaces (NV12, I420): colour conversion fused into the letterbox, so that no RGB frame is
+ * ever written.  One launch for N frames of different sizes; the result is bit for bit cnl_letterbox_bilinear_u8 (C = 3) applied
+ * to the frames converted by the rule below.
+ *
+ * `table` is a device array of N records, one per frame (or per tile: a tile is a window), 72 bytes each, 8-byte aligned:
+ *     offset  0  const void* y, u, v      first byte of the Y plane and the first U and V samples (uint8, device memory)
+ *     offset 24  int32 y_pitch, c_pitch   bytes from one row to the next in the Y plane / in the chroma plane(s)
+ *     offset 32  int32 c_step             bytes from one chroma sample to the next: 2 with v = u + 1 for NV12 (interleaved UV), 1 for I420
+ *     offset 36  int32 x0, y0             where the window starts in the frame (odd origins are legal)
+ *     offset 44  int32 h, w               size of the window, >= 1 (the whole frame: x0 = y0 = 0 and the frame's size)
+ *     offset 52  int32 new_h, new_w       size of the resized window inside the canvas, 1..height / 1..width
+ *     offset 60  int32 pad_top, pad_left  where it starts: pad_top + new_h <= height, pad_left + new_w <= width
+ *     offset 68  int32 reserved           0
+ * The frame itself has even height and width; its chroma planes are half its size.  Window pixel (sy, sx) is Y byte
+ * y[(y0 + sy) * y_pitch + x0 + sx] with the chroma sample at row (y0 + sy) >> 1, column (x0 + sx) >> 1 (nearest chroma: what OpenCV's
+ * cvtColor(COLOR_YUV2RGB_NV12 / _I420) does).  The resize taps are clamped to the window, as cnl_letterbox_bilinear_u8 clamps to its frame.
+ *
+ * coef: six int32 in HOST memory, {y_off, CY, CVR, CVG, CUG, CUB}.  In 32-bit integers, >> an arithmetic shift, sat8 a clamp to 0..255:
+ *     yy = max(0, Y - y_off) * CY + (1 << 19)
+ *     R = sat8((yy + CVR * (V - 128)) >> 20),  G = sat8((yy + CVG * (V - 128) + CUG * (U - 128)) >> 20),  B = sat8((yy + CUB * (U - 128)) >> 20)
+ * OpenCV's BT.601 limited-range constants are {16, 1220542, 1673527, -852492, -409993, 2116026}; the library knows no colour
+ * standard, the host chooses the integers.  CNL_E_UNSUPPORTED for a set that could overflow 32 bits: y_off in 0..255, CY >= 0 and
+ * 255 * CY + 2^19 + 128 * max(|CVR|, |CVG| + |CUG|, |CUB|) < 2^31 are required.
+ *
+ * out: [N, height, width, 3] RGB u8, height and width positive multiples of 32, 4-byte aligned; outside a window byte c of every pixel
+ * is bits 8c..8c+7 of fill_rgba.  Every byte is written exactly once; a frame's result depends on its record only.  N = 0 is a no-op.
+ */
+typedef struct cnl_yuv420_frame {
+    const void* y;
+    const void* u;
+    const void* v;
+    int32_t y_pitch, c_pitch;
+    int32_t c_step;
+    int32_t x0, y0;
+    int32_t h, w;
+    int32_t new_h, new_w;
+    int32_t pad_top, pad_left;
+    int32_t reserved;
+} cnl_yuv420_frame;
+int cnl_letterbox_yuv420_u8(const void* table, uint8_t* out, int32_t N, int32_t height, int32_t width, const int32_t* coef,
+                            uint32_t fill_rgba, void* stream);
+
+/*
  * Sliced inference, the merge: the decoded boxes of the V views (network-sized tiles cut out of a frame, plus optionally the whole
  * frame letterboxed) of N frames go back into each frame's own pixels, and the duplicates the tile overlaps create are removed by a
  * greedy non-maximum suppression per frame.  Three launches for the whole batch, no device synchronisation, no float atomics.  (The
