@@ -1,0 +1,85 @@
+"""The one host path into the gather launch (csrc/letterbox.hip) that letterbox_uint8, tile_uint8, letterbox_yuv420 and tile_yuv420
+share: what they check of uint8 frames, and records -> one pinned upload -> one launch.  No device sync anywhere."""
+import ctypes
+from typing import NamedTuple, Optional
+
+import torch
+
+from . import _lib
+
+
+def require_hip(tensors, what: str) -> None:
+    for t in tensors:
+        if not (isinstance(t, torch.Tensor) and t.is_cuda):
+            raise RuntimeError(f"{what} runs on HIP devices only (no CPU fallback)")
+
+
+def uint8_frames(frames, what: str):
+    """A sequence of uint8 [h_i, w_i, C] tensors on one HIP device, C in 1..4 and the same for all -> (list of them, device, C)."""
+    frames = list(frames)
+    if not frames:
+        raise ValueError(f"{what}: no frames")
+    require_hip(frames, what)
+    dev, C = frames[0].device, frames[0].shape[-1] if frames[0].dim() == 3 else -1
+    for f in frames:
+        if f.dtype != torch.uint8 or f.dim() != 3 or f.shape[-1] != C or not 1 <= C <= 4:
+            raise ValueError(f"expected uint8 [h,w,C<=4] frames with one C, got {f.dtype} {tuple(f.shape)}")
+        if f.device != dev:
+            raise ValueError(f"frames live on different devices ({dev}, {f.device})")
+    return frames, dev, C
+
+
+class Gathered(NamedTuple):
+    """What gather returns: the canvas and views of the one uploaded device buffer (None for the parts that were not asked for)."""
+    canvas: torch.Tensor                         # [V, height, width, C] uint8
+    table: torch.Tensor                          # [V, 5] int64: cnl_letterbox_frame records
+    yuv_table: Optional[torch.Tensor]            # [V, 9] int64: cnl_yuv420_frame records
+    merge_table: Optional[torch.Tensor]          # [V, 8] int32: the merge's view records
+    first_view: Optional[torch.Tensor]           # [N + 1] int32
+
+
+def gather(dev, windows, plain, height: int, width: int, C: int, word: int, planes=None, coef=None, merge_records=None,
+           frame_first_view=None) -> Gathered:
+    """One pinned upload and one launch for the V windows [(frame, y0, x0, h, w, new_h, new_w, pad_top, pad_left)].
+
+    plain[i] = (address, row stride) of window i as a packed frame: its cnl_letterbox_frame record, which the launch reads unless
+    `planes` is given and unletterbox reads in any case.  planes[i] = (y, u, v addresses, y_pitch, c_pitch, c_step) of window i with
+    the six integers `coef`: the cnl_yuv420_frame records, and cnl_letterbox_yuv420_u8 is the launch.  merge_records ([V x 8] int32
+    words) and frame_first_view (N + 1 entries): the tables of a tiled gather.  The buffer is [V x 9] int64 YUV records | [V x 5] int64
+    plain records | [V x 4] int64 merge records | N + 1 int32 (padded to int64), absent parts left out."""
+    import numpy as np
+    V = len(windows)
+    n_first = len(frame_first_view) if merge_records is not None else 0
+    o_plain = V * 9 if planes is not None else 0
+    o_merge = o_plain + V * 5
+    o_first = o_merge + (V * 4 if merge_records is not None else 0)
+    buf = np.zeros(o_first + (n_first + 1) // 2, dtype=np.int64)
+    assert ctypes.sizeof(_lib.Yuv420Frame) == 72 and ctypes.sizeof(_lib.LetterboxFrame) == 40 and ctypes.sizeof(_lib.MergeView) == 32
+    rec = buf[o_plain:o_merge].reshape(V, 5)                      # cnl_letterbox_frame: 8-byte pointer + 8 int32
+    rec[:, 0] = [address for (address, _) in plain]
+    rec.view(np.int32).reshape(V, 10)[:, 2:9] = [(h, w, stride, nh, nw, pt, pl)
+                                                 for (_, _, _, h, w, nh, nw, pt, pl), (_, stride) in zip(windows, plain)]
+    if planes is not None:
+        rec = buf[:o_plain].reshape(V, 9)                         # cnl_yuv420_frame: 3 pointers + 12 int32
+        rec[:, :3] = [p[:3] for p in planes]
+        rec.view(np.int32).reshape(V, 18)[:, 6:17] = [tuple(p[3:]) + (x0, y0, h, w, nh, nw, pt, pl)
+                                                      for p, (_, y0, x0, h, w, nh, nw, pt, pl) in zip(planes, windows)]
+    if merge_records is not None:
+        buf[o_merge:o_first].view(np.int32).reshape(V, 8)[:] = np.array(merge_records, dtype=np.int32)
+        buf[o_first:].view(np.int32)[:n_first] = frame_first_view
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        host = torch.empty((buf.size,), dtype=torch.int64, pin_memory=True)
+        host.copy_(torch.from_numpy(buf))
+        d = host.to(dev, non_blocking=True)
+        out = Gathered(canvas=torch.empty((V, height, width, C), device=dev, dtype=torch.uint8),
+                       table=d[o_plain:o_merge].view(V, 5),
+                       yuv_table=d[:o_plain].view(V, 9) if planes is not None else None,
+                       merge_table=d[o_merge:o_first].view(torch.int32).view(V, 8) if merge_records is not None else None,
+                       first_view=d[o_first:].view(torch.int32)[:n_first] if merge_records is not None else None)
+        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        # the two entry points differ in one argument: the six colour integers where the packed one takes C
+        entry, table, c = (("cnl_letterbox_yuv420_u8", out.yuv_table, (ctypes.c_int32 * 6)(*coef)) if planes is not None else
+                           ("cnl_letterbox_bilinear_u8", out.table, C))
+        _lib.check(getattr(lib, entry)(table.data_ptr(), out.canvas.data_ptr(), V, height, width, c, word, stream), entry)
+    return out

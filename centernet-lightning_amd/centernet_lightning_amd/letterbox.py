@@ -9,7 +9,7 @@ from typing import List, Sequence, Tuple
 
 import torch
 
-from . import _lib
+from . import _gather, _lib
 
 
 def letterbox_geometry(h: int, w: int, height: int, width: int) -> Tuple[int, int, int, int]:
@@ -38,10 +38,13 @@ def letterbox_geometry(h: int, w: int, height: int, width: int) -> Tuple[int, in
 
 class LetterboxGeometry:
     """What letterbox_uint8 did to each frame: `table` is the device array of cnl_letterbox_frame records the kernels read,
-    `frames` the host-side list of (h, w, new_h, new_w, pad_top, pad_left), `height` / `width` the canvas size."""
+    `frames` the host-side list of (h, w, new_h, new_w, pad_top, pad_left), `height` / `width` the canvas size; `yuv_table` is the
+    device array of cnl_yuv420_frame records letterbox_yuv420's launch read, None for packed frames."""
 
-    def __init__(self, table: torch.Tensor, frames: List[Tuple[int, int, int, int, int, int]], height: int, width: int, keep=()):
+    def __init__(self, table: torch.Tensor, frames: List[Tuple[int, int, int, int, int, int]], height: int, width: int, keep=(),
+                 yuv_table=None):
         self.table = table
+        self.yuv_table = yuv_table
         self.frames = frames
         self.height = height
         self.width = width
@@ -67,46 +70,22 @@ def _fill_word(fill, C: int) -> int:
 def letterbox_uint8(frames, height: int, width: int, fill=(0, 0, 0)):
     """frames: a sequence of uint8 [h_i, w_i, C] tensors on one HIP device (C in 1..4, the same for all), or one [N, h, w, C] tensor
     -> (canvas [N, height, width, C] uint8, LetterboxGeometry).  One launch; one pinned-memory upload (the table); no device sync."""
-    import numpy as np
     if isinstance(frames, torch.Tensor):
         if frames.dim() != 4:
             raise ValueError(f"expected a sequence of uint8 [h,w,C] frames or one [N,h,w,C] tensor, got {tuple(frames.shape)}")
-        if not frames.is_cuda:
-            raise RuntimeError("letterbox_uint8 runs on HIP devices only (no CPU fallback)")
+        _gather.require_hip([frames], "letterbox_uint8")
         if frames.dtype != torch.uint8:
             raise ValueError(f"expected uint8 frames, got {frames.dtype}")
-        frames = list(frames.contiguous().unbind(0))
-    frames = list(frames)
-    if not frames:
-        raise ValueError("letterbox_uint8: no frames")
-    for f in frames:
-        if not (isinstance(f, torch.Tensor) and f.is_cuda):
-            raise RuntimeError("letterbox_uint8 runs on HIP devices only (no CPU fallback)")
-    dev, C = frames[0].device, frames[0].shape[-1] if frames[0].dim() == 3 else -1
-    for f in frames:
-        if f.dtype != torch.uint8 or f.dim() != 3 or f.shape[-1] != C or not 1 <= C <= 4:
-            raise ValueError(f"expected uint8 [h,w,C<=4] frames with one C, got {f.dtype} {tuple(f.shape)}")
-        if f.device != dev:
-            raise ValueError(f"frames live on different devices ({dev}, {f.device})")
+        frames = frames.contiguous().unbind(0)
+    frames, dev, C = _gather.uint8_frames(frames, "letterbox_uint8")
     height, width = int(height), int(width)
     geo = [(f.shape[0], f.shape[1]) + letterbox_geometry(f.shape[0], f.shape[1], height, width) for f in frames]
     word = _fill_word(fill, C)
     frames = [f.contiguous() for f in frames]
-    N = len(frames)
-    rec = np.zeros((N, 5), dtype=np.int64)                       # cnl_letterbox_frame: 8-byte pointer + 8 int32
-    rec[:, 0] = [f.data_ptr() for f in frames]
-    i32 = rec.view(np.int32).reshape(N, 10)
-    i32[:, 2:9] = [(h, w, w * C, nh, nw, pt, pl) for (h, w, nh, nw, pt, pl) in geo]
-    assert rec.nbytes == N * ctypes.sizeof(_lib.LetterboxFrame)
-    lib = _lib.load()
-    with torch.cuda.device(dev):
-        host = torch.empty((N, 5), dtype=torch.int64, pin_memory=True)
-        host.copy_(torch.from_numpy(rec))
-        table = host.to(dev, non_blocking=True)
-        canvas = torch.empty((N, height, width, C), device=dev, dtype=torch.uint8)
-        _lib.check(lib.cnl_letterbox_bilinear_u8(table.data_ptr(), canvas.data_ptr(), N, height, width, C, word,
-                                                 ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "cnl_letterbox_bilinear_u8")
-    return canvas, LetterboxGeometry(table, geo, height, width, keep=frames)
+    windows = [(n, 0, 0) + g for n, g in enumerate(geo)]
+    plain = [(f.data_ptr(), f.shape[1] * C) for f in frames]
+    g = _gather.gather(dev, windows, plain, height, width, C, word)
+    return g.canvas, LetterboxGeometry(g.table, geo, height, width, keep=frames)
 
 
 def unletterbox_(bboxes: torch.Tensor, geom: LetterboxGeometry, clip: bool = True) -> torch.Tensor:

@@ -10,7 +10,7 @@ from typing import List, Tuple
 
 import torch
 
-from . import _lib
+from . import _gather, _lib
 from .letterbox import _fill_word, letterbox_geometry
 
 METRICS = {"iou": 0, "ios": 1}
@@ -49,11 +49,13 @@ class TileGeometry:
     """What tile_uint8 did.  `table`: the device array of cnl_letterbox_frame records, one per view; `merge_table`: the device array of
     the merge's view records ([V, 8] int32 words: frame_w, frame_h, x0, y0, pad_left, pad_top, and the bits of the floats sx, sy);
     `first_view`: device int32 [N + 1], frame n owns views first_view[n] .. first_view[n + 1] - 1 (`frame_first_view` is the same list
-    on the host); `views`: the host list of (frame, y0, x0, th, tw) — the full-frame view is (frame, 0, 0, h, w); `sizes`: (h, w) per frame.
+    on the host); `views`: the host list of (frame, y0, x0, th, tw) — the full-frame view is (frame, 0, 0, h, w); `sizes`: (h, w) per frame;
+    `yuv_table`: the device array of cnl_yuv420_frame records tile_yuv420's launch read, None for packed frames.
     tile_uint8 is the constructor users need; from_records (below) builds a merge-only geometry for tests and tools."""
 
-    def __init__(self, table, merge_table, first_view, views, frame_first_view, sizes, tile_h, tile_w, keep=()):
+    def __init__(self, table, merge_table, first_view, views, frame_first_view, sizes, tile_h, tile_w, keep=(), yuv_table=None):
         self.table = table
+        self.yuv_table = yuv_table
         self.merge_table = merge_table
         self.first_view = first_view
         self.views = views
@@ -130,56 +132,20 @@ def tile_uint8(frames, tile_h: int = 512, tile_w: int = 512, overlap: float = 0.
     [N, h, w, C] tensor -> (views [V, tile_h, tile_w, C] uint8, TileGeometry).  The views of a frame are its tile_grid tiles, row-major
     (a frame smaller than a tile is padded with `fill` on the right / bottom), then with full_frame=True the whole frame letterboxed to
     the tile size.  One launch for all views of all frames; one pinned-memory upload (the tables); no device sync."""
-    import numpy as np
     if isinstance(frames, torch.Tensor):
         if frames.dim() != 4:
             raise ValueError(f"expected a sequence of uint8 [h,w,C] frames or one [N,h,w,C] tensor, got {tuple(frames.shape)}")
-        if not frames.is_cuda:
-            raise RuntimeError("tile_uint8 runs on HIP devices only (no CPU fallback)")
-        frames = list(frames.unbind(0))
-    frames = list(frames)
-    if not frames:
-        raise ValueError("tile_uint8: no frames")
-    for f in frames:
-        if not (isinstance(f, torch.Tensor) and f.is_cuda):
-            raise RuntimeError("tile_uint8 runs on HIP devices only (no CPU fallback)")
-    dev, C = frames[0].device, frames[0].shape[-1] if frames[0].dim() == 3 else -1
-    for f in frames:
-        if f.dtype != torch.uint8 or f.dim() != 3 or f.shape[-1] != C or not 1 <= C <= 4:
-            raise ValueError(f"expected uint8 [h,w,C<=4] frames with one C, got {f.dtype} {tuple(f.shape)}")
-        if f.device != dev:
-            raise ValueError(f"frames live on different devices ({dev}, {f.device})")
+        _gather.require_hip([frames], "tile_uint8")
+        frames = frames.unbind(0)
+    frames, dev, C = _gather.uint8_frames(frames, "tile_uint8")
     word = _fill_word(fill, C)
     frames = [f if _row_strided(f) else f.contiguous() for f in frames]
     sizes = [(int(f.shape[0]), int(f.shape[1])) for f in frames]
     windows, mg, views, ffv = _view_records(sizes, tile_h, tile_w, overlap, full_frame)
-    lb = []
-    for (n, y0, x0, h, w, nh, nw, pt, pl) in windows:
-        f = frames[n]
-        stride = int(f.stride(0)) if f.shape[0] > 1 else f.shape[1] * C
-        lb.append((f.data_ptr() + y0 * stride + x0 * C, h, w, stride, nh, nw, pt, pl))
-    V, N = len(views), len(frames)
-    # one upload: [V x 5] int64 letterbox records | [V x 4] int64 = [V x 8] int32 merge records | N + 1 int32 (padded to int64)
-    n_ffv = (N + 2) // 2
-    buf = np.zeros(V * 9 + n_ffv, dtype=np.int64)
-    rec = buf[:V * 5].reshape(V, 5)
-    rec[:, 0] = [r[0] for r in lb]
-    rec.view(np.int32).reshape(V, 10)[:, 2:9] = [r[1:] for r in lb]
-    assert rec.nbytes == V * ctypes.sizeof(_lib.LetterboxFrame) and ctypes.sizeof(_lib.MergeView) == 32
-    buf[V * 5:V * 9].view(np.int32).reshape(V, 8)[:] = np.array(mg, dtype=np.int32)
-    buf[V * 9:].view(np.int32)[:N + 1] = ffv
-    lib = _lib.load()
-    with torch.cuda.device(dev):
-        host = torch.empty((buf.size,), dtype=torch.int64, pin_memory=True)
-        host.copy_(torch.from_numpy(buf))
-        d = host.to(dev, non_blocking=True)
-        table = d[:V * 5].view(V, 5)
-        merge_table = d[V * 5:V * 9].view(torch.int32).view(V, 8)
-        first_view = d[V * 9:].view(torch.int32)[:N + 1]
-        out = torch.empty((V, tile_h, tile_w, C), device=dev, dtype=torch.uint8)
-        _lib.check(lib.cnl_letterbox_bilinear_u8(table.data_ptr(), out.data_ptr(), V, tile_h, tile_w, C, word,
-                                                 ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "cnl_letterbox_bilinear_u8")
-    return out, TileGeometry(table, merge_table, first_view, views, ffv, sizes, tile_h, tile_w, keep=(frames, d))
+    strides = [int(f.stride(0)) if f.shape[0] > 1 else f.shape[1] * C for f in frames]
+    plain = [(frames[n].data_ptr() + y0 * strides[n] + x0 * C, strides[n]) for (n, y0, x0, *_) in windows]
+    g = _gather.gather(dev, windows, plain, tile_h, tile_w, C, word, merge_records=mg, frame_first_view=ffv)
+    return g.canvas, TileGeometry(g.table, g.merge_table, g.first_view, views, ffv, sizes, tile_h, tile_w, keep=frames)
 
 
 def merge_tiles(bboxes: torch.Tensor, scores: torch.Tensor, labels: torch.Tensor, geom: TileGeometry, max_detections: int = 300,

@@ -1,7 +1,7 @@
 """YUV 4:2:0 video surfaces (NV12 from hardware decoders, I420 from software decoders) straight to the network-sized RGB canvas.
 
 letterbox_yuv420 is letterbox_uint8 and tile_yuv420 is tile_uint8 for frames that are still Y / U / V planes: the colour conversion is
-fused into the resize taps of ONE launch of cnl_letterbox_yuv420_u8 (csrc/letterbox_yuv.hip), so no RGB frame is written.  The result
+fused into the resize taps of ONE launch of cnl_letterbox_yuv420_u8 (csrc/letterbox.hip), so no RGB frame is written.  The result
 is bit for bit "convert with the integer rule of include/centernet_gfx950.h, then letterbox_uint8 / tile_uint8".  The planes are read
 in place, whatever their row pitch.
 
@@ -11,13 +11,12 @@ A frame is given as
     (c) (y [h, w], u [h / 2, w / 2], v [h / 2, w / 2]): I420 planes
 and `frames` is a sequence of such frames (or one [N, h * 3 / 2, w] tensor: N equal frames of form (a)).
 """
-import ctypes
 from fractions import Fraction
 from typing import Tuple
 
 import torch
 
-from . import _lib
+from . import _gather
 from .letterbox import LetterboxGeometry, _fill_word, letterbox_geometry
 from .tiles import TileGeometry, _view_records
 
@@ -133,9 +132,7 @@ def _parse(frames, layout: str, what: str):
 
 def _device(parsed, what: str):
     """The one HIP device all frames live on."""
-    for p in parsed:
-        if not p[0].is_cuda:
-            raise RuntimeError(f"{what} runs on HIP devices only (no CPU fallback)")
+    _gather.require_hip([p[0] for p in parsed], what)
     dev = parsed[0][0].device
     for p in parsed:
         if p[0].device != dev:
@@ -143,34 +140,11 @@ def _device(parsed, what: str):
     return dev
 
 
-def _gather(dev, parsed, windows, height: int, width: int, coef, word: int, extra_i64):
-    """One pinned upload ([V x 9] int64 cnl_yuv420_frame records | [V x 5] int64 cnl_letterbox_frame records | extra_i64) and one launch
-    for the V windows [(frame, y0, x0, h, w, new_h, new_w, pad_top, pad_left)] -> (canvas [V, height, width, 3], the device buffer)."""
-    import numpy as np
-    V = len(windows)
-    buf = np.zeros(V * 14 + len(extra_i64), dtype=np.int64)
-    yuv, lb = buf[:V * 9].reshape(V, 9), buf[V * 9:V * 14].reshape(V, 5)
-    assert yuv.nbytes == V * ctypes.sizeof(_lib.Yuv420Frame) and lb.nbytes == V * ctypes.sizeof(_lib.LetterboxFrame)
-    rows, plain = [], []
-    for (n, y0, x0, h, w, nh, nw, pt, pl) in windows:
-        y, u, v, yp, cp, step, _, _ = parsed[n]
-        yuv_ptrs = (y.data_ptr(), u.data_ptr(), v.data_ptr())
-        rows.append((yuv_ptrs, (yp, cp, step, x0, y0, h, w, nh, nw, pt, pl)))
-        plain.append((y.data_ptr() + y0 * yp + x0, (h, w, yp, nh, nw, pt, pl)))      # the window's Y plane as a one-channel frame
-    yuv[:, :3] = [r[0] for r in rows]
-    yuv.view(np.int32).reshape(V, 18)[:, 6:17] = [r[1] for r in rows]
-    lb[:, 0] = [r[0] for r in plain]
-    lb.view(np.int32).reshape(V, 10)[:, 2:9] = [r[1] for r in plain]
-    buf[V * 14:] = extra_i64
-    lib = _lib.load()
-    with torch.cuda.device(dev):
-        host = torch.empty((buf.size,), dtype=torch.int64, pin_memory=True)
-        host.copy_(torch.from_numpy(buf))
-        d = host.to(dev, non_blocking=True)
-        out = torch.empty((V, height, width, 3), device=dev, dtype=torch.uint8)
-        _lib.check(lib.cnl_letterbox_yuv420_u8(d.data_ptr(), out.data_ptr(), V, height, width, (ctypes.c_int32 * 6)(*coef), word,
-                                               ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "cnl_letterbox_yuv420_u8")
-    return out, d
+def _records(parsed, windows):
+    """What _gather.gather needs per window besides the window: the window's Y plane as a one-channel packed frame, and the planes."""
+    plain = [(parsed[n][0].data_ptr() + y0 * parsed[n][3] + x0, parsed[n][3]) for (n, y0, x0, *_) in windows]
+    planes = [(y.data_ptr(), u.data_ptr(), v.data_ptr(), yp, cp, step) for (y, u, v, yp, cp, step, _, _) in (parsed[w[0]] for w in windows)]
+    return plain, planes
 
 
 def letterbox_yuv420(frames, height: int, width: int, layout: str = "nv12", matrix: str = "bt601", full_range: bool = False, fill=(0, 0, 0)):
@@ -185,9 +159,9 @@ def letterbox_yuv420(frames, height: int, width: int, layout: str = "nv12", matr
     word = _fill_word(fill, 3)
     dev = _device(parsed, "letterbox_yuv420")
     windows = [(n, 0, 0) + g for n, g in enumerate(geo)]
-    N = len(parsed)
-    canvas, d = _gather(dev, parsed, windows, height, width, coef, word, [])
-    return canvas, LetterboxGeometry(d[N * 9:N * 14].view(N, 5), geo, height, width, keep=(parsed, d))
+    plain, planes = _records(parsed, windows)
+    g = _gather.gather(dev, windows, plain, height, width, 3, word, planes=planes, coef=coef)
+    return g.canvas, LetterboxGeometry(g.table, geo, height, width, keep=parsed, yuv_table=g.yuv_table)
 
 
 def tile_yuv420(frames, tile_h: int = 512, tile_w: int = 512, overlap: float = 0.2, full_frame: bool = True, fill=(0, 0, 0),
@@ -195,19 +169,12 @@ def tile_yuv420(frames, tile_h: int = 512, tile_w: int = 512, overlap: float = 0
     """tile_uint8 for YUV 4:2:0 frames -> (views [V, tile_h, tile_w, 3] uint8 RGB, TileGeometry): the tile_grid tiles of every frame
     (windows into its planes; an odd origin takes the chroma sample of its 2 x 2 block) and, with full_frame, the whole frame
     letterboxed, converted and gathered by one launch.  merge_tiles takes the geometry as it takes tile_uint8's."""
-    import numpy as np
     coef = yuv_coefficients(matrix, full_range)
     parsed = _parse(frames, layout, "tile_yuv420")
     word = _fill_word(fill, 3)
     sizes = [(p[6], p[7]) for p in parsed]
     windows, mg, views, ffv = _view_records(sizes, tile_h, tile_w, overlap, full_frame)
     dev = _device(parsed, "tile_yuv420")
-    V, N = len(views), len(parsed)
-    extra = np.zeros(V * 4 + (N + 2) // 2, dtype=np.int64)                # [V x 8] int32 merge records | N + 1 int32 (padded to int64)
-    extra[:V * 4].view(np.int32).reshape(V, 8)[:] = np.array(mg, dtype=np.int32)
-    extra[V * 4:].view(np.int32)[:N + 1] = ffv
-    out, d = _gather(dev, parsed, windows, tile_h, tile_w, coef, word, extra)
-    table = d[V * 9:V * 14].view(V, 5)
-    merge_table = d[V * 14:V * 18].view(torch.int32).view(V, 8)
-    first_view = d[V * 18:].view(torch.int32)[:N + 1]
-    return out, TileGeometry(table, merge_table, first_view, views, ffv, sizes, tile_h, tile_w, keep=(parsed, d))
+    plain, planes = _records(parsed, windows)
+    g = _gather.gather(dev, windows, plain, tile_h, tile_w, 3, word, planes=planes, coef=coef, merge_records=mg, frame_first_view=ffv)
+    return g.canvas, TileGeometry(g.table, g.merge_table, g.first_view, views, ffv, sizes, tile_h, tile_w, keep=parsed, yuv_table=g.yuv_table)

@@ -1,24 +1,39 @@
-// letterbox.hip — the batch entry for frames of DIFFERENT sizes, and the way back for the decoded boxes.
+// letterbox.hip — the batch entry for frames of DIFFERENT sizes, from packed uint8 HWC frames or straight from YUV 4:2:0 video surfaces
+// (NV12 / I420), and the way back for the decoded boxes.
 //
-//   letterbox_kernel     N uint8 HWC frames, each with its own size, -> one [N, height, width, C] canvas: keep-aspect bilinear resize
-//                        (albumentations LongestMaxSize = cv2.resize INTER_LINEAR, the 8-bit fixed-point rule of preprocess.hip's
-//                        resize_bilinear_u8_kernel, bit for bit) centred on a constant border (PadIfNeeded(position="center",
-//                        border_mode=BORDER_CONSTANT)), in ONE launch that writes every canvas byte exactly once.
-//   unletterbox_kernel   decoded boxes in canvas pixels -> each frame's own pixels, in place.
+//   letterbox_kernel<Source>   N frames (or windows of frames: tiles), each with its own size, -> one [N, height, width, C] canvas:
+//                              keep-aspect bilinear resize (albumentations LongestMaxSize = cv2.resize INTER_LINEAR, the 8-bit fixed-point
+//                              rule of preprocess.hip's resize_bilinear_u8_kernel, bit for bit) centred on a constant border
+//                              (PadIfNeeded(position="center", border_mode=BORDER_CONSTANT)), in ONE launch that writes every canvas
+//                              byte exactly once.  ONE body; what a source pixel is comes from the Source policy:
+//       PackedSource<C>        cnl_letterbox_frame records: C-channel bytes, C in 1..4
+//       Yuv420Source           cnl_yuv420_frame records: Y / U / V planes, converted to RGB on the resize's taps in registers by the
+//                              integer rule of include/centernet_gfx950.h (OpenCV's cvtColor arithmetic, nearest chroma), so the RGB
+//                              frame between the decoder and the network is never written; bit for bit PackedSource<3> on the
+//                              converted frames
+//   unletterbox_kernel         decoded boxes in canvas pixels -> each frame's own pixels, in place.
 //
 // The reference does this on the host, one image at a time (configs/centernet.yaml val_data.transforms; datasets/inference.py carries
 // original_height / original_width), and therefore validates at batch size 1.
 //
 // Decomposition of letterbox_kernel (a pure streaming kernel: 2 source rows read per output row, no reuse worth staging):
-//   grid.y = frame, grid.x = (block of LB_ROWS canvas rows) x (column tile of <= 1024 canvas columns).  A frame is never one workgroup's
+//   grid.y = record, grid.x = (block of LB_ROWS canvas rows) x (column tile of <= 1024 canvas columns).  A frame is never one workgroup's
 //   job: a 1080p frame and a 7 x 5 frame in one batch cost the same number of equally sized workgroups (the canvas is what is tiled).
-//   The frame's record is read through a uniform pointer (scalar loads).  The per-column terms (source byte offset, the two 11-bit
-//   weights) are the same for every row of a frame and the per-row terms for every column: both are computed once per workgroup into
-//   LDS — fp64 multiply, floor and two roundings per COLUMN instead of per pixel — and read back as one 32-byte LDS read per thread.
-//   A thread owns 4 neighbouring canvas pixels = C whole 32-bit words (3 words at C = 3, one 16-byte store at C = 4): width % 32 == 0
-//   keeps every row word-aligned, so no byte store exists.  The two source pixels of a tap are one unaligned 8-byte load (sx*C .. +2C-1,
-//   the start pulled back so the load never leaves the row; rows shorter than 8 bytes take byte loads), and the 8 loads of a thread's
-//   group are issued together.  Measured rate and what limits it: DESIGN.md §12.
+//   The record is read through a uniform pointer (scalar loads).  The per-column terms (the source column as the policy addresses it,
+//   the two 11-bit weights) are the same for every row of a frame and the per-row terms for every column: both are computed once per
+//   workgroup into LDS — fp64 multiply, floor and two roundings per COLUMN instead of per pixel — and read back as one 32-byte LDS read
+//   per thread.  A thread owns 4 neighbouring canvas pixels = C whole 32-bit words (3 words at C = 3, one 16-byte store at C = 4):
+//   width % 32 == 0 keeps every row word-aligned, so no byte store exists.
+// A Source policy supplies: Frame (its record; both carry h, w, new_h, new_w, pad_top, pad_left), Params (kernel arguments of its own),
+//   C, column(sx) (what the column table keeps for source column sx), load() (ALL loads of a thread's 4-pixel group, issued together
+//   before the first is used) and taps() (pixel p's four tap values, channel c at bits 8c: upper-left, upper-right, lower-left,
+//   lower-right).  The format is a template parameter: no branch on it exists at run time.
+//   Packed: the two source pixels of a tap are one unaligned 8-byte load (sx*C .. +2C-1, the start pulled back so the load never leaves
+//   the row; rows shorter than 8 bytes take byte loads): 8 loads per thread.  YUV: a tap is one Y byte load and its chroma sample (one
+//   2-byte load for NV12's interleaved UV, two byte loads for I420): 32 / 48 loads per thread, 1.5 bytes per source pixel instead of 3.
+//   Measured rates and what limits them: DESIGN.md §12, §15.
+#include <algorithm>
+#include <cstdlib>
 #include "cnl_common.h"
 
 #pragma clang fp contract(off)   // OpenCV rounds (dx + 0.5) * scale and the subtraction separately
@@ -29,11 +44,13 @@ constexpr int LB_THREADS = 256;
 constexpr int LB_ROWS = 8;           // canvas rows per workgroup
 constexpr int LB_TILE_GROUPS = 256;  // 4-pixel groups per column tile (1024 canvas columns)
 
-typedef cnl_letterbox_frame Frame;   // include/centernet_gfx950.h (40 bytes)
+typedef unsigned short u16_unaligned __attribute__((aligned(1)));
 typedef unsigned long long u64_unaligned __attribute__((aligned(1)));
 // the frames' pointers come out of the table, so the compiler cannot tell their address space: name it (global_load, not flat_load)
 typedef const __attribute__((address_space(1))) unsigned char* gbytes;
+typedef const __attribute__((address_space(1))) u16_unaligned* gpairs;
 typedef const __attribute__((address_space(1))) u64_unaligned* gwords;
+static_assert(sizeof(cnl_yuv420_frame) == 72, "cnl_yuv420_frame is 72 bytes");
 
 // resize_bilinear_u8_kernel's coefficient rule for one axis position
 __device__ __forceinline__ void axis_coef(int d, double scale, int& s, float& f) {
@@ -42,14 +59,130 @@ __device__ __forceinline__ void axis_coef(int d, double scale, int& s, float& f)
     f -= (float)s;
 }
 
-template <int C>
-__global__ __launch_bounds__(LB_THREADS) void letterbox_kernel(const Frame* __restrict__ table, unsigned char* __restrict__ out, int height,
-                                                               int width, unsigned fill, int tiles_x, int groups_per_tile) {
-    // col: .x = source byte offset of the left tap within a row (-1: border), .y = a0 | a1 << 16
+// packed C-channel bytes (cnl_letterbox_frame, 40 bytes); the column table keeps the byte offset of the left tap within a row
+template <int CH>
+struct PackedSource {
+    static constexpr int C = CH;
+    typedef cnl_letterbox_frame Frame;
+    struct Params {};
+    struct Taps {
+        unsigned long long t0[4], t1[4];         // per pixel, upper / lower source row; bytes 0..C-1: left tap, C..2C-1: right tap
+    };
+    const Frame& f;
+    const gbytes src;
+    const int row_bytes;                         // bytes of a source row that belong to the frame (row_stride may be larger)
+    const bool wide;
+
+    __device__ __forceinline__ PackedSource(const Frame& f, const Params&) : f(f), src((gbytes)f.src), row_bytes(f.w * C), wide(row_bytes >= 8) {}
+    static __device__ __forceinline__ int column(int sx) { return sx * C; }
+
+    // a border pixel (c4[p].x < 0) reads its row's first bytes; the caller drops them
+    __device__ __forceinline__ void load(int y0, int y1, const int2 (&c4)[4], Taps& t) const {
+        const gbytes r0 = src + (size_t)y0 * f.row_stride;
+        const gbytes r1 = src + (size_t)y1 * f.row_stride;
+        if (wide) {
+#pragma unroll
+            for (int p = 0; p < 4; ++p) {
+                const int x0 = max(c4[p].x, 0), o = min(x0, row_bytes - 8);
+                t.t0[p] = *(gwords)(r0 + o);
+                t.t1[p] = *(gwords)(r1 + o);
+            }
+#pragma unroll
+            for (int p = 0; p < 4; ++p) {
+                const int x0 = max(c4[p].x, 0), sh = (x0 - min(x0, row_bytes - 8)) * 8;
+                t.t0[p] >>= sh;
+                t.t1[p] >>= sh;
+            }
+        } else {
+            for (int p = 0; p < 4; ++p) {
+                const int x0 = max(c4[p].x, 0);
+                t.t0[p] = t.t1[p] = 0;
+                for (int b = 0; b < 2 * C && x0 + b < row_bytes; ++b) {
+                    t.t0[p] |= (unsigned long long)r0[x0 + b] << (8 * b);
+                    t.t1[p] |= (unsigned long long)r1[x0 + b] << (8 * b);
+                }
+            }
+        }
+    }
+    // at the last column the right tap's bytes are zeros shifted in: its weight a1 is 0 there
+    __device__ __forceinline__ void taps(const Taps& t, int p, unsigned (&v)[4]) const {
+        v[0] = (unsigned)t.t0[p];
+        v[1] = (unsigned)(t.t0[p] >> (8 * C));
+        v[2] = (unsigned)t.t1[p];
+        v[3] = (unsigned)(t.t1[p] >> (8 * C));
+    }
+};
+
+// YUV 4:2:0 planes (cnl_yuv420_frame, 72 bytes): the record's window (x0, y0, h, w) lies inside the frame, and chroma is addressed in
+// FRAME coordinates; the column table keeps the window column of the left tap
+struct Yuv420Source {
+    static constexpr int C = 3;
+    typedef cnl_yuv420_frame Frame;
+    struct Params {
+        int y_off, cy, cvr, cvg, cug, cub;
+    };
+    struct Taps {
+        int Y[4][4], UV[4][4];                   // [pixel][tap]; UV = U | V << 8
+    };
+    const Frame& f;
+    const Params& k;
+    const gbytes yp, up, vp;
+    const bool interleaved;                      // NV12: U and V in one 2-byte load
+
+    __device__ __forceinline__ Yuv420Source(const Frame& f, const Params& k)
+        : f(f), k(k), yp((gbytes)f.y), up((gbytes)f.u), vp((gbytes)f.v),
+          interleaved(f.c_step == 2 && f.v == (const void*)((const unsigned char*)f.u + 1)) {}
+    static __device__ __forceinline__ int column(int sx) { return sx; }
+
+    // a border pixel reads its row's first column; the caller drops it.  The right tap of the window's last column is the left tap
+    // again: its weight a1 is 0 there.
+    __device__ __forceinline__ void load(int y0, int y1, const int2 (&c4)[4], Taps& t) const {
+        const int fy0 = f.y0 + y0, fy1 = f.y0 + y1;                     // the two source rows, in frame coordinates
+        const gbytes y0r = yp + (size_t)fy0 * f.y_pitch, y1r = yp + (size_t)fy1 * f.y_pitch;
+        const size_t c0r = (size_t)(fy0 >> 1) * f.c_pitch, c1r = (size_t)(fy1 >> 1) * f.c_pitch;
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+            const int sx = max(c4[p].x, 0);
+            const int xl = f.x0 + sx, xr = f.x0 + min(sx + 1, f.w - 1);
+            const int cl = (xl >> 1) * f.c_step, cr = (xr >> 1) * f.c_step;
+            t.Y[p][0] = y0r[xl];
+            t.Y[p][1] = y0r[xr];
+            t.Y[p][2] = y1r[xl];
+            t.Y[p][3] = y1r[xr];
+            if (interleaved) {
+                t.UV[p][0] = *(gpairs)(up + c0r + cl);
+                t.UV[p][1] = *(gpairs)(up + c0r + cr);
+                t.UV[p][2] = *(gpairs)(up + c1r + cl);
+                t.UV[p][3] = *(gpairs)(up + c1r + cr);
+            } else {
+                t.UV[p][0] = up[c0r + cl] | (vp[c0r + cl] << 8);
+                t.UV[p][1] = up[c0r + cr] | (vp[c0r + cr] << 8);
+                t.UV[p][2] = up[c1r + cl] | (vp[c1r + cl] << 8);
+                t.UV[p][3] = up[c1r + cr] | (vp[c1r + cr] << 8);
+            }
+        }
+    }
+    static __device__ __forceinline__ unsigned sat8(int v) { return (unsigned)min(max(v, 0), 255); }
+    // one source pixel -> R | G << 8 | B << 16
+    __device__ __forceinline__ unsigned yuv_to_rgb(int Y, int U, int V) const {
+        const int yy = max(Y - k.y_off, 0) * k.cy + (1 << 19), u = U - 128, v = V - 128;
+        return sat8((yy + k.cvr * v) >> 20) | (sat8((yy + k.cvg * v + k.cug * u) >> 20) << 8) | (sat8((yy + k.cub * u) >> 20) << 16);
+    }
+    __device__ __forceinline__ void taps(const Taps& t, int p, unsigned (&v)[4]) const {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) v[q] = yuv_to_rgb(t.Y[p][q], t.UV[p][q] & 255, t.UV[p][q] >> 8);
+    }
+};
+
+template <class Source>
+__global__ __launch_bounds__(LB_THREADS) void letterbox_kernel(const typename Source::Frame* __restrict__ table, unsigned char* __restrict__ out,
+                                                               int height, int width, typename Source::Params params, unsigned fill,
+                                                               int tiles_x, int groups_per_tile) {
+    constexpr int C = Source::C;
+    // col: .x = Source::column of the left tap's source column (-1: border), .y = a0 | a1 << 16
     __shared__ __attribute__((aligned(16))) int2 col[LB_TILE_GROUPS * 4];
     __shared__ int4 row[LB_ROWS];                // .x = y0 (-1: border row), .y = y1, .z = b0, .w = b1
-    const Frame f = table[blockIdx.y];           // uniform address: scalar loads
-    const gbytes src = (gbytes)f.src;
+    const typename Source::Frame f = table[blockIdx.y];          // uniform address: scalar loads
     const int tile = (int)(blockIdx.x % (unsigned)tiles_x), rblk = (int)(blockIdx.x / (unsigned)tiles_x);
     const int groups = width >> 2;
     const int g_begin = tile * groups_per_tile, g_end = min(groups, g_begin + groups_per_tile);
@@ -69,7 +202,7 @@ __global__ __launch_bounds__(LB_THREADS) void letterbox_kernel(const Frame* __re
             if (sx < 0) { fx = 0.f; sx = 0; }
             if (sx >= f.w - 1) { fx = 0.f; sx = f.w - 1; }
             const int a0 = (short)__float2int_rn((1.f - fx) * 2048.f), a1 = (short)__float2int_rn(fx * 2048.f);
-            e = make_int2(sx * C, (a0 & 0xffff) | (a1 << 16));
+            e = make_int2(Source::column(sx), (a0 & 0xffff) | (a1 << 16));
         }
         col[i] = e;
     }
@@ -79,7 +212,7 @@ __global__ __launch_bounds__(LB_THREADS) void letterbox_kernel(const Frame* __re
         if (dy >= 0 && dy < f.new_h) {
             int sy;
             float fy;
-            axis_coef(dy, scale_y, sy, fy);       // fy is not clamped: the two source rows are clipped to the image instead
+            axis_coef(dy, scale_y, sy, fy);       // fy is not clamped: the two source rows are clipped to the frame (window) instead
             e.x = min(max(sy, 0), f.h - 1);
             e.y = min(max(sy + 1, 0), f.h - 1);
             e.z = (short)__float2int_rn((1.f - fy) * 2048.f);
@@ -89,8 +222,7 @@ __global__ __launch_bounds__(LB_THREADS) void letterbox_kernel(const Frame* __re
     }
     __syncthreads();
 
-    const int row_bytes = f.w * C;               // bytes of a source row that belong to the frame (row_stride may be larger)
-    const bool wide = row_bytes >= 8;
+    const Source source(f, params);
     unsigned char* const canvas = out + (size_t)blockIdx.y * height * width * C;
     const int items = n_rows * n_groups;
     for (int i = threadIdx.x; i < items; i += LB_THREADS) {
@@ -100,44 +232,20 @@ __global__ __launch_bounds__(LB_THREADS) void letterbox_kernel(const Frame* __re
 #pragma unroll
         for (int p = 0; p < 4; ++p) px[p] = fill;
         if (rc.x >= 0) {
-            const gbytes r0 = src + (size_t)rc.x * f.row_stride;
-            const gbytes r1 = src + (size_t)rc.y * f.row_stride;
             const int4 c01 = reinterpret_cast<const int4*>(col)[g * 2], c23 = reinterpret_cast<const int4*>(col)[g * 2 + 1];
             const int2 c4[4] = {make_int2(c01.x, c01.y), make_int2(c01.z, c01.w), make_int2(c23.x, c23.y), make_int2(c23.z, c23.w)};
-            // all eight loads of the group are issued before the first is used; a border pixel reads its row's first bytes and drops them
-            unsigned long long t0[4], t1[4];     // bytes 0..C-1: left tap, C..2C-1: right tap
-            if (wide) {
-#pragma unroll
-                for (int p = 0; p < 4; ++p) {
-                    const int x0 = max(c4[p].x, 0), o = min(x0, row_bytes - 8);
-                    t0[p] = *(gwords)(r0 + o);
-                    t1[p] = *(gwords)(r1 + o);
-                }
-#pragma unroll
-                for (int p = 0; p < 4; ++p) {
-                    const int x0 = max(c4[p].x, 0), sh = (x0 - min(x0, row_bytes - 8)) * 8;
-                    t0[p] >>= sh;
-                    t1[p] >>= sh;
-                }
-            } else {
-                for (int p = 0; p < 4; ++p) {
-                    const int x0 = max(c4[p].x, 0);
-                    t0[p] = t1[p] = 0;
-                    for (int b = 0; b < 2 * C && x0 + b < row_bytes; ++b) {
-                        t0[p] |= (unsigned long long)r0[x0 + b] << (8 * b);
-                        t1[p] |= (unsigned long long)r1[x0 + b] << (8 * b);
-                    }
-                }
-            }
+            typename Source::Taps loaded;
+            source.load(rc.x, rc.y, c4, loaded);
 #pragma unroll
             for (int p = 0; p < 4; ++p) {
                 const int a0 = (short)(c4[p].y & 0xffff), a1 = c4[p].y >> 16;
-                // at the last column the right tap's bytes are zeros shifted in: its weight a1 is 0 there
+                unsigned t[4];
+                source.taps(loaded, p, t);
                 unsigned v4 = 0;
 #pragma unroll
                 for (int c = 0; c < C; ++c) {
-                    const int d0 = (int)((t0[p] >> (8 * c)) & 255u) * a0 + (int)((t0[p] >> (8 * (c + C))) & 255u) * a1;
-                    const int d1 = (int)((t1[p] >> (8 * c)) & 255u) * a0 + (int)((t1[p] >> (8 * (c + C))) & 255u) * a1;
+                    const int d0 = (int)((t[0] >> (8 * c)) & 255u) * a0 + (int)((t[1] >> (8 * c)) & 255u) * a1;
+                    const int d1 = (int)((t[2] >> (8 * c)) & 255u) * a0 + (int)((t[3] >> (8 * c)) & 255u) * a1;
                     const int v = (((rc.z * (d0 >> 4)) >> 16) + ((rc.w * (d1 >> 4)) >> 16) + 2) >> 2;
                     v4 |= (unsigned)min(max(v, 0), 255) << (8 * c);
                 }
@@ -156,10 +264,11 @@ __global__ __launch_bounds__(LB_THREADS) void letterbox_kernel(const Frame* __re
 }
 
 // boxes [N, k, 4] (x1 y1 x2 y2) in canvas pixels -> the frame's own pixels, in place; one thread per box (one 16-byte load and store)
-__global__ __launch_bounds__(256) void unletterbox_kernel(float4* __restrict__ boxes, const Frame* __restrict__ table, int N, int k, int clip) {
+__global__ __launch_bounds__(256) void unletterbox_kernel(float4* __restrict__ boxes, const cnl_letterbox_frame* __restrict__ table, int N, int k,
+                                                          int clip) {
     const long total = (long)N * k;
     for (long t = (long)blockIdx.x * 256 + threadIdx.x; t < total; t += (long)gridDim.x * 256) {
-        const Frame& f = table[t / k];
+        const cnl_letterbox_frame& f = table[t / k];
         const float sx = (float)f.new_w / (float)f.w, sy = (float)f.new_h / (float)f.h;
         const float pl = (float)f.pad_left, pt = (float)f.pad_top;
         float4 b = boxes[t];
@@ -178,37 +287,65 @@ __global__ __launch_bounds__(256) void unletterbox_kernel(float4* __restrict__ b
     }
 }
 
-template <int C>
-static int launch(const void* table, uint8_t* out, int N, int height, int width, unsigned fill, hipStream_t stream) {
+// what both gather entry points require of the canvas, and then (the YUV entry checks its coefficients in between) of the pointers;
+// `entry` names the one that was called
+static int check_canvas(const char* entry, int N, int height, int width, int C) {
+    CNL_REQUIRE(N >= 0 && N <= 65535, CNL_E_BAD_ARG, "%s: N = %d outside 0..65535", entry, N);
+    CNL_REQUIRE(C >= 1 && C <= 4, CNL_E_BAD_ARG, "%s: C = %d outside 1..4", entry, C);
+    CNL_REQUIRE(height > 0 && width > 0 && height % 32 == 0 && width % 32 == 0, CNL_E_BAD_ARG,
+                "%s: canvas %d x %d is not a positive multiple of 32", entry, height, width);
+    CNL_REQUIRE((long)height * width * C <= 0x7fffffffL, CNL_E_BAD_ARG, "%s: the canvas of one frame exceeds 2 GiB", entry);
+    return CNL_OK;
+}
+static int check_pointers(const char* entry, const void* table, const uint8_t* out, int N) {
+    if (N == 0) return CNL_OK;                   // an empty batch is a no-op: its pointers are not looked at
+    CNL_REQUIRE(table && out, CNL_E_BAD_ARG, "%s: null pointer", entry);
+    CNL_REQUIRE(((uintptr_t)table & 7) == 0 && ((uintptr_t)out & 3) == 0, CNL_E_BAD_ARG, "%s: table must be 8-byte and out 4-byte aligned", entry);
+    return CNL_OK;
+}
+
+// after the checks; `kernel` is the name a launch error is reported under
+template <class Source>
+static int launch(const char* kernel, const void* table, uint8_t* out, int N, int height, int width, typename Source::Params params, unsigned fill,
+                  void* stream) {
+    if (N == 0) return CNL_OK;
     const int groups = width / 4;
     const int tiles_x = (groups + LB_TILE_GROUPS - 1) / LB_TILE_GROUPS;
     const int groups_per_tile = (groups + tiles_x - 1) / tiles_x;           // equal tiles: 1088 columns = 2 x 136 groups, not 256 + 16
     const int row_blocks = (height + LB_ROWS - 1) / LB_ROWS;
-    hipLaunchKernelGGL(letterbox_kernel<C>, dim3((unsigned)(tiles_x * row_blocks), (unsigned)N), dim3(LB_THREADS), 0, stream,
-                       static_cast<const Frame*>(table), out, height, width, fill, tiles_x, groups_per_tile);
-    return cnl::check_launch("letterbox_kernel");
+    hipLaunchKernelGGL(letterbox_kernel<Source>, dim3((unsigned)(tiles_x * row_blocks), (unsigned)N), dim3(LB_THREADS), 0, (hipStream_t)stream,
+                       static_cast<const typename Source::Frame*>(table), out, height, width, params, fill, tiles_x, groups_per_tile);
+    return cnl::check_launch(kernel);
 }
 
 }  // namespace cnl_letterbox
 
 extern "C" int cnl_letterbox_bilinear_u8(const void* table, uint8_t* out, int32_t N, int32_t height, int32_t width, int32_t C,
                                          uint32_t fill_rgba, void* stream) {
-    CNL_REQUIRE(N >= 0 && N <= 65535, CNL_E_BAD_ARG, "cnl_letterbox_bilinear_u8: N = %d outside 0..65535", N);
-    CNL_REQUIRE(C >= 1 && C <= 4, CNL_E_BAD_ARG, "cnl_letterbox_bilinear_u8: C = %d outside 1..4", C);
-    CNL_REQUIRE(height > 0 && width > 0 && height % 32 == 0 && width % 32 == 0, CNL_E_BAD_ARG,
-                "cnl_letterbox_bilinear_u8: canvas %d x %d is not a positive multiple of 32", height, width);
-    CNL_REQUIRE((long)height * width * C <= 0x7fffffffL, CNL_E_BAD_ARG, "cnl_letterbox_bilinear_u8: the canvas of one frame exceeds 2 GiB");
-    if (N == 0) return CNL_OK;
-    CNL_REQUIRE(table && out, CNL_E_BAD_ARG, "cnl_letterbox_bilinear_u8: null pointer");
-    CNL_REQUIRE(((uintptr_t)table & 7) == 0 && ((uintptr_t)out & 3) == 0, CNL_E_BAD_ARG,
-                "cnl_letterbox_bilinear_u8: table must be 8-byte and out 4-byte aligned");
-    hipStream_t s = (hipStream_t)stream;
+    using namespace cnl_letterbox;
+    if (int e = check_canvas("cnl_letterbox_bilinear_u8", N, height, width, C)) return e;
+    if (int e = check_pointers("cnl_letterbox_bilinear_u8", table, out, N)) return e;
     switch (C) {
-        case 1: return cnl_letterbox::launch<1>(table, out, N, height, width, fill_rgba, s);
-        case 2: return cnl_letterbox::launch<2>(table, out, N, height, width, fill_rgba, s);
-        case 3: return cnl_letterbox::launch<3>(table, out, N, height, width, fill_rgba, s);
-        default: return cnl_letterbox::launch<4>(table, out, N, height, width, fill_rgba, s);
+        case 1: return launch<PackedSource<1>>("letterbox_kernel", table, out, N, height, width, {}, fill_rgba, stream);
+        case 2: return launch<PackedSource<2>>("letterbox_kernel", table, out, N, height, width, {}, fill_rgba, stream);
+        case 3: return launch<PackedSource<3>>("letterbox_kernel", table, out, N, height, width, {}, fill_rgba, stream);
+        default: return launch<PackedSource<4>>("letterbox_kernel", table, out, N, height, width, {}, fill_rgba, stream);
     }
+}
+
+extern "C" int cnl_letterbox_yuv420_u8(const void* table, uint8_t* out, int32_t N, int32_t height, int32_t width, const int32_t* coef,
+                                       uint32_t fill_rgba, void* stream) {
+    using namespace cnl_letterbox;
+    if (int e = check_canvas("cnl_letterbox_yuv420_u8", N, height, width, 3)) return e;
+    CNL_REQUIRE(coef, CNL_E_BAD_ARG, "cnl_letterbox_yuv420_u8: null coefficients");
+    const Yuv420Source::Params k = {coef[0], coef[1], coef[2], coef[3], coef[4], coef[5]};
+    const long chroma = std::max(std::max(std::labs((long)k.cvr), std::labs((long)k.cvg) + std::labs((long)k.cug)), std::labs((long)k.cub));
+    CNL_REQUIRE(k.y_off >= 0 && k.y_off <= 255 && k.cy >= 0 && 255L * k.cy + (1L << 19) + 128L * chroma < (1L << 31), CNL_E_UNSUPPORTED,
+                "cnl_letterbox_yuv420_u8: coefficients {%d, %d, %d, %d, %d, %d} can overflow 32-bit arithmetic", k.y_off, k.cy, k.cvr, k.cvg,
+                k.cug, k.cub);
+    if (int e = check_pointers("cnl_letterbox_yuv420_u8", table, out, N)) return e;
+    // the message keeps the name this launch has always been reported under; the kernel is letterbox_kernel<Yuv420Source>
+    return launch<Yuv420Source>("letterbox_yuv420_kernel", table, out, N, height, width, k, fill_rgba, stream);
 }
 
 extern "C" int cnl_unletterbox_boxes_f32(float* boxes, const void* table, int32_t N, int32_t k, int32_t clip, void* stream) {
@@ -221,6 +358,6 @@ extern "C" int cnl_unletterbox_boxes_f32(float* boxes, const void* table, int32_
     long blocks = (total + 255) / 256;
     if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(cnl_letterbox::unletterbox_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
-                       reinterpret_cast<float4*>(boxes), static_cast<const cnl_letterbox::Frame*>(table), N, k, clip);
+                       reinterpret_cast<float4*>(boxes), static_cast<const cnl_letterbox_frame*>(table), N, k, clip);
     return cnl::check_launch("unletterbox_kernel");
 }

@@ -14,7 +14,7 @@ import letterbox_ref
 import tiled_ref
 import yuv_ref
 import centernet_lightning_amd as cl
-from centernet_lightning_amd import _lib, yuv
+from centernet_lightning_amd import _gather, _lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRY = "cnl_letterbox_yuv420_u8"
@@ -192,12 +192,12 @@ def test_geometry_is_letterbox_geometry_and_tile_grid_of_the_frame_size(monkeypa
     class Captured(Exception):
         pass
 
-    def fake_gather(dev, parsed, windows, height, width, coef, word, extra):
-        seen.update(windows=windows, size=(height, width), coef=coef, word=word)
+    def fake_gather(dev, windows, plain, height, width, C, word, planes=None, coef=None, merge_records=None, frame_first_view=None):
+        seen.update(windows=windows, size=(height, width), coef=coef, word=word, C=C)
         raise Captured
 
-    monkeypatch.setattr(yuv, "_gather", fake_gather)
-    monkeypatch.setattr(yuv, "_device", lambda parsed, what: "cpu")
+    monkeypatch.setattr(_gather, "gather", fake_gather)                 # the one launch path of the YUV and the packed functions
+    monkeypatch.setattr(_gather, "require_hip", lambda tensors, what: None)
     sizes = [(1080, 1920), (720, 1280), (1280, 720), (2, 2), (16, 8), (34, 1000), (1000, 34), (1000, 1500)]
     frames = [planes(h, w) for (h, w) in sizes]
     for (height, width) in ((512, 512), (608, 1088)):
@@ -221,6 +221,17 @@ def test_geometry_is_letterbox_geometry_and_tile_grid_of_the_frame_size(monkeypa
         i += 1
         assert i == ffv[n + 1]
     assert any(x0 % 2 or y0 % 2 for (_, y0, x0, *_) in seen["windows"])            # odd origins occur: overlap 0.1 of 512 is a step of 461
+    # letterbox_uint8 / tile_uint8 hand the same launch path the same windows
+    yuv_tile_windows = seen["windows"]
+    rgb = [torch.zeros((h, w, 3), dtype=torch.uint8) for (h, w) in sizes]
+    for (height, width) in ((512, 512), (608, 1088)):
+        with pytest.raises(Captured):
+            cl.letterbox.letterbox_uint8(rgb, height, width, fill=(1, 2, 3))
+        assert seen["size"] == (height, width) and seen["coef"] is None and seen["word"] == 0x030201 and seen["C"] == 3
+        assert seen["windows"] == [(n, 0, 0, h, w) + cl.letterbox_geometry(h, w, height, width) for n, (h, w) in enumerate(sizes)]
+    with pytest.raises(Captured):
+        cl.tile_uint8(rgb, 512, 512, 0.1, True)
+    assert seen["size"] == (512, 512) and seen["coef"] is None and seen["windows"] == yuv_tile_windows
 
 
 # ----------------------------------------------------------------------------- the C ABI
@@ -260,6 +271,15 @@ def test_entry_point_validates_arguments_without_a_device():
     for bad in ((16, 1 << 24, 0, 0, 0, 0), (16, 1220542, 1 << 24, 0, 0, 0), (16, 1220542, 0, -(1 << 23), -(1 << 23), 0), (16, 1220542, 0, 0, 0, -(1 << 24)),
                 (-1, 1220542, 0, 0, 0, 0), (256, 1220542, 0, 0, 0, 0), (16, -1, 0, 0, 0, 0)):
         assert f(fake, fake, 1, 512, 512, (ctypes.c_int32 * 6)(*bad), 0, None) == U and "overflow" in _lib.last_error(), bad
+    # two faults at once: N, the canvas, the coefficients (of an empty batch too), then the pointers — in that order
+    over = (ctypes.c_int32 * 6)(16, 1 << 24, 0, 0, 0, 0)
+    assert f(fake, fake, -1, 500, 512, None, 0, None) == E and "N = -1" in _lib.last_error()
+    assert f(fake, fake, 1, 500, 512, None, 0, None) == E and "multiple of 32" in _lib.last_error()
+    assert f(fake, fake, 1, 500, 512, over, 0, None) == E and "multiple of 32" in _lib.last_error()
+    assert f(None, fake + 2, 1, 512, 512, None, 0, None) == E and "null coefficients" in _lib.last_error()
+    assert f(None, None, 1, 512, 512, over, 0, None) == U and "overflow" in _lib.last_error()
+    assert f(None, None, 0, 512, 512, over, 0, None) == U and f(None, None, 0, 512, 512, None, 0, None) == E
+    assert f(None, fake + 2, 1, 512, 512, coef, 0, None) == E and "null pointer" in _lib.last_error()
     assert f(None, None, 0, 512, 512, coef, 0, None) == 0           # an empty batch is a no-op
     for matrix, full_range in COMBOS:                               # every set the host can choose passes the overflow condition
         assert f(None, None, 0, 512, 512, (ctypes.c_int32 * 6)(*cl.yuv_coefficients(matrix, full_range)), 0, None) == 0

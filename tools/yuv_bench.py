@@ -97,8 +97,8 @@ def main():
         return cl.letterbox_yuv420(nv12[r % args.sets], height, width)[0]
 
     def b_kernel(r):
-        geom = prepared[r % args.sets][1]              # its _keep holds the device buffer that starts with the cnl_yuv420_frame records
-        _lib.check(lib.cnl_letterbox_yuv420_u8(geom._keep[1].data_ptr(), canvas.data_ptr(), len(geo), height, width, c_coef, 0, stream))
+        geom = prepared[r % args.sets][1]
+        _lib.check(lib.cnl_letterbox_yuv420_u8(geom.yuv_table.data_ptr(), canvas.data_ptr(), len(geo), height, width, c_coef, 0, stream))
 
     def c_torch(r):
         return cl.letterbox.letterbox_uint8([nv12_to_rgb_torch(f, coef) for f in nv12[r % args.sets]], height, width)[0]
