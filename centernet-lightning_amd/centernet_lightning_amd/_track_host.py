@@ -1,0 +1,455 @@
+"""Host side of the tracking association that `Tracker` and `TrackerBank` (tracker.py) share: layouts and readers of the records the
+association kernels write, the single-stream launch, the two-stage assignment, the track life cycle, the device track table, the settings
+and the input normaliser — each once."""
+import contextlib
+import ctypes
+import warnings
+import weakref
+from collections import namedtuple
+from enum import Enum, auto
+
+import numpy as np
+import torch
+from scipy.optimize import linear_sum_assignment
+
+from . import _lib
+
+_BOX_MODES = {None: 0, "iou": 1, "giou": 2}
+_LABEL_KINDS = {torch.int64: 1, torch.int32: 2, torch.float32: 3}     # det_label element types cnl_track_frame_f32 reads
+_REID_METRICS = {"cosine": 0, "euclidean": 1, "sqeuclidean": 2, "cityblock": 3, "chebyshev": 4, "canberra": 5, "braycurtis": 6, "correlation": 7}
+# ^ the scipy cdist metrics with a gfx950 kernel (float64, scipy's operation order); "manhattan" etc. are scipy aliases -> host path
+
+_NO_GUARD = contextlib.nullcontext()
+
+
+def _on(dev):
+    """Device guard for the launches — skipped when `dev` is the current device already (torch.cuda.device() costs ~6 us per use,
+    twice per frame)."""
+    return _NO_GUARD if torch.cuda.current_device() == dev.index else torch.cuda.device(dev)
+
+
+class _Mapped:
+    """Page-locked host memory that the device addresses through the same pointer (cnl_host_alloc): the frame record the association
+    kernel writes and the index lists the table update reads cross PCIe as the kernels' own stores / loads — no copy operation, and one
+    stream synchronisation per frame.  `np` is a uint8 view of the whole block (valid while this object lives)."""
+
+    def __init__(self, nbytes):
+        lib = _lib.load()
+        p = ctypes.c_void_p()
+        _lib.check(lib.cnl_host_alloc(nbytes, ctypes.byref(p)), "cnl_host_alloc")
+        self.ptr, self.nbytes = p.value, nbytes
+        self.np = np.ctypeslib.as_array((ctypes.c_uint8 * nbytes).from_address(self.ptr))
+        self._finalizer = weakref.finalize(self, lib.cnl_host_free, ctypes.c_void_p(self.ptr))
+        self._finalizer.atexit = False          # at interpreter exit the HIP runtime may be gone already; the process frees the pages
+
+
+def _grown(buf, need, floor):
+    """`buf` if it holds `need` bytes, else a new block of twice that (at least `floor`): persistent, nothing allocated per frame."""
+    return buf if buf is not None and buf.nbytes >= need else _Mapped(max(2 * need, floor))
+
+
+# ---------------------------------------------------------------------------------------------------------------- record layouts
+# The size helpers of the library (cnl_track_frame_bytes, cnl_track_streams_record_bytes / _workspace_bytes) restated in Python: a ctypes
+# call costs ~2 us of a 150 us frame.  tests/test_track_host.py holds them to the C helpers.
+FrameLayout = namedtuple("FrameLayout", "off_index off_dets off_reid bytes")
+StreamsLayout = namedtuple("StreamsLayout", "off_index off_dets off_match off_udet off_utrk bytes")
+# int32 header words of the frame record (csrc/track.hip: frame_kernel) ...
+F_N, F_K, F_T, F_WITH_DETS, F_OFF_INDEX, F_OFF_DETS, F_OFF_REID, F_OFF_BOX = range(8)
+# ... and of one stream's record (csrc/track_streams.hip: streams_costs_kernel, streams_assign_kernel); M1 = matches of stage 1 alone
+(S_N, S_K, S_T, S_STATUS, S_OFF_INDEX, S_OFF_DETS, S_OFF_MATCH, S_OFF_UDET, S_OFF_UTRK, S_M, S_M1, S_NUDET, S_NUTRK, S_WITH_DETS, S_SLOT,
+ S_STREAM) = range(16)
+_STATUS_TOO_LARGE = (3, 4, 19)          # status words of a stream whose k / T lie beyond the supported sizes
+
+
+def frame_layout(k, T, with_dets):
+    """[header 32 B | det_index[k] | (boxes[k][4] scores[k] labels[k]) | reid f64 n*T | box f32 n*T]; `bytes` is the worst case n = k (the
+    box matrix follows the re-ID matrix of the n the kernel found: header word F_OFF_BOX)."""
+    off_dets = (32 + 4 * k + 7) & ~7
+    off_reid = (off_dets + (24 * k if with_dets else 0) + 7) & ~7
+    return FrameLayout(32, off_dets, off_reid, off_reid + 12 * k * T)
+
+
+def streams_layout(k, T_max, with_dets):
+    """One stream's record: [header 64 B | det_index[k] | (boxes scores labels) | matches[k][2] | unmatched dets[k] | unmatched tracks[T_max]];
+    `bytes` is the stride between the streams' records."""
+    off_dets = (64 + 4 * k + 7) & ~7
+    off_match = off_dets + (24 * k if with_dets else 0)
+    off_utrk = off_match + 12 * k
+    return StreamsLayout(64, off_dets, off_match, off_match + 8 * k, off_utrk, (off_utrk + 4 * T_max + 7) & ~7)
+
+
+def streams_workspace_bytes(S, k, R):
+    """Device workspace of one step over S streams whose pooled table has R rows: 20 B per (detection, row) pair + the index lists."""
+    return 20 * k * R + 4 * (S + 2 * S * k + 2 * R)
+
+
+def _read_dets(r, off, k):
+    """(boxes f32 [k,4], scores f32 [k], labels i64 [k]) at byte `off` of a record.  Boxes and labels are copies: a Track keeps its box,
+    and the record is overwritten by the next frame; nothing keeps the scores (a view)."""
+    f = r[off:off + 20 * k].view(np.float32)
+    return f[:4 * k].reshape(k, 4).copy(), f[4 * k:], r[off + 20 * k:off + 24 * k].view(np.int32).astype(np.int64)
+
+
+def read_frame_record(h, with_box):
+    """uint8 view of a frame record -> (n, det_index, boxes, scores, labels, reid f64 [n,T], box f32 [n,T] | None).  boxes / scores / labels
+    are None when the record carries no detections; the matrices are views (valid until the next launch into the record)."""
+    hdr = h[:32].view(np.int32).tolist()
+    n, k, T = hdr[F_N], hdr[F_K], hdr[F_T]
+    dets = _read_dets(h, hdr[F_OFF_DETS], k) if hdr[F_WITH_DETS] else (None, None, None)
+    off_index, off_reid, off_box = hdr[F_OFF_INDEX], hdr[F_OFF_REID], hdr[F_OFF_BOX]
+    reid = h[off_reid:off_reid + 8 * n * T].view(np.float64).reshape(n, T)
+    box = h[off_box:off_box + 4 * n * T].view(np.float32).reshape(n, T) if with_box else None
+    return (n, h[off_index:off_index + 4 * n].view(np.int32).copy(), *dets, reid, box)
+
+
+def read_stream_record(r):
+    """uint8 view of one stream's record -> (n, T, status, det_index, boxes, scores, labels, matches, unmatched_dets, unmatched_tracks):
+    the three lists as `match_with_threshold` twice yields them (empty when status != 0: the device did not assign)."""
+    hdr = r[:64].view(np.int32).tolist()
+    n, k, m = hdr[S_N], hdr[S_K], hdr[S_M]
+    dets = _read_dets(r, hdr[S_OFF_DETS], k) if hdr[S_WITH_DETS] else (None, None, None)
+    off_index, off_match, off_udet, off_utrk = hdr[S_OFF_INDEX], hdr[S_OFF_MATCH], hdr[S_OFF_UDET], hdr[S_OFF_UTRK]
+    matches = [tuple(p) for p in r[off_match:off_match + 8 * m].view(np.int32).reshape(m, 2).tolist()]
+    return (n, hdr[S_T], hdr[S_STATUS], r[off_index:off_index + 4 * n].view(np.int32).copy(), *dets, matches,
+            r[off_udet:off_udet + 4 * hdr[S_NUDET]].view(np.int32).tolist(), r[off_utrk:off_utrk + 4 * hdr[S_NUTRK]].view(np.int32).tolist())
+
+
+def launch_frame(lib, rec, d_emb, d_box, d_score, d_label, label_kind, k, E, detection_threshold, t_emb, t_box, T, box_mode, reid_metric,
+                 with_dets, cur):
+    """ONE launch (operands as device addresses, None = absent) writes the frame record straight into the mapped host memory `rec`, packed by
+    the n the kernel finds; ONE synchronisation makes it readable: the frame's only device -> host traffic.  -> read_frame_record's tuple."""
+    _lib.check(lib.cnl_track_frame_f32(d_emb, d_box, d_score, d_label, label_kind, k, E, float(detection_threshold), t_emb, t_box, T, box_mode,
+                                       reid_metric, int(with_dets), rec.ptr, rec.nbytes, ctypes.c_void_p(cur.cuda_stream)), "cnl_track_frame_f32")
+    cur.synchronize()
+    return read_frame_record(rec.np, box_mode)
+
+
+def check_kept_count(h_score, detection_threshold, n, where=""):
+    n_host = int(np.count_nonzero(np.asarray(h_score, dtype=np.float32) >= np.float32(detection_threshold)))
+    if n_host != n:
+        raise RuntimeError(f"{where}detection count mismatch between host ({n_host}) and device ({n}): scores on the host and on the device differ")
+
+
+def match_with_threshold(cost_matrix, threshold):
+    """tracker.py:27-43: optimal assignment, keeping only pairs with cost < threshold.  Same result and order as the reference's loop
+    (matches in row order, unmatched rows / columns ascending), vectorised: the loop over sets cost more than the Hungarian step itself."""
+    row_ind, col_ind = linear_sum_assignment(cost_matrix)
+    keep = cost_matrix[row_ind, col_ind] < threshold
+    rows, cols = row_ind[keep], col_ind[keep]
+    free_r = np.ones(cost_matrix.shape[0], dtype=bool)
+    free_c = np.ones(cost_matrix.shape[1], dtype=bool)
+    free_r[rows] = False
+    free_c[cols] = False
+    return list(zip(rows.tolist(), cols.tolist())), np.flatnonzero(free_r).tolist(), np.flatnonzero(free_c).tolist()
+
+
+def two_stage_assignment(reid, reid_threshold, box_threshold, box=None):
+    """tracker.py:139-176: re-ID costs first, then box costs on the pairs that remain -> (matches, unmatched_dets, unmatched_tracks).
+    `box`: the full [n, T] matrix (element-wise costs: the remaining-pairs matrix of tracker.py:157-162 is a sub-matrix of it), a callable
+    (unmatched_dets, unmatched_tracks) -> that sub-matrix, or None (no second stage)."""
+    if reid.shape[1] == 0:
+        return [], list(range(reid.shape[0])), []
+    matches, unmatched_dets, unmatched_tracks = match_with_threshold(reid, reid_threshold)
+    if box is not None:
+        sub = box(unmatched_dets, unmatched_tracks) if callable(box) else box[np.ix_(unmatched_dets, unmatched_tracks)]
+        new_matches, ud, ut = match_with_threshold(sub, box_threshold)
+        matches.extend((unmatched_dets[x], unmatched_tracks[y]) for x, y in new_matches)
+        unmatched_dets, unmatched_tracks = [unmatched_dets[x] for x in ud], [unmatched_tracks[y] for y in ut]
+    return matches, unmatched_dets, unmatched_tracks
+
+
+class TrackState(Enum):
+    UNCONFIRMED = auto()
+    ACTIVE = auto()
+    INACTIVE = auto()
+    TO_DELETE = auto()
+
+
+class BoxKalman:
+    """The 8-state constant-velocity Kalman filter the reference builds per track with filterpy (tracker.py:243-262, 281-301, 317-323):
+    state = box corners x1 y1 x2 y2 + their velocities, measurement = the corners.  filterpy is third-party and absent from the image;
+    its published predict / update equations (filterpy/kalman/kalman_filter.py: x = Fx, P = FPF' + Q;  y = z - Hx, S = HPH' + R,
+    K = PH'S^-1, x += Ky, P = (I-KH)P(I-KH)' + KRK') are restated in float64 numpy — "parity unpinned" (no reference test pins it)."""
+
+    def __init__(self, bbox):
+        self.x = np.zeros(8)
+        self.x[:4] = bbox
+        self.F = np.eye(8)
+        self.F[:4, 4:] = np.eye(4)
+        self.H = np.eye(4, 8)
+        wh = np.asarray(bbox[2:], np.float64) - np.asarray(bbox[:2], np.float64)
+        std = np.tile(wh, 4)                                  # adapted from DeepSORT (tracker.py:256-260)
+        std[:4] /= 10
+        std[4:] /= 16
+        self.P = np.diag(std ** 2)
+
+    def predict(self):
+        wh = self.x[2:4] - self.x[:2]
+        std = np.tile(wh, 4)                                  # tracker.py:284-289
+        std[:4] /= 20
+        std[4:] /= 160
+        self.x = self.F @ self.x
+        self.P = self.F @ self.P @ self.F.T + np.diag(np.square(std))
+
+    def update(self, z):
+        wh = self.x[2:4] - self.x[:2]
+        R = np.diag((np.tile(wh, 2) / 20) ** 2)               # tracker.py:318-320
+        y = np.asarray(z, np.float64) - self.H @ self.x
+        PHT = self.P @ self.H.T
+        S = self.H @ PHT + R
+        K = PHT @ np.linalg.inv(S)
+        self.x = self.x + K @ y
+        I_KH = np.eye(8) - K @ self.H
+        self.P = I_KH @ self.P @ I_KH.T + K @ R @ K.T
+        return self.x[:4].copy()
+
+
+class Track:
+    """Host record of one track (tracker.py:217-347).  bbox / label live here (they are reported every frame); the embedding
+    lives in the tracker's device table and is fetched on access."""
+
+    def __init__(self, tracker, track_id, bbox, label, min_birth_age=2, max_inactive_age=30, smoothing_factor=0.9, use_kalman=False):
+        self._tracker = tracker
+        self.kf = BoxKalman(bbox) if use_kalman else None
+        self._row = -1
+        self.track_id = track_id
+        self.state = TrackState.UNCONFIRMED
+        self.birth_age = 0
+        self.inactive_age = 0
+        self.bbox = bbox
+        self.label = label
+        self.min_birth_age = min_birth_age
+        self.max_inactive_age = max_inactive_age
+        self.smoothing_factor = smoothing_factor
+
+    @property
+    def active(self):
+        return self.state == TrackState.ACTIVE
+
+    @property
+    def confirmed(self):
+        return self.state != TrackState.UNCONFIRMED
+
+    @property
+    def to_delete(self):
+        return self.state == TrackState.TO_DELETE
+
+    @property
+    def embedding(self):
+        return self._tracker._emb[self._row].cpu().numpy()
+
+    def update_matched(self, bbox):
+        if self.state == TrackState.UNCONFIRMED:
+            self.birth_age += 1
+            if self.birth_age >= self.min_birth_age:
+                self.state = TrackState.ACTIVE
+        elif self.state == TrackState.INACTIVE:
+            self.state = TrackState.ACTIVE
+            self.inactive_age = 0
+        # tracker.py:311-323: the detection's box, or the filtered state when the track carries a Kalman filter
+        self.bbox = bbox if self.kf is None else self.kf.update(bbox)
+
+    def kalman_predict(self):
+        """tracker.py:281-290 (called at the end of every Tracker.update; `bbox` keeps the last UPDATED state, as in the reference,
+        where it is a view of the array that filterpy's predict replaces)."""
+        if self.kf is not None:
+            self.kf.predict()
+
+    def update_unmatched(self):
+        if self.state == TrackState.UNCONFIRMED:
+            self.state = TrackState.TO_DELETE
+        elif self.state == TrackState.ACTIVE:
+            self.state = TrackState.INACTIVE
+            self.inactive_age = 0
+        elif self.state == TrackState.INACTIVE:
+            self.inactive_age += 1
+            if self.inactive_age >= self.max_inactive_age:
+                self.state = TrackState.TO_DELETE
+
+    def __repr__(self):
+        return f"track id: {self.track_id}, bbox: {self.bbox}, label: {self.label}, state: {self.state.name}"
+
+
+def life_cycle(tracks, matches, unmatched_dets, unmatched_tracks, det_index, boxes, labels, next_id, settings):
+    """One frame of the track life cycle (tracker.py:164-196) from an assignment; pure host code (no torch, no library call).  `boxes` /
+    `labels`: the frame's UNfiltered [k, ...] arrays; `settings`: the tracker or bank (its min_birth_age, max_inactive_age, smoothing_factor
+    and use_kalman go to the tracks born now, whose `embedding` reads its device table).
+    Returns (tracks, next_id, old_rows, det_rows): per surviving track its row in `tracks` as given (-1: born now) and the detection row
+    that feeds its table row (-1: carried over) — the two index lists of cnl_track_apply_f32."""
+    old_rows = list(range(len(tracks)))
+    det_rows = [-1] * len(tracks)
+    for det_idx, track_idx in matches:
+        # reference quirk kept (tracker.py:171): the match indexes the thresholded arrays but the update reads the
+        # unfiltered ones at the same position; identical when scores are sorted descending (gather_tracking2d output)
+        tracks[track_idx].update_matched(boxes[det_idx])
+        det_rows[track_idx] = det_idx
+    for track_idx in unmatched_tracks:
+        tracks[track_idx].update_unmatched()
+    tracks = list(tracks)
+    for det_idx in unmatched_dets:
+        src = int(det_index[det_idx])
+        tracks.append(Track(settings, next_id, boxes[src], labels[src], min_birth_age=settings.min_birth_age,
+                            max_inactive_age=settings.max_inactive_age, smoothing_factor=settings.smoothing_factor,
+                            use_kalman=settings.use_kalman))
+        next_id += 1
+        old_rows.append(-1)
+        det_rows.append(src)
+    keep = [i for i, t in enumerate(tracks) if t.state is not TrackState.TO_DELETE]
+    return [tracks[i] for i in keep], next_id, [old_rows[i] for i in keep], [det_rows[i] for i in keep]
+
+
+class TrackTable:
+    """The device track table: `emb` [capacity, E] / `box` [capacity, 4] float32 (first rows live), the spare pair the next update writes
+    (ping-pong), the mapped host memory holding the two index lists cnl_track_apply_f32 reads, the stream of the last update."""
+    __slots__ = ("emb", "box", "stream", "_spare", "_src", "_lists")
+
+    def __init__(self):
+        self.emb = self.box = self.stream = self._spare = self._src = self._lists = None
+
+    def wait_for_other_stream(self, cur=None):
+        """The caller changed streams between frames: the previous table update (which reads the mapped index lists and writes the tables
+        this frame reads) ran on another stream — finish it first (same stream: stream order does it; None: finish it anyway)."""
+        if self.stream is not None and (cur is None or self.stream != cur):
+            self.stream.synchronize()
+
+    def clear(self):
+        """Forget the rows, behind the last update (the mapped index lists stay)."""
+        self.wait_for_other_stream()
+        self.emb = self.box = self.stream = self._spare = None
+
+    def apply(self, src_trk, src_det, d_emb, d_box, E, smoothing_factor, cur):
+        """One cnl_track_apply_f32 launch on `cur` builds the new table: row r is old row src_trk[r] (-1: a birth), updated from detection
+        row src_det[r] of d_emb / d_box (-1: copied through).  The caller holds the device guard."""
+        rows = len(src_trk)
+        if rows == 0:
+            return
+        # the two index lists sit in mapped host memory that the kernel reads directly (2 x rows int32 over PCIe): no host -> device
+        # copy.  The kernel still reads them after the host has moved on: they are overwritten only behind the synchronisation of the
+        # next frame's association, which follows this launch in stream order (another stream: wait_for_other_stream)
+        if self._src is None or self._src.nbytes < 8 * rows:
+            self._src = _Mapped(8 * max(1024, 1 << (rows - 1).bit_length()))
+            self._lists = self._src.np.view(np.int32).reshape(2, -1)
+        lists = self._lists
+        lists[0, :rows] = src_trk
+        lists[1, :rows] = src_det
+        if self._spare is None or self._spare[0].shape[0] < rows or self._spare[0].shape[1] != E:
+            cap = max(64, 1 << (rows - 1).bit_length())
+            self._spare = (torch.empty((cap, E), device=d_emb.device, dtype=torch.float32),
+                           torch.empty((cap, 4), device=d_emb.device, dtype=torch.float32))
+        new_emb, new_box = self._spare
+        old = self.emb is not None
+        _lib.check(_lib.load().cnl_track_apply_f32(self.emb.data_ptr() if old else None, self.box.data_ptr() if old else None, d_emb.data_ptr(),
+                                                   d_box.data_ptr(), self._src.ptr, self._src.ptr + 4 * lists.shape[1], rows, E,
+                                                   float(smoothing_factor), new_emb.data_ptr(), new_box.data_ptr(),
+                                                   ctypes.c_void_p(cur.cuda_stream)), "cnl_track_apply_f32")
+        self.stream = cur
+        self._spare, self.emb, self.box = ((self.emb, self.box) if old else None), new_emb, new_box
+
+    def upload_boxes(self, tracks):
+        """use_kalman: the table's boxes are the detections' (cnl_track_apply_f32); a Kalman track's box is its filtered state, computed on
+        the host with the life cycle (8x8 float64 algebra per track): the boxes of `tracks` (rows 0..len - 1) go up in ONE copy."""
+        boxes = np.asarray([np.asarray(t.bbox, np.float64) for t in tracks], np.float32).reshape(len(tracks), 4)
+        with torch.cuda.device(self.box.device):
+            self.box[:len(tracks)].copy_(torch.from_numpy(boxes), non_blocking=False)
+
+
+class TrackerSettings:
+    """What `Tracker` and `TrackerBank` share: the reference's constructor arguments (tracker.py:50), the device, the model run."""
+    _update_name = "update"
+    d2h_bytes = 0               # bytes the association kernels stored over PCIe in the last update
+
+    def __init__(self, model=None, nms_kernel=3, num_detections=300, detection_threshold=0.3, reid_cost="cosine",
+                 reid_threshold=0.2, box_cost="iou", box_threshold=0.5, smoothing_factor=0.5, use_kalman=False,
+                 max_inactive_age=30, min_birth_age=2, device=None, allow_host_cost=False):
+        """reid_cost: "cosine" (default), "euclidean", "sqeuclidean", "cityblock", "chebyshev", "canberra", "braycurtis", "correlation" run on the device.  The reference accepts ANY scipy cdist metric name or
+        a callable (tracker.py:51, 62-64), and a callable box_cost: those are computed on the HOST from copies of the frame's kept embeddings /
+        boxes and the track table (two more device -> host copies per frame) — only with allow_host_cost=True, otherwise they raise: a silent
+        CPU detour is not what a caller of a gfx950 tracker expects."""
+        self.model = model
+        if model is None:
+            warnings.warn(f"A model was not provided. Only `.{self._update_name}()` will work")
+        self._host_reid = None if reid_cost in _REID_METRICS else reid_cost
+        self._host_box = box_cost if callable(box_cost) else None
+        if (self._host_reid is not None or self._host_box is not None) and not allow_host_cost:
+            raise ValueError(f"reid_cost={reid_cost!r} / box_cost={box_cost!r}: only {sorted(_REID_METRICS)} and 'iou' / 'giou' / None have gfx950 "
+                             "kernels; pass allow_host_cost=True to compute other scipy metrics or callables on the host (slower: the embeddings "
+                             "then travel to the host every frame)")
+        if self._host_box is None and box_cost not in _BOX_MODES:
+            raise ValueError(f"box_cost={box_cost!r}: expected 'iou', 'giou', None or (with allow_host_cost=True) a callable")
+        self.nms_kernel = nms_kernel
+        self.num_detections = num_detections
+        self.detection_threshold = detection_threshold
+        self.reid_cost = reid_cost
+        self.reid_threshold = reid_threshold
+        self.box_cost = box_cost
+        self.box_threshold = box_threshold
+        self.smoothing_factor = smoothing_factor
+        self.use_kalman = bool(use_kalman)
+        self.max_inactive_age = max_inactive_age
+        self.min_birth_age = min_birth_age
+        self._device = torch.device(device) if device is not None else None
+        self._table = TrackTable()
+        self._rec = None            # mapped host memory the association kernel writes its record(s) into
+        self.reset()
+
+    @property
+    def device(self):
+        if self._device is None:
+            if self.model is not None:
+                self._device = next(self.model.parameters()).device
+            else:
+                self._device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
+        if self._device.type != "cuda":
+            raise RuntimeError("the tracker's association kernels need a HIP device ('cuda'); there is no CPU fallback")
+        return self._device
+
+    _emb = property(lambda self: self._table.emb)       # device track table [capacity, E] / [capacity, 4] (Track.embedding, tests, tools)
+    _box = property(lambda self: self._table.box)
+
+    def _thresholds(self, kwargs):
+        """(detection, re-ID, box) thresholds of one call: the settings unless the call overrides them."""
+        if not kwargs:
+            return self.detection_threshold, self.reid_threshold, self.box_threshold
+        return (kwargs.get("detection_threshold", self.detection_threshold), kwargs.get("reid_threshold", self.reid_threshold),
+                kwargs.get("box_threshold", self.box_threshold))
+
+    def _detect(self, images, kwargs):
+        """The model's detections for a batch of frames (tracker.py:98-104); the kernel that computes a frame's costs also writes its
+        boxes / scores / labels into the frame record: no separate copy."""
+        self.model.eval()
+        heatmap, box_2d, reid = self.model(images.to(self.device))
+        return self.model.gather_tracking2d(heatmap, box_2d, reid, nms_kernel=kwargs.get("nms_kernel", self.nms_kernel),
+                                            num_detections=kwargs.get("num_detections", self.num_detections), normalize_bbox=True)
+
+
+def _to_dev(a, dev):
+    if isinstance(a, torch.Tensor) and a.device == dev and a.dtype == torch.float32 and a.is_contiguous():
+        return a                                   # already where the kernels read it (each .to() costs ~7 us of host time)
+    return torch.as_tensor(a).to(device=dev, dtype=torch.float32).contiguous()
+
+
+def _to_host(a):
+    return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+
+
+def normalise_detections(dev, bboxes, labels, scores, embeddings, lead=()):
+    """[*lead, k, 4], [*lead, k], [*lead, k], [*lead, k, E] (`lead` = () for one frame, (L,) for one frame per stream) as numpy arrays or torch
+    tensors anywhere -> (d_box, d_score, d_emb, d_label, host, label_kind): contiguous float32 tensors on `dev`, and EITHER the labels on
+    `dev` + the element type the kernel reads them as (device inputs: the three small arrays the host-side life cycle reads come back inside
+    the record, `host` None) OR `host` = (boxes, labels, scores) as numpy arrays, which the caller holds already (d_label None, kind 0)."""
+    try:
+        shape = embeddings.shape[:-1]               # [*lead, k]; checked before anything moves to the device
+        if len(shape) != len(lead) + 1 or shape[:-1] != lead or bboxes.shape != (*shape, 4) or scores.shape != shape or \
+                labels.shape[:len(shape)] != shape:
+            raise ValueError(f"detections: boxes {tuple(bboxes.shape)}, labels {tuple(labels.shape)}, scores {tuple(scores.shape)}, embeddings "
+                             f"{tuple(embeddings.shape)}, expected [{', '.join(map(str, lead + ('k', 'E')))}] embeddings and k boxes / labels / scores")
+    except AttributeError:                          # nested lists: as arrays
+        return normalise_detections(dev, *(np.asarray(a) for a in (bboxes, labels, scores, embeddings)), lead)
+    d_box, d_score, d_emb = _to_dev(bboxes, dev), _to_dev(scores, dev), _to_dev(embeddings, dev)
+    if not all(isinstance(a, torch.Tensor) and a.is_cuda for a in (bboxes, labels, scores)):
+        return d_box, d_score, d_emb, None, (_to_host(bboxes), _to_host(labels), _to_host(scores)), 0
+    d_label = labels.to(dev)
+    label_kind = _LABEL_KINDS.get(d_label.dtype, 0)
+    if not label_kind:
+        d_label, label_kind = d_label.to(torch.int64), 1
+    return d_box, d_score, d_emb, d_label.contiguous(), None, label_kind

@@ -343,29 +343,34 @@ def test_what_crosses_pcie():
 
 
 def test_non_finite_costs_raise_what_tracker_raises_and_leave_every_stream_untouched():
-    S = 3
+    S = 4
     tk = dict(detection_threshold=0.3, reid_cost="cosine")
-    seqs = [tracker_ref.synth_sequence(20 + s, frames=6, objects=9 + s, k=48) for s in range(S)]
+    seqs = [tracker_ref.synth_sequence(20 + s, frames=6, objects=9 + s if s < 3 else 30, k=48) for s in range(S)]
     bank = _quiet(cl.TrackerBank, num_streams=S, device=DEV, **tk)
     trks = [_quiet(cl.Tracker, device=DEV, **tk) for _ in range(S)]
     for f in range(4):
         bank.update_batch(*_stack([seqs[s][f] for s in range(S)], as_torch=True))
         for s in range(S):
             trks[s].update(*seqs[s][f])
-    fr = [list(seqs[s][4]) for s in range(S)]
-    fr[1][3] = fr[1][3].copy()
-    fr[1][3][0] = 0.0                                                    # a zero embedding on a kept detection: cosine = 0 / 0
-    with pytest.raises(ValueError) as want:
-        trks[1].update(*fr[1])
-    before = [_snapshot(bank, s) for s in range(S)]
-    with pytest.raises(ValueError) as got:
-        bank.update_batch(*_stack(fr, as_torch=True))
-    assert str(got.value) == str(want.value)
-    for s in range(S):                                                   # documented: the exception leaves EVERY stream as it was
-        assert _same(before[s], _snapshot(bank, s)), s
+    # two consecutive steps that each redo one stream through the single-stream path: stream 1, then stream 3 with about three times the
+    # tracks — its record is more than twice the first one's, so the mapped buffer the bank keeps for redone streams has to grow
+    sizes = []
+    for bad in (1, 3):
+        fr = [list(seqs[s][4]) for s in range(S)]
+        fr[bad][3] = fr[bad][3].copy()
+        fr[bad][3][0] = 0.0                                              # a zero embedding on a kept detection: cosine = 0 / 0
+        with pytest.raises(ValueError) as want:
+            trks[bad].update(*fr[bad])
+        before = [_snapshot(bank, s) for s in range(S)]
+        with pytest.raises(ValueError) as got:
+            bank.update_batch(*_stack(fr, as_torch=True))
+        assert str(got.value) == str(want.value)
+        for s in range(S):                                               # documented: the exception leaves EVERY stream as it was
+            assert _same(before[s], _snapshot(bank, s)), s
+        sizes.append((len(bank[bad].tracks), bank._redo_rec.nbytes))
+    assert sizes[1][0] > 2 * sizes[0][0] and sizes[1][1] > sizes[0][1]
     bank.update_batch(*_stack([seqs[s][4] for s in range(S)], as_torch=True))        # and the bank goes on with a clean frame
-    trks[1].update(*seqs[1][4])
-    for s in (0, 2):
+    for s in range(S):
         trks[s].update(*seqs[s][4])
     for s in range(S):
         assert [t.track_id for t in bank[s].tracks] == [t.track_id for t in trks[s].tracks]
