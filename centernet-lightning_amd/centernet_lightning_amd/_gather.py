@@ -1,5 +1,6 @@
 """The one host path into the gather launch (csrc/letterbox.hip) that letterbox_uint8, tile_uint8, letterbox_yuv420 and tile_yuv420
-share: what they check of uint8 frames, and records -> one pinned upload -> one launch.  No device sync anywhere."""
+share: what they check of uint8 frames, and records -> one pinned upload -> one launch.  No device sync anywhere.  crop_detections
+packs its whole-frame records with the same two functions (pack_plain, pack_yuv) and uploads them the same way (upload)."""
 import ctypes
 from typing import NamedTuple, Optional
 
@@ -38,6 +39,35 @@ class Gathered(NamedTuple):
     first_view: Optional[torch.Tensor]           # [N + 1] int32
 
 
+def pack_plain(rec, windows, plain) -> None:
+    """Fill rec ([V, 5] int64, zeroed) with the cnl_letterbox_frame records (8-byte pointer + 8 int32) of the V windows
+    [(frame, y0, x0, h, w, new_h, new_w, pad_top, pad_left)]; plain[i] = (address, row stride) of window i."""
+    import numpy as np
+    assert ctypes.sizeof(_lib.LetterboxFrame) == 40
+    V = len(windows)
+    rec[:, 0] = [address for (address, _) in plain]
+    rec.view(np.int32).reshape(V, 10)[:, 2:9] = [(h, w, stride, nh, nw, pt, pl)
+                                                 for (_, _, _, h, w, nh, nw, pt, pl), (_, stride) in zip(windows, plain)]
+
+
+def pack_yuv(rec, windows, planes) -> None:
+    """Fill rec ([V, 9] int64, zeroed) with the cnl_yuv420_frame records (3 pointers + 12 int32) of the V windows;
+    planes[i] = (y, u, v addresses, y_pitch, c_pitch, c_step) of window i."""
+    import numpy as np
+    assert ctypes.sizeof(_lib.Yuv420Frame) == 72
+    V = len(windows)
+    rec[:, :3] = [p[:3] for p in planes]
+    rec.view(np.int32).reshape(V, 18)[:, 6:17] = [tuple(p[3:]) + (x0, y0, h, w, nh, nw, pt, pl)
+                                                  for p, (_, y0, x0, h, w, nh, nw, pt, pl) in zip(planes, windows)]
+
+
+def upload(buf, dev) -> torch.Tensor:
+    """The int64 numpy buffer -> device memory through one pinned staging tensor, asynchronously (call under torch.cuda.device(dev))."""
+    host = torch.empty((buf.size,), dtype=torch.int64, pin_memory=True)
+    host.copy_(torch.from_numpy(buf))
+    return host.to(dev, non_blocking=True)
+
+
 def gather(dev, windows, plain, height: int, width: int, C: int, word: int, planes=None, coef=None, merge_records=None,
            frame_first_view=None) -> Gathered:
     """One pinned upload and one launch for the V windows [(frame, y0, x0, h, w, new_h, new_w, pad_top, pad_left)].
@@ -54,24 +84,16 @@ def gather(dev, windows, plain, height: int, width: int, C: int, word: int, plan
     o_merge = o_plain + V * 5
     o_first = o_merge + (V * 4 if merge_records is not None else 0)
     buf = np.zeros(o_first + (n_first + 1) // 2, dtype=np.int64)
-    assert ctypes.sizeof(_lib.Yuv420Frame) == 72 and ctypes.sizeof(_lib.LetterboxFrame) == 40 and ctypes.sizeof(_lib.MergeView) == 32
-    rec = buf[o_plain:o_merge].reshape(V, 5)                      # cnl_letterbox_frame: 8-byte pointer + 8 int32
-    rec[:, 0] = [address for (address, _) in plain]
-    rec.view(np.int32).reshape(V, 10)[:, 2:9] = [(h, w, stride, nh, nw, pt, pl)
-                                                 for (_, _, _, h, w, nh, nw, pt, pl), (_, stride) in zip(windows, plain)]
+    assert ctypes.sizeof(_lib.MergeView) == 32
+    pack_plain(buf[o_plain:o_merge].reshape(V, 5), windows, plain)
     if planes is not None:
-        rec = buf[:o_plain].reshape(V, 9)                         # cnl_yuv420_frame: 3 pointers + 12 int32
-        rec[:, :3] = [p[:3] for p in planes]
-        rec.view(np.int32).reshape(V, 18)[:, 6:17] = [tuple(p[3:]) + (x0, y0, h, w, nh, nw, pt, pl)
-                                                      for p, (_, y0, x0, h, w, nh, nw, pt, pl) in zip(planes, windows)]
+        pack_yuv(buf[:o_plain].reshape(V, 9), windows, planes)
     if merge_records is not None:
         buf[o_merge:o_first].view(np.int32).reshape(V, 8)[:] = np.array(merge_records, dtype=np.int32)
         buf[o_first:].view(np.int32)[:n_first] = frame_first_view
     lib = _lib.load()
     with torch.cuda.device(dev):
-        host = torch.empty((buf.size,), dtype=torch.int64, pin_memory=True)
-        host.copy_(torch.from_numpy(buf))
-        d = host.to(dev, non_blocking=True)
+        d = upload(buf, dev)
         out = Gathered(canvas=torch.empty((V, height, width, C), device=dev, dtype=torch.uint8),
                        table=d[o_plain:o_merge].view(V, 5),
                        yuv_table=d[:o_plain].view(V, 9) if planes is not None else None,

@@ -19,6 +19,7 @@ from typing import Any, Dict, Union
 import torch
 from torch import nn
 
+from . import crops as _crops
 from . import decode as _decode
 from . import letterbox as _letterbox
 from . import tiles as _tiles
@@ -250,6 +251,13 @@ class CenterNet(nn.Module):
         dets = gather(out, num_detections=num_detections, nms_kernel=nms_kernel, normalize_bbox=False)
         _letterbox.unletterbox_(dets["bboxes"], geom, True)
         return dets
+
+    def crop_detections(self, frames, bboxes, size=(128, 64), scores=None, score_threshold=None, count=None, pad: float = 0.0,
+                        keep_aspect: bool = False, fill=(0, 0, 0), pixel_format: str = "rgb", matrix: str = "bt601", full_range: bool = False):
+        """The boxes detect_frames / detect_tiled returned, cut out of the same frames at one size for a second-stage network ->
+        (crops [N,k,size[0],size[1],C] uint8, windows [N,k,4] int32 x0 y0 w h), on the GPU (cnl_crop_boxes_u8); see crops.crop_detections."""
+        return _crops.crop_detections(frames, bboxes, size, scores, score_threshold, count, pad, keep_aspect, fill, pixel_format, matrix,
+                                      full_range)
 
     # ------------------------------------------------------------------ frames larger than the network input
     def tile_uint8(self, frames, tile_h: int = 512, tile_w: int = 512, overlap: float = 0.2, full_frame: bool = True, fill=(0, 0, 0)):

@@ -12,6 +12,8 @@
 //                              frame between the decoder and the network is never written; bit for bit PackedSource<3> on the
 //                              converted frames
 //   unletterbox_kernel         decoded boxes in canvas pixels -> each frame's own pixels, in place.
+//   crop_records_kernel<Frame> boxes [N, k, 4] in frame pixels -> one window record per slot, made on the device; letterbox_kernel over
+//                              those records is cnl_crop_boxes_u8: every detection cut out of its frame at one size.
 //
 // The reference does this on the host, one image at a time (configs/centernet.yaml val_data.transforms; datasets/inference.py carries
 // original_height / original_width), and therefore validates at batch size 1.
@@ -41,7 +43,7 @@
 namespace cnl_letterbox {
 
 constexpr int LB_THREADS = 256;
-constexpr int LB_ROWS = 8;           // canvas rows per workgroup
+constexpr int LB_ROWS = 8;           // canvas rows per workgroup (the two letterbox entries)
 constexpr int LB_TILE_GROUPS = 256;  // 4-pixel groups per column tile (1024 canvas columns)
 
 typedef unsigned short u16_unaligned __attribute__((aligned(1)));
@@ -174,21 +176,22 @@ struct Yuv420Source {
     }
 };
 
-template <class Source>
+template <class Source, int ROWS>
 __global__ __launch_bounds__(LB_THREADS) void letterbox_kernel(const typename Source::Frame* __restrict__ table, unsigned char* __restrict__ out,
                                                                int height, int width, typename Source::Params params, unsigned fill,
                                                                int tiles_x, int groups_per_tile) {
     constexpr int C = Source::C;
     // col: .x = Source::column of the left tap's source column (-1: border), .y = a0 | a1 << 16
     __shared__ __attribute__((aligned(16))) int2 col[LB_TILE_GROUPS * 4];
-    __shared__ int4 row[LB_ROWS];                // .x = y0 (-1: border row), .y = y1, .z = b0, .w = b1
+    __shared__ int4 row[ROWS];                   // .x = y0 (-1: border row), .y = y1, .z = b0, .w = b1
+    static_assert(ROWS >= 1 && ROWS <= LB_THREADS, "one thread fills one row entry");
     const typename Source::Frame f = table[blockIdx.y];          // uniform address: scalar loads
     const int tile = (int)(blockIdx.x % (unsigned)tiles_x), rblk = (int)(blockIdx.x / (unsigned)tiles_x);
     const int groups = width >> 2;
     const int g_begin = tile * groups_per_tile, g_end = min(groups, g_begin + groups_per_tile);
     const int n_groups = g_end - g_begin;
     const int x_begin = g_begin * 4, n_cols = n_groups * 4;
-    const int row_begin = rblk * LB_ROWS, n_rows = min(LB_ROWS, height - row_begin);
+    const int row_begin = rblk * ROWS, n_rows = min(ROWS, height - row_begin);
 
     // OpenCV: inv_scale = dsize / ssize (double), scale = 1 / inv_scale
     const double scale_x = 1.0 / ((double)f.new_w / (double)f.w), scale_y = 1.0 / ((double)f.new_h / (double)f.h);
@@ -287,6 +290,79 @@ __global__ __launch_bounds__(256) void unletterbox_kernel(float4* __restrict__ b
     }
 }
 
+// ---- crops: cnl_crop_boxes_u8 = crop_records_kernel (boxes -> one record per slot, on the device) + letterbox_kernel over those records
+// canvas rows per workgroup for crop canvases.  LB_ROWS = 8 leaves half of a workgroup's threads without an item on a 64-pixel-wide crop
+// and rebuilds the fp64 column table 16 times per 128-row crop; measured candidates and the choice: DESIGN.md §16, tools/crop_bench.py
+#ifndef CNL_CROP_ROWS
+#define CNL_CROP_ROWS 32
+#endif
+constexpr int CROP_ROWS = CNL_CROP_ROWS;
+
+struct CropRule {
+    int k, C, crop_h, crop_w, keep_aspect;
+    float pad, threshold;
+};
+
+// where a slot's window starts, in the record of its frame's type: a packed frame moves its pointer, a YUV frame names the origin
+// (chroma is addressed in frame coordinates, so odd origins need nothing more)
+__device__ __forceinline__ void set_origin(cnl_letterbox_frame& r, int x0, int y0, int C) {
+    r.src = (const unsigned char*)r.src + (size_t)y0 * r.row_stride + (size_t)x0 * C;
+}
+__device__ __forceinline__ void set_origin(cnl_yuv420_frame& r, int x0, int y0, int) {
+    r.x0 = x0;
+    r.y0 = y0;
+}
+// clamp in float, then convert: a NaN becomes 0 and no magnitude overflows the conversion
+__device__ __forceinline__ int clamp_to_int(float v, float limit) {
+    v = v > 0.f ? v : 0.f;
+    return (int)(v < limit ? v : limit);
+}
+
+// one thread per slot (n, j) of boxes [N, k, 4]; the window, live and target rules are those of include/centernet_gfx950.h, one fp32
+// operation per step (fp contract is off in this file)
+template <class Frame>
+__global__ __launch_bounds__(256) void crop_records_kernel(const Frame* __restrict__ frames, const float4* __restrict__ boxes,
+                                                           const float* __restrict__ scores, const int* __restrict__ count,
+                                                           Frame* __restrict__ records, int4* __restrict__ windows, long total, CropRule q) {
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= total) return;
+    const int n = (int)(t / q.k), j = (int)(t - (long)n * q.k);
+    Frame r = frames[n];                         // the whole frame: h, w are its size
+    const float4 b = boxes[t];
+    const bool live = (!count || j < count[n]) && (!scores || scores[t] >= q.threshold) && __builtin_isfinite(b.x) &&
+                      __builtin_isfinite(b.y) && __builtin_isfinite(b.z) && __builtin_isfinite(b.w);
+    const float W = (float)r.w, H = (float)r.h;
+    const float bw = b.z - b.x, bh = b.w - b.y;
+    const float px = q.pad * bw, py = q.pad * bh;
+    const int x0 = clamp_to_int(floorf(b.x - px), W), xe = clamp_to_int(ceilf(b.z + px), W);
+    const int y0 = clamp_to_int(floorf(b.y - py), H), ye = clamp_to_int(ceilf(b.w + py), H);
+    const int w = xe - x0, h = ye - y0;
+    int4 win = make_int4(0, 0, 0, 0);
+    if (live && w >= 1 && h >= 1) {
+        win = make_int4(x0, y0, w, h);
+        set_origin(r, x0, y0, q.C);
+        r.h = h;
+        r.w = w;
+        r.new_h = q.crop_h;
+        r.new_w = q.crop_w;
+        if (q.keep_aspect) {                     // letterbox_geometry's rule, in double
+            const double ratio = fmin((double)q.crop_h / (double)h, (double)q.crop_w / (double)w);
+            r.new_h = min(q.crop_h, max(1, (int)rint((double)h * ratio)));
+            r.new_w = min(q.crop_w, max(1, (int)rint((double)w * ratio)));
+        }
+        r.pad_top = (q.crop_h - r.new_h) / 2;
+        r.pad_left = (q.crop_w - r.new_w) / 2;
+    } else {                                     // dead: every canvas pixel is border, and no size is 0 for the gather to divide by
+        set_origin(r, 0, 0, q.C);
+        r.h = r.w = r.new_h = r.new_w = 1;
+        r.pad_top = q.crop_h;
+        r.pad_left = q.crop_w;
+    }
+    r.reserved = 0;
+    records[t] = r;
+    windows[t] = win;
+}
+
 // what both gather entry points require of the canvas, and then (the YUV entry checks its coefficients in between) of the pointers;
 // `entry` names the one that was called
 static int check_canvas(const char* entry, int N, int height, int width, int C) {
@@ -297,6 +373,15 @@ static int check_canvas(const char* entry, int N, int height, int width, int C) 
     CNL_REQUIRE((long)height * width * C <= 0x7fffffffL, CNL_E_BAD_ARG, "%s: the canvas of one frame exceeds 2 GiB", entry);
     return CNL_OK;
 }
+// the six colour integers of a YUV entry -> the kernel's Params, refused where the 32-bit conversion arithmetic could overflow
+static int check_coefficients(const char* entry, const int32_t* coef, Yuv420Source::Params& k) {
+    CNL_REQUIRE(coef, CNL_E_BAD_ARG, "%s: null coefficients", entry);
+    k = {coef[0], coef[1], coef[2], coef[3], coef[4], coef[5]};
+    const long chroma = std::max(std::max(std::labs((long)k.cvr), std::labs((long)k.cvg) + std::labs((long)k.cug)), std::labs((long)k.cub));
+    CNL_REQUIRE(k.y_off >= 0 && k.y_off <= 255 && k.cy >= 0 && 255L * k.cy + (1L << 19) + 128L * chroma < (1L << 31), CNL_E_UNSUPPORTED,
+                "%s: coefficients {%d, %d, %d, %d, %d, %d} can overflow 32-bit arithmetic", entry, k.y_off, k.cy, k.cvr, k.cvg, k.cug, k.cub);
+    return CNL_OK;
+}
 static int check_pointers(const char* entry, const void* table, const uint8_t* out, int N) {
     if (N == 0) return CNL_OK;                   // an empty batch is a no-op: its pointers are not looked at
     CNL_REQUIRE(table && out, CNL_E_BAD_ARG, "%s: null pointer", entry);
@@ -304,18 +389,38 @@ static int check_pointers(const char* entry, const void* table, const uint8_t* o
     return CNL_OK;
 }
 
-// after the checks; `kernel` is the name a launch error is reported under
-template <class Source>
+// after the checks; `kernel` is the name a launch error is reported under.  ROWS = canvas rows per workgroup: LB_ROWS for the network-sized
+// canvases of the two letterbox entries, CROP_ROWS for the small canvases of cnl_crop_boxes_u8
+template <class Source, int ROWS = LB_ROWS>
 static int launch(const char* kernel, const void* table, uint8_t* out, int N, int height, int width, typename Source::Params params, unsigned fill,
                   void* stream) {
     if (N == 0) return CNL_OK;
     const int groups = width / 4;
     const int tiles_x = (groups + LB_TILE_GROUPS - 1) / LB_TILE_GROUPS;
     const int groups_per_tile = (groups + tiles_x - 1) / tiles_x;           // equal tiles: 1088 columns = 2 x 136 groups, not 256 + 16
-    const int row_blocks = (height + LB_ROWS - 1) / LB_ROWS;
-    hipLaunchKernelGGL(letterbox_kernel<Source>, dim3((unsigned)(tiles_x * row_blocks), (unsigned)N), dim3(LB_THREADS), 0, (hipStream_t)stream,
+    const int row_blocks = (height + ROWS - 1) / ROWS;
+    hipLaunchKernelGGL((letterbox_kernel<Source, ROWS>), dim3((unsigned)(tiles_x * row_blocks), (unsigned)N), dim3(LB_THREADS), 0, (hipStream_t)stream,
                        static_cast<const typename Source::Frame*>(table), out, height, width, params, fill, tiles_x, groups_per_tile);
     return cnl::check_launch(kernel);
+}
+
+// both launches of cnl_crop_boxes_u8, after the checks; the gather runs in chunks of grid.y's limit
+template <class Source>
+static int crop(const void* frames, const float* boxes, const float* scores, const int32_t* count, void* records, int32_t* windows, uint8_t* out,
+                long total, const CropRule& q, typename Source::Params params, unsigned fill, void* stream) {
+    typedef typename Source::Frame Frame;
+    hipLaunchKernelGGL(crop_records_kernel<Frame>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       static_cast<const Frame*>(frames), reinterpret_cast<const float4*>(boxes), scores, count, static_cast<Frame*>(records),
+                       reinterpret_cast<int4*>(windows), total, q);
+    if (int e = cnl::check_launch("crop_records_kernel")) return e;
+    const size_t crop_bytes = (size_t)q.crop_h * q.crop_w * Source::C;
+    for (long first = 0; first < total; first += 65535) {
+        const int n = (int)std::min(65535L, total - first);
+        if (int e = launch<Source, CROP_ROWS>("letterbox_kernel", static_cast<const Frame*>(records) + first, out + (size_t)first * crop_bytes, n,
+                                              q.crop_h, q.crop_w, params, fill, stream))
+            return e;
+    }
+    return CNL_OK;
 }
 
 }  // namespace cnl_letterbox
@@ -337,12 +442,8 @@ extern "C" int cnl_letterbox_yuv420_u8(const void* table, uint8_t* out, int32_t 
                                        uint32_t fill_rgba, void* stream) {
     using namespace cnl_letterbox;
     if (int e = check_canvas("cnl_letterbox_yuv420_u8", N, height, width, 3)) return e;
-    CNL_REQUIRE(coef, CNL_E_BAD_ARG, "cnl_letterbox_yuv420_u8: null coefficients");
-    const Yuv420Source::Params k = {coef[0], coef[1], coef[2], coef[3], coef[4], coef[5]};
-    const long chroma = std::max(std::max(std::labs((long)k.cvr), std::labs((long)k.cvg) + std::labs((long)k.cug)), std::labs((long)k.cub));
-    CNL_REQUIRE(k.y_off >= 0 && k.y_off <= 255 && k.cy >= 0 && 255L * k.cy + (1L << 19) + 128L * chroma < (1L << 31), CNL_E_UNSUPPORTED,
-                "cnl_letterbox_yuv420_u8: coefficients {%d, %d, %d, %d, %d, %d} can overflow 32-bit arithmetic", k.y_off, k.cy, k.cvr, k.cvg,
-                k.cug, k.cub);
+    Yuv420Source::Params k;
+    if (int e = check_coefficients("cnl_letterbox_yuv420_u8", coef, k)) return e;
     if (int e = check_pointers("cnl_letterbox_yuv420_u8", table, out, N)) return e;
     // the message keeps the name this launch has always been reported under; the kernel is letterbox_kernel<Yuv420Source>
     return launch<Yuv420Source>("letterbox_yuv420_kernel", table, out, N, height, width, k, fill_rgba, stream);
@@ -360,4 +461,36 @@ extern "C" int cnl_unletterbox_boxes_f32(float* boxes, const void* table, int32_
     hipLaunchKernelGGL(cnl_letterbox::unletterbox_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
                        reinterpret_cast<float4*>(boxes), static_cast<const cnl_letterbox_frame*>(table), N, k, clip);
     return cnl::check_launch("unletterbox_kernel");
+}
+
+extern "C" int cnl_crop_boxes_u8(const void* frames, const float* boxes, const float* scores, float score_threshold, const int32_t* count, int32_t N,
+                                 int32_t k, int32_t C, const int32_t* coef, float pad, int32_t keep_aspect, void* records, int32_t* windows,
+                                 uint8_t* out, int32_t crop_h, int32_t crop_w, uint32_t fill_rgba, void* stream) {
+    using namespace cnl_letterbox;
+    CNL_REQUIRE(N >= 0 && k >= 0, CNL_E_BAD_ARG, "cnl_crop_boxes_u8: negative N or k");
+    const long total = (long)N * k;
+    CNL_REQUIRE(total <= 0x7fffffffL, CNL_E_BAD_ARG, "cnl_crop_boxes_u8: N * k = %ld slots exceed 2^31 - 1", total);
+    CNL_REQUIRE(C >= 1 && C <= 4, CNL_E_BAD_ARG, "cnl_crop_boxes_u8: C = %d outside 1..4", C);
+    CNL_REQUIRE(!coef || C == 3, CNL_E_BAD_ARG, "cnl_crop_boxes_u8: YUV frames give C = 3 crops, not C = %d", C);
+    CNL_REQUIRE(crop_h >= 1 && crop_w >= 4 && crop_w % 4 == 0, CNL_E_BAD_ARG,
+                "cnl_crop_boxes_u8: crop %d x %d needs a height >= 1 and a width that is a positive multiple of 4", crop_h, crop_w);
+    CNL_REQUIRE((long)crop_h * crop_w * C <= 0x7fffffffL, CNL_E_BAD_ARG, "cnl_crop_boxes_u8: one crop exceeds 2 GiB");
+    CNL_REQUIRE(__builtin_isfinite(pad) && pad >= 0.f, CNL_E_BAD_ARG, "cnl_crop_boxes_u8: pad = %g must be finite and >= 0", (double)pad);
+    CNL_REQUIRE(!scores || score_threshold == score_threshold, CNL_E_BAD_ARG, "cnl_crop_boxes_u8: score_threshold is NaN");
+    Yuv420Source::Params yuv = {};
+    if (coef)
+        if (int e = check_coefficients("cnl_crop_boxes_u8", coef, yuv)) return e;
+    if (total == 0) return CNL_OK;               // no slots: the pointers are not looked at
+    CNL_REQUIRE(frames && boxes && records && windows && out, CNL_E_BAD_ARG, "cnl_crop_boxes_u8: null pointer");
+    CNL_REQUIRE(((uintptr_t)frames & 7) == 0 && ((uintptr_t)records & 7) == 0 && ((uintptr_t)boxes & 15) == 0 && ((uintptr_t)windows & 15) == 0 &&
+                    ((uintptr_t)out & 3) == 0 && ((uintptr_t)scores & 3) == 0 && ((uintptr_t)count & 3) == 0,
+                CNL_E_BAD_ARG, "cnl_crop_boxes_u8: frames and records must be 8-byte, boxes and windows 16-byte, out, scores and count 4-byte aligned");
+    const CropRule q = {k, C, crop_h, crop_w, keep_aspect != 0, pad, score_threshold};
+    if (coef) return crop<Yuv420Source>(frames, boxes, scores, count, records, windows, out, total, q, yuv, fill_rgba, stream);
+    switch (C) {
+        case 1: return crop<PackedSource<1>>(frames, boxes, scores, count, records, windows, out, total, q, {}, fill_rgba, stream);
+        case 2: return crop<PackedSource<2>>(frames, boxes, scores, count, records, windows, out, total, q, {}, fill_rgba, stream);
+        case 3: return crop<PackedSource<3>>(frames, boxes, scores, count, records, windows, out, total, q, {}, fill_rgba, stream);
+        default: return crop<PackedSource<4>>(frames, boxes, scores, count, records, windows, out, total, q, {}, fill_rgba, stream);
+    }
 }

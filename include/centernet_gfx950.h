@@ -363,6 +363,42 @@ int cnl_letterbox_yuv420_u8(const void* table, uint8_t* out, int32_t N, int32_t 
                             uint32_t fill_rgba, void* stream);
 
 /*
+ * Detected objects cut out of their frames at one fixed size: boxes [N, k, 4] (x1 y1 x2 y2 f32 in each frame's own pixels, 16-byte
+ * aligned, e.g. what cnl_unletterbox_boxes_f32 or cnl_merge_tiles_f32 left) -> out [N, k, crop_h, crop_w, C] u8.  Two launches on
+ * `stream`, nothing goes to the host: a record kernel turns every slot (n, j) into one record of the frame's own type, and the gather
+ * kernel of the two entry points above runs over those N * k records, so a crop is bit for bit what cnl_letterbox_bilinear_u8 gives for
+ * the window sliced out of the frame (for YUV frames: out of the converted frame).
+ *
+ * frames: device array of N WHOLE-FRAME records.  coef == NULL: cnl_letterbox_frame records of C-channel frames.  coef != NULL:
+ * cnl_yuv420_frame records with x0 = y0 = 0, coef being the six integers of cnl_letterbox_yuv420_u8 in host memory (same overflow
+ * condition), and C must be 3.  Of a record only the pointers, strides / pitches and h, w (the frame's size H, W) are read.
+ *
+ * Live rule.  Slot (n, j) is live when (count == NULL or j < count[n]) and (scores == NULL or scores[n * k + j] >= score_threshold);
+ * count: N int32, scores: [N, k] f32, both in device memory and optional.  A NaN score is not live.
+ *
+ * Window rule.  Every step is ONE fp32 operation (no fused multiply-add), so that numpy float32 reproduces it bit for bit:
+ *     bw = x2 - x1, bh = y2 - y1
+ *     xa = x1 - pad * bw, xb = x2 + pad * bw       (the product and the sum round separately; y alike with bh)
+ *     x0 = (int)clamp(floorf(xa), 0, W), xe = (int)clamp(ceilf(xb), 0, W), w = xe - x0      (y alike with H)
+ * with clamp(v, 0, L): t = v > 0 ? v : 0, then t < L ? t : L, in float before the conversion (a NaN becomes 0, +-1e30 stays in
+ * range).  The slot is DEAD if it is not live, if any of x1 y1 x2 y2 is not finite, or if w < 1 or h < 1 (a box outside the frame,
+ * an inverted box, x1 == x2 on an integer).  windows [N, k, 4] int32 (16-byte aligned) receives (x0, y0, w, h), (0, 0, 0, 0) for a
+ * dead slot.
+ *
+ * Target.  keep_aspect == 0: the window is stretched to crop_h x crop_w.  keep_aspect != 0: the geometry rule of
+ * cnl_letterbox_bilinear_u8 above on (h, w, crop_h, crop_w), evaluated on the device in double (two divisions, min, a multiply,
+ * round half to even, clamped to 1..target), centred with the odd pixel at the bottom / right, the rest fill_rgba.  A dead slot's
+ * crop is fill_rgba everywhere.  Every byte of `out` is written exactly once.
+ *
+ * records: workspace of N * k records of the frames' type (40 / 72 bytes each, 8-byte aligned); the library allocates nothing.
+ * crop_w is a multiple of 4, >= 4 (112 x 112, 256 x 128, 128 x 64 are all fine); crop_h >= 1; a crop is smaller than 2 GiB; pad is
+ * finite and >= 0; N, k >= 0 with N * k < 2^31 (above 65535 slots the gather is launched in chunks).  N == 0 or k == 0 is a no-op.
+ */
+int cnl_crop_boxes_u8(const void* frames, const float* boxes, const float* scores, float score_threshold, const int32_t* count, int32_t N,
+                      int32_t k, int32_t C, const int32_t* coef, float pad, int32_t keep_aspect, void* records, int32_t* windows, uint8_t* out,
+                      int32_t crop_h, int32_t crop_w, uint32_t fill_rgba, void* stream);
+
+/*
  * Sliced inference, the merge: the decoded boxes of the V views (network-sized tiles cut out of a frame, plus optionally the whole
  * frame letterboxed) of N frames go back into each frame's own pixels, and the duplicates the tile overlaps create are removed by a
  * greedy non-maximum suppression per frame.  Three launches for the whole batch, no device synchronisation, no float atomics.  (The
