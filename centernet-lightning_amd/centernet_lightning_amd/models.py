@@ -22,6 +22,7 @@ from torch import nn
 from . import crops as _crops
 from . import decode as _decode
 from . import letterbox as _letterbox
+from . import overlay as _overlay
 from . import tiles as _tiles
 from . import yuv as _yuv
 from .collate import collate_detections
@@ -258,6 +259,14 @@ class CenterNet(nn.Module):
         (crops [N,k,size[0],size[1],C] uint8, windows [N,k,4] int32 x0 y0 w h), on the GPU (cnl_crop_boxes_u8); see crops.crop_detections."""
         return _crops.crop_detections(frames, bboxes, size, scores, score_threshold, count, pad, keep_aspect, fill, pixel_format, matrix,
                                       full_range)
+
+    def draw_detections(self, frames, bboxes, labels=None, scores=None, score_threshold=None, count=None, numbers=None,
+                        palette=_overlay.DEFAULT_PALETTE, text_color=(255, 255, 255), thickness: int = 2, fill_alpha: int = 0,
+                        tag_scale: int = 2, pixel_format: str = "rgb", matrix: str = "bt601", full_range: bool = False, inplace: bool = False):
+        """The boxes detect_frames / detect_tiled returned, drawn onto the same frames (outlines, optional fills and number tags) on
+        the GPU (cnl_draw_boxes_u8) -> the painted frames, in the form they were given; see overlay.draw_detections."""
+        return _overlay.draw_detections(frames, bboxes, labels, scores, score_threshold, count, numbers, palette, text_color, thickness,
+                                        fill_alpha, tag_scale, pixel_format, matrix, full_range, inplace)
 
     # ------------------------------------------------------------------ frames larger than the network input
     def tile_uint8(self, frames, tile_h: int = 512, tile_w: int = 512, overlap: float = 0.2, full_frame: bool = True, fill=(0, 0, 0)):

@@ -47,6 +47,29 @@ def yuv_coefficients(matrix: str = "bt601", full_range: bool = False) -> Tuple[i
     return (0 if full_range else 16, cy) + tuple(round(v * 2 ** 20) for v in c)
 
 
+def rgb_to_yuv(color, matrix: str = "bt601", full_range: bool = False) -> Tuple[int, int, int]:
+    """(R, G, B) bytes -> (Y, U, V) bytes of the standard matrix, exact in Fractions: with (Kr, Kb) = MATRICES[matrix] and
+    Kg = 1 - Kr - Kb, Y = Kr R + Kg G + Kb B, Cb = (B - Y) / (2 (1 - Kb)), Cr = (R - Y) / (2 (1 - Kr)); limited range gives
+    16 + 219/255 Y, 128 + 224/255 Cb, 128 + 224/255 Cr, full range Y, 128 + Cb, 128 + Cr; each rounded half to even and clamped to
+    0..255.  The forward direction of yuv_coefficients: what draw_detections paints a YUV surface with."""
+    if matrix not in MATRICES:
+        raise ValueError(f"matrix must be one of {sorted(MATRICES)}, got {matrix!r}")
+    try:
+        r, g, b = (int(v) for v in color)
+    except (TypeError, ValueError):
+        raise ValueError(f"a colour is three bytes (R, G, B), got {color!r}") from None
+    if not all(0 <= v <= 255 for v in (r, g, b)):
+        raise ValueError(f"a colour is three bytes (R, G, B), got {color!r}")
+    kr, kb = MATRICES[matrix]
+    y = kr * r + (1 - kr - kb) * g + kb * b
+    cb, cr = (b - y) / (2 * (1 - kb)), (r - y) / (2 * (1 - kr))
+    if bool(full_range):
+        out = (y, 128 + cb, 128 + cr)
+    else:
+        out = (16 + Fraction(219, 255) * y, 128 + Fraction(224, 255) * cb, 128 + Fraction(224, 255) * cr)
+    return tuple(min(max(round(v), 0), 255) for v in out)
+
+
 def split_planes(frame, layout: str = "nv12"):
     """One frame in form (a), (b) or (c) -> (y [h, w], u [h / 2, w / 2], v [h / 2, w / 2]) as VIEWS of the given memory (for NV12, u and
     v are the two interleaved halves of the UV plane: element stride 2).  Nothing is copied except a form-(a) I420 tensor whose rows

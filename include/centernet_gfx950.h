@@ -399,6 +399,61 @@ int cnl_crop_boxes_u8(const void* frames, const float* boxes, const float* score
                       int32_t crop_h, int32_t crop_w, uint32_t fill_rgba, void* stream);
 
 /*
+ * Detections drawn onto their frames, in place: the output side of the frame pipeline (annotated preview, evidence clips, the
+ * surface handed to an encoder).  boxes [N, k, 4] (x1 y1 x2 y2 f32 in each frame's own pixels, 16-byte aligned) and the frames as
+ * cnl_crop_boxes_u8 takes them: `frames` is a device array of N WHOLE-FRAME records, of type cnl_letterbox_frame when yuv == 0 (C = 3
+ * or 4 channels; channel 3 is never modified), of type cnl_yuv420_frame with x0 = y0 = 0 when yuv != 0 (C = 3).  Of a record only the pointers,
+ * strides / pitches, c_step and h, w (the frame's size H, W <= 32768) are read.  Two launches on `stream` (a record kernel, one thread
+ * per slot; a paint kernel over the tiles of a max_h x max_w frame, the largest of the batch: pixels of a frame beyond that size are
+ * not painted), nothing goes to the host, no float atomics.  Everything below is integer once the corners are rounded.
+ *
+ * Colours.  The library knows no colour standard: palette is P + 1 four-byte entries in device memory (1 <= P <= 256), ALREADY in the
+ * frames' own space, byte c of an entry = bits 8c..8c+7: R G B for packed frames, Y U V for YUV frames; entry P is text_color.  The
+ * slot colour is palette[labels[n * k + j] mod P] with a non-negative modulus (labels: [N, k] int64, optional: entry 0 without).
+ *
+ * Live rule.  cnl_crop_boxes_u8's: slot (n, j) is live when (count == NULL or j < count[n]) and (scores == NULL or
+ * scores[n * k + j] >= score_threshold).  A NaN score is not live.
+ *
+ * Corners.  For each coordinate, one fp32 operation per step: v = rintf(x) (round half to even); v = v > -32768 ? v : -32768;
+ * v = v < 32767 ? v : 32767; then the conversion to int.  This gives X1, Y1, X2, Y2.  A slot is DEAD if it is not live, if any
+ * coordinate is not finite, or if X2 < X1 or Y2 < Y1.  A box wholly outside the frame is live but paints nothing.
+ *
+ * Layers of a slot.  With t = thickness (1..32), o = (t - 1) / 2 in integer division, i = t - o:
+ *     Interior  pixels with X1 <= x <= X2 and Y1 <= y <= Y2, painted only when fill_alpha = a > 0 (a in 0..256), per byte
+ *               out = (old * (256 - a) + colour * a + 128) >> 8.
+ *     Ring      pixels with X1 - o <= x <= X2 + o and Y1 - o <= y <= Y2 + o that are NOT in X1 + i <= x <= X2 - i and
+ *               Y1 + i <= y <= Y2 - i, set to the slot colour: t pixels wide, with SQUARE corners (cv2.rectangle rounds the corners
+ *               of thick lines; this rule does not).
+ *     Tag       only when tag_scale = s > 0 (s in 0..8) and numbers[n * k + j] = m >= 0 (numbers: [N, k] int32, optional), d the
+ *               count of m's decimal digits: a rectangle (6 d + 1) s wide and 9 s high, its left edge at X1 - o, its top at
+ *               T = Y1 - o - 9 s, or at T = Y1 - o if that is negative (the tag moves inside the box).  For the tag pixel at offset
+ *               (ty, tx): gy = ty / s - 1, gx = tx / s - 1, q = gx / 6, c = gx % 6 (integer division of non-negative values).  The
+ *               pixel is text_color when 0 <= gy < 7, gx >= 0, q < d, c < 5 and bit (4 - c) of row gy of the glyph of the q-th most
+ *               significant digit is set; otherwise the slot colour.  Glyph rows, top to bottom, five bits, the most significant
+ *               the left column:
+ *                   0: 01110 10001 10011 10101 11001 10001 01110      5: 11111 10000 11110 00001 00001 10001 01110
+ *                   1: 00100 01100 00100 00100 00100 00100 01110      6: 00110 01000 10000 11110 10001 10001 01110
+ *                   2: 01110 10001 00001 00010 00100 01000 11111      7: 11111 00001 00010 00100 01000 01000 01000
+ *                   3: 11111 00010 00100 00010 00001 10001 01110      8: 01110 10001 10001 01110 10001 10001 01110
+ *                   4: 00010 00110 01010 10010 11111 00010 00010      9: 01110 10001 10001 01111 00001 00010 01100
+ *
+ * Order.  A pixel's final value is the result of applying the slots j = k - 1 down to 0 (slot 0, the top score, ends on top); within
+ * a slot interior, then ring, then tag.  Everything is clipped to the frame.  A byte that no layer of any slot covers keeps its
+ * value: pitch padding and everything outside the h x w window of a surface included.
+ *
+ * YUV 4:2:0.  The Y plane follows the rule with byte 0 of the colours.  Chroma sample (cy, cx) is painted as if it were the pixel
+ * (2 cy, 2 cx) (nearest chroma, as in cnl_letterbox_yuv420_u8) through the same layers in the same order with bytes 1 and 2 (U, V);
+ * the blend is applied per plane.  Interleaved UV (c_step == 2, v == u + 1) and separate planes both go through c_step.
+ *
+ * records: workspace of N * k * 64 bytes, 16-byte aligned; the library allocates nothing.  N <= 65535, N * k < 2^31.  N == 0 or
+ * k == 0 is a no-op.
+ */
+int cnl_draw_boxes_u8(const void* frames, const float* boxes, const int64_t* labels, const int32_t* numbers, const float* scores,
+                      float score_threshold, const int32_t* count, int32_t N, int32_t k, int32_t C, int32_t yuv, const uint32_t* palette,
+                      int32_t P, int32_t thickness, int32_t fill_alpha, int32_t tag_scale, int32_t max_h, int32_t max_w,
+                      void* records, void* stream);
+
+/*
  * Sliced inference, the merge: the decoded boxes of the V views (network-sized tiles cut out of a frame, plus optionally the whole
  * frame letterboxed) of N frames go back into each frame's own pixels, and the duplicates the tile overlaps create are removed by a
  * greedy non-maximum suppression per frame.  Three launches for the whole batch, no device synchronisation, no float atomics.  (The
