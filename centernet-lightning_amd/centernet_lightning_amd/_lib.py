@@ -71,6 +71,15 @@ class MergeView(Structure):
                 ("sx", c_float), ("sy", c_float)]
 
 
+class FlipMap(Structure):
+    """cnl_flip_map: one head map of cnl_flip_merge_f32 (128 bytes): the two halves of the doubled batch and the destination, each a
+    pointer with the element strides of the logical axes (n, c, y, x)."""
+    _fields_ = [("a", c_void_p), ("a_sn", c_int64), ("a_sc", c_int64), ("a_sh", c_int64), ("a_sw", c_int64),
+                ("b", c_void_p), ("b_sn", c_int64), ("b_sc", c_int64), ("b_sh", c_int64), ("b_sw", c_int64),
+                ("dst", c_void_p), ("d_sn", c_int64), ("d_sc", c_int64), ("d_sh", c_int64), ("d_sw", c_int64),
+                ("C", c_int32), ("swap_lr", c_int32)]
+
+
 _SIGNATURES = {
     "cnl_version": (ctypes.c_int, []),
     "cnl_sizeof_params": (c_size_t, [ctypes.c_int32]),
@@ -115,6 +124,8 @@ _SIGNATURES = {
                                          c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_uint32, c_void_p]),
     "cnl_draw_boxes_u8": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int32, c_int32, c_int32, c_int32,
                                          c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    "cnl_flip_merge_f32": (ctypes.c_int, [POINTER(FlipMap), c_int32, c_int32, c_int32, c_int32, c_void_p]),
+    "cnl_mirror_append_u8": (ctypes.c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "cnl_merge_tiles_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32]),
     "cnl_merge_tiles_f32": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32,
                                            c_float, c_float, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

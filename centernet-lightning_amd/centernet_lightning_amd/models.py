@@ -21,6 +21,7 @@ from torch import nn
 
 from . import crops as _crops
 from . import decode as _decode
+from . import flip as _flip
 from . import letterbox as _letterbox
 from . import overlay as _overlay
 from . import tiles as _tiles
@@ -136,14 +137,23 @@ class CenterNet(nn.Module):
         return super().train(False)
 
     # ------------------------------------------------------------------ forward
-    def get_encoded_outputs(self, x: torch.Tensor) -> Dict[str, torch.Tensor]:
-        """Forward pass returning a dict of logits (heatmap BEFORE sigmoid) — docs/implementation.md:77."""
+    def get_encoded_outputs(self, x: torch.Tensor, flip_test: bool = False) -> Dict[str, torch.Tensor]:
+        """Forward pass returning a dict of logits (heatmap BEFORE sigmoid) — docs/implementation.md:77.
+        flip_test: as in forward(); the heatmap LOGITS of the image and of its mirror are averaged."""
+        if flip_test:
+            return _flip.flip_merge(dict(self._engine.forward(_flip.mirror_append(x), sigmoid=False)), x.shape[0])
         return dict(self._engine.forward(x, sigmoid=False))
 
     get_output_dict = get_encoded_outputs          # alias used at utils/image_annotate.py:220, fairmot.py:88
 
-    def forward(self, x: torch.Tensor):
-        """namedtuple(heatmap after sigmoid, box_2d[, reid]) — docs/implementation.md:78; tests/test_models.py:88-99."""
+    def forward(self, x: torch.Tensor, flip_test: bool = False):
+        """namedtuple(heatmap after sigmoid, box_2d[, reid]) — docs/implementation.md:78; tests/test_models.py:88-99.
+        flip_test: the flip test of the original CenterNet.  The network runs on 2N inputs, the images and their left-right mirrors
+        (torch.cat((x, x.flip(-1))); the video path is forward_uint8), and every head map is the mean of the image's and the mirror's,
+        mirrored back, before any decode (flip.flip_merge, one launch: the post-sigmoid heatmaps are averaged; box_2d swaps left and
+        right and is averaged as the raw head output, which with box_log is a geometric mean of the sizes)."""
+        if flip_test:
+            return _flip.flip_merge(self.forward(_flip.mirror_append(x)), x.shape[0])
         out = self._engine.forward(x, sigmoid=True)
         if "reid" in out:
             return TrackingOutput(out["heatmap"], out["box_2d"], out["reid"])
@@ -201,12 +211,16 @@ class CenterNet(nn.Module):
                                                   ctypes.c_void_p(torch.cuda.current_stream(images.device).cuda_stream)), "cnl_resize_bilinear_u8")
         return out
 
-    def forward_uint8(self, images: torch.Tensor, resize=None, mean=IMAGENET_MEAN, std=IMAGENET_STD):
+    def forward_uint8(self, images: torch.Tensor, resize=None, mean=IMAGENET_MEAN, std=IMAGENET_STD, flip_test: bool = False):
         """The reference's inference pre-processing fused into the path (README.md:79-101): uint8 HWC frames [N,H,W,3] ->
         [A.Resize(*resize) ->] A.Normalize -> forward().  The normalisation happens on the stem kernel's staged patch
-        (cnl_stem_conv7x7_u8), so no fp32 image tensor is ever written: bit-identical to forward(preprocess_uint8(images))."""
+        (cnl_stem_conv7x7_u8), so no fp32 image tensor is ever written: bit-identical to forward(preprocess_uint8(images)).
+        flip_test: as in forward(); the (resized) frames are doubled by flip.mirror_append_uint8 (one launch) and the 2N outputs merged
+        by flip.flip_merge (one launch)."""
         if resize is not None:
             images = self.resize_uint8(images, int(resize[0]), int(resize[1]))
+        if flip_test:
+            return _flip.flip_merge(self.forward_uint8(_flip.mirror_append_uint8(images), mean=mean, std=std), images.shape[0])
         m, r = self._norm_constants(mean, std)
         out = self._engine.forward_u8(images.contiguous(), m, r, sigmoid=True)
         if "reid" in out:
@@ -233,12 +247,13 @@ class CenterNet(nn.Module):
 
     def detect_frames(self, frames, height: int = 512, width: int = 512, fill=(0, 0, 0), mean=IMAGENET_MEAN, std=IMAGENET_STD,
                       num_detections: int = 100, nms_kernel: int = 3, pixel_format: str = "rgb", matrix: str = "bt601",
-                      full_range: bool = False):
+                      full_range: bool = False, flip_test: bool = False):
         """Frames of different sizes -> {"bboxes" (each frame's own pixels, clipped to it), "labels", "scores"[, "embeddings"]}:
         letterbox_uint8 -> forward_uint8 on the canvas (the stem normalises: still no fp32 image in memory) -> the decode ->
         unletterbox.  Nothing between the frames and the result touches the host except the table upload.
         pixel_format "nv12" / "i420": the frames are YUV 4:2:0 surfaces (yuv.letterbox_yuv420 in place of letterbox_uint8; `matrix` and
-        `full_range` choose the conversion); "rgb" ignores both."""
+        `full_range` choose the conversion); "rgb" ignores both.
+        flip_test: forward_uint8's; the CANVAS is mirrored, after the letterbox, so the geometry table and unletterbox are untouched."""
         if pixel_format == "rgb":
             canvas, geom = _letterbox.letterbox_uint8(frames, height, width, fill)
         elif pixel_format in _yuv.LAYOUTS:
@@ -247,7 +262,7 @@ class CenterNet(nn.Module):
             raise ValueError(f"pixel_format must be 'rgb' or one of {list(_yuv.LAYOUTS)}, got {pixel_format!r}")
         if canvas.shape[-1] != 3:
             raise ValueError(f"detect_frames expects 3-channel frames, got {canvas.shape[-1]} channels")
-        out = self.forward_uint8(canvas, mean=mean, std=std)
+        out = self.forward_uint8(canvas, mean=mean, std=std, flip_test=flip_test)
         gather = self.gather_tracking2d if len(out) == 3 else self.gather_detection2d
         dets = gather(out, num_detections=num_detections, nms_kernel=nms_kernel, normalize_bbox=False)
         _letterbox.unletterbox_(dets["bboxes"], geom, True)
@@ -286,13 +301,16 @@ class CenterNet(nn.Module):
     def detect_tiled(self, frames, tile=(512, 512), overlap: float = 0.2, full_frame: bool = True, batch: int = 32, fill=(0, 0, 0),
                      mean=IMAGENET_MEAN, std=IMAGENET_STD, num_detections: int = 100, nms_kernel: int = 3, max_detections: int = 300,
                      score_threshold: float = 0.1, match_threshold: float = 0.5, match_metric: str = "iou", class_aware: bool = True,
-                     max_candidates: int = 4096, pixel_format: str = "rgb", matrix: str = "bt601", full_range: bool = False):
+                     max_candidates: int = 4096, pixel_format: str = "rgb", matrix: str = "bt601", full_range: bool = False,
+                     flip_test: bool = False):
         """Sliced inference for frames larger than the network input -> {"bboxes" [N,max_detections,4] (each frame's own pixels),
         "labels", "scores", "count" [N] int32[, "embeddings"]}; rows past a frame's count are zero.
         tile_uint8 (one launch) -> forward_uint8 + the decode on chunks of at most `batch` views -> one merge over all frames
         (class-aware greedy NMS, IoU or intersection-over-smaller) -> for tracking models the embeddings of the survivors.
         Nothing between the frames and the result touches the host except the table upload.
-        pixel_format "nv12" / "i420": the frames are YUV 4:2:0 surfaces (yuv.tile_yuv420 in place of tile_uint8), as in detect_frames."""
+        pixel_format "nv12" / "i420": the frames are YUV 4:2:0 surfaces (yuv.tile_yuv420 in place of tile_uint8), as in detect_frames.
+        flip_test: forward_uint8's, on the gathered VIEWS (the tile table and merge_tiles are untouched): a chunk is still at most
+        `batch` views, and its forward sees twice that many inputs."""
         if isinstance(batch, bool) or not isinstance(batch, int) or batch < 1:
             raise ValueError(f"detect_tiled: batch must be a positive int, got {batch!r}")
         if pixel_format == "rgb":
@@ -305,7 +323,7 @@ class CenterNet(nn.Module):
             raise ValueError(f"detect_tiled expects 3-channel frames, got {views.shape[-1]} channels")
         parts = []
         for i in range(0, views.shape[0], batch):
-            out = self.forward_uint8(views[i:i + batch], mean=mean, std=std)
+            out = self.forward_uint8(views[i:i + batch], mean=mean, std=std, flip_test=flip_test)
             gather = self.gather_tracking2d if len(out) == 3 else self.gather_detection2d
             parts.append(gather(out, num_detections=num_detections, nms_kernel=nms_kernel, normalize_bbox=False))
         dets = {key: (torch.cat([p[key] for p in parts]) if len(parts) > 1 else parts[0][key]) for key in parts[0]}

@@ -454,6 +454,47 @@ int cnl_draw_boxes_u8(const void* frames, const float* boxes, const int64_t* lab
                       void* records, void* stream);
 
 /*
+ * The flip test (test-time augmentation of the original CenterNet): the network also sees every image mirrored left-right and the two
+ * sets of head outputs are averaged BEFORE pseudo-NMS and top-k.  For a batch of N images the network runs on 2N inputs, input N + n
+ * being input n mirrored AT THE NETWORK INPUT, x -> W_in - 1 - x.  W_in is a multiple of 32 and the output stride divides it, so input
+ * column x maps to feature column W - 1 - x exactly.  The doubled batch is ONE forward, so both halves come from one plan and one
+ * launch list, whatever the batch size.
+ *
+ * cnl_mirror_append_u8 builds the doubled uint8 input in one launch: src [N,H,W,C] and dst [2N,H,W,C] dense, C in 1..4,
+ *     dst[n] = src[n],   dst[N + n, y, x] = src[n, y, W - 1 - x].
+ * dst must not overlap src; 2 * N * H * W * C < 2^31; an empty batch is a no-op.
+ *
+ * cnl_flip_merge_f32 merges up to three head maps of the 2N forward (logical shape [2N, C, H, W] each) in one launch.  The rule:
+ *     merged[n, c, y, x] = 0.5f * ( a[n, c, y, x] + b[n, p(c), y, W - 1 - x] )
+ * where a is the map of the first N inputs and b the map of the mirrored ones.  p(c) = c, except for a map with swap_lr != 0 (box_2d:
+ * its channels are the distances left, top, right, bottom, and left and right trade places under a mirror; C must be 4), where p swaps
+ * channels 0 and 2.  The arithmetic is one IEEE fp32 add followed by one multiply by 0.5, nothing fused: NaN and inf propagate as
+ * they fall, denormals are kept, and the result equals (a + b.flip(-1)[:, perm]) * 0.5 in torch bit for bit.  The heatmap operand is
+ * whatever map the caller has (post-sigmoid or logits); box_2d is averaged as the raw head output, before the decode's exp /
+ * multiplier / clamp (with box_log the average of logarithms: a geometric mean of the sizes).
+ *
+ * `maps` is a HOST array of n_maps (0..3) descriptors, copied into the launch.  a, b and dst are device pointers, 4-byte aligned, each
+ * addressed through its own element strides of the logical axes (n, c, y, x) as the decode does: element (n, c, y, x) of a lies at
+ * a + n * a_sn + c * a_sc + y * a_sh + x * a_sw.  a and b are separate pointers, not one [2N] tensor: a forward that ran in
+ * sub-batches may hand its halves over separately.  dst elements must be distinct and must not overlap a or b.  Channels-last maps
+ * (every channel stride 1, C % 4 == 0) and plane maps (every column stride 1) move 16 bytes per access, everything else single
+ * elements; no alignment beyond 4 bytes is asked for in either.  N * C * H * W < 2^31 per map.  N, H or W == 0, or n_maps == 0, is a
+ * no-op.  No allocation, no synchronisation.
+ */
+typedef struct cnl_flip_map {
+    const float* a;                    /* the map of inputs 0 .. N-1 */
+    int64_t a_sn, a_sc, a_sh, a_sw;
+    const float* b;                    /* the map of inputs N .. 2N-1 (the mirrored images) */
+    int64_t b_sn, b_sc, b_sh, b_sw;
+    float* dst;                        /* merged, logical [N, C, H, W] */
+    int64_t d_sn, d_sc, d_sh, d_sw;
+    int32_t C;
+    int32_t swap_lr;                   /* != 0: channels 0 and 2 of b trade places (C == 4) */
+} cnl_flip_map;                        /* 128 bytes */
+int cnl_flip_merge_f32(const cnl_flip_map* maps, int32_t n_maps, int32_t N, int32_t H, int32_t W, void* stream);
+int cnl_mirror_append_u8(const uint8_t* src, uint8_t* dst, int32_t N, int32_t H, int32_t W, int32_t C, void* stream);
+
+/*
  * Sliced inference, the merge: the decoded boxes of the V views (network-sized tiles cut out of a frame, plus optionally the whole
  * frame letterboxed) of N frames go back into each frame's own pixels, and the duplicates the tile overlaps create are removed by a
  * greedy non-maximum suppression per frame.  Three launches for the whole batch, no device synchronisation, no float atomics.  (The
