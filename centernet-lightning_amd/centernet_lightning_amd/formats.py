@@ -8,7 +8,8 @@ with the detector, produced from this package's device-resident outputs.
   load_checkpoint              <- CenterNet.load_from_checkpoint as used by tools/export.py:8,15: Lightning `.ckpt` -> this model
 
 Only the box conversion is device work (cnl_boxes_xyxy_to_xywh_f32); the rest is host-side record building, kept identical to
-the reference's so that its evaluators (pycocotools / TrackEval — not in this image) read the same bytes.
+the reference's so that its evaluators (pycocotools / TrackEval) read the same bytes.  COCO box metrics need neither these records
+nor pycocotools: coco_eval.CocoEvaluator computes them on the device from the detections as decoded.
 """
 import ctypes
 import json

@@ -19,6 +19,7 @@ from typing import Any, Dict, Union
 import torch
 from torch import nn
 
+from . import coco_eval as _coco_eval
 from . import crops as _crops
 from . import decode as _decode
 from . import flip as _flip
@@ -370,6 +371,10 @@ class CenterNet(nn.Module):
     @staticmethod
     def gather_and_decode_boxes(box_offsets, indices, normalize_boxes=False, box_log=False, box_multiplier=1.0, stride=4):
         return _decode.gather_boxes(box_offsets, indices, normalize_boxes, box_log, box_multiplier, stride)
+
+    def evaluator(self, device=None):
+        """A CocoEvaluator for this model's classes: feed it gather_detection2d's dict and the targets, batch by batch (coco_eval.py)."""
+        return _coco_eval.CocoEvaluator(self.num_classes, device)
 
     # ------------------------------------------------------------------ multi-GPU
     def collate(self, detections: Dict[str, torch.Tensor], group=None):

@@ -542,6 +542,59 @@ int cnl_merge_tiles_f32(const float* boxes, const float* scores, const int64_t* 
                         void* stream);
 
 /*
+ * COCO box evaluation (eval/coco.py: CocoEvaluator -> pycocotools COCOeval, iouType "bbox") without pycocotools and without the
+ * detections leaving the device.  Two entry points (pure additions: the ABI number stays); both are asynchronous on `stream`, allocate
+ * nothing and do no device synchronisation.
+ *
+ * The rule — COCOeval on the records CocoEvaluator.create_coco builds (eval/coco.py:78-107): every annotation has iscrowd = 0 and no
+ * `ignore`, area = w * h, categories 0 .. num_classes-1, image ids in order of arrival.  tests/coco_eval_ref.py restates it in numpy;
+ * every comparison with it is an equality of float64 bits.
+ *   Parameters.  T: iouThrs = np.linspace(.5, .95, 10).  R: recThrs = np.linspace(0, 1, 101).  M: maxDets = (1, 10, 100).  A: the area
+ *     ranges all [0, 1e10], small [0, 32^2], medium [32^2, 96^2], large [96^2, 1e10]; a box is OUT of a range when area < lo or
+ *     area > hi (both bounds inclusive: area 1024 is small and medium).
+ *   Numbers.  All arithmetic is float64, every operation rounded on its own (no fused multiply-add; the division is the IEEE one).
+ *     Detection boxes are fp32 x1 y1 x2 y2: w = x2 - x1 and h = y2 - y1 are formed in fp32 and then widened, x = x1, y = y1.  Ground
+ *     truths are float64 x y w h as given.  Areas are the float64 products w * h.  Coordinates and scores must be finite.
+ *   IoU of detection D and ground truth G: w = min(Dx + Dw, Gx + Gw) - max(Dx, Gx), h alike; IoU = 0 if w <= 0 or h <= 0; otherwise
+ *     i = w * h, u = (Dw * Dh + Gw * Gh) - i, IoU = i / u.
+ *   Per image and category: the detections of the category (slots below count[n]; a label outside 0..num_classes-1 is dropped) ordered
+ *     by descending score, stably (equal scores keep their slot order); the first 100 are kept, a detection's place in that list is
+ *     its CLASS RANK (0-based).
+ *   Per (image, category, area range a, threshold t): a ground truth is IGNORED when its area is out of range a.  The detections are
+ *     walked in class-rank order; for each one, with best = min(t, 1 - 1e-10): among the not yet taken, not ignored ground truths of
+ *     the category with IoU >= best the largest IoU wins, the LAST in order of arrival among equals; only if there is none, the same
+ *     choice among the not yet taken ignored ones.  A winner is taken; the detection is matched and inherits the winner's ignored
+ *     flag.  (This is COCOeval's sequential walk over the ground truths sorted not-ignored first: tests/test_coco_eval_host.py checks
+ *     the equivalence.)  An unmatched detection whose own area is out of range a is ignored.
+ *   Accumulate, per (category c, range a, maxDet m): the detections of c with class rank < m, in order of arrival (image, then rank),
+ *     ordered by descending score, stably.  npig = the not ignored ground truths of c in range a over all images.  npig == 0: the
+ *     cell's precision and recall stay -1.  Otherwise per t: tp = cumsum(matched & ~ignored), fp = cumsum(~matched & ~ignored),
+ *     rc = tp / npig, pr = tp / (fp + tp + 2^-52); recall[t, c, a, m] = rc[-1] (0 without detections); pr is made non-increasing from
+ *     the right (pr[i-1] = max(pr[i-1], pr[i])); precision[t, r, c, a, m] = pr[first i with rc[i] >= R[r]], 0 when there is none.
+ *   Summarise (host): AP = the mean of the entries > -1 of a precision slice, AR of a recall slice, -1 for a slice without any.
+ *
+ * cnl_coco_match_f64: one launch for a batch of N images, one workgroup per image.  boxes [N, k, 4] fp32 (16-byte aligned), scores
+ * [N, k] fp32, labels [N, k] i64, count NULL or [N] i32 (the slots that hold detections; clamped to 0..k); gt_boxes [N, Gmax, 4] f64
+ * x y w h, gt_labels [N, Gmax] i64 (a label outside 0..num_classes-1 takes no part), gt_count [N] i32 (clamped to 0..Gmax).  Written
+ * for every detection slot: out_rank [N, k] i32 (the class rank; -1 for a dropped slot: past the count, label out of range, or rank
+ * >= 100), out_matched and out_ignored [N, k] i64 (bit a * 10 + t of each; 0 for a dropped slot).  npig [num_classes, 4] i64 is
+ * INCREMENTED (integer atomics): the caller zeroes it once per epoch.  A record depends on its own image only.
+ * Limits (CNL_E_BAD_ARG otherwise): N in 0..2^20 (0 is a no-op), k in 1..1024, Gmax in 1..1024, num_classes in 1..2^20.
+ *
+ * cnl_coco_accumulate_f64: one launch per evaluation, one workgroup per (category, range, maxDet).  The caller has ordered the epoch's
+ * `total` records (total < 2^31) by category, inside a category by descending score, equal scores in order of arrival (two stable
+ * sorts), with the dropped records (rank -1) behind the last category: rank, matched, ignored are the match's outputs in that order,
+ * and segment_first [num_classes + 1] i64 holds where each category's records start (entries are forced into 0..total on the
+ * device).  npig as above.  Written, every element: precision [10, 101, num_classes, 4, 3] f64 and recall [10, num_classes, 4, 3] f64,
+ * both dense with the last axis fastest.
+ */
+int cnl_coco_match_f64(const float* boxes, const float* scores, const int64_t* labels, const int32_t* count, const double* gt_boxes,
+                       const int64_t* gt_labels, const int32_t* gt_count, int32_t N, int32_t k, int32_t Gmax, int32_t num_classes,
+                       int32_t* out_rank, int64_t* out_matched, int64_t* out_ignored, int64_t* npig, void* stream);
+int cnl_coco_accumulate_f64(const int32_t* rank, const int64_t* matched, const int64_t* ignored, const int64_t* segment_first,
+                            const int64_t* npig, int64_t total, int32_t num_classes, double* precision, double* recall, void* stream);
+
+/*
  * ResNet stem: Conv2d(3,64,7,stride=2,padding=3,bias=False)+BN+ReLU (torchvision resnet.conv1/bn1/relu).
  * x is read through explicit element strides (sn,sc,sh,sw) so NCHW-contiguous and channels_last
  * callers are both zero-copy (models/meta.py:97-98 precedent); y is NHWC [N, H/2, W/2, 64].
