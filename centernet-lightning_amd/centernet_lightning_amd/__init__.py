@@ -9,9 +9,9 @@ from .models import CenterNet, DetectionOutput, TrackingOutput, build_centernet
 from .collate import (Collator, all_gather_records, collate_detections, pack_detections, shard_range, unpack_detections)
 from .tracker import Tracker, TrackerBank, Track, TrackState, build_tracker, match_with_threshold
 from . import decode, formats
-from .letterbox import LetterboxGeometry, letterbox_geometry
-from .tiles import TileGeometry, merge_tiles, tile_grid, tile_uint8
-from .yuv import letterbox_yuv420, rgb_to_yuv, split_planes, tile_yuv420, yuv_coefficients
+from .letterbox import LetterboxGeometry, letterbox_geometry, letterbox_yuv420
+from .tiles import TileGeometry, merge_tiles, tile_grid, tile_uint8, tile_yuv420
+from .yuv import rgb_to_yuv, split_planes, yuv_coefficients
 from .crops import crop_detections
 from .overlay import DEFAULT_PALETTE, draw_detections
 from .flip import flip_merge, mirror_append_uint8

@@ -1,6 +1,7 @@
 """The one host path into the gather launch (csrc/letterbox.hip) that letterbox_uint8, tile_uint8, letterbox_yuv420 and tile_yuv420
-share: what they check of uint8 frames, and records -> one pinned upload -> one launch.  No device sync anywhere.  crop_detections
-packs its whole-frame records with the same two functions (pack_plain, pack_yuv) and uploads them the same way (upload)."""
+share: records -> one pinned upload -> one launch.  No device sync anywhere.  crop_detections and draw_detections build their
+whole-frame records with the same packer (pack_records) and upload them the same way (upload).  The windows and the (plain, planes)
+records come from a frame source (_frames.Frames.records)."""
 import ctypes
 from typing import NamedTuple, Optional
 
@@ -13,21 +14,6 @@ def require_hip(tensors, what: str) -> None:
     for t in tensors:
         if not (isinstance(t, torch.Tensor) and t.is_cuda):
             raise RuntimeError(f"{what} runs on HIP devices only (no CPU fallback)")
-
-
-def uint8_frames(frames, what: str):
-    """A sequence of uint8 [h_i, w_i, C] tensors on one HIP device, C in 1..4 and the same for all -> (list of them, device, C)."""
-    frames = list(frames)
-    if not frames:
-        raise ValueError(f"{what}: no frames")
-    require_hip(frames, what)
-    dev, C = frames[0].device, frames[0].shape[-1] if frames[0].dim() == 3 else -1
-    for f in frames:
-        if f.dtype != torch.uint8 or f.dim() != 3 or f.shape[-1] != C or not 1 <= C <= 4:
-            raise ValueError(f"expected uint8 [h,w,C<=4] frames with one C, got {f.dtype} {tuple(f.shape)}")
-        if f.device != dev:
-            raise ValueError(f"frames live on different devices ({dev}, {f.device})")
-    return frames, dev, C
 
 
 class Gathered(NamedTuple):
@@ -61,6 +47,19 @@ def pack_yuv(rec, windows, planes) -> None:
                                                   for p, (_, y0, x0, h, w, nh, nw, pt, pl) in zip(planes, windows)]
 
 
+def pack_records(windows, plain, planes=None, tail_words: int = 0):
+    """-> the zeroed int64 numpy buffer [V x 9] cnl_yuv420_frame records (planes given) or [V x 5] cnl_letterbox_frame records, then
+    tail_words words for the caller.  windows, plain, planes: as Frames.records gives them.  Needs neither a device nor the library."""
+    import numpy as np
+    V, words = len(windows), 9 if planes is not None else 5
+    buf = np.zeros(V * words + tail_words, dtype=np.int64)
+    if planes is not None:
+        pack_yuv(buf[:V * 9].reshape(V, 9), windows, planes)
+    else:
+        pack_plain(buf[:V * 5].reshape(V, 5), windows, plain)
+    return buf
+
+
 def upload(buf, dev) -> torch.Tensor:
     """The int64 numpy buffer -> device memory through one pinned staging tensor, asynchronously (call under torch.cuda.device(dev))."""
     host = torch.empty((buf.size,), dtype=torch.int64, pin_memory=True)
@@ -83,11 +82,13 @@ def gather(dev, windows, plain, height: int, width: int, C: int, word: int, plan
     o_plain = V * 9 if planes is not None else 0
     o_merge = o_plain + V * 5
     o_first = o_merge + (V * 4 if merge_records is not None else 0)
-    buf = np.zeros(o_first + (n_first + 1) // 2, dtype=np.int64)
+    # pack_records writes the records the launch reads, which come first ([V x 9] YUV or [V x 5] plain), and leaves the rest of the
+    # layout above as its zeroed tail: [lead records | tail]; of a YUV gather the tail starts with the plain records.
+    lead = o_plain if planes is not None else o_merge
+    buf = pack_records(windows, plain, planes, tail_words=o_first + (n_first + 1) // 2 - lead)
     assert ctypes.sizeof(_lib.MergeView) == 32
-    pack_plain(buf[o_plain:o_merge].reshape(V, 5), windows, plain)
-    if planes is not None:
-        pack_yuv(buf[:o_plain].reshape(V, 9), windows, planes)
+    if planes is not None:                       # the launch reads the YUV records; unletterbox reads the plain ones
+        pack_plain(buf[o_plain:o_merge].reshape(V, 5), windows, plain)
     if merge_records is not None:
         buf[o_merge:o_first].view(np.int32).reshape(V, 8)[:] = np.array(merge_records, dtype=np.int32)
         buf[o_first:].view(np.int32)[:n_first] = frame_first_view

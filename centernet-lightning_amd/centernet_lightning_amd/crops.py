@@ -12,12 +12,9 @@ tests/crop_ref.py.
 import ctypes
 import math
 
-import numpy as np
 import torch
 
-from . import _gather, _lib
-from . import yuv as _yuv
-from .letterbox import _fill_word
+from . import _frames, _gather, _lib
 
 
 def _size(size):
@@ -31,17 +28,6 @@ def _size(size):
     if ch < 1 or cw < 4 or cw % 4:
         raise ValueError(f"crop size {ch} x {cw} needs a height >= 1 and a width that is a positive multiple of 4")
     return ch, cw
-
-
-def _per_slot(t, name, dtype, shape, dev):
-    if not isinstance(t, torch.Tensor):
-        raise ValueError(f"{name} must be a tensor, got {type(t).__name__}")
-    _gather.require_hip([t], "crop_detections")
-    if t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous():
-        raise ValueError(f"expected contiguous {dtype} {name} of shape {list(shape)}, got {t.dtype} {tuple(t.shape)}")
-    if t.device != dev:
-        raise ValueError(f"{name} lives on {t.device}, the frames on {dev}")
-    return t
 
 
 def crop_detections(frames, bboxes, size=(128, 64), scores=None, score_threshold=None, count=None, pad: float = 0.0,
@@ -61,52 +47,20 @@ def crop_detections(frames, bboxes, size=(128, 64), scores=None, score_threshold
     ch, cw = _size(size)
     if isinstance(pad, bool) or not isinstance(pad, (int, float)) or not math.isfinite(pad) or pad < 0:
         raise ValueError(f"pad must be a finite number >= 0, got {pad!r}")
-    if (scores is None) != (score_threshold is None):
-        raise ValueError("scores and score_threshold are given together")
-    if score_threshold is not None and (isinstance(score_threshold, bool) or not isinstance(score_threshold, (int, float))
-                                        or math.isnan(score_threshold)):
-        raise ValueError(f"score_threshold must be a number, got {score_threshold!r}")
-    if pixel_format == "rgb":
-        if isinstance(frames, torch.Tensor):
-            if frames.dim() != 4:
-                raise ValueError(f"expected a sequence of uint8 [h,w,C] frames or one [N,h,w,C] tensor, got {tuple(frames.shape)}")
-            _gather.require_hip([frames], what)
-            if frames.dtype != torch.uint8:
-                raise ValueError(f"expected uint8 frames, got {frames.dtype}")
-            frames = frames.contiguous().unbind(0)
-        frames, dev, C = _gather.uint8_frames(frames, what)
-        keep = [f.contiguous() for f in frames]
-        windows = [(n, 0, 0, f.shape[0], f.shape[1], 1, 1, 0, 0) for n, f in enumerate(keep)]
-        plain, planes, coef = [(f.data_ptr(), f.shape[1] * C) for f in keep], None, None
-    elif pixel_format in _yuv.LAYOUTS:
-        coef = (ctypes.c_int32 * 6)(*_yuv.yuv_coefficients(matrix, full_range))
-        keep = _yuv._parse(frames, pixel_format, what)
-        dev, C = _yuv._device(keep, what), 3
-        windows = [(n, 0, 0, p[6], p[7], 1, 1, 0, 0) for n, p in enumerate(keep)]
-        plain, planes = _yuv._records(keep, windows)
-    else:
-        raise ValueError(f"pixel_format must be 'rgb' or one of {list(_yuv.LAYOUTS)}, got {pixel_format!r}")
-    word = _fill_word(fill, C)
-    N = len(windows)
-    if not isinstance(bboxes, torch.Tensor):
-        raise ValueError(f"bboxes must be a tensor, got {type(bboxes).__name__}")
-    _gather.require_hip([bboxes], what)
-    if bboxes.dtype != torch.float32 or bboxes.dim() != 3 or bboxes.shape[-1] != 4 or not bboxes.is_contiguous():
-        raise ValueError(f"expected contiguous float32 [N,k,4] boxes, got {bboxes.dtype} {tuple(bboxes.shape)}")
-    if bboxes.shape[0] != N or bboxes.device != dev:
-        raise ValueError(f"boxes of {bboxes.shape[0]} frames on {bboxes.device} against {N} frames on {dev}")
-    k = int(bboxes.shape[1])
+    _frames.check_score_pair(scores, score_threshold)
+    src = _frames.open_frames(frames, pixel_format, what, matrix, full_range)
+    dev, C, N = src.check_device(), src.C, len(src)
+    word = _frames.fill_word(fill, C)
+    k = _frames.check_boxes(bboxes, N, dev, what)
     if scores is not None:
-        scores = _per_slot(scores, "scores", torch.float32, (N, k), dev)
+        scores = _frames.per_slot(scores, "scores", torch.float32, (N, k), dev, what)
     if count is not None:
-        count = _per_slot(count, "count", torch.int32, (N,), dev)
+        count = _frames.per_slot(count, "count", torch.int32, (N,), dev, what)
 
-    words = 9 if planes is not None else 5                        # int64 words of a cnl_yuv420_frame / cnl_letterbox_frame
-    buf = np.zeros(N * words, dtype=np.int64)
-    if planes is not None:
-        _gather.pack_yuv(buf.reshape(N, 9), windows, planes)
-    else:
-        _gather.pack_plain(buf.reshape(N, 5), windows, plain)
+    windows = src.whole()
+    buf = _gather.pack_records(windows, *src.records(windows))
+    words = 9 if src.kind == _frames.YUV else 5                   # int64 words of a cnl_yuv420_frame / cnl_letterbox_frame
+    coef = (ctypes.c_int32 * 6)(*src.coef) if src.coef is not None else None
     lib = _lib.load()
     with torch.cuda.device(dev):
         table = _gather.upload(buf, dev)

@@ -5,11 +5,11 @@ original_height / original_width) one image at a time on the host.  Here the geo
 sync), the pixels are one launch of cnl_letterbox_bilinear_u8 and the boxes one launch of cnl_unletterbox_boxes_f32.
 """
 import ctypes
-from typing import List, Sequence, Tuple
+from typing import List, Tuple
 
 import torch
 
-from . import _gather, _lib
+from . import _frames, _gather, _lib
 
 
 def letterbox_geometry(h: int, w: int, height: int, width: int) -> Tuple[int, int, int, int]:
@@ -57,45 +57,38 @@ class LetterboxGeometry:
         return f"LetterboxGeometry(n={len(self.frames)}, canvas={self.height}x{self.width})"
 
 
-def _fill_word(fill, C: int) -> int:
-    vals = [fill] * 4 if isinstance(fill, int) else list(fill)
-    if len(vals) < C or any((not isinstance(v, int)) or v < 0 or v > 255 for v in vals):
-        raise ValueError(f"fill must be one uint8 value or at least {C} of them, got {fill!r}")
-    word = 0
-    for c, v in enumerate(vals[:4]):
-        word |= v << (8 * c)
-    return word
+def letterbox_frames(frames, height: int, width: int, fill=(0, 0, 0), pixel_format: str = "rgb", matrix: str = "bt601", full_range: bool = False):
+    """The one function behind letterbox_uint8 (pixel_format "rgb") and letterbox_yuv420 ("nv12" / "i420"), which detect_frames calls with
+    its pixel_format: frame source -> geometry -> one gather."""
+    src = _frames.open_frames(frames, pixel_format, "letterbox_uint8" if pixel_format == "rgb" else "letterbox_yuv420", matrix, full_range)
+    height, width = int(height), int(width)
+    geo = [(h, w) + letterbox_geometry(h, w, height, width) for (h, w) in src.sizes]
+    word = _frames.fill_word(fill, src.C)
+    windows = [(n, 0, 0) + g for n, g in enumerate(geo)]
+    plain, planes = src.records(windows)
+    dev = src.check_device()                     # (YUV frames: only now, after the canvas and the fill)
+    g = _gather.gather(dev, windows, plain, height, width, src.C, word, planes=planes, coef=src.coef)
+    return g.canvas, LetterboxGeometry(g.table, geo, height, width, keep=src.keep, yuv_table=g.yuv_table)
 
 
 def letterbox_uint8(frames, height: int, width: int, fill=(0, 0, 0)):
     """frames: a sequence of uint8 [h_i, w_i, C] tensors on one HIP device (C in 1..4, the same for all), or one [N, h, w, C] tensor
     -> (canvas [N, height, width, C] uint8, LetterboxGeometry).  One launch; one pinned-memory upload (the table); no device sync."""
-    if isinstance(frames, torch.Tensor):
-        if frames.dim() != 4:
-            raise ValueError(f"expected a sequence of uint8 [h,w,C] frames or one [N,h,w,C] tensor, got {tuple(frames.shape)}")
-        _gather.require_hip([frames], "letterbox_uint8")
-        if frames.dtype != torch.uint8:
-            raise ValueError(f"expected uint8 frames, got {frames.dtype}")
-        frames = frames.contiguous().unbind(0)
-    frames, dev, C = _gather.uint8_frames(frames, "letterbox_uint8")
-    height, width = int(height), int(width)
-    geo = [(f.shape[0], f.shape[1]) + letterbox_geometry(f.shape[0], f.shape[1], height, width) for f in frames]
-    word = _fill_word(fill, C)
-    frames = [f.contiguous() for f in frames]
-    windows = [(n, 0, 0) + g for n, g in enumerate(geo)]
-    plain = [(f.data_ptr(), f.shape[1] * C) for f in frames]
-    g = _gather.gather(dev, windows, plain, height, width, C, word)
-    return g.canvas, LetterboxGeometry(g.table, geo, height, width, keep=frames)
+    return letterbox_frames(frames, height, width, fill)
+
+
+def letterbox_yuv420(frames, height: int, width: int, layout: str = "nv12", matrix: str = "bt601", full_range: bool = False, fill=(0, 0, 0)):
+    """frames: a sequence of YUV 4:2:0 frames on one HIP device (forms (a), (b), (c) of yuv.py's docstring; sizes may differ)
+    -> (canvas [N, height, width, 3] uint8 RGB, LetterboxGeometry): letterbox_uint8 of the converted frames, bit for bit, without the
+    converted frames.  One launch; one pinned-memory upload (the tables); no device sync.  The geometry carries an ordinary
+    cnl_letterbox_frame table: unletterbox / unletterbox_ take it as they take letterbox_uint8's."""
+    return letterbox_frames(frames, height, width, fill, _frames.yuv_layout(layout), matrix, full_range)
 
 
 def unletterbox_(bboxes: torch.Tensor, geom: LetterboxGeometry, clip: bool = True) -> torch.Tensor:
     """In place: [N, k, 4] x1 y1 x2 y2 in canvas pixels -> each frame's own pixels."""
-    if not (isinstance(bboxes, torch.Tensor) and bboxes.is_cuda):
-        raise RuntimeError("unletterbox runs on HIP devices only (no CPU fallback)")
-    if bboxes.dtype != torch.float32 or bboxes.dim() != 3 or bboxes.shape[-1] != 4 or not bboxes.is_contiguous():
-        raise ValueError(f"expected contiguous float32 [N,k,4] boxes, got {bboxes.dtype} {tuple(bboxes.shape)}")
-    if bboxes.shape[0] != len(geom) or bboxes.device != geom.table.device:
-        raise ValueError(f"boxes of {bboxes.shape[0]} frames on {bboxes.device} against a geometry of {len(geom)} frames on {geom.table.device}")
+    _gather.require_hip([bboxes], "unletterbox")                  # first and whatever N: anything but a device tensor is a RuntimeError here
+    _frames.check_boxes(bboxes, len(geom), geom.table.device, "unletterbox")
     lib = _lib.load()
     with torch.cuda.device(bboxes.device):
         _lib.check(lib.cnl_unletterbox_boxes_f32(bboxes.data_ptr(), geom.table.data_ptr(), bboxes.shape[0], bboxes.shape[1], int(bool(clip)),
@@ -106,6 +99,5 @@ def unletterbox_(bboxes: torch.Tensor, geom: LetterboxGeometry, clip: bool = Tru
 def unletterbox(bboxes: torch.Tensor, geom: LetterboxGeometry, clip: bool = True) -> torch.Tensor:
     """A new tensor: the boxes gather_detection2d / gather_tracking2d return for normalize_bbox=False, in each frame's own pixel
     coordinates; clip=True clamps them to [0, w] x [0, h]."""
-    if not (isinstance(bboxes, torch.Tensor) and bboxes.is_cuda):
-        raise RuntimeError("unletterbox runs on HIP devices only (no CPU fallback)")
+    _gather.require_hip([bboxes], "unletterbox")
     return unletterbox_(bboxes.clone(memory_format=torch.contiguous_format), geom, clip)

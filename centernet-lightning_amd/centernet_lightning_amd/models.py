@@ -26,7 +26,6 @@ from . import flip as _flip
 from . import letterbox as _letterbox
 from . import overlay as _overlay
 from . import tiles as _tiles
-from . import yuv as _yuv
 from .collate import collate_detections
 from .config import model_section
 from .engine import Engine
@@ -243,8 +242,8 @@ class CenterNet(nn.Module):
     def letterbox_yuv420(self, frames, height: int, width: int, layout: str = "nv12", matrix: str = "bt601", full_range: bool = False,
                          fill=(0, 0, 0)):
         """letterbox_uint8 for YUV 4:2:0 video surfaces (NV12 / I420 planes of any pitch): the colour conversion happens inside the one
-        launch (cnl_letterbox_yuv420_u8), no RGB frame is written; see yuv.letterbox_yuv420."""
-        return _yuv.letterbox_yuv420(frames, height, width, layout, matrix, full_range, fill)
+        launch (cnl_letterbox_yuv420_u8), no RGB frame is written; see letterbox.letterbox_yuv420."""
+        return _letterbox.letterbox_yuv420(frames, height, width, layout, matrix, full_range, fill)
 
     def detect_frames(self, frames, height: int = 512, width: int = 512, fill=(0, 0, 0), mean=IMAGENET_MEAN, std=IMAGENET_STD,
                       num_detections: int = 100, nms_kernel: int = 3, pixel_format: str = "rgb", matrix: str = "bt601",
@@ -252,15 +251,10 @@ class CenterNet(nn.Module):
         """Frames of different sizes -> {"bboxes" (each frame's own pixels, clipped to it), "labels", "scores"[, "embeddings"]}:
         letterbox_uint8 -> forward_uint8 on the canvas (the stem normalises: still no fp32 image in memory) -> the decode ->
         unletterbox.  Nothing between the frames and the result touches the host except the table upload.
-        pixel_format "nv12" / "i420": the frames are YUV 4:2:0 surfaces (yuv.letterbox_yuv420 in place of letterbox_uint8; `matrix` and
+        pixel_format "nv12" / "i420": the frames are YUV 4:2:0 surfaces (letterbox_yuv420 in place of letterbox_uint8; `matrix` and
         `full_range` choose the conversion); "rgb" ignores both.
         flip_test: forward_uint8's; the CANVAS is mirrored, after the letterbox, so the geometry table and unletterbox are untouched."""
-        if pixel_format == "rgb":
-            canvas, geom = _letterbox.letterbox_uint8(frames, height, width, fill)
-        elif pixel_format in _yuv.LAYOUTS:
-            canvas, geom = _yuv.letterbox_yuv420(frames, height, width, pixel_format, matrix, full_range, fill)
-        else:
-            raise ValueError(f"pixel_format must be 'rgb' or one of {list(_yuv.LAYOUTS)}, got {pixel_format!r}")
+        canvas, geom = _letterbox.letterbox_frames(frames, height, width, fill, pixel_format, matrix, full_range)
         if canvas.shape[-1] != 3:
             raise ValueError(f"detect_frames expects 3-channel frames, got {canvas.shape[-1]} channels")
         out = self.forward_uint8(canvas, mean=mean, std=std, flip_test=flip_test)
@@ -292,8 +286,8 @@ class CenterNet(nn.Module):
 
     def tile_yuv420(self, frames, tile_h: int = 512, tile_w: int = 512, overlap: float = 0.2, full_frame: bool = True, fill=(0, 0, 0),
                     layout: str = "nv12", matrix: str = "bt601", full_range: bool = False):
-        """tile_uint8 for YUV 4:2:0 video surfaces, converted inside the one launch; see yuv.tile_yuv420."""
-        return _yuv.tile_yuv420(frames, tile_h, tile_w, overlap, full_frame, fill, layout, matrix, full_range)
+        """tile_uint8 for YUV 4:2:0 video surfaces, converted inside the one launch; see tiles.tile_yuv420."""
+        return _tiles.tile_yuv420(frames, tile_h, tile_w, overlap, full_frame, fill, layout, matrix, full_range)
 
     def merge_tiles(self, bboxes, scores, labels, geom, **kwargs):
         """The detections of all views -> per frame, in its own pixels, duplicates removed (cnl_merge_tiles_f32); see tiles.merge_tiles."""
@@ -309,17 +303,12 @@ class CenterNet(nn.Module):
         tile_uint8 (one launch) -> forward_uint8 + the decode on chunks of at most `batch` views -> one merge over all frames
         (class-aware greedy NMS, IoU or intersection-over-smaller) -> for tracking models the embeddings of the survivors.
         Nothing between the frames and the result touches the host except the table upload.
-        pixel_format "nv12" / "i420": the frames are YUV 4:2:0 surfaces (yuv.tile_yuv420 in place of tile_uint8), as in detect_frames.
+        pixel_format "nv12" / "i420": the frames are YUV 4:2:0 surfaces (tile_yuv420 in place of tile_uint8), as in detect_frames.
         flip_test: forward_uint8's, on the gathered VIEWS (the tile table and merge_tiles are untouched): a chunk is still at most
         `batch` views, and its forward sees twice that many inputs."""
         if isinstance(batch, bool) or not isinstance(batch, int) or batch < 1:
             raise ValueError(f"detect_tiled: batch must be a positive int, got {batch!r}")
-        if pixel_format == "rgb":
-            views, geom = _tiles.tile_uint8(frames, int(tile[0]), int(tile[1]), overlap, full_frame, fill)
-        elif pixel_format in _yuv.LAYOUTS:
-            views, geom = _yuv.tile_yuv420(frames, int(tile[0]), int(tile[1]), overlap, full_frame, fill, pixel_format, matrix, full_range)
-        else:
-            raise ValueError(f"pixel_format must be 'rgb' or one of {list(_yuv.LAYOUTS)}, got {pixel_format!r}")
+        views, geom = _tiles.tile_frames(frames, int(tile[0]), int(tile[1]), overlap, full_frame, fill, pixel_format, matrix, full_range)
         if views.shape[-1] != 3:
             raise ValueError(f"detect_tiled expects 3-channel frames, got {views.shape[-1]} channels")
         parts = []

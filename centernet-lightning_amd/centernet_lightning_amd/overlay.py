@@ -16,12 +16,11 @@ and black, which are the usual text colours): label l is drawn in entry l mod 20
 """
 import ctypes
 import functools
-import math
 
 import numpy as np
 import torch
 
-from . import _gather, _lib
+from . import _frames, _gather, _lib
 from . import yuv as _yuv
 
 DEFAULT_PALETTE = ((230, 25, 75), (60, 180, 75), (255, 225, 25), (0, 130, 200), (245, 130, 48), (145, 30, 180), (70, 240, 240),
@@ -60,71 +59,11 @@ def _to_yuv(rgb_bytes: bytes, matrix: str, full_range: bool) -> bytes:
     return np.array([_yuv.rgb_to_yuv(c, matrix, full_range) for c in rgb.tolist()], dtype=np.uint8).tobytes()
 
 
-def _per_slot(t, name, dtype, shape, dev):
-    if not isinstance(t, torch.Tensor):
-        raise ValueError(f"{name} must be a tensor, got {type(t).__name__}")
-    _gather.require_hip([t], _WHAT)
-    if t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous():
-        raise ValueError(f"expected contiguous {dtype} {name} of shape {list(shape)}, got {t.dtype} {tuple(t.shape)}")
-    if t.device != dev:
-        raise ValueError(f"{name} lives on {t.device}, the frames on {dev}")
-    return t
-
-
-def _dense(t):
-    return t.clone(memory_format=torch.contiguous_format)
-
-
-def _packed(frames, inplace):
-    """-> (what to return, the per-frame views to paint, their device, C); device and C are None for an empty batch."""
-    if isinstance(frames, torch.Tensor):
-        if frames.dim() != 4:
-            raise ValueError(f"expected a sequence of uint8 [h,w,C] frames or one [N,h,w,C] tensor, got {tuple(frames.shape)}")
-        _gather.require_hip([frames], _WHAT)
-        if frames.dtype != torch.uint8:
-            raise ValueError(f"expected uint8 frames, got {frames.dtype}")
-        out = frames if inplace else _dense(frames)
-        views = list(out.unbind(0))
-    else:
-        views = list(frames)
-        if views:
-            views, _, _ = _gather.uint8_frames(views, _WHAT)
-            if not inplace:
-                views = [_dense(f) for f in views]
-        out = tuple(views) if isinstance(frames, tuple) else views
-    if not views:
-        return out, views, None, None
-    views, dev, C = _gather.uint8_frames(views, _WHAT)
-    if C not in (3, 4):
-        raise ValueError(f"packed frames have 3 or 4 channels (RGB / RGBA), got C = {C}")
-    return out, views, dev, C
-
-
-def _packed_records(views, C):
-    plain = []
-    for f in views:
-        h, w = int(f.shape[0]), int(f.shape[1])
-        if not (1 <= h <= MAX_SIDE and 1 <= w <= MAX_SIDE):
-            raise ValueError(f"frame sides must be in 1..{MAX_SIDE}, got {h} x {w}")
-        pitch = int(f.stride(0)) if h > 1 else w * C
-        if f.stride(2) != 1 or (w > 1 and f.stride(1) != C) or not w * C <= pitch < 2 ** 31:
-            raise ValueError(f"a frame painted in place needs packed pixels and rows that do not overlap, got strides {f.stride()}")
-        plain.append((f.data_ptr(), pitch))
-    return plain
-
-
-def _yuv_copy(frames, layout):
-    if isinstance(frames, torch.Tensor):
-        return _dense(frames)
-    out = []
-    for f in frames:
-        if isinstance(f, torch.Tensor):
-            out.append(_dense(f))
-        elif isinstance(f, (tuple, list)) and all(isinstance(p, torch.Tensor) for p in f):
-            out.append(type(f)(_dense(p) for p in f))
-        else:
-            raise ValueError("a YUV 4:2:0 frame is one [h*3/2, w] tensor, (y, uv) or (y, u, v)")
-    return tuple(out) if isinstance(frames, tuple) else out
+def _clone(x):
+    """Dense clones of a tensor, or of the tensors in a list / tuple of frames or planes, in the form given."""
+    if isinstance(x, torch.Tensor):
+        return x.clone(memory_format=torch.contiguous_format)
+    return type(x)(_clone(p) for p in x) if isinstance(x, (tuple, list)) else x          # (not a frame: left for open_frames to refuse)
 
 
 def draw_detections(frames, bboxes, labels=None, scores=None, score_threshold=None, count=None, numbers=None, palette=DEFAULT_PALETTE,
@@ -150,77 +89,42 @@ def draw_detections(frames, bboxes, labels=None, scores=None, score_threshold=No
     fill_alpha = _int_in(fill_alpha, "fill_alpha", 0, 256)
     tag_scale = _int_in(tag_scale, "tag_scale", 0, 8)
     colours = _colours(palette, text_color)
-    if (scores is None) != (score_threshold is None):
-        raise ValueError("scores and score_threshold are given together")
-    if score_threshold is not None and (isinstance(score_threshold, bool) or not isinstance(score_threshold, (int, float))
-                                        or math.isnan(score_threshold)):
-        raise ValueError(f"score_threshold must be a number, got {score_threshold!r}")
-    inplace = bool(inplace)
-    if pixel_format == "rgb":
-        out, views, dev, C = _packed(frames, inplace)
-        planes = None
-        if views:
-            plain = _packed_records(views, C)
-            windows = [(n, 0, 0, f.shape[0], f.shape[1], 1, 1, 0, 0) for n, f in enumerate(views)]
-    elif pixel_format in _yuv.LAYOUTS:
-        colours = np.frombuffer(_to_yuv(colours.tobytes(), _check_matrix(matrix), bool(full_range)), dtype=np.uint8).reshape(-1, 3)
-        empty = frames.shape[0] == 0 if isinstance(frames, torch.Tensor) and frames.dim() == 3 else \
-            (not isinstance(frames, torch.Tensor) and len(frames) == 0)
-        if inplace:
-            out = frames
-            if pixel_format == "i420" and not empty:     # a form-(a) I420 tensor with a pitch is copied by split_planes: not paintable
-                for f in (frames.unbind(0) if isinstance(frames, torch.Tensor) else frames):
-                    if isinstance(f, torch.Tensor) and not f.is_contiguous():
-                        raise ValueError("an I420 frame given as one tensor must be contiguous to be painted in place (its chroma planes "
-                                         "are flat byte ranges); give (y, u, v) planes instead")
-        else:
-            out = _yuv_copy(frames, pixel_format)
-        views, dev, C = [], None, 3
-        if not empty:
-            views = _yuv._parse(out, pixel_format, _WHAT)
-            dev = _yuv._device(views, _WHAT)
-            for p in views:
-                if not (p[6] <= MAX_SIDE and p[7] <= MAX_SIDE):
-                    raise ValueError(f"frame sides must be in 1..{MAX_SIDE}, got {p[6]} x {p[7]}")
-            windows = [(n, 0, 0, p[6], p[7], 1, 1, 0, 0) for n, p in enumerate(views)]
-            plain, planes = _yuv._records(views, windows)
-    else:
-        raise ValueError(f"pixel_format must be 'rgb' or one of {list(_yuv.LAYOUTS)}, got {pixel_format!r}")
-    N = len(views)
-    if not isinstance(bboxes, torch.Tensor):
-        raise ValueError(f"bboxes must be a tensor, got {type(bboxes).__name__}")
-    if bboxes.dtype != torch.float32 or bboxes.dim() != 3 or bboxes.shape[-1] != 4 or not bboxes.is_contiguous():
-        raise ValueError(f"expected contiguous float32 [N,k,4] boxes, got {bboxes.dtype} {tuple(bboxes.shape)}")
-    if bboxes.shape[0] != N:
-        raise ValueError(f"boxes of {bboxes.shape[0]} frames against {N} frames")
-    k = int(bboxes.shape[1])
+    _frames.check_score_pair(scores, score_threshold)
+    if not isinstance(frames, (torch.Tensor, tuple, list)):
+        frames = list(frames)
+    out = frames if inplace else _clone(frames)
+    src = _frames.open_frames(out, pixel_format, _WHAT, matrix, full_range, copy=_frames.IN_PLACE, allow_empty=True)
+    dev, C, N = src.check_device(), src.C, len(src)
+    if N and C not in (3, 4):
+        raise ValueError(f"packed frames have 3 or 4 channels (RGB / RGBA), got C = {C}")
+    for (h, w) in src.sizes:
+        if not (1 <= h <= MAX_SIDE and 1 <= w <= MAX_SIDE):
+            raise ValueError(f"frame sides must be in 1..{MAX_SIDE}, got {h} x {w}")
+    k = _frames.check_boxes(bboxes, N, dev, _WHAT)
     if N == 0:
         return out                               # no frames: nothing to paint
-    _gather.require_hip([bboxes], _WHAT)
-    if bboxes.device != dev:
-        raise ValueError(f"boxes on {bboxes.device} against frames on {dev}")
     if labels is not None:
-        labels = _per_slot(labels, "labels", torch.int64, (N, k), dev)
+        labels = _frames.per_slot(labels, "labels", torch.int64, (N, k), dev, _WHAT)
     if numbers is not None:
-        numbers = _per_slot(numbers, "numbers", torch.int32, (N, k), dev)
+        numbers = _frames.per_slot(numbers, "numbers", torch.int32, (N, k), dev, _WHAT)
     if scores is not None:
-        scores = _per_slot(scores, "scores", torch.float32, (N, k), dev)
+        scores = _frames.per_slot(scores, "scores", torch.float32, (N, k), dev, _WHAT)
     if count is not None:
-        count = _per_slot(count, "count", torch.int32, (N,), dev)
+        count = _frames.per_slot(count, "count", torch.int32, (N,), dev, _WHAT)
     if N > 65535:
         raise ValueError(f"at most 65535 frames per call, got {N}")
     if k == 0:
         return out
 
-    words = 9 if planes is not None else 5                        # int64 words of a cnl_yuv420_frame / cnl_letterbox_frame
+    is_yuv = src.kind == _frames.YUV
+    if is_yuv:
+        colours = np.frombuffer(_to_yuv(colours.tobytes(), matrix, bool(full_range)), dtype=np.uint8).reshape(-1, 3)
     P = colours.shape[0] - 1
-    buf = np.zeros(N * words + (P + 2) // 2, dtype=np.int64)
-    if planes is not None:
-        _gather.pack_yuv(buf[:N * words].reshape(N, 9), windows, planes)
-    else:
-        _gather.pack_plain(buf[:N * words].reshape(N, 5), windows, plain)
+    windows = src.whole()
+    buf = _gather.pack_records(windows, *src.records(windows), tail_words=(P + 2) // 2)
+    words = 9 if is_yuv else 5                   # int64 words of a cnl_yuv420_frame / cnl_letterbox_frame
     buf[N * words:].view(np.uint8)[:(P + 1) * 4].reshape(P + 1, 4)[:, :3] = colours       # P four-byte entries, then the text colour
-    max_h, max_w = max(w[3] for w in windows), max(w[4] for w in windows)
+    max_h, max_w = max(h for (h, _) in src.sizes), max(w for (_, w) in src.sizes)
     lib = _lib.load()
     with torch.cuda.device(dev):
         table = _gather.upload(buf, dev)
@@ -230,13 +134,7 @@ def draw_detections(frames, bboxes, labels=None, scores=None, score_threshold=No
         def ptr(t):
             return t.data_ptr() if t is not None else None
         _lib.check(lib.cnl_draw_boxes_u8(table.data_ptr(), bboxes.data_ptr(), ptr(labels), ptr(numbers), ptr(scores),
-                                         float(score_threshold) if scores is not None else 0.0, ptr(count), N, k, C, int(planes is not None),
+                                         float(score_threshold) if scores is not None else 0.0, ptr(count), N, k, C, int(is_yuv),
                                          table[N * words:].data_ptr(), P, thickness, fill_alpha, tag_scale, int(max_h), int(max_w),
                                          records.data_ptr(), stream), "cnl_draw_boxes_u8")
     return out
-
-
-def _check_matrix(matrix):
-    if matrix not in _yuv.MATRICES:
-        raise ValueError(f"matrix must be one of {sorted(_yuv.MATRICES)}, got {matrix!r}")
-    return matrix

@@ -10,8 +10,8 @@ from typing import List, Tuple
 
 import torch
 
-from . import _gather, _lib
-from .letterbox import _fill_word, letterbox_geometry
+from . import _frames, _gather, _lib
+from .letterbox import letterbox_geometry
 
 METRICS = {"iou": 0, "ios": 1}
 
@@ -99,12 +99,6 @@ class TileGeometry:
         return cls(None, merge_table, first_view, views, ffv, [], 0, 0)
 
 
-def _row_strided(f: torch.Tensor) -> bool:
-    """Can the kernel read this [h, w, C] frame in place?  Pixels and channels packed, rows any positive stride."""
-    h, w, C = f.shape
-    return f.stride(2) == 1 and f.stride(1) == C and (h == 1 or (f.stride(0) >= w * C and f.stride(0) < 2 ** 31))
-
-
 def _view_records(sizes, tile_h: int, tile_w: int, overlap: float, full_frame: bool):
     """The views of frames of the given (h, w) sizes -> (windows [(frame, y0, x0, h, w, new_h, new_w, pad_top, pad_left)]: what the
     gather kernel needs per view, the merge records, TileGeometry.views, frame_first_view).  A tile is a 1:1 window at the canvas'
@@ -127,25 +121,36 @@ def _view_records(sizes, tile_h: int, tile_w: int, overlap: float, full_frame: b
     return windows, mg, views, ffv
 
 
+def tile_frames(frames, tile_h: int = 512, tile_w: int = 512, overlap: float = 0.2, full_frame: bool = True, fill=(0, 0, 0),
+                pixel_format: str = "rgb", matrix: str = "bt601", full_range: bool = False):
+    """The one function behind tile_uint8 (pixel_format "rgb") and tile_yuv420 ("nv12" / "i420"), which detect_tiled calls with its
+    pixel_format: frame source (rows read in place) -> views -> one gather."""
+    src = _frames.open_frames(frames, pixel_format, "tile_uint8" if pixel_format == "rgb" else "tile_yuv420", matrix, full_range,
+                              copy=_frames.ROWS)
+    word = _frames.fill_word(fill, src.C)
+    windows, mg, views, ffv = _view_records(src.sizes, tile_h, tile_w, overlap, full_frame)
+    plain, planes = src.records(windows)
+    dev = src.check_device()                     # (YUV frames: only now, after the fill and the tile grid)
+    g = _gather.gather(dev, windows, plain, tile_h, tile_w, src.C, word, planes=planes, coef=src.coef, merge_records=mg,
+                       frame_first_view=ffv)
+    return g.canvas, TileGeometry(g.table, g.merge_table, g.first_view, views, ffv, src.sizes, tile_h, tile_w, keep=src.keep,
+                                  yuv_table=g.yuv_table)
+
+
 def tile_uint8(frames, tile_h: int = 512, tile_w: int = 512, overlap: float = 0.2, full_frame: bool = True, fill=(0, 0, 0)):
     """frames: a sequence of uint8 [h_i, w_i, C] tensors on one HIP device (C in 1..4, the same for all; rows may be strided), or one
     [N, h, w, C] tensor -> (views [V, tile_h, tile_w, C] uint8, TileGeometry).  The views of a frame are its tile_grid tiles, row-major
     (a frame smaller than a tile is padded with `fill` on the right / bottom), then with full_frame=True the whole frame letterboxed to
     the tile size.  One launch for all views of all frames; one pinned-memory upload (the tables); no device sync."""
-    if isinstance(frames, torch.Tensor):
-        if frames.dim() != 4:
-            raise ValueError(f"expected a sequence of uint8 [h,w,C] frames or one [N,h,w,C] tensor, got {tuple(frames.shape)}")
-        _gather.require_hip([frames], "tile_uint8")
-        frames = frames.unbind(0)
-    frames, dev, C = _gather.uint8_frames(frames, "tile_uint8")
-    word = _fill_word(fill, C)
-    frames = [f if _row_strided(f) else f.contiguous() for f in frames]
-    sizes = [(int(f.shape[0]), int(f.shape[1])) for f in frames]
-    windows, mg, views, ffv = _view_records(sizes, tile_h, tile_w, overlap, full_frame)
-    strides = [int(f.stride(0)) if f.shape[0] > 1 else f.shape[1] * C for f in frames]
-    plain = [(frames[n].data_ptr() + y0 * strides[n] + x0 * C, strides[n]) for (n, y0, x0, *_) in windows]
-    g = _gather.gather(dev, windows, plain, tile_h, tile_w, C, word, merge_records=mg, frame_first_view=ffv)
-    return g.canvas, TileGeometry(g.table, g.merge_table, g.first_view, views, ffv, sizes, tile_h, tile_w, keep=frames)
+    return tile_frames(frames, tile_h, tile_w, overlap, full_frame, fill)
+
+
+def tile_yuv420(frames, tile_h: int = 512, tile_w: int = 512, overlap: float = 0.2, full_frame: bool = True, fill=(0, 0, 0),
+                layout: str = "nv12", matrix: str = "bt601", full_range: bool = False):
+    """tile_uint8 for YUV 4:2:0 frames -> (views [V, tile_h, tile_w, 3] uint8 RGB, TileGeometry): the tile_grid tiles of every frame
+    (windows into its planes; an odd origin takes the chroma sample of its 2 x 2 block) and, with full_frame, the whole frame
+    letterboxed, converted and gathered by one launch.  merge_tiles takes the geometry as it takes tile_uint8's."""
+    return tile_frames(frames, tile_h, tile_w, overlap, full_frame, fill, _frames.yuv_layout(layout), matrix, full_range)
 
 
 def merge_tiles(bboxes: torch.Tensor, scores: torch.Tensor, labels: torch.Tensor, geom: TileGeometry, max_detections: int = 300,

@@ -1,9 +1,10 @@
 """YUV 4:2:0 video surfaces (NV12 from hardware decoders, I420 from software decoders) straight to the network-sized RGB canvas.
 
-letterbox_yuv420 is letterbox_uint8 and tile_yuv420 is tile_uint8 for frames that are still Y / U / V planes: the colour conversion is
-fused into the resize taps of ONE launch of cnl_letterbox_yuv420_u8 (csrc/letterbox.hip), so no RGB frame is written.  The result
-is bit for bit "convert with the integer rule of include/centernet_gfx950.h, then letterbox_uint8 / tile_uint8".  The planes are read
-in place, whatever their row pitch.
+letterbox.letterbox_yuv420 is letterbox_uint8 and tiles.tile_yuv420 is tile_uint8 for frames that are still Y / U / V planes: the colour
+conversion is fused into the resize taps of ONE launch of cnl_letterbox_yuv420_u8 (csrc/letterbox.hip), so no RGB frame is written.
+The result is bit for bit "convert with the integer rule of include/centernet_gfx950.h, then letterbox_uint8 / tile_uint8".  The
+planes are read in place, whatever their row pitch.  This module holds what is YUV about that: the plane forms and the two colour
+rules; the frame source (_frames.open_frames) turns the planes into records.
 
 A frame is given as
     (a) one 2-D uint8 tensor [h * 3 / 2, w], the decoder / cv2 layout, read as NV12 or I420 according to `layout`,
@@ -15,10 +16,6 @@ from fractions import Fraction
 from typing import Tuple
 
 import torch
-
-from . import _gather
-from .letterbox import LetterboxGeometry, _fill_word, letterbox_geometry
-from .tiles import TileGeometry, _view_records
 
 LAYOUTS = ("nv12", "i420")
 # (Kr, Kb) of Y = Kr R + (1 - Kr - Kb) G + Kb B
@@ -121,83 +118,3 @@ def split_planes(frame, layout: str = "nv12"):
     if y.stride(1) != 1 or (w > 2 and (u.stride(1) != step or v.stride(1) != step)):      # (a one-column plane has no element stride)
         raise ValueError(f"the innermost stride of a plane must be 1, got strides {y.stride()}, {u.stride()}, {v.stride()}")
     return y, u, v
-
-
-def _pitch(p: torch.Tensor, step: int) -> int:
-    """Bytes between the rows of a plane whose samples are `step` bytes apart (a one-row plane has no pitch: its packed width)."""
-    return int(p.stride(0)) if p.shape[0] > 1 else int(p.shape[1]) * step
-
-
-def _parse(frames, layout: str, what: str):
-    """-> [(y, u, v, y_pitch, c_pitch, c_step, h, w)] per frame; ValueError for what split_planes refuses and for pitches the record
-    cannot express."""
-    if layout not in LAYOUTS:
-        raise ValueError(f"layout must be one of {list(LAYOUTS)}, got {layout!r}")
-    if isinstance(frames, torch.Tensor):
-        if frames.dim() != 3:
-            raise ValueError(f"expected a sequence of YUV 4:2:0 frames or one [N, h*3/2, w] tensor, got {tuple(frames.shape)}")
-        frames = list(frames.unbind(0))
-    frames = list(frames)
-    if not frames:
-        raise ValueError(f"{what}: no frames")
-    parsed = []
-    for f in frames:
-        y, u, v = split_planes(f, layout)
-        step = int(u.stride(1)) if u.shape[1] > 1 else 1
-        yp, cp = _pitch(y, 1), _pitch(u, step)
-        if _pitch(v, step) != cp:
-            raise ValueError(f"the U and V planes of a frame must share one row pitch, got {cp} and {_pitch(v, step)}")
-        if not (y.shape[1] <= yp < 2 ** 31 and u.shape[1] * step <= cp < 2 ** 31):
-            raise ValueError(f"the rows of a plane must not overlap (pitch {yp} for {y.shape[1]} bytes, {cp} for {u.shape[1] * step})")
-        parsed.append((y, u, v, yp, cp, step, int(y.shape[0]), int(y.shape[1])))
-    return parsed
-
-
-def _device(parsed, what: str):
-    """The one HIP device all frames live on."""
-    _gather.require_hip([p[0] for p in parsed], what)
-    dev = parsed[0][0].device
-    for p in parsed:
-        if p[0].device != dev:
-            raise ValueError(f"frames live on different devices ({dev}, {p[0].device})")
-    return dev
-
-
-def _records(parsed, windows):
-    """What _gather.gather needs per window besides the window: the window's Y plane as a one-channel packed frame, and the planes."""
-    plain = [(parsed[n][0].data_ptr() + y0 * parsed[n][3] + x0, parsed[n][3]) for (n, y0, x0, *_) in windows]
-    planes = [(y.data_ptr(), u.data_ptr(), v.data_ptr(), yp, cp, step) for (y, u, v, yp, cp, step, _, _) in (parsed[w[0]] for w in windows)]
-    return plain, planes
-
-
-def letterbox_yuv420(frames, height: int, width: int, layout: str = "nv12", matrix: str = "bt601", full_range: bool = False, fill=(0, 0, 0)):
-    """frames: a sequence of YUV 4:2:0 frames on one HIP device (forms (a), (b), (c) of the module docstring; sizes may differ)
-    -> (canvas [N, height, width, 3] uint8 RGB, LetterboxGeometry): letterbox_uint8 of the converted frames, bit for bit, without the
-    converted frames.  One launch; one pinned-memory upload (the tables); no device sync.  The geometry carries an ordinary
-    cnl_letterbox_frame table: unletterbox / unletterbox_ take it as they take letterbox_uint8's."""
-    coef = yuv_coefficients(matrix, full_range)
-    parsed = _parse(frames, layout, "letterbox_yuv420")
-    height, width = int(height), int(width)
-    geo = [(p[6], p[7]) + letterbox_geometry(p[6], p[7], height, width) for p in parsed]
-    word = _fill_word(fill, 3)
-    dev = _device(parsed, "letterbox_yuv420")
-    windows = [(n, 0, 0) + g for n, g in enumerate(geo)]
-    plain, planes = _records(parsed, windows)
-    g = _gather.gather(dev, windows, plain, height, width, 3, word, planes=planes, coef=coef)
-    return g.canvas, LetterboxGeometry(g.table, geo, height, width, keep=parsed, yuv_table=g.yuv_table)
-
-
-def tile_yuv420(frames, tile_h: int = 512, tile_w: int = 512, overlap: float = 0.2, full_frame: bool = True, fill=(0, 0, 0),
-                layout: str = "nv12", matrix: str = "bt601", full_range: bool = False):
-    """tile_uint8 for YUV 4:2:0 frames -> (views [V, tile_h, tile_w, 3] uint8 RGB, TileGeometry): the tile_grid tiles of every frame
-    (windows into its planes; an odd origin takes the chroma sample of its 2 x 2 block) and, with full_frame, the whole frame
-    letterboxed, converted and gathered by one launch.  merge_tiles takes the geometry as it takes tile_uint8's."""
-    coef = yuv_coefficients(matrix, full_range)
-    parsed = _parse(frames, layout, "tile_yuv420")
-    word = _fill_word(fill, 3)
-    sizes = [(p[6], p[7]) for p in parsed]
-    windows, mg, views, ffv = _view_records(sizes, tile_h, tile_w, overlap, full_frame)
-    dev = _device(parsed, "tile_yuv420")
-    plain, planes = _records(parsed, windows)
-    g = _gather.gather(dev, windows, plain, tile_h, tile_w, 3, word, planes=planes, coef=coef, merge_records=mg, frame_first_view=ffv)
-    return g.canvas, TileGeometry(g.table, g.merge_table, g.first_view, views, ffv, sizes, tile_h, tile_w, keep=parsed, yuv_table=g.yuv_table)
