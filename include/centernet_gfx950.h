@@ -58,7 +58,10 @@ enum {
  *                  transforms amplify rounding: error against float64 2.4-4.6 x the fp32 matrix core's (tests/test_gpu_conv.py pins <= 6 x), inside the
  *                  path's 1e-4 by two orders of magnitude but above AUTO's promise — hence a class of its own, never what AUTO takes.  Batch-invariant.
  *   CNL_ALGO_FORCE + v  tests / A-B measurements: pin kernel variant v (2, 5, 6, 9, 10, 11, 13; 1, 3, 4, 7 in `make experiments` builds) wherever
- *                  it can run at all.
+ *                  it can run at all.  A launch v cannot take — a shape, stride or alignment outside its eligibility rule — is NOT an error: it runs
+ *                  the nearest variant that can (9 / 10 / 11 -> 5; 13 -> 9, else 5; 6 with Cout % 128 != 0 -> 5; Cin % 16 != 0 -> 2), correctly,
+ *                  and cnl_conv3x3_winograd_variant reports which.  The one exception is a launch with fuse_w, which only variant 9 implements:
+ *                  it fails with CNL_E_UNSUPPORTED and writes nothing (tests/test_gpu_strided_io.py pins both).
  */
 enum {
     CNL_ALGO_AUTO = 0,
@@ -105,6 +108,16 @@ typedef struct cnl_conv_params {
     int32_t N, H_in, W_in, Cin, Cout;
     int32_t KH, KW, stride, pad;
     int32_t ldx, ldy, ldr;  /* pixel strides in elements                                             */
+    /* Layout rules of the conv entry points (cnl_conv2d_nhwc_f32, cnl_conv3x3_winograd_f32, cnl_conv3x3_up2_nhwc_f32, cnl_pointwise_nhwc_f32,
+     * cnl_deconv2x_nhwc_f32; pinned by tests/test_gpu_strided_io.py).  INPUT: ldx >= Cin, ldx % 4 == 0 and x 16-byte aligned (likewise ldx2 / x2),
+     * else CNL_E_BAD_ARG (cnl_conv3x3_winograd_f32: CNL_E_UNSUPPORTED for the stride) before anything is launched.  OUTPUT and RESIDUAL: any
+     * ldy >= Cout, ldr >= Cout and any 4-byte aligned y / residual are accepted, so a tensor may be a channel slice at any offset of a wider
+     * buffer.  A launch writes the Cout channels of its N * H_out * W_out pixels and NOTHING else: not the other ldy - Cout channels of a pixel,
+     * not a byte behind the last pixel.  The result does not depend on the layout as long as the same kernel runs; the kernels with 16-byte
+     * epilogues are chosen only where Cout % 4 == 0, ldy % 4 == 0, y is 16-byte aligned and, with a residual, ldr % 4 == 0 and the residual is
+     * 16-byte aligned (the row-Winograd variants 9 / 10 / 11 / 13 — another layout runs variant 2 / 5 / 6, other arithmetic of the same class
+     * promise — and the vector epilogue of CNL_UPSAMPLE_OUT_ADD, whose scalar form gives the same bits).  The elementwise entry points
+     * (cnl_upsample2x / cnl_fuse_sum / cnl_depthwise3x3) ask for every stride % 4 == 0 and every pointer 16-byte aligned and refuse anything else. */
     uint32_t flags;         /* CNL_RELU | CNL_SIGMOID | CNL_UPSAMPLE_IN | CNL_UPSAMPLE_OUT_ADD        */
     /* Optional hand-over of the per-image maximum magnitude of a tensor between launches (cnl_conv3x3_winograd_f32 only; NULL =
      * unused).  Both point to N * cnl_absmax_stride() floats: image n's value sits at element n * cnl_absmax_stride() (32 floats = one 128-byte line

@@ -336,6 +336,17 @@ def test_resnet50_plan_replays_launch_by_launch_against_float64(capsys):
         assert torch.equal(outs[k].permute(0, 3, 1, 2), want[k]), k
 
 
+def test_resnet50_launches_write_only_their_declared_outputs_and_arena_reuse_changes_no_byte(capsys):
+    """The footprint and lock-step replays of tests/test_gpu_plan_replay.py on the bottleneck plan (the pointwise launches through _pw_io): every launch
+    changes only its declared outputs, and the plan that reuses its arena gives the bits of the one that does not at every launch."""
+    x = rp.structured_images(2, 128, 160, 50).cuda()
+    pw = _lib.load().cnl_pointwise_nhwc_f32
+
+    model, _ = _model("resnet50_fpn.yaml")
+    rec = rp.footprint_and_lockstep(lambda reuse: (rp.plan_with(model, x, reuse_buffers=reuse), x, None), capsys, io=lambda plan, L, x_, at: _pw_io(plan, L, x_, at) if L.fn is pw else rp.launch_io(plan, L, x_, at))
+    assert sum("conv3+downsample" in what for what, _, _ in rec) == 4
+
+
 # ------------------------------------------------------------------------------------------------------------------- end to end
 def _features(model, plan):
     nb, nh, nw, nc, nup = plan.neck_out

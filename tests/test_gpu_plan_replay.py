@@ -21,6 +21,7 @@ Bit-exact launches (max-pool, nearest upsample, cnl_absmax_per_image_f32, unweig
 held to their own R_CLASS.  The per-image max |x| hand-over is checked exactly: a slot a launch reads equals max |x| of each image of ITS input (or of
 the documented superset it belongs to), a slot a launch fills equals max |y| of what it wrote."""
 import ctypes
+import hashlib
 import os
 from collections import OrderedDict
 
@@ -157,7 +158,12 @@ PLANS = OrderedDict([
 ])
 
 
-SMALL_PLANS = {"C1_256": ("resnet34_simple.yaml", 2, 256, 256, {}, None, False)}        # the sensitivity tests' plan
+SMALL_PLANS = {"C1_256": ("resnet34_simple.yaml", 2, 256, 256, {}, None, False),        # the sensitivity tests' plan
+               "C2_256": ("resnet34_fpn.yaml", 2, 256, 256, {}, None, False),           # (with the two below: the footprint / lock-step replays)
+               "C4_96x160": ("tracking_resnet34_fpn.yaml", 2, 96, 160, {}, None, True)}
+# the plans small enough for a device-side clone-and-compare around every launch (not the 512 x 512 or 608 x 1088 ones)
+FOOTPRINT_PLANS = list(SMALL_PLANS) + ["neck_simple_deconv4_separable", "neck_fpn_deconv2_separable", "neck_fpn_deformable", "neck_simple_deformable_v1_bilinear",
+                                       "neck_fpn_deconv_weighted", "neck_ida_bilinear_weighted", "neck_bifpn_nearest"]
 
 
 def build_plan(name):
@@ -249,6 +255,8 @@ def launch_io(plan, L, x, at):
         outs["y"] = at.nhwc(p.y, N, ho, wo, p.Cout, p.ldy)
         if p.y_absmax:
             outs["yslot"] = at.slots(p.y_absmax, N)
+        if p.splitk > 1 and p.splitk_scratch:                    # the partial sums of a split reduction: scratch this launch owns
+            outs["scratch"] = at(p.splitk_scratch, (lib.cnl_conv2d_splitk_scratch_bytes(ctypes.byref(p)) // (4 * p.Cout), p.Cout), (p.Cout, 1))
         if p.fuse_w:
             outs["part"] = at(p.fuse_part, ((p.Cout + 63) // 64 * 2, N * ho * wo, 4), (N * ho * wo * 4, 4, 1))
     elif isinstance(L.args, DeconvParams):
@@ -291,11 +299,59 @@ def launch_io(plan, L, x, at):
     return ins, outs
 
 
-def replay(plan, x, norm=None, check=None, before=None, after=None, stop=None):
+class Footprint:
+    """"Declared outputs only": device clones of everything a plan's launches may write (its arena, its absmax array, the output tensors of this call)
+    taken before a launch; after it, every int32 word that changed must lie inside the views launch_io declares as the launch's outputs — y, the
+    absmax slots it fills, splitk_scratch, fuse_part.  A store past a ragged edge, into a padding channel or into a neighbour's buffer shows up at the
+    launch that made it, although no later launch of the replay would ever notice (each is recomputed from its own input bytes)."""
+
+    def __init__(self, plan, tensors):
+        self.plan = plan
+        self.tensors = OrderedDict((k, t) for k, t in tensors.items() if t is not None)
+        self.saved = None
+
+    def arm(self):
+        self.saved = {k: t.detach().clone() for k, t in self.tensors.items()}
+
+    def _where(self, name, word):
+        if name == "arena":
+            for k, b in enumerate(self.plan.buffers):
+                if b.offset is not None and b.offset // 4 <= word < (b.offset + b.nbytes) // 4:
+                    e, idx = word - b.offset // 4, []
+                    for d in reversed(b.shape):
+                        e, r = divmod(e, d)
+                        idx.append(r)
+                    return f"arena word {word}: buffer #{k} {tuple(b.shape)} at {tuple(reversed(idx))}" + (" (+ wrapped: in the buffer's 256-byte padding)" if e else "")
+            return f"arena word {word}: in no buffer of the plan"
+        t = self.tensors[name]
+        return f"{name} at {tuple(int(v) for v in torch.unravel_index(torch.tensor(word), t.shape))}"
+
+    def verify(self, outs):
+        """-> None, or a description of the first word that changed outside the declared outputs `outs` (device views)."""
+        for name, t in self.tensors.items():
+            changed = t.reshape(-1).view(torch.int32) != self.saved[name].reshape(-1).view(torch.int32)
+            if not bool(changed.any()):
+                continue
+            lo, hi = t.data_ptr(), t.data_ptr() + t.numel() * 4
+            for v in outs.values():
+                if lo <= v.data_ptr() < hi:
+                    assert v.dtype == torch.float32 and (v.data_ptr() - lo) % 4 == 0
+                    changed.as_strided(v.shape, v.stride(), (v.data_ptr() - lo) // 4).fill_(False)
+            n = int(changed.sum())
+            if n:
+                first = int(torch.nonzero(changed)[0])
+                return f"{n} word(s) changed outside the declared outputs {sorted(outs)}; first: {self._where(name, first)}"
+        return None
+
+
+def replay(plan, x, norm=None, check=None, before=None, after=None, stop=None, footprint=False, violations=None, io=None):
     """Plan.run one launch at a time (engine.py Plan.run: fresh output tensors patched into out_params, absmax slots zeroed, plan.launch per launch).
     Before a launch its inputs are copied to the CPU, after it (and a synchronisation) its outputs; check(i, L, pre, post) sees both — so arena reuse
     and in-place writes of the default plans need no special handling.  before / after(i, L, ins, outs) may edit the device views (sensitivity
-    tests).  Returns the outputs as Plan.run does."""
+    tests).  footprint=True: the words a launch (and its `after` hook) changes must lie inside its declared outputs (class Footprint); an offender
+    is appended to `violations` as (launch index, what, description), or raised when no list is given.  io: launch_io, or a function with its
+    signature that also knows launch kinds launch_io does not.  Returns the outputs as Plan.run does."""
+    io = io or launch_io
     outs = OrderedDict()
     oh, ow = plan.out_hw
     for name, (p, c) in plan.out_params.items():
@@ -307,17 +363,26 @@ def replay(plan, x, norm=None, check=None, before=None, after=None, stop=None):
         plan.absmax.zero_()
     at = _At([plan.arena, plan.absmax, x] + list(outs.values()))
     stream = _stream()
+    fp = Footprint(plan, OrderedDict([("arena", plan.arena), ("absmax", plan.absmax)] + [(f"output {k}", v) for k, v in outs.items()])) if footprint else None
     for i, L in enumerate(plan.launches):
-        ins, res = launch_io(plan, L, x, at)
+        ins, res = io(plan, L, x, at)
         if before is not None:
             before(i, L, ins, res)
         torch.cuda.synchronize()
         pre = {k: v.cpu().clone() for k, v in ins.items()} if check is not None else None
+        if fp is not None:
+            fp.arm()
         _lib.check(plan.launch(L, x, stream), L.what)
         torch.cuda.synchronize()
         if after is not None:
             after(i, L, ins, res)
             torch.cuda.synchronize()
+        if fp is not None:
+            why = fp.verify(res)
+            if why is not None:
+                if violations is None:
+                    raise AssertionError(f"launch {i} {L.what}: {why}")
+                violations.append((i, L.what, why))
         if check is not None:
             check(i, L, pre, {k: v.cpu().clone() for k, v in res.items()})
         if stop is not None and i == stop:
@@ -843,3 +908,88 @@ def test_one_bad_element_flags_that_launch_only(capsys):
         print(f"\n[one bad element] launch {target} ({plan.launches[target].what}): +{hit['delta']:.3g} at (0, {hit['y']}, {hit['x']}, {hit['c']}) "
               f"(median u s + floor of the launch {hit['median']:.3g}); flagged launches {flagged}, ratio {chk.launch_ratio.get(target, 0):.3g}")
     assert flagged == [target], chk.report()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------- where a launch writes
+def _digest(t):
+    return hashlib.blake2b(t.contiguous().numpy().tobytes(), digest_size=16).digest()
+
+
+def footprint_and_lockstep(build, capsys=None, io=None):
+    """build(reuse_buffers) -> (plan, x, norm), the same model and input twice.  Both plans are replayed with footprint=True (every launch changes
+    only its declared outputs), and in lock step: the same launch list, and at every launch index the same input and output BITS — the plan without
+    reuse is alias-free by construction, so a liveness mistake of Plan._bind (a pointer field it does not enumerate, two live buffers on one range)
+    shows at the launch where it bites, not only — or not at all — in the final outputs.  splitk_scratch is zeroed before its launch in both replays
+    (slices the launcher drops as empty are never written), so the partial sums are part of the comparison too.  -> the per-launch digests."""
+    seen = []
+    for reuse in (True, False):
+        plan, x, norm = build(reuse)
+        rec, bad = [], []
+
+        def check(i, L, pre, post, rec=rec):
+            rec.append((L.what, {("pre", k): _digest(v) for k, v in pre.items()}, {("post", k): _digest(v) for k, v in post.items()}))
+
+        def before(i, L, ins, outs_):
+            if "scratch" in outs_:
+                outs_["scratch"].zero_()
+
+        outs = replay(plan, x, norm, check=check, before=before, footprint=True, violations=bad, io=io)
+        assert not bad, "\n".join(f"launch {i} {what}: {why}" for i, what, why in bad)
+        seen.append((plan, rec, OrderedDict((k, v.clone()) for k, v in outs.items())))
+        del plan
+    (pa, a, oa), (pb, b, ob) = seen
+    assert pa.options.reuse_buffers and not pb.options.reuse_buffers and pa.arena_bytes < pb.arena_bytes
+    assert [w for w, _, _ in a] == [w for w, _, _ in b], "the launch lists differ"
+    for i, ((what, pre_a, post_a), (_, pre_b, post_b)) in enumerate(zip(a, b)):
+        diff = sorted(k for k in set(pre_a) | set(pre_b) | set(post_a) | set(post_b) if {**pre_a, **post_a}.get(k) != {**pre_b, **post_b}.get(k))
+        assert not diff, f"launch {i} {what}: {diff} differ between the plan that reuses its arena and the one that does not"
+    for k in oa:
+        assert torch.equal(oa[k], ob[k]), k
+    if capsys is not None:
+        with capsys.disabled():
+            print(f"\n[footprint + lock step] {len(a)} launches, arena {pa.arena_bytes} bytes with reuse / {pb.arena_bytes} without")
+    return a
+
+
+def plan_with(model, x, norm=None, **options):
+    """The plan the same model (same packed weights) uses for the same input under other kernel options: the engine keys its plans by them."""
+    opts = model.set_kernel_options(**options)
+    if norm is not None:
+        model._engine.forward_u8(x, norm[0], norm[1], sigmoid=True)
+    else:
+        model._engine.forward(x, sigmoid=True)
+    torch.cuda.synchronize()
+    (plan,) = [p for p in model._engine.plans.values() if p.options == opts]
+    return plan
+
+
+@pytest.mark.parametrize("name", FOOTPRINT_PLANS)
+def test_launches_write_only_their_declared_outputs_and_arena_reuse_changes_no_byte(name, capsys):
+    model, _, plan, x, norm = build_plan(name)
+    footprint_and_lockstep(lambda reuse: (plan if reuse else plan_with(model, x, norm, reuse_buffers=False), x, norm), capsys)
+
+
+def test_one_float_past_an_output_view_flags_that_launch_only(capsys):
+    """With footprint=True, an `after` hook changes ONE word of the arena just behind a launch's output view: the replay flags that launch and no
+    other — every other launch is compared against the bytes as they were just before it ran, the planted word included."""
+    model, sd, plan, x, norm = build_plan(SENS_PLAN)
+    target = _split_reader(plan)
+    hit = {}
+
+    def after(i, L, ins, outs):
+        if i != target:
+            return
+        v = outs["y"]
+        word = (v.data_ptr() - plan.arena.data_ptr()) // 4 + sum((d - 1) * s for d, s in zip(v.shape, v.stride())) + 1
+        assert 0 < word < plan.arena.numel()
+        plan.arena.view(torch.int32)[word] += 1                 # (an integer add: the old bytes may be a NaN, which a float add would keep)
+        hit["word"] = word
+
+    bad = []
+    replay(plan, x, norm, after=after, footprint=True, violations=bad)
+    with capsys.disabled():
+        print(f"\n[one float past the view] launch {target} ({plan.launches[target].what}): arena word {hit['word']}; flagged: {bad}")
+    assert [b[0] for b in bad] == [target] and f"arena word {hit['word']}" in bad[0][2], bad
+    clean = []
+    replay(plan, x, norm, footprint=True, violations=clean)
+    assert not clean, clean
