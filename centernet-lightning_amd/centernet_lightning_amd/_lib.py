@@ -144,6 +144,7 @@ _SIGNATURES = {
     "cnl_maxpool3x3s2_nhwc_f32": (ctypes.c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "cnl_decode_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32]),
     "cnl_decode_f32": (ctypes.c_int, [POINTER(DecodeParams), c_void_p]),
+    "cnl_decode_forms": (ctypes.c_int, [POINTER(DecodeParams), POINTER(c_int32), POINTER(c_int32), POINTER(c_int32), POINTER(c_int32)]),
     "cnl_gather_boxes_f32": (ctypes.c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p,
                                             c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_float, c_float, c_void_p]),
     "cnl_gather_embeddings_f32": (ctypes.c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p,

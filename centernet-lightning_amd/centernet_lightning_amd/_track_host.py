@@ -424,7 +424,9 @@ class TrackerSettings:
 
 def _to_dev(a, dev):
     if isinstance(a, torch.Tensor) and a.device == dev and a.dtype == torch.float32 and a.is_contiguous():
-        return a                                   # already where the kernels read it (each .to() costs ~7 us of host time)
+        # already where the kernels read it (each .to() costs ~7 us of host time) — unless it is a view that starts off a 16-byte boundary: the cost
+        # kernels read boxes and embedding rows 16 bytes at a time and their launchers refuse such a pointer, so it is copied to an allocation of its own
+        return a if a.data_ptr() % 16 == 0 else a.clone()
     return torch.as_tensor(a).to(device=dev, dtype=torch.float32).contiguous()
 
 

@@ -630,6 +630,19 @@ struct TopkArgs {
     float* scores; long long* indices; long long* labels; float* boxes; float* emb;
 };
 
+// Where topk_kernel keeps an image's score keys (cnl_decode_forms' *topk): the kernel's flags in_regs / klds / reg48 / k16 (phase A, below) as one rule, for
+// the launcher's report.  r48 is the kernel's instantiation, kch the keys per thread, hw4 whether H * W % 4 == 0, the last two the launcher's LDS budget
+// decisions (TopkArgs).  The kernel keeps its own four expressions (rewriting them through this function changes its register allocation): a change of
+// either goes with the other.
+enum { TK_REGS16 = 0, TK_LDS32 = 1, TK_REGS48 = 2, TK_LDS16 = 3, TK_MEMORY = 4 };
+constexpr int topk_key_storage(bool r48, int kch, bool hw4, bool keys_in_lds, bool keys16_in_lds) {
+    return !r48 && kch <= 16 ? TK_REGS16                      // sixteen registers per thread
+         : keys_in_lds ? TK_LDS32
+         : r48 ? (hw4 && kch <= 48 ? TK_REGS48 : TK_MEMORY)   // twelve quads per thread
+         : keys16_in_lds ? TK_LDS16                           // the keys' upper halves: a prefilter
+         : TK_MEMORY;
+}
+
 // order-preserving float -> uint key (larger float => larger key); -0.0 is folded onto +0.0 so the
 // ordering matches float comparison semantics (torch treats them as equal)
 __device__ __forceinline__ unsigned score_key(float f) {
@@ -721,6 +734,7 @@ __global__ __launch_bounds__(TK_THREADS) void topk_kernel(const TopkArgs a) {
     unsigned tmax = 0u;
     // Maps of at most 16 x 1024 pixels (128 x 128): the thread's 16 keys (indices tid + 1024 j) simply stay in registers — no LDS copy, no
     // index arithmetic; the fallback re-reads the scores from memory.  Larger maps: keys in LDS ([owner thread][odd pitch]) when they fit.
+    // (in_regs / klds / k16 / reg48 below are restated as ONE rule in topk_key_storage, above, for cnl_decode_forms: change both together)
     const bool in_regs = !R48 && KCH <= 16;                 // (the launcher picks the R48 instantiation for 16 < KCH <= 48 only: it carries no kreg)
     const bool klds = a.keys_in_lds && !in_regs;
     // Maps whose 32-bit keys do not fit the LDS budget (the 152 x 272 maps of 608 x 1088 frames: 165 KB) keep the UPPER HALVES of the keys there (round 6):
@@ -1285,7 +1299,21 @@ extern "C" size_t cnl_decode_workspace_bytes(int32_t N, int32_t H, int32_t W) {
     return (size_t)N * H * W * 8 + 256;
 }
 
-extern "C" int cnl_decode_f32(const cnl_decode_params* p, void* stream) {
+// The launch cnl_decode_f32 makes for a parameter block: its argument checks, the stage-1 kernel with its vector width and block geometry, and the top-k's key
+// storage.  cnl_decode_f32 launches what this returns and cnl_decode_forms reports it: one decision, no restatement.
+enum { S1_CMINOR = 1, S1_C8 = 2, S1_PLANES = 3, S1_GENERIC = 4 };                          // cnl_decode_forms' *stage1
+struct DecodePlan {
+    int HW, P;
+    int stage1, vec;
+    int CG, PXB, R, tiles_x, strips;      // PeakArgs' geometry (R: the strip height)
+    int CG8, RUNS, TW, rp;                // S1_C8 only
+    long long blocks;
+    size_t lds;                           // stage 1's dynamic LDS
+    int topk, keys_in_lds, keys16_in_lds, r48;
+    size_t key_bytes;                     // the top-k's dynamic LDS
+};
+
+static int decode_plan(const cnl_decode_params* p, DecodePlan* d) {
     CNL_REQUIRE(p, CNL_E_BAD_ARG, "cnl_decode_f32: null params");
     CNL_REQUIRE(p->heat && p->box && p->scores && p->indices && p->labels && p->boxes, CNL_E_BAD_ARG,
                 "cnl_decode_f32: null tensor pointer");
@@ -1303,15 +1331,10 @@ extern "C" int cnl_decode_f32(const cnl_decode_params* p, void* stream) {
                 "cnl_decode_f32: workspace %zu bytes < required %zu", p->workspace_bytes, need_ws);
     CNL_REQUIRE(((uintptr_t)p->workspace & 15) == 0, CNL_E_BAD_ARG, "cnl_decode_f32: workspace must be 16-byte aligned");
 
-    hipStream_t s = (hipStream_t)stream;
     const int P = (p->nms_kernel - 1) / 2;
-    PeakArgs a;
-    a.heat = p->heat; a.sn = p->heat_sn; a.sc = p->heat_sc; a.sh = p->heat_sh; a.sw = p->heat_sw;
-    a.N = p->N; a.C = p->C; a.H = p->H; a.W = p->W;
-    a.ws_score = (float*)p->workspace;
-    a.ws_label = (int*)((char*)p->workspace + (size_t)p->N * HW * 4);
-
-    int rc;
+    d->HW = HW; d->P = P;
+    d->CG8 = d->RUNS = d->TW = d->rp = 0;
+    d->lds = 0;
     const bool cminor = p->heat_sc == 1;
     int vec = 1;
     if (cminor) {
@@ -1322,25 +1345,91 @@ extern "C" int cnl_decode_f32(const cnl_decode_params* p, void* stream) {
         vec = ok(4) ? 4 : (ok(2) ? 2 : 1);
     }
     if (cminor && vec == 4 && p->C % 8 == 0 && p->C / 8 <= PK8_THREADS && P <= 3 && p->W >= 8) {
-        Peak8Args q;
-        q.CG8 = p->C / 8;
-        q.RUNS = PK8_THREADS / q.CG8;
-        if (q.RUNS > 32) q.RUNS = 32;                      // blocks at most 128 pixels wide: R x TW x 8 bytes of LDS stays small for any C
+        d->stage1 = S1_C8; d->vec = 4;
+        d->CG8 = p->C / 8;
+        d->RUNS = PK8_THREADS / d->CG8;
+        if (d->RUNS > 32) d->RUNS = 32;                    // blocks at most 128 pixels wide: R x TW x 8 bytes of LDS stays small for any C
         int R8 = 16;
         // pixels per run: 2 for the 3 x 3 pool (P = 1; r6q: 111 registers, four 160-thread workgroups per CU instead of two at 195, 32-pixel blocks: 30.4 -> 28.5 us at C1 =
         // 5.9 TB/s, what a plain read-once stream of the same bytes gets), 4 otherwise
-        const int rp = P >= 1 ? 2 : 4;      // (5 x 5: 176 registers at two-pixel runs; four-pixel runs spilled 424)
-        const int runs_w = (p->W + rp - 1) / rp;
-        if (q.RUNS > runs_w) q.RUNS = runs_w;
-        q.TW = q.RUNS * rp;
-        a.tiles_x = (p->W + q.TW - 1) / q.TW;
-        if ((long long)p->N * a.tiles_x * ((p->H + 15) / 16) < 256) R8 = 4;      // few images: more, shorter strips (results are identical)
-        a.strips = (p->H + R8 - 1) / R8;
-        a.CG = q.CG8; a.PXB = q.TW; a.R = R8;
+        d->rp = P >= 1 ? 2 : 4;             // (5 x 5: 176 registers at two-pixel runs; four-pixel runs spilled 424)
+        const int runs_w = (p->W + d->rp - 1) / d->rp;
+        if (d->RUNS > runs_w) d->RUNS = runs_w;
+        d->TW = d->RUNS * d->rp;
+        d->tiles_x = (p->W + d->TW - 1) / d->TW;
+        if ((long long)p->N * d->tiles_x * ((p->H + 15) / 16) < 256) R8 = 4;      // few images: more, shorter strips (results are identical)
+        d->strips = (p->H + R8 - 1) / R8;
+        d->CG = d->CG8; d->PXB = d->TW; d->R = R8;
+        d->lds = (size_t)R8 * d->TW * 8;
+    } else if (cminor && p->C / vec <= 256) {
+        d->stage1 = S1_CMINOR; d->vec = vec;
+        d->CG = p->C / vec;
+        d->PXB = 256 / d->CG;
+        if (d->PXB > p->W) d->PXB = p->W;
+        d->R = 8;                                         // measured best of {4, 8, 16, 32} rows per strip at C1; = CM_R in peaks_cminor_kernel (its batched-load form unrolls over it)
+        d->tiles_x = (p->W + d->PXB - 1) / d->PXB;
+        d->strips = (p->H + d->R - 1) / d->R;
+        d->lds = (size_t)d->R * d->PXB * d->CG * 8;
+    } else if (P <= 3 && p->C >= PLANES_MIN_C && p->heat_sw == 1 && (p->W & 3) == 0 && ((p->heat_sn | p->heat_sc | p->heat_sh) & 3) == 0 && ((uintptr_t)p->heat & 15) == 0) {
+        d->stage1 = S1_PLANES; d->vec = 4;
+        d->CG = p->C >= 16 ? 16 : (p->C >= 8 ? 8 : 4);     // contiguous rows (NCHW): class planes; class groups x runs = 256 threads
+        d->PXB = 256 / d->CG * 4;
+        d->R = P <= 1 ? 8 : 4;
+        d->tiles_x = (p->W + d->PXB - 1) / d->PXB;
+        d->strips = (p->H + d->R - 1) / d->R;
+        d->lds = (size_t)d->R * d->PXB * 8;
+    } else {
+        d->stage1 = S1_GENERIC; d->vec = 1;
+        d->CG = 1; d->PXB = 64; d->R = 8;
+        d->tiles_x = (p->W + 63) / 64;
+        d->strips = (p->H + 4 * d->R - 1) / (4 * d->R);
+    }
+    d->blocks = (long long)p->N * d->tiles_x * d->strips;
+    CNL_REQUIRE(d->blocks < (1ll << 31), CNL_E_UNSUPPORTED, "cnl_decode_f32: grid too large");
+
+    // 40 KB of static LDS + the keys: one workgroup per CU either way (1024 threads)
+    const size_t key_words = (size_t)((HW + TK_THREADS - 1) / TK_THREADS) * TK_THREADS;
+    d->keys_in_lds = key_words * 4 <= 96 * 1024;
+    d->keys16_in_lds = !d->keys_in_lds && key_words * 2 <= 96 * 1024;
+    d->key_bytes = d->keys_in_lds ? key_words * 4 : (d->keys16_in_lds ? key_words * 2 : 0);
+    const int kch = (HW + TK_THREADS - 1) / TK_THREADS;
+    d->r48 = (HW & 3) == 0 && !d->keys_in_lds && kch > 16 && kch <= 48;
+    d->topk = topk_key_storage(d->r48, kch, (HW & 3) == 0, d->keys_in_lds, d->keys16_in_lds);
+    return CNL_OK;
+}
+
+extern "C" int cnl_decode_forms(const cnl_decode_params* p, int32_t* stage1, int32_t* vec, int32_t* strip, int32_t* topk) {
+    DecodePlan d;
+    const int rc = decode_plan(p, &d);
+    if (rc != CNL_OK) return rc;
+    if (stage1) *stage1 = d.stage1;
+    if (vec) *vec = d.vec;
+    if (strip) *strip = d.R;
+    if (topk) *topk = d.topk;
+    return CNL_OK;
+}
+
+extern "C" int cnl_decode_f32(const cnl_decode_params* p, void* stream) {
+    DecodePlan d;
+    int rc = decode_plan(p, &d);
+    if (rc != CNL_OK) return rc;
+    const int HW = d.HW, P = d.P;
+
+    hipStream_t s = (hipStream_t)stream;
+    PeakArgs a;
+    a.heat = p->heat; a.sn = p->heat_sn; a.sc = p->heat_sc; a.sh = p->heat_sh; a.sw = p->heat_sw;
+    a.N = p->N; a.C = p->C; a.H = p->H; a.W = p->W;
+    a.ws_score = (float*)p->workspace;
+    a.ws_label = (int*)((char*)p->workspace + (size_t)p->N * HW * 4);
+    a.CG = d.CG; a.PXB = d.PXB; a.R = d.R; a.tiles_x = d.tiles_x; a.strips = d.strips;
+    const long long blocks = d.blocks;
+    const size_t lds = d.lds;
+
+    if (d.stage1 == S1_C8) {
+        Peak8Args q;
+        q.CG8 = d.CG8; q.RUNS = d.RUNS; q.TW = d.TW;
         q.p = a;
-        const long long blocks = (long long)p->N * a.tiles_x * a.strips;
-        CNL_REQUIRE(blocks < (1ll << 31), CNL_E_UNSUPPORTED, "cnl_decode_f32: grid too large");
-        const size_t lds = (size_t)R8 * q.TW * 8;
+        const int R8 = d.R, rp = d.rp;
 #define PK8_LAUNCH(P_, R_) hipLaunchKernelGGL((peaks_c8_kernel<P_, R_>), dim3((unsigned)blocks), dim3(PK8_THREADS), lds, s, q)
         if (R8 == 16) {
             if (P == 0) PK8_LAUNCH(0, 16); else if (P == 1 && rp == 2) hipLaunchKernelGGL((peaks_c8_kernel<1, 16, 2>), dim3((unsigned)blocks), dim3(PK8_THREADS), lds, s, q); else if (P == 1) PK8_LAUNCH(1, 16); else if (P == 2) hipLaunchKernelGGL((peaks_c8_kernel<2, 16, 2>), dim3((unsigned)blocks), dim3(PK8_THREADS), lds, s, q); else hipLaunchKernelGGL((peaks_c8_kernel<3, 16, 2>), dim3((unsigned)blocks), dim3(PK8_THREADS), lds, s, q);
@@ -1349,29 +1438,11 @@ extern "C" int cnl_decode_f32(const cnl_decode_params* p, void* stream) {
         }
 #undef PK8_LAUNCH
         rc = cnl::check_launch("peaks_c8_kernel");
-    } else if (cminor && p->C / vec <= 256) {
-        a.CG = p->C / vec;
-        a.PXB = 256 / a.CG;
-        if (a.PXB > p->W) a.PXB = p->W;
-        a.R = 8;                                          // measured best of {4, 8, 16, 32} rows per strip at C1; = CM_R in peaks_cminor_kernel (its batched-load form unrolls over it)
-        a.tiles_x = (p->W + a.PXB - 1) / a.PXB;
-        a.strips = (p->H + a.R - 1) / a.R;
-        const long long blocks = (long long)p->N * a.tiles_x * a.strips;
-        CNL_REQUIRE(blocks < (1ll << 31), CNL_E_UNSUPPORTED, "cnl_decode_f32: grid too large");
-        const size_t lds = (size_t)a.R * a.PXB * a.CG * 8;
-        if (vec == 4) rc = launch_cminor<4>(a, P, lds, (unsigned)blocks, s);
-        else if (vec == 2) rc = launch_cminor<2>(a, P, lds, (unsigned)blocks, s);
+    } else if (d.stage1 == S1_CMINOR) {
+        if (d.vec == 4) rc = launch_cminor<4>(a, P, lds, (unsigned)blocks, s);
+        else if (d.vec == 2) rc = launch_cminor<2>(a, P, lds, (unsigned)blocks, s);
         else rc = launch_cminor<1>(a, P, lds, (unsigned)blocks, s);
-    } else if (P <= 3 && p->C >= PLANES_MIN_C && p->heat_sw == 1 && (p->W & 3) == 0 && ((p->heat_sn | p->heat_sc | p->heat_sh) & 3) == 0 && ((uintptr_t)p->heat & 15) == 0) {
-        a.CG = p->C >= 16 ? 16 : (p->C >= 8 ? 8 : 4);      // contiguous rows (NCHW): class planes; class groups x runs = 256 threads
-        a.PXB = 256 / a.CG * 4;
-        const int R = P <= 1 ? 8 : 4;
-        a.R = R;
-        a.tiles_x = (p->W + a.PXB - 1) / a.PXB;
-        a.strips = (p->H + R - 1) / R;
-        const long long blocks = (long long)p->N * a.tiles_x * a.strips;
-        CNL_REQUIRE(blocks < (1ll << 31), CNL_E_UNSUPPORTED, "cnl_decode_f32: grid too large");
-        const size_t lds = (size_t)R * a.PXB * 8;
+    } else if (d.stage1 == S1_PLANES) {
         switch (P) {
             case 0: hipLaunchKernelGGL((peaks_planes_kernel<0, 8>), dim3((unsigned)blocks), dim3(256), lds, s, a); break;
             case 1: hipLaunchKernelGGL((peaks_planes_kernel<1, 8>), dim3((unsigned)blocks), dim3(256), lds, s, a); break;
@@ -1380,12 +1451,7 @@ extern "C" int cnl_decode_f32(const cnl_decode_params* p, void* stream) {
         }
         rc = cnl::check_launch("peaks_planes_kernel");
     } else {
-        constexpr int R = 8;
-        a.CG = 1; a.PXB = 64; a.R = R;
-        a.tiles_x = (p->W + 63) / 64;
-        a.strips = (p->H + 4 * R - 1) / (4 * R);
-        const long long blocks = (long long)p->N * a.tiles_x * a.strips;
-        CNL_REQUIRE(blocks < (1ll << 31), CNL_E_UNSUPPORTED, "cnl_decode_f32: grid too large");
+        constexpr int R = 8;                               // = d.R
         switch (P) {
             case 0: hipLaunchKernelGGL((peaks_generic_kernel<0, R>), dim3((unsigned)blocks), dim3(256), 0, s, a); break;
             case 1: hipLaunchKernelGGL((peaks_generic_kernel<1, R>), dim3((unsigned)blocks), dim3(256), 0, s, a); break;
@@ -1407,13 +1473,10 @@ extern "C" int cnl_decode_f32(const cnl_decode_params* p, void* stream) {
     t.normalize = p->normalize_boxes; t.box_log = p->box_log; t.mult = p->box_multiplier; t.stride = p->stride;
     t.scores = p->scores; t.indices = (long long*)p->indices; t.labels = (long long*)p->labels; t.boxes = p->boxes;
     t.emb = p->emb;
-    // 40 KB of static LDS + the keys: one workgroup per CU either way (1024 threads)
-    const size_t key_words = (size_t)((HW + TK_THREADS - 1) / TK_THREADS) * TK_THREADS;
-    t.keys_in_lds = key_words * 4 <= 96 * 1024;
-    t.keys16_in_lds = !t.keys_in_lds && key_words * 2 <= 96 * 1024;
-    const size_t key_bytes = t.keys_in_lds ? key_words * 4 : (t.keys16_in_lds ? key_words * 2 : 0);
-    const int kch = (HW + TK_THREADS - 1) / TK_THREADS;
-    const bool r48 = (HW & 3) == 0 && !t.keys_in_lds && kch > 16 && kch <= 48;
+    t.keys_in_lds = d.keys_in_lds;
+    t.keys16_in_lds = d.keys16_in_lds;
+    const size_t key_bytes = d.key_bytes;
+    const bool r48 = d.r48;
     static cnl::DeviceOnce once, once48;
     rc = r48 ? cnl::kernel_setup(once48, reinterpret_cast<const void*>(&topk_kernel<true>), 96 * 1024) : cnl::kernel_setup(once, reinterpret_cast<const void*>(&topk_kernel<false>), 96 * 1024);
     if (rc != CNL_OK) return rc;

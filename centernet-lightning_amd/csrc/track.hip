@@ -113,6 +113,7 @@ extern "C" int cnl_track_costs_metric_f32(const float* det_emb, const float* det
     CNL_REQUIRE(T == 0 || (trk_emb && reid_cost), CNL_E_BAD_ARG, "cnl_track_costs_f32: T > 0 without track table / reid_cost");
     CNL_REQUIRE(T == 0 || box_cost == 0 || (trk_box && box_cost_out), CNL_E_BAD_ARG,
                 "cnl_track_costs_f32: box cost requested without track boxes / output");
+    CNL_REQUIRE(inputs_aligned(det_emb, det_box, trk_emb, trk_box, E, T, box_cost), CNL_E_BAD_ARG, "cnl_track_costs_metric_f32: %s", INPUTS_ALIGNED);
     const long pairs = (long)k * T;
     const unsigned grid = (unsigned)(pairs > 0 ? (pairs + 255) / 256 : 1);
     hipLaunchKernelGGL(costs_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, det_emb, det_box, det_score, k, E,
@@ -140,6 +141,7 @@ extern "C" int cnl_track_frame_f32(const float* det_emb, const float* det_box, c
     CNL_REQUIRE(T == 0 || trk_emb, CNL_E_BAD_ARG, "cnl_track_frame_f32: T > 0 without track table");
     CNL_REQUIRE(T == 0 || box_cost == 0 || trk_box, CNL_E_BAD_ARG, "cnl_track_frame_f32: box cost requested without track boxes");
     CNL_REQUIRE(((uintptr_t)record & 7) == 0, CNL_E_BAD_ARG, "cnl_track_frame_f32: record must be 8-byte aligned");
+    CNL_REQUIRE(inputs_aligned(det_emb, det_box, trk_emb, trk_box, E, T, box_cost), CNL_E_BAD_ARG, "cnl_track_frame_f32: %s", INPUTS_ALIGNED);
     const int64_t need = cnl_track_frame_bytes(k, T, with_detections);
     CNL_REQUIRE(record_bytes >= need && need < (1l << 31), record_bytes < need ? CNL_E_BAD_ARG : CNL_E_UNSUPPORTED,
                 "cnl_track_frame_f32: record holds %ld bytes, k = %d, T = %d needs %ld (cnl_track_frame_bytes; below 2 GiB)", (long)record_bytes, k, T, (long)need);

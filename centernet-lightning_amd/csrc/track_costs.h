@@ -11,6 +11,15 @@ namespace cnl_track {
 
 constexpr int MAXK = 1024;     // detections per frame (decode's k limit)
 
+// What pair_costs reads 16 bytes at a time: a box of either side (box_cost != 0) and, when E % 4 == 0, four embedding elements (seq_dots).  The
+// launchers refuse anything less aligned — but only what a launch reads: without tracks (T == 0) there are no pairs and nothing is required.
+constexpr const char* INPUTS_ALIGNED = "with tracks, det_box / trk_box (box_cost != 0) and, when E % 4 == 0, det_emb / trk_emb must be 16-byte aligned";
+inline bool inputs_aligned(const float* det_emb, const float* det_box, const float* trk_emb, const float* trk_box, int E, int T, int box_cost) {
+    if (T == 0) return true;
+    const uintptr_t boxes = box_cost ? (uintptr_t)det_box | (uintptr_t)trk_box : 0, embs = (E & 3) == 0 ? (uintptr_t)det_emb | (uintptr_t)trk_emb : 0;
+    return ((boxes | embs) & 15) == 0;
+}
+
 // numpy maximum/minimum propagate NaN (fmaxf/fminf do not)
 __device__ __forceinline__ float np_max(float a, float b) { return (a != a) ? a : (b != b) ? b : (a > b ? a : b); }
 __device__ __forceinline__ float np_min(float a, float b) { return (a != a) ? a : (b != b) ? b : (a < b ? a : b); }

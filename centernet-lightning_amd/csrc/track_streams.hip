@@ -399,6 +399,7 @@ extern "C" int cnl_track_streams_f32(const float* det_emb, const float* det_box,
     CNL_REQUIRE(R == 0 || box_cost == 0 || trk_box, CNL_E_BAD_ARG, "cnl_track_streams_f32: box cost requested without track boxes");
     CNL_REQUIRE(((uintptr_t)record & 7) == 0 && ((uintptr_t)workspace & 7) == 0 && (record_stride & 7) == 0, CNL_E_BAD_ARG,
                 "cnl_track_streams_f32: record, record_stride and workspace must be 8-byte aligned");
+    CNL_REQUIRE(inputs_aligned(det_emb, det_box, trk_emb, trk_box, E, R, box_cost), CNL_E_BAD_ARG, "cnl_track_streams_f32: %s", INPUTS_ALIGNED);
     const int wd = with_detections ? 1 : 0;
     const int64_t rec_need = stream_rec(k, T_max, wd).bytes, ws_need = (int64_t)streams_ws_bytes(S, k, R);
     CNL_REQUIRE(record_stride >= rec_need, CNL_E_BAD_ARG, "cnl_track_streams_f32: record_stride %ld, k = %d, T_max = %d needs %ld (cnl_track_streams_record_bytes)",

@@ -277,7 +277,8 @@ int cnl_winograd_transform_weights_f32(const float* w_ohwi, float* u, int32_t Ci
  * Step before the path: uint8 HWC frames -> normalised fp32 NHWC, replacing albumentations
  * A.Normalize + ToTensorV2 of the reference's inference pre-processing (README.md:79-87, datasets/utils.py:9-21):
  * y = (float(x) - mean255[c]) * inv_std255[c], with HOST arrays mean255 = mean*255, inv_std255 = 1/(std*255) (3 floats each).
- * x: [N,H,W,3] u8, y: [N,H,W,3] f32 (feed cnl_stem_conv7x7_f32 with strides sn=H*W*3, sc=1, sh=W*3, sw=3).
+ * x: [N,H,W,3] u8, 4-byte aligned; y: [N,H,W,3] f32, 16-byte aligned (CNL_E_BAD_ARG otherwise; feed cnl_stem_conv7x7_f32 with strides
+ * sn=H*W*3, sc=1, sh=W*3, sw=3).
  */
 int cnl_normalize_u8_nhwc_f32(const uint8_t* x, float* y, int32_t N, int32_t H, int32_t W, const float* mean255,
                               const float* inv_std255, void* stream);
@@ -286,7 +287,7 @@ int cnl_normalize_u8_nhwc_f32(const uint8_t* x, float* y, int32_t N, int32_t H, 
  * albumentations A.Resize(height, width) = cv2.resize(img, (W_out, H_out), interpolation=cv2.INTER_LINEAR) on uint8 HWC frames
  * (README.md:84; datasets/utils.py:24-33 build the same pipeline for training): OpenCV's 8-bit fixed-point bilinear rule (half-pixel
  * centres, 11-bit coefficients, the two-stage rounding of VResizeLinear<uchar>), restated in csrc/preprocess.hip.
- * x: [N, H_in, W_in, C] u8 -> y: [N, H_out, W_out, C] u8, C <= 4.
+ * x: [N, H_in, W_in, C] u8 -> y: [N, H_out, W_out, C] u8, C <= 4.  Any byte alignment.
  */
 int cnl_resize_bilinear_u8(const uint8_t* x, uint8_t* y, int32_t N, int32_t H_in, int32_t W_in, int32_t H_out, int32_t W_out,
                            int32_t C, void* stream);
@@ -475,7 +476,8 @@ int cnl_draw_boxes_u8(const void* frames, const float* boxes, const int64_t* lab
  *
  * cnl_mirror_append_u8 builds the doubled uint8 input in one launch: src [N,H,W,C] and dst [2N,H,W,C] dense, C in 1..4,
  *     dst[n] = src[n],   dst[N + n, y, x] = src[n, y, W - 1 - x].
- * dst must not overlap src; 2 * N * H * W * C < 2^31; an empty batch is a no-op.
+ * dst must not overlap src; 2 * N * H * W * C < 2^31; an empty batch is a no-op.  Any byte alignment (4-byte aligned pointers with
+ * W * C % 4 == 0 move whole words).
  *
  * cnl_flip_merge_f32 merges up to three head maps of the 2N forward (logical shape [2N, C, H, W] each) in one launch.  The rule:
  *     merged[n, c, y, x] = 0.5f * ( a[n, c, y, x] + b[n, p(c), y, W - 1 - x] )
@@ -655,7 +657,11 @@ int cnl_maxpool3x3s2_nhwc_f32(const float* x, float* y, int32_t N, int32_t H, in
  *   box decode to x1y1x2y2.
  * heat/box/reid element (n,c,y,x) at n*s_n + c*s_c + y*s_h + x*s_w (elements): any NCHW or NHWC view.
  * Outputs: scores [N,k] f32, indices [N,k] i64 (flat y*W+x), labels [N,k] i64, boxes [N,k,4] f32,
- * emb [N,k,E] f32 (may be null when reid is null).
+ * emb [N,k,E] f32 (may be null when reid is null).  Exactly those N*k (x 4, x E) elements are written, each once.
+ * Alignment: heat / box / reid and every output need the alignment of their element only (4 bytes; 8 for indices /
+ * labels) — wider loads and stores are chosen per launch where the pointer, the strides and C / E allow them and never
+ * change a result.  workspace: cnl_decode_workspace_bytes(N, H, W) bytes, 16-byte aligned (else CNL_E_BAD_ARG), no byte
+ * beyond that size is touched.  The standalone gathers below: element alignment throughout.
  */
 typedef struct cnl_decode_params {
     const float* heat; int64_t heat_sn, heat_sc, heat_sh, heat_sw;
@@ -674,6 +680,18 @@ typedef struct cnl_decode_params {
 
 size_t cnl_decode_workspace_bytes(int32_t N, int32_t H, int32_t W);
 int cnl_decode_f32(const cnl_decode_params* p, void* stream);
+/* Which kernels cnl_decode_f32 runs for p (a pure host function, reporting only: the launcher itself calls the same decision; nothing is
+ * launched and no pointer is dereferenced).  Returns what cnl_decode_f32 returns for the same arguments short of a HIP error; on CNL_OK
+ * (each output may be null):
+ *   *stage1  1 channel-minor (heat_sc == 1)   2 channel-minor with C % 8 == 0 (16-byte loads, strips of 16 or 4 rows)
+ *            3 class planes (heat_sw == 1, W % 4 == 0, the other strides % 4 == 0, 16-byte aligned, C >= 4)   4 generic (any strides)
+ *   *vec     floats per load of stage 1: 4 / 2 / 1 for the channel-minor kernel — the widest that divides C and the n / y / x strides
+ *            at a base pointer aligned to it; 4 for kernels 2 and 3, 1 for the generic one
+ *   *strip   rows of the map per workgroup
+ *   *topk    where the top-k keeps an image's score keys: 0 sixteen registers per thread (H*W <= 16384), 1 LDS (<= 24576),
+ *            2 forty-eight registers (<= 49152 and H*W % 4 == 0), 3 their upper halves in LDS (<= 49152), 4 memory only.
+ * Every combination computes the same bytes.                                                                                            */
+int cnl_decode_forms(const cnl_decode_params* p, int32_t* stage1, int32_t* vec, int32_t* strip, int32_t* topk);
 
 /*
  * Standalone gathers at caller-supplied flat indices [N,k] (i64), for the Gen-A per-head calls
@@ -689,7 +707,8 @@ int cnl_gather_embeddings_f32(const float* reid, int64_t sn, int64_t sc, int64_t
 
 /*
  * All-gather record (replaces the pickled all_gather_object of eval/coco.py:10-18):
- * rec[n][j][0:4] = box, [4] = score, [5] = bit pattern of (int32)label, [6:6+E] = embedding.
+ * rec[n][j][0:4] = box, [4] = score, [5] = bit pattern of (int32)label, [6:6+E] = embedding.  E may be 0 (emb null).  Every pointer
+ * needs its element's alignment only (4 bytes; 8 for labels).
  */
 int cnl_pack_detections_f32(const float* boxes, const float* scores, const int64_t* labels, const float* emb,
                             float* rec, int32_t N, int32_t k, int32_t E, void* stream);
@@ -781,6 +800,11 @@ int cnl_deform_sample_nhwc_f32(const float* x, const float* om, float* col, int3
  *   src_trk[r] >= 0, src_det[r] >= 0 : emb = (1-s)*old + s*e/|e|, box = det_box[src_det[r]]   (e = det_emb[src_det[r]])
  *   src_trk[r] <  0, src_det[r] >= 0 : emb = e/|e|,               box = det_box[src_det[r]]   (new track)
  * src_trk / src_det are device int32 arrays of T_new entries; new_emb/new_box must not alias the old table.
+ * Alignment (the cost entries, cnl_track_frame_f32 and cnl_track_streams_f32), for a launch with tracks (T > 0; R > 0): det_box and trk_box
+ * 16-byte aligned when box_cost != 0, det_emb and trk_emb 16-byte aligned when E % 4 == 0 (boxes and embedding rows are then read 16 bytes
+ * at a time), else CNL_E_BAD_ARG; every other pointer, the outputs
+ * n_det / det_index / reid_cost / box_cost_out and all of cnl_track_apply_f32's included, needs its element's alignment only.  Of
+ * det_index only the first n_det entries and of the cost matrices only the n_det x T part are written.
  */
 int cnl_track_costs_f32(const float* det_emb, const float* det_box, const float* det_score, int32_t k, int32_t E,
                         float detection_threshold, const float* trk_emb, const float* trk_box, int32_t T, int32_t box_cost,
@@ -854,6 +878,8 @@ int cnl_lsap_batch_f64(const double* cost, const int64_t* cost_offset, const int
  *      status: 0 ok; 1 / 2 / 3 as cnl_lsap_batch_f64 for stage 1, 17 / 18 / 19 for stage 2; 4 trk_off inconsistent with R.  With a status
  *      set the lists are not valid (a non-finite cost, e.g. a zero embedding under "cosine": scipy raises there — the caller redoes that
  *      stream through the single-stream path).
+ * workspace, record and record_stride are 8-byte aligned (CNL_E_BAD_ARG otherwise); between the records of a larger record_stride, in the
+ * records of streams that are not in `live`, and past workspace_bytes nothing is written.
  * cnl_track_streams_record_bytes(k, T_max, with_detections) is the smallest record_stride; cnl_track_streams_workspace_bytes(S, k, T_max)
  * bounds the device workspace (20 bytes per pair of the pooled table, k * R pairs, R <= S * T_max, plus the index lists); the sections of
  * stream s start at k * trk_off[s] pairs.
@@ -872,6 +898,7 @@ int cnl_track_streams_f32(const float* det_emb, const float* det_box, const floa
 /*
  * Wire formats: COCO boxes are xywh — torchvision box_convert(boxes, "xyxy", "xywh") of
  * CenterNet.validation_step (models/centernet.py:207): out[i] = (x1, y1, x2 - x1, y2 - y1); n boxes of 4 floats, may be in place.
+ * boxes and out are 16-byte aligned (a box is moved as one 16-byte word; CNL_E_BAD_ARG otherwise).
  */
 int cnl_boxes_xyxy_to_xywh_f32(const float* boxes, float* out, int64_t n, void* stream);
 

@@ -87,6 +87,46 @@ def test_winograd_dispatcher_is_host_code_and_keeps_the_arithmetic_class_whateve
     assert ask(lib.cnl_conv3x3_winograd_variant, 1, 64, 128, 128, 64, algo=_lib.CNL_ALGO_F32) == 2
 
 
+def test_decode_forms_is_host_code_and_answers_as_the_launcher_would():
+    """cnl_decode_forms is a pure host function of the parameter block (no GPU needed): the launcher's own decision — stage-1 kernel, floats per
+    load, strip height, the top-k's key storage — and the launcher's error codes for the same arguments."""
+    lib = _lib.load()
+
+    def ask(N, C, H, W, strides, k=10, nms=3, heat=1 << 20, ws=1 << 24):
+        p = _lib.DecodeParams()
+        p.heat = heat
+        p.box = p.scores = p.indices = p.labels = p.boxes = 1 << 22
+        p.heat_sn, p.heat_sc, p.heat_sh, p.heat_sw = strides
+        p.N, p.C, p.H, p.W, p.k, p.nms_kernel = N, C, H, W, k, nms
+        p.workspace, p.workspace_bytes = ws, lib.cnl_decode_workspace_bytes(N, H, W)
+        out = [ctypes.c_int32(-1) for _ in range(4)]
+        rc = lib.cnl_decode_forms(ctypes.byref(p), *(ctypes.byref(o) for o in out))
+        return rc if rc else tuple(o.value for o in out)
+
+    nhwc = lambda C, H, W, ld=None: (H * W * (ld or C), 1, W * (ld or C), ld or C)
+    nchw = lambda C, H, W, pitch=None: (C * H * (pitch or W), H * (pitch or W), pitch or W, 1)
+    assert ask(2, 80, 128, 128, nhwc(80, 128, 128)) == (2, 4, 4, 0)                    # C % 8 == 0, few workgroups: strips of 4 rows, keys in registers
+    assert ask(32, 80, 128, 128, nhwc(80, 128, 128)) == (2, 4, 16, 0)
+    assert ask(2, 12, 20, 20, nhwc(12, 20, 20)) == (1, 4, 8, 0)                        # channel-minor at 4 / 2 / 1 floats: C ...
+    assert ask(2, 6, 20, 20, nhwc(6, 20, 20)) == (1, 2, 8, 0)
+    assert ask(2, 5, 20, 20, nhwc(5, 20, 20)) == (1, 1, 8, 0)
+    assert ask(2, 12, 20, 20, nhwc(12, 20, 20, 18)) == (1, 2, 8, 0)                    # ... a pixel stride ...
+    assert ask(2, 12, 20, 20, nhwc(12, 20, 20, 15)) == (1, 1, 8, 0)
+    assert ask(2, 12, 20, 20, nhwc(12, 20, 20), heat=(1 << 20) + 8) == (1, 2, 8, 0)    # ... or the base pointer decides
+    assert ask(2, 80, 20, 20, nhwc(80, 20, 20), heat=(1 << 20) + 4) == (1, 1, 8, 0)
+    assert ask(1, 80, 128, 128, nchw(80, 128, 128)) == (3, 4, 8, 0)                    # class planes: contiguous rows, W % 4 == 0
+    assert ask(1, 80, 128, 128, nchw(80, 128, 128), nms=5) == (3, 4, 4, 0)
+    assert ask(1, 80, 128, 128, nchw(80, 128, 128, 136)) == (3, 4, 8, 0)               # a window of a wider buffer, pitch % 4 == 0
+    assert ask(1, 80, 128, 128, nchw(80, 128, 128, 133)) == (4, 1, 8, 0)               # an odd pitch: generic
+    assert ask(1, 2, 128, 128, nchw(2, 128, 128)) == (4, 1, 8, 0)                      # fewer than 4 classes
+    assert [ask(1, 2, H, W, nhwc(2, H, W), k=5)[3] for H, W in ((128, 128), (150, 150), (152, 272), (199, 201), (224, 224))] == [0, 1, 2, 3, 4]
+    assert ask(1, 2, 8, 8, nhwc(2, 8, 8), k=65) == _lib.CNL_E_UNSUPPORTED and "num_detections" in _lib.last_error()
+    assert ask(1, 2, 8, 8, nhwc(2, 8, 8), nms=4) == _lib.CNL_E_UNSUPPORTED
+    assert ask(1, 2, 8, 8, nhwc(2, 8, 8), ws=(1 << 24) + 8) == _lib.CNL_E_BAD_ARG and "16-byte" in _lib.last_error()
+    assert ask(1, 2, 8, 8, nhwc(2, 8, 8), ws=0) == _lib.CNL_E_WORKSPACE
+    assert lib.cnl_decode_forms(None, None, None, None, None) == _lib.CNL_E_BAD_ARG
+
+
 def test_missing_library_fails_loudly(monkeypatch, tmp_path):
     monkeypatch.setattr(_lib, "_lib", None)
     monkeypatch.setenv("CENTERNET_GFX950_LIB", str(tmp_path / "nope.so"))
