@@ -16,6 +16,7 @@ from .crops import crop_detections
 from .overlay import DEFAULT_PALETTE, draw_detections
 from .flip import flip_merge, mirror_append_uint8
 from .coco_eval import CocoEvaluator
+from .mot_eval import MotEvaluator, evaluate_mot_tracking_sequence
 from .export import TraceableCenterNet, export_onnx, export_torchscript
 
 __all__ = ["CenterNet", "build_centernet", "load_config", "DetectionOutput", "TrackingOutput", "decode",
@@ -23,4 +24,5 @@ __all__ = ["CenterNet", "build_centernet", "load_config", "DetectionOutput", "Tr
            "Tracker", "TrackerBank", "Track", "TrackState", "build_tracker", "match_with_threshold", "formats", "TraceableCenterNet", "export_torchscript", "export_onnx",
            "letterbox_geometry", "LetterboxGeometry", "TileGeometry", "tile_grid", "tile_uint8", "merge_tiles",
            "letterbox_yuv420", "tile_yuv420", "yuv_coefficients", "split_planes", "crop_detections",
-           "draw_detections", "DEFAULT_PALETTE", "rgb_to_yuv", "flip_merge", "mirror_append_uint8", "CocoEvaluator"]
+           "draw_detections", "DEFAULT_PALETTE", "rgb_to_yuv", "flip_merge", "mirror_append_uint8", "CocoEvaluator",
+           "MotEvaluator", "evaluate_mot_tracking_sequence"]

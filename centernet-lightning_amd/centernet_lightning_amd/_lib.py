@@ -80,6 +80,15 @@ class FlipMap(Structure):
                 ("C", c_int32), ("swap_lr", c_int32)]
 
 
+class MotTables(Structure):
+    """cnl_mot_tables: the pooled input of one tracking evaluation — device pointers, then sizes; every member is 8 bytes."""
+    POINTERS = ("gt_boxes", "pr_boxes", "gt_ids", "pr_ids", "gt_off", "pr_off", "sim_off", "frm_seq", "seq_frm", "seq_gid", "seq_tid", "seq_pair",
+                "seq_idm", "gt_count", "pr_count")
+    SCALARS = ("F", "S", "n_gt", "n_pr", "sim_total", "pair_total", "sum_g", "sum_t", "id_total", "max_gids", "max_gt_frame", "max_pr_frame",
+               "max_frame_pairs")
+    _fields_ = [(n, c_void_p) for n in POINTERS] + [(n, c_int64) for n in SCALARS]
+
+
 _SIGNATURES = {
     "cnl_version": (ctypes.c_int, []),
     "cnl_sizeof_params": (c_size_t, [ctypes.c_int32]),
@@ -133,6 +142,13 @@ _SIGNATURES = {
     "cnl_coco_match_f64": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32,
                                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "cnl_coco_accumulate_f64": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p]),
+    "cnl_mot_similarity_f64": (ctypes.c_int, [POINTER(MotTables), c_void_p, c_void_p]),
+    "cnl_mot_hota_workspace_bytes": (c_int64, [POINTER(MotTables)]),
+    "cnl_mot_hota_f64": (ctypes.c_int, [POINTER(MotTables), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "cnl_mot_clear_workspace_bytes": (c_int64, [POINTER(MotTables)]),
+    "cnl_mot_clear_f64": (ctypes.c_int, [POINTER(MotTables), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "cnl_mot_identity_workspace_bytes": (c_int64, [POINTER(MotTables)]),
+    "cnl_mot_identity_f64": (ctypes.c_int, [POINTER(MotTables), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "cnl_stem_conv7x7_u8": (ctypes.c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, POINTER(c_float), POINTER(c_float), c_void_p, c_void_p,
                                            c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "cnl_stem_packed_weight_floats": (c_size_t, []),

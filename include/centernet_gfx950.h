@@ -610,6 +610,112 @@ int cnl_coco_accumulate_f64(const int32_t* rank, const int64_t* matched, const i
                             const int64_t* npig, int64_t total, int32_t num_classes, double* precision, double* recall, void* stream);
 
 /*
+ * Multi-object-tracking evaluation (eval/mot_challenge.py: evaluate_mot_tracking_sequence -> TrackEval) without TrackEval: HOTA, CLEAR
+ * and Identity for MotChallenge2DBox.  Entry points only (the ABI number stays); all are asynchronous on `stream`, allocate nothing and
+ * do no device synchronisation; the workspace queries are pure host functions.
+ *
+ * The rule — TrackEval's HOTA, CLEAR and Identity on the data the reference's writer produces: every ground truth of class 1 with
+ * confidence 1, every prediction with confidence 1, one class, so TrackEval's preprocessing removes nothing and only relabels the ids of
+ * each side to 0..n-1 in ascending order of the original id (the caller does that).  The boxes are evaluated as given: no text round
+ * trip, no +1.  TrackEval is not at hand to compare against: this text is the authority, tests/mot_eval_ref.py restates it in numpy +
+ * scipy, and every comparison with it is an equality (integers, float64 bits).
+ *   Numbers.  All arithmetic is float64, every operation rounded on its own (no fused multiply-add; the division is the IEEE one).
+ *     eps = 2^-52.  Coordinates must be finite.  An id repeated inside one frame is an error (refused by the caller).
+ *   Assignment.  scipy.optimize.linear_sum_assignment's, ties included (csrc/lsap_device.h).
+ *   Similarity s of ground truth g and prediction d, both x y w h: x0 = x, y0 = y, x1 = x + w, y1 = y + h;
+ *     iw = max(min(x1g, x1d) - max(x0g, x0d), 0), ih alike; I = iw * ih; area = (x1 - x0) * (y1 - y0) per box; U = (areag + aread) - I;
+ *     s = 0 when either area <= eps or U <= eps, otherwise I / U.  A frame's matrix is [ground truths, predictions] in slot order.
+ *   Counts.  gt_count[gid] / trk_count[tid]: the frames that hold the id.
+ *   HOTA, alpha = np.arange(0.05, 0.99, 0.05) (19 float64 values, passed in).
+ *     Pass 1, per frame in frame order: r_i = the sum of row i in ascending prediction slot, sequentially (from 0.0); c_j = the sum of
+ *       column j in ascending ground-truth slot, sequentially; den = (c_j + r_i) - s; sim_iou = s / den where den > eps, else 0;
+ *       potential[gid, tid] += sim_iou, a pair's contributions arriving in FRAME ORDER (a zero adds +0.0 and may be skipped).
+ *     gas = potential / ((gt_count + trk_count) - potential).
+ *     Pass 2, per frame: no ground truth: FP[a] += n_pred; no prediction: FN[a] += n_gt; otherwise the assignment on
+ *       -(gas[gid, tid] * s); per alpha the matched pairs with s >= alpha - eps count: TP[a] += n, FN[a] += n_gt - n, FP[a] += n_pred - n,
+ *       the frame's sum of their s (ascending ground-truth slot, sequentially, from 0.0) is added to LocA_sum[a] in frame order, and
+ *       matches[a][gid, tid] += 1.
+ *     Per alpha: AssA = sum(m * (m / max(1, (gt_count + trk_count) - m))) / max(1, TP), each row (ground-truth id) summed in ascending
+ *       tracker id from 0.0, the rows then added in ascending ground-truth id from 0.0 (a zero adds +0.0 and may be skipped); AssRe with
+ *       max(1, gt_count) and AssPr with max(1, trk_count) in place of the inner denominator, in the same order.
+ *     Host: LocA = max(1e-10, LocA_sum) / max(1e-10, TP); DetRe = TP / max(1, TP + FN); DetPr = TP / max(1, TP + FP);
+ *       DetA = TP / max(1, TP + FN + FP); HOTA = sqrt(DetA * AssA); OWTA = sqrt(DetRe * AssA).  A sequence without predictions:
+ *       FN = n_gt_dets, LocA = 1, every other field 0; without ground truth: FP = n_pred_dets, LocA = 1 (the general rule gives the same).
+ *   CLEAR, threshold 0.5, per sequence, frames strictly in order; state prev[gid] and prev_step[gid], both "none" at first.
+ *     No ground truth in the frame: FP += n_pred, the state is NOT touched.  No prediction: FN += n_gt, the state is not touched.
+ *     Otherwise score = 1000 * (tid == prev_step[gid]) + s, set to 0 where s < 0.5 - eps; the assignment on -score; the pairs with
+ *     score > eps are KEPT.  IDSW += the kept pairs whose prev[gid] is set and differs from tid; matched_count[gid] += 1 for the kept;
+ *     prev[gid] = tid for the kept; prev_step is cleared, then set for the kept; frag_count[gid] += 1 where prev_step was "none" before
+ *     the frame and is set after it; TP += kept, FN += n_gt - kept, FP += n_pred - kept; MOTP_sum += the frame's sum of s over the kept
+ *     pairs (ascending ground-truth slot, sequentially, from 0.0), in frame order.  At the end ratio = matched_count / gt_count over the
+ *     ids (gt_count > 0); MT = #(ratio > 0.8); PT = #(ratio >= 0.2) - MT; ML = n_gt_ids - MT - PT; Frag = sum(frag_count - 1 over
+ *     frag_count > 0); CLR_Frames = the number of frames.
+ *     Host: MOTA = (TP - FP - IDSW) / max(1, TP + FN); MOTP = MOTP_sum / max(1, TP); MODA = (TP - FP) / max(1, TP + FN);
+ *       CLR_Re = TP / max(1, TP + FN); CLR_Pr = TP / max(1, TP + FP); CLR_F1 = TP / max(1, TP + 0.5 * FN + 0.5 * FP);
+ *       MTR, PTR, MLR = MT, PT, ML / max(1, MT + ML + PT); sMOTA = (MOTP_sum - FP - IDSW) / max(1, TP + FN);
+ *       FP_per_frame = FP / max(1, CLR_Frames); MOTAL = (TP - FP - (log10(IDSW) if IDSW > 0 else IDSW)) / max(1, TP + FN).
+ *       A sequence without predictions: CLR_FN = n_gt_dets, ML = n_gt_ids, MLR = 1, everything else 0 (CLR_Frames too) and no final
+ *       fields; without ground truth: CLR_FP = n_pred_dets, MLR = 1, everything else 0.
+ *   Identity, threshold 0.5: pm[gid, tid] = the frames with s >= 0.5.  With G ground-truth and T tracker ids, (G + T)^2 matrices:
+ *     fn[i, :T] = gt_count[i] - pm[i, :], fn[i, T + i] = gt_count[i], fn[:G, T:] otherwise 1e10; fp[:G, j] = trk_count[j] - pm[:, j],
+ *     fp[G + j, j] = trk_count[j], fp[G:, :T] otherwise 1e10; the rest 0.  One assignment on fn + fp; IDFN / IDFP = the sums of fn / fp
+ *     over it (integers); IDTP = sum(gt_count) - IDFN; IDR = IDTP / max(1, IDTP + IDFN); IDP = IDTP / max(1, IDTP + IDFP);
+ *     IDF1 = IDTP / max(1, IDTP + 0.5 * IDFP + 0.5 * IDFN).  Without predictions: IDFN = n_gt_dets and no final fields; without ground
+ *     truth: IDFP = n_pred_dets.
+ *   COMBINED_SEQ (host), TrackEval's rule: integer fields and the *_sum fields are summed over the sequences; AssA, AssRe, AssPr are
+ *     averaged weighted by each sequence's HOTA_TP, per alpha: sum(x * TP) / max(1, sum(TP)), sequences in order of arrival;
+ *     LocA = max(1e-10, sum(LocA * TP)) / max(1e-10, sum(TP)); then the final fields are recomputed.
+ *
+ * cnl_mot_tables: the pooled input of one evaluation (host struct of device pointers; every member is 8 bytes).  Frame f of F owns ground
+ * truths gt_off[f] .. gt_off[f + 1], predictions pr_off[f] .. pr_off[f + 1] and the row-major [ng, np] matrix at sim_off[f]; frm_seq[f] is
+ * its sequence.  Sequence s of S owns frames seq_frm[s] .. seq_frm[s + 1], ground-truth ids seq_gid[s] .. (G of them: gt_ids of its frames
+ * are 0..G-1), tracker ids seq_tid[s] .. (T), the [G, T] pair block at seq_pair[s] and, for Identity, (G + T)^2 workspace entries at
+ * seq_idm[s] (none where G + T > 1024).  gt_count [sum_g] / pr_count [sum_t]: the frames that hold each id.  The scalars repeat what
+ * the tables say (pool sizes, the largest G, the largest frame sides and the largest ng * np); the device checks every offset it reads
+ * against them and reports a contradiction as status 5 instead of indexing with it.
+ * Limits: a frame holds at most 1024 objects on its smaller side and 4096 on its larger (CNL_E_UNSUPPORTED); S in 1..65535,
+ * F < 2^26, n_gt, n_pr, sum_g, sum_t < 2^31, null or misaligned pointers, negative or contradictory sizes, a workspace smaller than
+ * the query's answer: CNL_E_BAD_ARG, before anything touches the device.
+ *
+ * cnl_mot_similarity_f64: one launch writes every frame's matrix into sim [sim_total].
+ * cnl_mot_hota_f64: sim as written above; alpha [19] f64 on the device.  Written: out_f64 [S, 4, 19] (LocA_sum, AssA, AssRe, AssPr),
+ *   out_i64 [S, 3, 19] (TP, FN, FP), status [S] i32 (0, or the worst frame's: 1 a non-finite score, 2 infeasible, 3 too large, 5 tables).
+ * cnl_mot_clear_f64: out_f64 [S] (MOTP_sum), out_i64 [S, 8] (TP, FN, FP, IDSW, MT, PT, ML, Frag), status [S]; one single-wave workgroup
+ *   per sequence.
+ * cnl_mot_identity_f64: pm [pair_total] i32 is written (zeroed, then counted with integer atomics); out_i64 [S, 2] (IDFN, IDFP);
+ *   status [S]: 3 for a sequence with G + T > 1024, whose pm block is the input for solving that one assignment elsewhere.
+ */
+typedef struct cnl_mot_tables {
+    const double* gt_boxes;      /* [n_gt, 4] x y w h */
+    const double* pr_boxes;      /* [n_pr, 4] */
+    const int32_t* gt_ids;       /* [n_gt] relabelled, per sequence */
+    const int32_t* pr_ids;       /* [n_pr] */
+    const int64_t* gt_off;       /* [F + 1] */
+    const int64_t* pr_off;       /* [F + 1] */
+    const int64_t* sim_off;      /* [F + 1] */
+    const int32_t* frm_seq;      /* [F] */
+    const int64_t* seq_frm;      /* [S + 1] */
+    const int64_t* seq_gid;      /* [S + 1] */
+    const int64_t* seq_tid;      /* [S + 1] */
+    const int64_t* seq_pair;     /* [S + 1] */
+    const int64_t* seq_idm;      /* [S + 1] */
+    const int32_t* gt_count;     /* [sum_g] */
+    const int32_t* pr_count;     /* [sum_t] */
+    int64_t F, S, n_gt, n_pr, sim_total, pair_total, sum_g, sum_t, id_total;
+    int64_t max_gids, max_gt_frame, max_pr_frame, max_frame_pairs;
+} cnl_mot_tables;
+int cnl_mot_similarity_f64(const cnl_mot_tables* tables, double* sim, void* stream);
+int64_t cnl_mot_hota_workspace_bytes(const cnl_mot_tables* tables);
+int cnl_mot_hota_f64(const cnl_mot_tables* tables, const double* sim, const double* alpha, double* out_f64, int64_t* out_i64,
+                     int32_t* status, void* workspace, int64_t workspace_bytes, void* stream);
+int64_t cnl_mot_clear_workspace_bytes(const cnl_mot_tables* tables);
+int cnl_mot_clear_f64(const cnl_mot_tables* tables, const double* sim, double* out_f64, int64_t* out_i64, int32_t* status,
+                      void* workspace, int64_t workspace_bytes, void* stream);
+int64_t cnl_mot_identity_workspace_bytes(const cnl_mot_tables* tables);
+int cnl_mot_identity_f64(const cnl_mot_tables* tables, const double* sim, int32_t* pm, int64_t* out_i64, int32_t* status,
+                         void* workspace, int64_t workspace_bytes, void* stream);
+
+/*
  * ResNet stem: Conv2d(3,64,7,stride=2,padding=3,bias=False)+BN+ReLU (torchvision resnet.conv1/bn1/relu).
  * x is read through explicit element strides (sn,sc,sh,sw) so NCHW-contiguous and channels_last
  * callers are both zero-copy (models/meta.py:97-98 precedent); y is NHWC [N, H/2, W/2, 64].
