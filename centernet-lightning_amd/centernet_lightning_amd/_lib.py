@@ -89,6 +89,13 @@ class MotTables(Structure):
     _fields_ = [(n, c_void_p) for n in POINTERS] + [(n, c_int64) for n in SCALARS]
 
 
+class LossParams(Structure):
+    """cnl_loss_params: the rule of one cnl_detection_loss_f64 call (72 bytes; cnl_sizeof_params(4))."""
+    _fields_ = [("stride", c_double), ("target_param", c_double), ("hm_alpha", c_double), ("hm_beta", c_double),
+                ("heatmap_weight", c_double), ("box_weight", c_double), ("box_multiplier", c_float), ("target_method", c_int32),
+                ("heatmap_loss", c_int32), ("box_loss", c_int32), ("box_log", c_int32), ("reserved", c_int32)]
+
+
 _SIGNATURES = {
     "cnl_version": (ctypes.c_int, []),
     "cnl_sizeof_params": (c_size_t, [ctypes.c_int32]),
@@ -149,6 +156,11 @@ _SIGNATURES = {
     "cnl_mot_clear_f64": (ctypes.c_int, [POINTER(MotTables), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "cnl_mot_identity_workspace_bytes": (c_int64, [POINTER(MotTables)]),
     "cnl_mot_identity_f64": (ctypes.c_int, [POINTER(MotTables), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "cnl_detection_loss_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32]),
+    "cnl_detection_loss_f64": (ctypes.c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int64,
+                                              c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int32, POINTER(LossParams),
+                                              c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                              c_void_p]),
     "cnl_stem_conv7x7_u8": (ctypes.c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, POINTER(c_float), POINTER(c_float), c_void_p, c_void_p,
                                            c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "cnl_stem_packed_weight_floats": (c_size_t, []),
@@ -226,7 +238,7 @@ def load():
     if lib.cnl_version() != ABI_VERSION:
         raise HipLibraryError(f"{path} has ABI version {lib.cnl_version()}, this binding expects {ABI_VERSION}: rebuild it "
                               "(__graft_entry__.build())")
-    for which, struct in enumerate((ConvParams, DecodeParams, DeconvParams)):       # the binding's struct layouts against the library's
+    for which, struct in ((0, ConvParams), (1, DecodeParams), (2, DeconvParams), (4, LossParams)):       # the binding's struct layouts against the library's
         if lib.cnl_sizeof_params(which) != ctypes.sizeof(struct):
             raise HipLibraryError(f"{path}: sizeof({struct.__name__}) is {lib.cnl_sizeof_params(which)} in the library, {ctypes.sizeof(struct)} in this binding")
     _lib = lib

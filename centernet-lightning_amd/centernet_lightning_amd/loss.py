@@ -1,0 +1,305 @@
+"""The validation value of the detection losses on the GPU: the reference's CenterNet.compute_loss (models/centernet.py:123-200: Gaussian target
+heatmap, heatmap loss, 3x3 centre-sampled box loss) without its Python loops over images and boxes, without a second N x C x H x W tensor and
+without the logits leaving the device.
+
+detection_loss() is ONE call of cnl_detection_loss_f64 (csrc/det_loss.hip: four launches, the logits read once); render_targets() runs the same
+kernel for the target heatmap alone; LossMeter accumulates the per-batch values on the device as Lightning's self.log averaging would.  The
+rule is stated in include/centernet_gfx950.h and restated in numpy in tests/loss_ref.py.  Forward value only: no gradient, no reid loss (the
+reference leaves it out at validation, fairmot.py:87-91).  No CPU fallback: a missing device or library raises.
+"""
+import ctypes
+import math
+
+import numpy as np
+import torch
+
+from . import _gather, _lib
+from .coco_eval import _upload
+
+MAX_PER_IMAGE = 1024          # boxes per image (csrc/det_loss.hip)
+MAX_CLASSES, MAX_SIDE, MAX_IMAGES = 1 << 16, 1 << 15, 1 << 16
+TARGET_METHODS = {"cornernet": (0, "min_overlap", 0.3), "ttfnet": (1, "alpha", 0.54), "fixed": (2, "r", 1.0)}
+# Gen-A YAML spelling (configs/base_resnet34.yaml:17-24) and Gen-B class names (losses/__init__.py)
+HEATMAP_LOSSES = {"cornernet_focal": 0, "CornerNetFocalLoss": 0, "quality": 1, "QualityFocalLoss": 1}
+BOX_LOSSES = {"l1": 0, "L1Loss": 0, "smooth_l1": 1, "SmoothL1Loss": 1, "iou": 2, "IoULoss": 2, "giou": 3, "GIoULoss": 3, "diou": 4, "DIoULoss": 4,
+              "ciou": 5, "CIoULoss": 5}
+METRIC_NAMES = ("heatmap_loss", "box_2d_loss", "total_loss")
+GEN_B_KEYS = ("heatmap_loss", "box_loss", "heatmap_loss_weight", "box_loss_weight", "heatmap_target", "heatmap_target_params")
+
+
+def _number(value, name, what, positive=False):
+    if isinstance(value, bool) or not isinstance(value, (int, float, np.integer, np.floating)) or not math.isfinite(float(value)) or \
+            (positive and float(value) <= 0):
+        raise ValueError(f"{what}: {name} must be a finite {'positive ' if positive else ''}number, got {value!r}")
+    return float(value)
+
+
+def loss_params(stride=4, heatmap_target="cornernet", heatmap_target_params=None, heatmap_loss="cornernet_focal", box_loss="giou",
+                heatmap_loss_weight=1.0, box_loss_weight=1.0, box_log=False, box_multiplier=1.0, what="detection_loss"):
+    """The checked cnl_loss_params block of these settings (needs neither a device nor the library)."""
+    if heatmap_target not in TARGET_METHODS:
+        raise ValueError(f"{what}: heatmap_target must be one of {sorted(TARGET_METHODS)}, got {heatmap_target!r}")
+    method, key, param = TARGET_METHODS[heatmap_target]
+    if heatmap_target_params is not None:
+        if not isinstance(heatmap_target_params, dict) or set(heatmap_target_params) - {key}:
+            raise ValueError(f"{what}: heatmap_target_params of '{heatmap_target}' may hold '{key}' only, got {heatmap_target_params!r}")
+        param = _number(heatmap_target_params.get(key, param), f"heatmap_target_params['{key}']", what)
+    if method == 0 and not 0.0 < param < 1.0:
+        raise ValueError(f"{what}: cornernet min_overlap must lie in (0, 1), got {param!r}")
+    if heatmap_loss not in HEATMAP_LOSSES:
+        raise ValueError(f"{what}: heatmap_loss must be one of {sorted(HEATMAP_LOSSES)}, got {heatmap_loss!r}")
+    if box_loss not in BOX_LOSSES:
+        raise ValueError(f"{what}: box_loss must be one of {sorted(BOX_LOSSES)}, got {box_loss!r}")
+    p = _lib.LossParams()
+    p.stride = _number(stride, "stride", what, positive=True)
+    p.target_param, p.target_method = param, method
+    p.heatmap_loss, p.box_loss = HEATMAP_LOSSES[heatmap_loss], BOX_LOSSES[box_loss]
+    p.hm_alpha, p.hm_beta = (2.0, 4.0) if p.heatmap_loss == 0 else (0.0, 2.0)          # the reference's defaults (heatmap_losses.py:15, 52)
+    p.heatmap_weight = _number(heatmap_loss_weight, "heatmap_loss_weight", what)
+    p.box_weight = _number(box_loss_weight, "box_loss_weight", what)
+    p.box_multiplier = _number(box_multiplier, "box_multiplier", what)
+    p.box_log = 1 if box_log else 0
+    return p
+
+
+def settings_from_config(output_heads=None, **gen_b):
+    """The keyword arguments of detection_loss a config asks for.  Gen-A: `output_heads.heatmap.{target_method, loss_function, loss_weight}` and
+    `output_heads.box_2d.{loss_function, loss_weight}`; Gen-B: `heatmap_loss`, `box_loss`, `heatmap_loss_weight`, `box_loss_weight`,
+    `heatmap_target`, `heatmap_target_params` (these win).  Keys that are absent leave detection_loss's defaults."""
+    out = {}
+    heads = output_heads or {}
+    hm, box = dict(heads.get("heatmap") or {}), dict(heads.get("box_2d") or {})
+    for src, key, name in ((hm, "target_method", "heatmap_target"), (hm, "loss_function", "heatmap_loss"), (hm, "loss_weight", "heatmap_loss_weight"),
+                           (box, "loss_function", "box_loss"), (box, "loss_weight", "box_loss_weight")):
+        if key in src:
+            out[name] = src[key]
+    for name in GEN_B_KEYS:
+        if gen_b.get(name) is not None:
+            out[name] = gen_b[name]
+    loss_params(what="loss settings of the config", **out)       # a misspelt name fails where the model is built
+    return out
+
+
+def _bad_boxes(boxes, labels, stride, C, H, W):
+    """Indices of the boxes the kernel would skip (the record rule of include/centernet_gfx950.h, in numpy float64)."""
+    with np.errstate(all="ignore"):
+        b = boxes / float(stride)
+        cx, cy = np.rint(b[:, 0] + b[:, 2] / 2), np.rint(b[:, 1] + b[:, 3] / 2)
+        ok = np.isfinite(b).all(axis=1) & (b[:, 2] >= 0) & (b[:, 3] >= 0) & (cx >= 0) & (cx <= W) & (cy >= 0) & (cy <= H) & (labels >= 0) & (labels < C)
+    return np.nonzero(~ok)[0]
+
+
+def _targets(targets, N, C, H, W, stride, what):
+    """-> (device or None, (boxes [N,Gmax,4] f64, labels [N,Gmax] i64, count [N] i32) as device tensors or numpy, Gmax)"""
+    if isinstance(targets, dict) or (isinstance(targets, (list, tuple)) and len(targets) == 3 and all(isinstance(t, torch.Tensor) for t in targets)):
+        if isinstance(targets, dict):
+            if any(name not in targets for name in ("boxes", "labels", "count")):
+                raise ValueError(f"{what}: device targets need 'boxes' [N,Gmax,4] f64, 'labels' [N,Gmax] i64 and 'count' [N] i32")
+            targets = (targets["boxes"], targets["labels"], targets["count"])
+        boxes, labels, count = targets
+        for name, t, dtype, dims in (("boxes", boxes, torch.float64, 3), ("labels", labels, torch.int64, 2), ("count", count, torch.int32, 1)):
+            if not isinstance(t, torch.Tensor):
+                raise ValueError(f"{what}: targets '{name}' must be a tensor, got {type(t).__name__}")
+            if t.dtype != dtype or t.dim() != dims:
+                raise ValueError(f"{what}: targets '{name}' must be {dtype} with {dims} dimensions, got {t.dtype} {tuple(t.shape)}")
+        Gmax = int(boxes.shape[1])
+        if tuple(boxes.shape) != (N, Gmax, 4) or tuple(labels.shape) != (N, Gmax) or tuple(count.shape) != (N,):
+            raise ValueError(f"{what}: expected target boxes [{N},Gmax,4], labels [{N},Gmax], count [{N}], got {tuple(boxes.shape)}, "
+                             f"{tuple(labels.shape)}, {tuple(count.shape)}")
+        if not 1 <= Gmax <= MAX_PER_IMAGE:
+            raise ValueError(f"{what}: Gmax = {Gmax} boxes per image; 1..{MAX_PER_IMAGE} are supported")
+        _gather.require_hip([boxes, labels, count], what)
+        if labels.device != boxes.device or count.device != boxes.device:
+            raise ValueError(f"{what}: target tensors live on different devices")
+        return boxes.device, (boxes.contiguous(), labels.contiguous(), count.contiguous()), Gmax
+    if not isinstance(targets, (list, tuple)):
+        raise ValueError(f"{what}: targets must be a list of per-image dicts or padded device tensors, got {type(targets).__name__}")
+    if len(targets) != N:
+        raise ValueError(f"{what}: {N} images of outputs against {len(targets)} of targets")
+    images = []
+    for i, d in enumerate(targets):
+        if not isinstance(d, dict) or "boxes" not in d or "labels" not in d:
+            raise ValueError(f"{what}: targets[{i}] must be a dict with 'boxes', 'labels'")
+        try:
+            b = np.asarray(d["boxes"].detach().cpu().numpy() if isinstance(d["boxes"], torch.Tensor) else d["boxes"]).astype(np.float64)
+            lab = np.asarray(d["labels"].detach().cpu().numpy() if isinstance(d["labels"], torch.Tensor) else d["labels"]).astype(np.int64).reshape(-1)
+        except (TypeError, ValueError) as e:
+            raise ValueError(f"{what}: targets[{i}] is not numeric: {e}") from e
+        if b.size == 0:
+            b = b.reshape(0, 4)
+        if b.ndim != 2 or b.shape[1] != 4 or b.shape[0] != lab.shape[0]:
+            raise ValueError(f"{what}: targets[{i}] has boxes {b.shape} and labels {lab.shape}; expected [n, 4] and [n]")
+        if lab.shape[0] > MAX_PER_IMAGE:
+            raise ValueError(f"{what}: targets[{i}] has {lab.shape[0]} boxes; at most {MAX_PER_IMAGE} per image are supported")
+        bad = _bad_boxes(b, lab, stride, C, H, W)
+        if bad.size:
+            j = int(bad[0])
+            raise ValueError(f"{what}: targets[{i}] box {j} = {b[j].tolist()} (label {int(lab[j])}) cannot be a target on a {H} x {W} map of {C} "
+                             f"classes at stride {stride}: non-finite, negative size, centre outside the map or label outside 0..{C - 1}")
+        images.append((b, lab))
+    Gmax = max([1] + [len(lab) for (_, lab) in images])
+    boxes, labels, count = np.zeros((N, Gmax, 4), dtype=np.float64), np.zeros((N, Gmax), dtype=np.int64), np.zeros((N,), dtype=np.int32)
+    for i, (b, lab) in enumerate(images):
+        boxes[i, :len(lab)], labels[i, :len(lab)], count[i] = b, lab, len(lab)
+    return None, (boxes, labels, count), Gmax
+
+
+def _check_map(t, name, channels, what):
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 4:
+        raise ValueError(f"{what}: {name} must be a float32 tensor [N, {channels}, H, W], got "
+                         f"{(t.dtype, tuple(t.shape)) if isinstance(t, torch.Tensor) else type(t).__name__}")
+
+
+def _check_sizes(N, C, H, W, what):
+    if not (0 <= N <= MAX_IMAGES and 1 <= C <= MAX_CLASSES and 1 <= H <= MAX_SIDE and 1 <= W <= MAX_SIDE):
+        raise ValueError(f"{what}: N x C x H x W = {N} x {C} x {H} x {W} outside 0..{MAX_IMAGES} x 1..{MAX_CLASSES} x 1..{MAX_SIDE} x 1..{MAX_SIDE}")
+
+
+def _run(heatmap, box_2d, targets, shape, params, want_targets, dev, what):
+    """The one call.  heatmap / box_2d None: targets only.  -> (out [N*4 + 3] f64, skipped [1] i32, target map or None)."""
+    N, C, H, W = shape
+    g_dev, gts, Gmax = _targets(targets, N, C, H, W, params.stride, what)
+    if dev is None:
+        dev = g_dev
+    if dev is None or dev.index is None:
+        if not torch.cuda.is_available():
+            raise RuntimeError(f"{what} runs on HIP devices only (no CPU fallback)")
+        dev = torch.device("cuda", torch.cuda.current_device())
+    if g_dev is not None and g_dev != dev:
+        raise ValueError(f"{what}: outputs on {dev}, targets on {g_dev}")
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        out = torch.zeros((N * 4 + 3,), dtype=torch.float64, device=dev)
+        skipped = torch.zeros((1,), dtype=torch.int32, device=dev)
+        tmap = torch.empty((N, C, H, W), dtype=torch.float32, device=dev, memory_format=torch.channels_last) if want_targets else None
+        if N == 0:
+            return out, skipped, tmap
+        if g_dev is None:
+            gts = _upload(list(gts), dev)
+        nbytes = lib.cnl_detection_loss_workspace_bytes(N, Gmax, H, W)
+        ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=dev)
+        hs, bs = (heatmap.stride(), box_2d.stride()) if heatmap is not None else ((0,) * 4, (0,) * 4)
+        ts = tmap.stride() if tmap is not None else (0,) * 4
+        _lib.check(lib.cnl_detection_loss_f64(None if heatmap is None else heatmap.data_ptr(), *hs, None if box_2d is None else box_2d.data_ptr(), *bs,
+                                              N, C, H, W, gts[0].data_ptr(), gts[1].data_ptr(), gts[2].data_ptr(), Gmax, ctypes.byref(params),
+                                              None if tmap is None else tmap.data_ptr(), *ts, out.data_ptr(), out.data_ptr() + 8 * 4 * N,
+                                              skipped.data_ptr(), ws.data_ptr(), nbytes,
+                                              ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "cnl_detection_loss_f64")
+    return out, skipped, tmap
+
+
+def detection_loss(heatmap, box_2d, targets, stride=4, heatmap_target="cornernet", heatmap_target_params=None, heatmap_loss="cornernet_focal",
+                   box_loss="giou", heatmap_loss_weight=1.0, box_loss_weight=1.0, box_log=False, box_multiplier=1.0, return_targets=False):
+    """The reference's compute_loss on the device.  heatmap [N, C, H, W] fp32 LOGITS and box_2d [N, 4, H, W] fp32 as get_encoded_outputs returns
+    them (any strides; channels-last is the fast path).  targets: the reference's list of per-image {"boxes" [m, 4] x y w h in input pixels,
+    "labels" [m]} (checked on the host: a box that cannot be a target raises ValueError; padded and uploaded in one copy), or padded device tensors
+    (boxes [N, Gmax, 4] float64, labels [N, Gmax] int64, count [N] int32) as a tuple or dict (a bad box is skipped and counted in "skipped").
+    At most 1024 boxes per image.  Loss names in the Gen-A YAML spelling or as Gen-B class names.
+    -> {"heatmap", "box_2d", "total"}: 0-dim float64 device tensors; "per_image" [N, 4] float64 rows (heatmap_sum, box_sum, num_dets, num_boxes);
+    "skipped": 0-dim int32; with return_targets also "targets", the fp32 target heatmap [N, C, H, W] (channels-last).  No synchronisation."""
+    what = "detection_loss"
+    params = loss_params(stride, heatmap_target, heatmap_target_params, heatmap_loss, box_loss, heatmap_loss_weight, box_loss_weight, box_log,
+                         box_multiplier, what)
+    _check_map(heatmap, "heatmap", "C", what)
+    _check_map(box_2d, "box_2d", 4, what)
+    N, C, H, W = (int(v) for v in heatmap.shape)
+    if tuple(box_2d.shape) != (N, 4, H, W):
+        raise ValueError(f"{what}: heatmap {tuple(heatmap.shape)} needs box_2d [{N}, 4, {H}, {W}], got {tuple(box_2d.shape)}")
+    _check_sizes(N, C, H, W, what)
+    _gather.require_hip([heatmap, box_2d], what)
+    if box_2d.device != heatmap.device:
+        raise ValueError(f"{what}: heatmap on {heatmap.device}, box_2d on {box_2d.device}")
+    out, skipped, tmap = _run(heatmap, box_2d, targets, (N, C, H, W), params, bool(return_targets), heatmap.device, what)
+    res = {"heatmap": out[4 * N], "box_2d": out[4 * N + 1], "total": out[4 * N + 2], "per_image": out[:4 * N].view(N, 4), "skipped": skipped[0]}
+    if return_targets:
+        res["targets"] = tmap
+    return res
+
+
+def render_targets(targets, num_classes, height, width, stride=4, heatmap_target="cornernet", heatmap_target_params=None, device=None):
+    """The fp32 target heatmap [N, num_classes, height, width] (channels-last) of the targets, from the kernel detection_loss runs (no logits are
+    read).  targets as for detection_loss; `device`: where to render when the targets come from the host (default: the current device)."""
+    what = "render_targets"
+    params = loss_params(stride, heatmap_target, heatmap_target_params, what=what)
+    for name, v in (("num_classes", num_classes), ("height", height), ("width", width)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"{what}: {name} must be an int, got {v!r}")
+    is_padded = isinstance(targets, dict) or (isinstance(targets, (list, tuple)) and len(targets) == 3 and all(isinstance(t, torch.Tensor) for t in targets))
+    if is_padded:
+        first = targets["boxes"] if isinstance(targets, dict) and "boxes" in targets else targets[0] if not isinstance(targets, dict) else None
+        N = int(first.shape[0]) if isinstance(first, torch.Tensor) and first.dim() else 0
+    elif isinstance(targets, (list, tuple)):
+        N = len(targets)
+    else:
+        raise ValueError(f"{what}: targets must be a list of per-image dicts or padded device tensors, got {type(targets).__name__}")
+    _check_sizes(N, int(num_classes), int(height), int(width), what)
+    dev = None if device is None else torch.device(device)
+    if dev is not None and dev.type != "cuda":
+        raise RuntimeError(f"{what} runs on HIP devices only (no CPU fallback)")
+    _, _, tmap = _run(None, None, targets, (N, int(num_classes), int(height), int(width)), params, True, dev, what)
+    return tmap
+
+
+class LossMeter:
+    """The validation curves of an epoch: update(outputs, targets) per batch, get_metrics() -> {"heatmap_loss", "box_2d_loss", "total_loss"}, the
+    per-batch values weighted by batch size (what Lightning's self.log averaging gives for val/heatmap_loss, val/box_2d_loss, val/total_loss).
+    It accumulates on the device; get_metrics makes the one download and raises if any box was skipped.  `settings`: detection_loss's keyword
+    arguments (model.loss_meter() fills them from the model)."""
+    metric_names = METRIC_NAMES
+
+    def __init__(self, **settings):
+        settings.pop("return_targets", None)
+        loss_params(what="LossMeter", **settings)
+        self.settings = settings
+        self._acc = None          # [5] float64 on the device: the three weighted sums, the images, the skipped boxes
+        self.reset()
+
+    def reset(self):
+        self.num_batches = 0
+        if self._acc is not None:
+            self._acc.zero_()
+
+    def update(self, outputs, targets):
+        """outputs: the dict of get_encoded_outputs ("heatmap" logits, "box_2d").  One call of detection_loss, no synchronisation."""
+        if not isinstance(outputs, dict) or "heatmap" not in outputs or "box_2d" not in outputs:
+            raise ValueError("LossMeter.update: outputs must be the dict of get_encoded_outputs with 'heatmap' and 'box_2d'")
+        res = detection_loss(outputs["heatmap"], outputs["box_2d"], targets, **self.settings)
+        n = int(outputs["heatmap"].shape[0])
+        step = torch.stack([res["heatmap"] * n, res["box_2d"] * n, res["total"] * n, res["total"].new_tensor(float(n)), res["skipped"].to(torch.float64)])
+        if self._acc is None:
+            self._acc = step
+        else:
+            if self._acc.device != step.device:
+                raise ValueError(f"LossMeter: state on {self._acc.device}, input on {step.device}")
+            self._acc += step
+        self.num_batches += 1
+
+    def state(self):
+        """{"sums" [5] float64 device tensor (a copy), "num_batches"}: what another meter's merge() takes."""
+        if self._acc is None:
+            raise RuntimeError("LossMeter.state: nothing has been measured yet")
+        return {"sums": self._acc.clone(), "num_batches": self.num_batches}
+
+    def merge(self, state):
+        """Add another meter's state() (how shards and ranks combine; no collective is involved)."""
+        if not isinstance(state, dict) or "sums" not in state or "num_batches" not in state:
+            raise ValueError("LossMeter.merge expects the dict another meter's state() returned")
+        sums = state["sums"]
+        if not isinstance(sums, torch.Tensor) or sums.dtype != torch.float64 or tuple(sums.shape) != (5,):
+            raise ValueError("LossMeter.merge: 'sums' must be float64 [5]")
+        _gather.require_hip([sums], "LossMeter.merge")
+        if self._acc is None:
+            self._acc = sums.clone()
+        else:
+            self._acc += sums.to(self._acc.device)
+        self.num_batches += int(state["num_batches"])
+
+    def get_metrics(self):
+        if self._acc is None:
+            raise RuntimeError("LossMeter.get_metrics: nothing has been measured yet")
+        heat, box, total, images, skipped = self._acc.cpu().tolist()
+        if skipped:
+            raise ValueError(f"LossMeter.get_metrics: {int(skipped)} target box(es) were skipped (non-finite, negative size, centre outside the map or "
+                             "label outside the classes): the reference's loss is not defined for them")
+        images = max(images, 1.0)
+        return dict(zip(METRIC_NAMES, (heat / images, box / images, total / images)))

@@ -24,6 +24,7 @@ from . import crops as _crops
 from . import decode as _decode
 from . import flip as _flip
 from . import letterbox as _letterbox
+from . import loss as _loss
 from . import overlay as _overlay
 from . import tiles as _tiles
 from .collate import collate_detections
@@ -89,6 +90,8 @@ class CenterNet(nn.Module):
         # Gen-B hyper-parameters of the decode (centernet.py:82-83,93-94)
         self.num_detections, self.nms_kernel = int(num_detections), int(nms_kernel)
         self.box_log, self.box_multiplier = bool(box_log), float(box_multiplier)
+        # the validation loss's settings: Gen-A keys under output_heads.heatmap / .box_2d, Gen-B keys beside the decode's (loss.settings_from_config)
+        self.loss_settings = _loss.settings_from_config(output_heads, **ignored)
 
         heads = OrderedDict()
         in_c = self.neck.out_channels
@@ -365,6 +368,20 @@ class CenterNet(nn.Module):
         """A CocoEvaluator for this model's classes: feed it gather_detection2d's dict and the targets, batch by batch (coco_eval.py)."""
         return _coco_eval.CocoEvaluator(self.num_classes, device)
 
+    def compute_loss(self, outputs: Dict[str, torch.Tensor], targets, stride=None):
+        """The reference's compute_loss (models/centernet.py:123-175) as a validation VALUE: outputs is the dict of get_encoded_outputs (heatmap
+        logits), targets the reference's list of per-image {"boxes" x y w h, "labels"} or padded device tensors -> {"heatmap", "box_2d", "total"}
+        (0-dim float64 device tensors), "per_image", "skipped" (loss.detection_loss).  Target method, loss functions and weights come from the
+        config, stride / box_log / box_multiplier from the model; the reid loss is left out, as the reference leaves it out at validation."""
+        return _loss.detection_loss(outputs["heatmap"], outputs["box_2d"], targets, **self._loss_kwargs(stride))
+
+    def loss_meter(self):
+        """A LossMeter with this model's loss settings: update(outputs, targets) per batch, get_metrics() at the end of the epoch (loss.py)."""
+        return _loss.LossMeter(**self._loss_kwargs(None))
+
+    def _loss_kwargs(self, stride):
+        return dict(self.loss_settings, stride=self.stride if stride is None else stride, box_log=self.box_log, box_multiplier=self.box_multiplier)
+
     # ------------------------------------------------------------------ multi-GPU
     def collate(self, detections: Dict[str, torch.Tensor], group=None):
         """All-gather this rank's detections over the process group (RCCL on HIP) — eval/coco.py:10-18 precedent."""
@@ -374,5 +391,5 @@ class CenterNet(nn.Module):
 def build_centernet(config: Union[str, Dict[str, Any]]) -> CenterNet:
     """Build from a YAML path or a dict (README.md:31-37).  Reads the `model:` section only."""
     m = model_section(config)
-    extra = {k: m[k] for k in ("num_detections", "nms_kernel", "box_log", "box_multiplier") if k in m}
+    extra = {k: m[k] for k in ("num_detections", "nms_kernel", "box_log", "box_multiplier") + _loss.GEN_B_KEYS if k in m}
     return CenterNet(m["backbone"], m["neck"], m["output_heads"], m.get("task", "detection"), **extra)

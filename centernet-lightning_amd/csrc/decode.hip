@@ -20,6 +20,7 @@
 //   LDS histograms) instead.  Then the label / ltrb box / embedding gathers and the box decode for the k winners only (the reference
 //   transforms the whole 4xHxW map first, centernet.py:282-286).
 #include "cnl_common.h"
+#include "box_decode.h"
 
 #pragma clang fp contract(off)   // one rounding per op, like ATen: box decode must be bit-exact
 
@@ -593,27 +594,8 @@ __global__ __launch_bounds__(256) void peaks_planes_kernel(const PeakArgs a) {
     }
 }
 
-// ---- box decode shared by the fused path and the standalone gather (centernet.py:278-303) ----
-__device__ __forceinline__ void decode_box(const float* bp, long bsc, int xi, int yi, int W, int H, int normalize, int box_log,
-                                           float mult, float stride, float* bo) {
-    const float cx = (float)xi + 0.5f, cy = (float)yi + 0.5f;
-    float g[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        float v = bp[(long)j * bsc];
-        if (box_log) v = expf(v);
-        v = v * mult;
-        g[j] = fmaxf(v, 0.f);
-    }
-    float x1 = cx - g[0], y1 = cy - g[1], x2 = cx + g[2], y2 = cy + g[3];
-    if (normalize) {
-        const float fw = (float)W, fh = (float)H;
-        x1 = x1 / fw; x2 = x2 / fw; y1 = y1 / fh; y2 = y2 / fh;
-    } else {
-        x1 *= stride; y1 *= stride; x2 *= stride; y2 *= stride;
-    }
-    bo[0] = x1; bo[1] = y1; bo[2] = x2; bo[3] = y2;
-}
+// ---- box decode shared by the fused path and the standalone gather (centernet.py:278-303): box_decode.h, which the validation loss shares ----
+using cnl::decode_box;
 
 
 // ---- stage 2: per-image top-k + gathers ----

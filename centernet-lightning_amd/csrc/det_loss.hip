@@ -1,0 +1,429 @@
+// det_loss.hip — the validation value of the detection losses (reference models/centernet.py:123-200 compute_loss / update_heatmap,
+// losses/heatmap_losses.py, losses/box_losses.py) on the device: Gaussian targets, heatmap loss and the 3x3 centre-sampled box loss of a
+// batch in four launches, the logits read once, no N x C x H x W target tensor unless the caller asks for it.  The rule is stated in
+// include/centernet_gfx950.h and restated in numpy in tests/loss_ref.py.  Forward value only: nothing here computes a gradient.
+//
+//   record_kernel    one thread per target slot: box -> (cx, cy, rx, ry, the two fp32 Gaussian denominators, label, state), all float64
+//                    as the reference's host code computes them.  Slots at or beyond count[n] are never read.
+//   heatmap_kernel   the hot path.  A workgroup owns a TILE_H x TILE_W tile of pixels of one image over ALL classes.  It compacts the
+//                    image's records whose window touches the tile into LDS in slot order (ballot + popcount prefix, PASS_SLOTS slots per
+//                    pass; an image of at most PASS_SLOTS boxes is staged once), reads each logit exactly once, forms the element's target
+//                    in registers (the maximum over the staged records of its class), and adds the element's float64 loss term to a
+//                    per-thread sum in element order; the workgroup folds its 256 sums in a fixed tree into ONE float64 partial.
+//                    Three element orders: channel stride 1 (the engine's channels-last maps: lanes along the classes of a pixel, then
+//                    along x), W stride 1 (planes: lanes along x, then y, classes outermost), and the plane order with free strides.
+//   sample_kernel    one workgroup per image: the up to nine box samples of every counted record, decoded by the decode's own device
+//                    function (box_decode.h), the loss per sample in float64, summed per thread in slot order and folded in a fixed tree.
+//   finish_kernel    one workgroup: a wave per image folds the image's tile partials (lane stripes in index order, then a fixed tree) into
+//                    its row; thread 0 then adds the rows in image order into the three totals.
+// No floating-point atomics, no atomics at all: an image's row is a function of that image alone.  Nothing here synchronises the device.
+#include "cnl_common.h"
+
+#pragma clang fp contract(off)   // one rounding per operation
+
+#include "box_decode.h"
+
+namespace cnl_det_loss {
+
+constexpr int THREADS = 256, WAVES = THREADS / 64;
+constexpr int TILE_W = 32, TILE_H = 8;             // TILE_W * TILE_H == THREADS: every thread of a tile makes the same number of element steps
+constexpr int PASS_SLOTS = 256;                    // target slots staged per pass (one per thread)
+constexpr int MAX_G = 1024;                        // boxes per image
+constexpr int RADIUS_CAP = 1 << 24;                // window radii beyond any map are clamped here (the Gaussian's width is not)
+static_assert(TILE_W * TILE_H == THREADS && PASS_SLOTS == THREADS, "one element / one slot per thread and step");
+
+struct alignas(16) Rec {
+    int cx, cy, rx, ry;
+    float den_x, den_y;        // fl32(2 sx sx), fl32(2 sy sy)
+    int label;
+    int state;                 // 0 skipped, 1 counted
+};
+static_assert(sizeof(Rec) == 32, "record layout");
+
+enum { LAYOUT_CMINOR = 0, LAYOUT_PLANE = 1, LAYOUT_GENERIC = 2 };
+
+__host__ __device__ inline int tiles_x(int W) { return (W + TILE_W - 1) / TILE_W; }
+__host__ __device__ inline int tiles_y(int H) { return (H + TILE_H - 1) / TILE_H; }
+
+struct Sections {              // the workspace: records | tile partials | per-image sample results
+    size_t rec, part, img, total;
+};
+inline Sections sections(int N, int Gmax, int H, int W) {
+    Sections s;
+    s.rec = 0;
+    s.part = s.rec + (size_t)N * Gmax * sizeof(Rec);
+    s.img = s.part + (size_t)N * tiles_x(W) * tiles_y(H) * sizeof(double);
+    s.total = s.img + (size_t)N * 4 * sizeof(double);
+    return s;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- records
+__device__ __forceinline__ double cornernet_radius(double w, double h, double mo) {      // centernet.py:38-58, operation by operation
+    const double b1 = h + w;
+    const double c1 = w * h * (1.0 - mo) / (1.0 + mo);
+    const double r1 = (b1 - sqrt(b1 * b1 - 4.0 * c1)) / 2.0;
+    const double b2 = 2.0 * (h + w);
+    const double c2 = (1.0 - mo) * w * h;
+    const double r2 = (b2 - sqrt(b2 * b2 - 16.0 * c2)) / 8.0;
+    const double a3 = 4.0 * mo;
+    const double b3 = -2.0 * mo * (h + w);
+    const double c3 = (mo - 1.0) * w * h;
+    const double r3 = (b3 + sqrt(b3 * b3 - 4.0 * a3 * c3)) / (2.0 * a3);
+    double r = r1;                                           // Python's min(r1, r2, r3): the first of the smallest
+    if (r2 < r) r = r2;
+    if (r3 < r) r = r3;
+    return r;
+}
+
+__global__ __launch_bounds__(THREADS) void record_kernel(const double* __restrict__ boxes, const long long* __restrict__ labels,
+                                                         const int* __restrict__ count, int N, int Gmax, int C, int H, int W, double stride,
+                                                         int method, double param, Rec* __restrict__ rec) {
+    const long i = (long)blockIdx.x * THREADS + threadIdx.x;
+    if (i >= (long)N * Gmax) return;
+    const int n = (int)(i / Gmax), s = (int)(i - (long)n * Gmax);
+    if (s >= min(max(count[n], 0), Gmax)) return;            // never read, never staged
+    const double* const b = boxes + i * 4;
+    const double x = b[0] / stride, y = b[1] / stride, w = b[2] / stride, h = b[3] / stride;
+    const long long label = labels[i];
+    Rec r;
+    r.cx = r.cy = r.rx = r.ry = 0; r.den_x = r.den_y = 1.f; r.label = -1; r.state = 0;
+    const double cx = rint(x + w / 2.0), cy = rint(y + h / 2.0);      // numpy's round: ties to even
+    double rx, ry;
+    if (method == 0) rx = ry = cornernet_radius(w, h, param);
+    else if (method == 1) { rx = w / 2.0 * param; ry = h / 2.0 * param; }
+    else rx = ry = param;
+    rx = rint(rx); ry = rint(ry);
+    // (every comparison is false for a NaN: a non-finite number anywhere skips the box)
+    const bool finite = fabs(x) < __builtin_inf() && fabs(y) < __builtin_inf() && w < __builtin_inf() && h < __builtin_inf() &&
+                        fabs(rx) < __builtin_inf() && fabs(ry) < __builtin_inf();
+    if (finite && w >= 0.0 && h >= 0.0 && cx >= 0.0 && cx <= (double)W && cy >= 0.0 && cy <= (double)H && label >= 0 && label < C) {
+        rx = fmax(rx, 0.0); ry = fmax(ry, 0.0);
+        const double sx = rx / 3.0 + 1.0 / 6.0, sy = ry / 3.0 + 1.0 / 6.0;
+        r.cx = (int)cx; r.cy = (int)cy;
+        r.rx = (int)fmin(rx, (double)RADIUS_CAP); r.ry = (int)fmin(ry, (double)RADIUS_CAP);
+        r.den_x = (float)(2.0 * (sx * sx)); r.den_y = (float)(2.0 * (sy * sy));
+        r.label = (int)label;
+        r.state = 1;
+    }
+    rec[i] = r;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- heatmap
+struct HeatArgs {
+    const float* heat; long sn, sc, sh, sw;        // NULL: targets only
+    float* tmap; long tn, tc, th, tw;              // NULL: never written
+    const Rec* rec;
+    const int* count;
+    double* part;
+    int C, H, W, Gmax, tx;
+    int loss;                                      // 0 cornernet_focal, 1 quality
+    int alpha_is_2, beta_is_4, beta_is_2;
+    double alpha, beta;
+};
+
+__device__ __forceinline__ double wave_sum_fixed(double v) {      // the same tree in every lane, every run
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+// sum over the workgroup in a fixed order; valid in thread 0
+__device__ __forceinline__ double block_sum_fixed(double v, double* s_part) {
+    v = wave_sum_fixed(v);
+    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = v;
+    __syncthreads();
+    double s = s_part[0];
+#pragma unroll
+    for (int w = 1; w < WAVES; ++w) s += s_part[w];
+    __syncthreads();
+    return s;
+}
+
+// one pass: the records of slots s0 .. s0 + PASS_SLOTS - 1 whose window touches the tile, compacted into s_rec in slot order -> how many
+__device__ __forceinline__ int stage(const Rec* __restrict__ recs, int s0, int M, int x0, int y0, int x1, int y1, int W, int H, Rec* s_rec,
+                                     int* s_cnt) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    __syncthreads();                                          // the readers of the previous pass are done
+    const int s = s0 + tid;
+    bool hit = false;
+    Rec r;
+    if (s < M) {
+        r = recs[s];
+        // (a centre ON cx == W or cy == H still renders the part of its window that lies inside the map, as the reference's slices do)
+        hit = r.state != 0 && r.cx - r.rx < x1 && r.cx + r.rx >= x0 && r.cy - r.ry < y1 && r.cy + r.ry >= y0;
+    }
+    const unsigned long long votes = __ballot(hit);
+    if (lane == 0) s_cnt[wave] = __popcll(votes);
+    __syncthreads();
+    int base = 0, total = 0;
+#pragma unroll
+    for (int w = 0; w < WAVES; ++w) {
+        const int c = s_cnt[w];
+        if (w < wave) base += c;
+        total += c;
+    }
+    if (hit) s_rec[base + __popcll(votes & ((1ull << lane) - 1ull))] = r;
+    __syncthreads();
+    return total;
+}
+
+__device__ __forceinline__ float target_of(const Rec* s_rec, int cnt, int x, int y, int c, float t) {
+    for (int j = 0; j < cnt; ++j) {
+        const Rec r = s_rec[j];                               // the same address in every lane: a broadcast
+        const int dx = x - r.cx, dy = y - r.cy;
+        if (r.label == c && abs(dx) <= r.rx && abs(dy) <= r.ry) {
+            const float g = (float)(dx * dx) / r.den_x + (float)(dy * dy) / r.den_y;
+            float v = (float)exp(-(double)g);
+            if (v < 1.1920928955078125e-07f) v = 0.f;         // the reference's cut at eps * max, max == 1
+            t = fmaxf(t, v);
+        }
+    }
+    return t;
+}
+
+__device__ __forceinline__ double pow_small(double v, double e, int is2, int is4) {
+    if (is2) return v * v;
+    if (is4) { const double v2 = v * v; return v2 * v2; }
+    return pow(v, e);
+}
+
+__device__ __forceinline__ double heat_term(const HeatArgs& a, float logit, float t) {
+    const double x = (double)logit, td = (double)t;
+    const double e = exp(-fabs(x));
+    const double l1p = log1p(e);
+    const double inv = 1.0 / (1.0 + e);
+    const double p = x >= 0.0 ? inv : e * inv;               // 1 / (1 + exp(-x)) without the overflow
+    if (a.loss == 0) {
+        const double pos = t == 1.f ? -pow_small(1.0 - p, a.alpha, a.alpha_is_2, 0) * (fmin(x, 0.0) - l1p) : 0.0;
+        const double neg = -pow_small(p, a.alpha, a.alpha_is_2, 0) * (fmin(-x, 0.0) - l1p) * pow_small(1.0 - td, a.beta, 0, a.beta_is_4);
+        return pos + neg;
+    }
+    return pow_small(fabs(td - p), a.beta, a.beta_is_2, 0) * (fmax(x, 0.0) - x * td + l1p);
+}
+
+template <int LAYOUT>
+__global__ __launch_bounds__(THREADS) void heatmap_kernel(const HeatArgs a) {
+    __shared__ Rec s_rec[PASS_SLOTS];
+    __shared__ int s_cnt[WAVES];
+    __shared__ double s_part[WAVES];
+    const int tid = threadIdx.x;
+    const int tiles = a.tx * tiles_y(a.H);
+    const int n = blockIdx.x / tiles, tile = blockIdx.x - n * tiles;
+    const int ty = tile / a.tx, txi = tile - ty * a.tx;
+    const int x0 = txi * TILE_W, y0 = ty * TILE_H, x1 = min(x0 + TILE_W, a.W), y1 = min(y0 + TILE_H, a.H);
+    const int M = min(max(a.count[n], 0), a.Gmax);
+    const Rec* const recs = a.rec + (long)n * a.Gmax;
+    const int passes = (M + PASS_SLOTS - 1) / PASS_SLOTS;
+    const long sw = LAYOUT == LAYOUT_PLANE ? 1 : a.sw, sc = LAYOUT == LAYOUT_CMINOR ? 1 : a.sc;
+    const float* const heat = a.heat ? a.heat + (long)n * a.sn : nullptr;
+    float* const tmap = a.tmap ? a.tmap + (long)n * a.tn : nullptr;
+
+    int cnt = passes == 1 ? stage(recs, 0, M, x0, y0, x1, y1, a.W, a.H, s_rec, s_cnt) : 0;
+    double acc = 0.0;
+    const unsigned row = (unsigned)TILE_W * (unsigned)a.C;
+    // THREADS * C elements, THREADS per step: the trip count is C in every thread, so the barriers of a multi-pass step are uniform
+    for (int step = 0; step < a.C; ++step) {
+        int x, y, c;
+        if (LAYOUT == LAYOUT_CMINOR) {                        // lanes along the classes of a pixel, then along x
+            const unsigned e = (unsigned)step * THREADS + (unsigned)tid;
+            const unsigned yy = e / row, j = e - yy * row, xx = j / (unsigned)a.C;
+            y = y0 + (int)yy; x = x0 + (int)xx; c = (int)(j - xx * (unsigned)a.C);
+        } else {                                              // lanes along x, then y; one class per step
+            c = step; y = y0 + tid / TILE_W; x = x0 + tid % TILE_W;
+        }
+        const bool inside = x < x1 && y < y1;
+        float logit = 0.f;
+        if (inside && heat) logit = heat[(long)c * sc + (long)y * a.sh + (long)x * sw];      // requested before the target's arithmetic
+        float t = 0.f;
+        if (passes <= 1) {
+            if (inside) t = target_of(s_rec, cnt, x, y, c, 0.f);
+        } else {
+            for (int p = 0; p < passes; ++p) {
+                cnt = stage(recs, p * PASS_SLOTS, M, x0, y0, x1, y1, a.W, a.H, s_rec, s_cnt);
+                if (inside) t = target_of(s_rec, cnt, x, y, c, t);
+            }
+        }
+        if (inside) {
+            if (tmap) tmap[(long)c * a.tc + (long)y * a.th + (long)x * a.tw] = t;
+            if (heat) acc += heat_term(a, logit, t);
+        }
+    }
+    const double total = block_sum_fixed(acc, s_part);
+    if (tid == 0) a.part[blockIdx.x] = total;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- box samples
+__device__ __forceinline__ double box_term(int kind, const float* pf, const float* tf) {      // losses/box_losses.py on (pred, target), float64
+    double p[4], t[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { p[j] = (double)pf[j]; t[j] = (double)tf[j]; }
+    if (kind <= 1) {                                          // l1, smooth_l1 (beta 1): the four coordinates in order
+        double s = 0.0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const double d = fabs(p[j] - t[j]);
+            s += kind == 0 ? d : (d < 1.0 ? 0.5 * d * d : d - 0.5);
+        }
+        return s;
+    }
+    const double eps = 1e-8;
+    const double area1 = (p[2] - p[0]) * (p[3] - p[1]), area2 = (t[2] - t[0]) * (t[3] - t[1]);
+    const double iw = fmax(fmin(p[2], t[2]) - fmax(p[0], t[0]), 0.0), ih = fmax(fmin(p[3], t[3]) - fmax(p[1], t[1]), 0.0);
+    const double inter = iw * ih;
+    const double uni = area1 + area2 - inter;
+    const double iou = inter / (uni + eps);
+    if (kind == 2) return 1.0 - iou;
+    const double ex1 = fmin(p[0], t[0]), ey1 = fmin(p[1], t[1]), ex2 = fmax(p[2], t[2]), ey2 = fmax(p[3], t[3]);
+    if (kind == 3) {
+        const double enclosing = (ex2 - ex1) * (ey2 - ey1);
+        const double giou = iou - (1.0 - uni / enclosing);
+        return 1.0 - giou;
+    }
+    const double ew = ex2 - ex1, eh = ey2 - ey1;
+    const double diagonal = ew * ew + eh * eh;
+    const double ddx = (t[0] + t[2]) / 2.0 - (p[0] + p[2]) / 2.0, ddy = (t[1] + t[3]) / 2.0 - (p[1] + p[3]) / 2.0;
+    const double penalty = (ddx * ddx + ddy * ddy) / diagonal;
+    if (kind == 4) return 1.0 - iou + penalty;
+    const double w1 = p[2] - p[0], h1 = p[3] - p[1], w2 = t[2] - t[0], h2 = t[3] - t[1];
+    const double angle = (atan(w1 / (h1 + eps)) - atan(w2 / (h2 + eps))) * 2.0 / 3.141592653589793;
+    const double v = angle * angle;
+    const double alpha = v / (1.0 - iou + v + eps);
+    return 1.0 - iou + penalty + alpha * v;
+}
+
+__global__ __launch_bounds__(THREADS) void sample_kernel(const float* __restrict__ box, long sn, long sc, long sh, long sw,
+                                                         const double* __restrict__ gt_boxes, const int* __restrict__ count,
+                                                         const Rec* __restrict__ rec, int Gmax, int H, int W, int kind, int box_log, float mult,
+                                                         float stride, double* __restrict__ img) {
+    __shared__ double s_part[WAVES];
+    const int n = blockIdx.x, tid = threadIdx.x;
+    const int M = min(max(count[n], 0), Gmax);
+    double sum = 0.0, dets = 0.0, samples = 0.0, skipped = 0.0;      // (counts below 2^53: exact)
+    for (int s = tid; s < M; s += THREADS) {
+        const Rec r = rec[(long)n * Gmax + s];
+        if (r.state == 0) { skipped += 1.0; continue; }
+        dets += 1.0;
+        const double* const b = gt_boxes + ((long)n * Gmax + s) * 4;
+        const float target[4] = {(float)b[0], (float)b[1], (float)(b[0] + b[2]), (float)(b[1] + b[3])};
+        for (int X = r.cx - 1; X <= r.cx + 1; ++X) {          // itertools.product(cxs, cys): x outer
+            if (X < 0 || X > W - 1) continue;
+            for (int Y = r.cy - 1; Y <= r.cy + 1; ++Y) {
+                if (Y < 0 || Y > H - 1) continue;
+                samples += 1.0;
+                if (box) {
+                    float pred[4];
+                    cnl::decode_box(box + (long)n * sn + (long)Y * sh + (long)X * sw, sc, X, Y, W, H, 0, box_log, mult, stride, pred);
+                    sum += box_term(kind, pred, target);
+                }
+            }
+        }
+    }
+    sum = block_sum_fixed(sum, s_part);
+    dets = block_sum_fixed(dets, s_part);
+    samples = block_sum_fixed(samples, s_part);
+    skipped = block_sum_fixed(skipped, s_part);
+    if (tid == 0) {
+        double* const o = img + (long)n * 4;
+        o[0] = sum; o[1] = dets; o[2] = samples; o[3] = skipped;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- finish
+__global__ __launch_bounds__(THREADS) void finish_kernel(const double* __restrict__ part, const double* __restrict__ img, int N, int tiles,
+                                                         double w_heat, double w_box, double* __restrict__ per_image,
+                                                         double* __restrict__ totals, int* __restrict__ skipped) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    for (int n = wave; n < N; n += WAVES) {
+        double s = 0.0;
+        for (int i = lane; i < tiles; i += 64) s += part[(long)n * tiles + i];      // a lane's stripe in index order
+        s = wave_sum_fixed(s);
+        if (lane == 0) {
+            double* const row = per_image + (long)n * 4;
+            row[0] = s; row[1] = img[(long)n * 4]; row[2] = img[(long)n * 4 + 1]; row[3] = img[(long)n * 4 + 2];
+        }
+    }
+    __threadfence_block();
+    __syncthreads();
+    if (tid == 0) {
+        double heat = 0.0, box = 0.0, dets = 0.0, samples = 0.0, skip = 0.0;
+        for (int n = 0; n < N; ++n) {                         // image order
+            const volatile double* const row = per_image + (long)n * 4;
+            heat += row[0]; box += row[1]; dets += row[2]; samples += row[3];
+            skip += img[(long)n * 4 + 3];
+        }
+        const double h = heat / fmax(1.0, dets), b = box / fmax(1.0, samples);
+        totals[0] = h; totals[1] = b; totals[2] = h * w_heat + b * w_box;
+        skipped[0] = (int)skip;
+    }
+}
+
+}  // namespace cnl_det_loss
+
+extern "C" size_t cnl_detection_loss_workspace_bytes(int32_t N, int32_t Gmax, int32_t H, int32_t W) {
+    using namespace cnl_det_loss;
+    if (N < 0 || N > (1 << 16) || Gmax < 1 || Gmax > MAX_G || H < 1 || H > (1 << 15) || W < 1 || W > (1 << 15)) return 0;
+    return sections(N, Gmax, H, W).total;
+}
+
+extern "C" int cnl_detection_loss_f64(const float* heat, int64_t heat_sn, int64_t heat_sc, int64_t heat_sh, int64_t heat_sw, const float* box,
+                                      int64_t box_sn, int64_t box_sc, int64_t box_sh, int64_t box_sw, int32_t N, int32_t C, int32_t H, int32_t W,
+                                      const double* gt_boxes, const int64_t* gt_labels, const int32_t* gt_count, int32_t Gmax,
+                                      const cnl_loss_params* p, float* target_map, int64_t t_sn, int64_t t_sc, int64_t t_sh, int64_t t_sw,
+                                      double* per_image, double* totals, int32_t* skipped, void* workspace, size_t workspace_bytes, void* stream) {
+    using namespace cnl_det_loss;
+    CNL_REQUIRE(p, CNL_E_BAD_ARG, "cnl_detection_loss_f64: null params");
+    CNL_REQUIRE(N >= 0 && N <= (1 << 16), CNL_E_BAD_ARG, "cnl_detection_loss_f64: N = %d outside 0..2^16", N);
+    CNL_REQUIRE(C >= 1 && C <= (1 << 16), CNL_E_BAD_ARG, "cnl_detection_loss_f64: C = %d outside 1..2^16", C);
+    CNL_REQUIRE(H >= 1 && H <= (1 << 15) && W >= 1 && W <= (1 << 15), CNL_E_BAD_ARG, "cnl_detection_loss_f64: H x W = %d x %d outside 1..2^15", H, W);
+    CNL_REQUIRE(Gmax >= 1 && Gmax <= MAX_G, CNL_E_BAD_ARG, "cnl_detection_loss_f64: Gmax = %d outside 1..%d", Gmax, MAX_G);
+    CNL_REQUIRE(p->target_method >= 0 && p->target_method <= 2, CNL_E_BAD_ARG, "cnl_detection_loss_f64: target_method = %d outside 0..2", p->target_method);
+    CNL_REQUIRE(p->heatmap_loss >= 0 && p->heatmap_loss <= 1, CNL_E_BAD_ARG, "cnl_detection_loss_f64: heatmap_loss = %d outside 0..1", p->heatmap_loss);
+    CNL_REQUIRE(p->box_loss >= 0 && p->box_loss <= 5, CNL_E_BAD_ARG, "cnl_detection_loss_f64: box_loss = %d outside 0..5", p->box_loss);
+    CNL_REQUIRE(p->stride > 0.0 && p->stride < 1e6, CNL_E_BAD_ARG, "cnl_detection_loss_f64: stride = %g must be positive", p->stride);
+    CNL_REQUIRE(p->target_method != 0 || (p->target_param > 0.0 && p->target_param < 1.0), CNL_E_BAD_ARG,
+                "cnl_detection_loss_f64: cornernet min_overlap = %g outside (0, 1)", p->target_param);
+    CNL_REQUIRE(p->target_param == p->target_param && p->hm_alpha == p->hm_alpha && p->hm_beta == p->hm_beta, CNL_E_BAD_ARG,
+                "cnl_detection_loss_f64: a NaN parameter");
+    CNL_REQUIRE((heat != nullptr) == (box != nullptr), CNL_E_BAD_ARG, "cnl_detection_loss_f64: heat and box come together (both NULL: targets only)");
+    CNL_REQUIRE(heat || target_map, CNL_E_BAD_ARG, "cnl_detection_loss_f64: neither logits nor a target map: nothing to do");
+    if (N == 0) return CNL_OK;
+    CNL_REQUIRE(gt_boxes && gt_labels && gt_count && per_image && totals && skipped && workspace, CNL_E_BAD_ARG, "cnl_detection_loss_f64: null pointer");
+    CNL_REQUIRE((((uintptr_t)gt_boxes | (uintptr_t)gt_labels | (uintptr_t)per_image | (uintptr_t)totals) & 7) == 0 && ((uintptr_t)workspace & 15) == 0 &&
+                    (((uintptr_t)heat | (uintptr_t)box | (uintptr_t)target_map | (uintptr_t)gt_count | (uintptr_t)skipped) & 3) == 0, CNL_E_BAD_ARG,
+                "cnl_detection_loss_f64: the float64 / int64 arrays must be 8-byte aligned, the workspace 16-byte aligned, the rest 4-byte aligned");
+    const Sections sec = sections(N, Gmax, H, W);
+    CNL_REQUIRE(workspace_bytes >= sec.total, CNL_E_WORKSPACE, "cnl_detection_loss_f64: workspace of %zu bytes, %zu needed", workspace_bytes, sec.total);
+    const int tiles = tiles_x(W) * tiles_y(H);
+    CNL_REQUIRE((long long)N * tiles < (1ll << 31), CNL_E_UNSUPPORTED, "cnl_detection_loss_f64: %d images x %d tiles exceed the grid", N, tiles);
+    char* const ws = static_cast<char*>(workspace);
+    Rec* const rec = reinterpret_cast<Rec*>(ws + sec.rec);
+    double* const part = reinterpret_cast<double*>(ws + sec.part);
+    double* const img = reinterpret_cast<double*>(ws + sec.img);
+    hipStream_t st = (hipStream_t)stream;
+
+    const long slots = (long)N * Gmax;
+    hipLaunchKernelGGL(record_kernel, dim3((unsigned)((slots + THREADS - 1) / THREADS)), dim3(THREADS), 0, st, gt_boxes,
+                       reinterpret_cast<const long long*>(gt_labels), gt_count, N, Gmax, C, H, W, p->stride, p->target_method, p->target_param, rec);
+    if (int rc = cnl::check_launch("det_loss record_kernel")) return rc;
+
+    HeatArgs a;
+    a.heat = heat; a.sn = heat_sn; a.sc = heat_sc; a.sh = heat_sh; a.sw = heat_sw;
+    a.tmap = target_map; a.tn = t_sn; a.tc = t_sc; a.th = t_sh; a.tw = t_sw;
+    a.rec = rec; a.count = gt_count; a.part = part;
+    a.C = C; a.H = H; a.W = W; a.Gmax = Gmax; a.tx = tiles_x(W);
+    a.loss = p->heatmap_loss; a.alpha = p->hm_alpha; a.beta = p->hm_beta;
+    a.alpha_is_2 = p->hm_alpha == 2.0; a.beta_is_4 = p->hm_beta == 4.0; a.beta_is_2 = p->hm_beta == 2.0;
+    const dim3 grid((unsigned)(N * tiles));
+    // with logits their layout picks the element order; a targets-only launch follows the target map's
+    const int64_t l_sc = heat ? heat_sc : t_sc, l_sw = heat ? heat_sw : t_sw;
+    if (l_sc == 1) hipLaunchKernelGGL(heatmap_kernel<LAYOUT_CMINOR>, grid, dim3(THREADS), 0, st, a);
+    else if (l_sw == 1 && heat) hipLaunchKernelGGL(heatmap_kernel<LAYOUT_PLANE>, grid, dim3(THREADS), 0, st, a);
+    else hipLaunchKernelGGL(heatmap_kernel<LAYOUT_GENERIC>, grid, dim3(THREADS), 0, st, a);
+    if (int rc = cnl::check_launch("det_loss heatmap_kernel")) return rc;
+
+    hipLaunchKernelGGL(sample_kernel, dim3((unsigned)N), dim3(THREADS), 0, st, box, (long)box_sn, (long)box_sc, (long)box_sh, (long)box_sw, gt_boxes,
+                       gt_count, rec, Gmax, H, W, p->box_loss, p->box_log, p->box_multiplier, (float)p->stride, img);
+    if (int rc = cnl::check_launch("det_loss sample_kernel")) return rc;
+
+    hipLaunchKernelGGL(finish_kernel, dim3(1), dim3(THREADS), 0, st, part, img, N, tiles, p->heatmap_weight, p->box_weight, per_image, totals, skipped);
+    return cnl::check_launch("det_loss finish_kernel");
+}

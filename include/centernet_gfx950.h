@@ -1008,8 +1008,67 @@ int cnl_track_streams_f32(const float* det_emb, const float* det_box, const floa
  */
 int cnl_boxes_xyxy_to_xywh_f32(const float* boxes, float* out, int64_t n, void* stream);
 
+/*
+ * The validation value of the detection losses (reference models/centernet.py:123-200 compute_loss / update_heatmap, losses/heatmap_losses.py,
+ * losses/box_losses.py; csrc/det_loss.hip): Gaussian target heatmap, heatmap loss and the 3x3 centre-sampled box loss of a batch in one call.
+ * Forward value only (validation curves, checkpoint selection, regression checks of converted weights): no gradient, no reid loss.  Every step the
+ * reference does on the host in float64 is float64 here; det_loss.hip is compiled with contraction off.  tests/loss_ref.py restates the rule in numpy.
+ *
+ * Targets: gt_boxes [N, Gmax, 4] float64 x y w h in INPUT pixels, gt_labels [N, Gmax] int64, gt_count [N] int32 (clamped to 0..Gmax), Gmax <= 1024.
+ * Slots at or beyond gt_count[n] are never read.
+ * Record of a box, float64:  b = box / stride;  cx = rint(b.x + b.w / 2), cy likewise (ties to even: numpy's round);
+ *   radius by target_method:  0 "cornernet": the three quadratics of centernet.py:38-58 with min_overlap = target_param (0 < . < 1), r = min(r1, r2, r3),
+ *   rx = ry = r;  1 "ttfnet": rx = b.w / 2 * target_param, ry = b.h / 2 * target_param;  2 "fixed": rx = ry = target_param;
+ *   then rx = max(0, rint(rx)), ry likewise;  sx = rx / 3 + 1 / 6, sy likewise.
+ * A box is SKIPPED whole (nothing rendered, nothing counted, no samples; it adds one to skipped[0]) when one of its numbers or radii is not finite, when
+ * w < 0 or h < 0, when its centre lies outside 0 <= cx <= W, 0 <= cy <= H, or when its label lies outside 0 .. C-1.
+ * Target value of class `label` at (x, y), 0 <= x < W, 0 <= y < H, |x - cx| <= rx, |y - cy| <= ry (a centre ON cx == W or cy == H has no peak inside the
+ * map but renders the part of its window that is inside, as the reference's slices do; it is counted and has its samples):
+ *   g = fl32(fl32(dx dx) / fl32(2 sx sx)) + fl32(fl32(dy dy) / fl32(2 sy sy)) added in fp32;  t = fl32(exp(-(double)g));  t = 0 where t < FLT_EPSILON;
+ * the target of an element is the maximum over the image's boxes of that class, 0 where no window reaches it; a peak inside the map is exactly 1.0f.
+ * Heatmap loss per element, float64, x the fp32 logit and t the fp32 target widened; p = 1 / (1 + exp(-x)), logsigmoid(x) = min(x, 0) - log1p(exp(-|x|)):
+ *   heatmap_loss 0 "cornernet_focal":  -(1 - p)^hm_alpha logsigmoid(x) [t == 1]  -  p^hm_alpha logsigmoid(-x) (1 - t)^hm_beta     (defaults 2, 4)
+ *   heatmap_loss 1 "quality":          |t - p|^hm_beta (max(x, 0) - x t + log1p(exp(-|x|)))                                         (default 2)
+ * (exponents 2 and 4 are formed by multiplication).
+ * Box loss: every counted box has the samples {cx-1, cx, cx+1} within [0, W-1] x {cy-1, cy, cy+1} within [0, H-1], cx outer.  At a sample the four
+ * box_2d values are decoded by the decode's own fp32 rule (cnl_decode_f32 with normalize_boxes = 0: box_log, box_multiplier, clamp at 0, cx + 0.5,
+ * times stride — the same device function); the target is (fl32(x), fl32(y), fl32(x + w), fl32(y + h)), the sums formed in float64.  The loss per
+ * sample is float64 on those fp32 values: box_loss 0 "l1", 1 "smooth_l1" (beta 1), 2 "iou", 3 "giou", 4 "diou", 5 "ciou", as losses/box_losses.py
+ * with eps = 1e-8, summed.
+ * Results: per_image [N, 4] float64 rows (heatmap_sum, box_sum, num_dets, num_boxes);  totals [3] float64:
+ *   heatmap = sum(heatmap_sum) / max(1, sum(num_dets)),  box_2d = sum(box_sum) / max(1, sum(num_boxes)),  total = heatmap heatmap_weight + box_2d box_weight;
+ * skipped [1] int32.  Every summation order is fixed (within a workgroup, over the workgroups of an image, over the images in index order; no
+ * floating-point atomics): a result is the same bits on every run, and an image's row does not depend on which other images share the launch.
+ * (The order within an image follows the layout path the heatmap's strides select: channel stride 1, W stride 1, or neither.)
+ *
+ * heat [N, C, H, W] logits and box [N, 4, H, W], fp32, each with the element strides of its logical axes (n, c, y, x), as the decode takes them.
+ * Both NULL with a target map: the targets are rendered and counted, the sums are 0.  target_map: NULL (never written), or fp32 [N, C, H, W] with its own
+ * strides: every element receives its target.  The workspace holds at least cnl_detection_loss_workspace_bytes(N, Gmax, H, W) bytes and is 16-byte
+ * aligned; float64 / int64 arrays are 8-byte aligned.  Four launches on `stream`, no synchronisation, no allocation.  N <= 2^16, C <= 2^16,
+ * H, W <= 2^15 (the workspace size is 0 outside these limits).  The struct's size is cnl_sizeof_params(4).
+ */
+typedef struct cnl_loss_params {
+    double stride;             /* output stride of the maps (boxes are divided by it) */
+    double target_param;       /* min_overlap / alpha / r of the target method */
+    double hm_alpha, hm_beta;  /* exponents of the heatmap loss (quality reads hm_beta only) */
+    double heatmap_weight, box_weight;
+    float box_multiplier;
+    int32_t target_method;     /* 0 cornernet, 1 ttfnet, 2 fixed */
+    int32_t heatmap_loss;      /* 0 cornernet_focal, 1 quality */
+    int32_t box_loss;          /* 0 l1, 1 smooth_l1, 2 iou, 3 giou, 4 diou, 5 ciou */
+    int32_t box_log;
+    int32_t reserved;          /* 0 */
+} cnl_loss_params;
+size_t cnl_detection_loss_workspace_bytes(int32_t N, int32_t Gmax, int32_t H, int32_t W);
+int cnl_detection_loss_f64(const float* heat, int64_t heat_sn, int64_t heat_sc, int64_t heat_sh, int64_t heat_sw, const float* box, int64_t box_sn,
+                           int64_t box_sc, int64_t box_sh, int64_t box_sw, int32_t N, int32_t C, int32_t H, int32_t W, const double* gt_boxes,
+                           const int64_t* gt_labels, const int32_t* gt_count, int32_t Gmax, const cnl_loss_params* p, float* target_map, int64_t t_sn,
+                           int64_t t_sc, int64_t t_sh, int64_t t_sw, double* per_image, double* totals, int32_t* skipped, void* workspace,
+                           size_t workspace_bytes, void* stream);
+
 int cnl_version(void);
-/* sizeof(cnl_conv_params) / sizeof(cnl_decode_params) / sizeof(cnl_deconv_params) (which = 0 / 1 / 2; else 0) as the library was compiled — the structs grow at the end between ABI
+/* sizeof(cnl_conv_params) / sizeof(cnl_decode_params) / sizeof(cnl_deconv_params) (which = 0 / 1 / 2) and sizeof(cnl_loss_params) (which = 4; 3 is
+ * unused; else 0) as the library was compiled — the structs grow at the end between ABI
  * versions: a binder (ctypes, cgo, JNI ...) compares its own struct's size before the first call (ABI v12). */
 size_t cnl_sizeof_params(int32_t which);
 /* Copies the calling thread's last error message (NUL-terminated) into buf; returns its length. */
