@@ -161,6 +161,11 @@ _SIGNATURES = {
                                               c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int32, POINTER(LossParams),
                                               c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
                                               c_void_p]),
+    "cnl_detection_loss_grad_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32]),
+    "cnl_detection_loss_grad_f32": (ctypes.c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int64,
+                                                   c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int32, POINTER(LossParams),
+                                                   c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64,
+                                                   c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
     "cnl_stem_conv7x7_u8": (ctypes.c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, POINTER(c_float), POINTER(c_float), c_void_p, c_void_p,
                                            c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "cnl_stem_packed_weight_floats": (c_size_t, []),

@@ -4,8 +4,13 @@ without the logits leaving the device.
 
 detection_loss() is ONE call of cnl_detection_loss_f64 (csrc/det_loss.hip: four launches, the logits read once); render_targets() runs the same
 kernel for the target heatmap alone; LossMeter accumulates the per-batch values on the device as Lightning's self.log averaging would.  The
-rule is stated in include/centernet_gfx950.h and restated in numpy in tests/loss_ref.py.  Forward value only: no gradient, no reid loss (the
-reference leaves it out at validation, fairmot.py:87-91).  No CPU fallback: a missing device or library raises.
+rule is stated in include/centernet_gfx950.h and restated in numpy in tests/loss_ref.py.
+
+detection_loss_grad() is ONE call of cnl_detection_loss_grad_f32 (at most four launches): the analytic gradient of that value with respect to the
+logits and the box values (tests/loss_grad_ref.py).  DetectionLoss is the criterion training calls: an nn.Module whose "heatmap", "box_2d" and
+"total" carry a grad_fn, so criterion(outputs, targets)["total"].backward() works on the head outputs of any torch model on the device.  fp32 inputs
+only, no double backward, no backward through the conv engine, no reid loss (the reference leaves it out at validation, fairmot.py:87-91).
+No CPU fallback: a missing device or library raises.
 """
 import ctypes
 import math
@@ -155,6 +160,20 @@ def _check_sizes(N, C, H, W, what):
         raise ValueError(f"{what}: N x C x H x W = {N} x {C} x {H} x {W} outside 0..{MAX_IMAGES} x 1..{MAX_CLASSES} x 1..{MAX_SIDE} x 1..{MAX_SIDE}")
 
 
+def _check_outputs(heatmap, box_2d, what):
+    """The head outputs of one call -> (N, C, H, W)"""
+    _check_map(heatmap, "heatmap", "C", what)
+    _check_map(box_2d, "box_2d", 4, what)
+    N, C, H, W = (int(v) for v in heatmap.shape)
+    if tuple(box_2d.shape) != (N, 4, H, W):
+        raise ValueError(f"{what}: heatmap {tuple(heatmap.shape)} needs box_2d [{N}, 4, {H}, {W}], got {tuple(box_2d.shape)}")
+    _check_sizes(N, C, H, W, what)
+    _gather.require_hip([heatmap, box_2d], what)
+    if box_2d.device != heatmap.device:
+        raise ValueError(f"{what}: heatmap on {heatmap.device}, box_2d on {box_2d.device}")
+    return N, C, H, W
+
+
 def _run(heatmap, box_2d, targets, shape, params, want_targets, dev, what):
     """The one call.  heatmap / box_2d None: targets only.  -> (out [N*4 + 3] f64, skipped [1] i32, target map or None)."""
     N, C, H, W = shape
@@ -200,20 +219,157 @@ def detection_loss(heatmap, box_2d, targets, stride=4, heatmap_target="cornernet
     what = "detection_loss"
     params = loss_params(stride, heatmap_target, heatmap_target_params, heatmap_loss, box_loss, heatmap_loss_weight, box_loss_weight, box_log,
                          box_multiplier, what)
-    _check_map(heatmap, "heatmap", "C", what)
-    _check_map(box_2d, "box_2d", 4, what)
-    N, C, H, W = (int(v) for v in heatmap.shape)
-    if tuple(box_2d.shape) != (N, 4, H, W):
-        raise ValueError(f"{what}: heatmap {tuple(heatmap.shape)} needs box_2d [{N}, 4, {H}, {W}], got {tuple(box_2d.shape)}")
-    _check_sizes(N, C, H, W, what)
-    _gather.require_hip([heatmap, box_2d], what)
-    if box_2d.device != heatmap.device:
-        raise ValueError(f"{what}: heatmap on {heatmap.device}, box_2d on {box_2d.device}")
+    N, C, H, W = _check_outputs(heatmap, box_2d, what)
     out, skipped, tmap = _run(heatmap, box_2d, targets, (N, C, H, W), params, bool(return_targets), heatmap.device, what)
     res = {"heatmap": out[4 * N], "box_2d": out[4 * N + 1], "total": out[4 * N + 2], "per_image": out[:4 * N].view(N, 4), "skipped": skipped[0]}
     if return_targets:
         res["targets"] = tmap
     return res
+
+
+WANT = ("heatmap", "box_2d")
+
+
+def _device_targets(targets, shape, stride, dev, what):
+    """targets in either form -> the padded (boxes, labels, count) device tensors of one call; a host list is checked, padded and uploaded in one copy."""
+    N, C, H, W = shape
+    g_dev, gts, _ = _targets(targets, N, C, H, W, stride, what)
+    if g_dev is not None and g_dev != dev:
+        raise ValueError(f"{what}: outputs on {dev}, targets on {g_dev}")
+    if g_dev is None:
+        with torch.cuda.device(dev):
+            gts = [torch.from_numpy(a).to(dev) for a in gts] if N == 0 else _upload(list(gts), dev)      # (an empty batch: nothing to stage)
+    return tuple(gts)
+
+
+def _scale(value, name, dev, what):
+    """A Python number, or a 0-dim / 1-element float64 tensor on the device -> a number or a 0-dim float64 device tensor"""
+    if isinstance(value, torch.Tensor):
+        if value.dtype != torch.float64 or value.numel() != 1:
+            raise ValueError(f"{what}: {name} as a tensor must be float64 with one element, got {value.dtype} {tuple(value.shape)}")
+        if value.device != dev:
+            raise ValueError(f"{what}: {name} on {value.device}, outputs on {dev}")
+        return value.detach().reshape(())
+    return _number(value, name, what)
+
+
+def _like(t):
+    """An uninitialised tensor of t's shape: t's strides when t is dense (contiguous or channels-last), else contiguous."""
+    if t.is_contiguous() or t.is_contiguous(memory_format=torch.channels_last):
+        return torch.empty_strided(tuple(t.shape), t.stride(), dtype=t.dtype, device=t.device)
+    return torch.empty(tuple(t.shape), dtype=t.dtype, device=t.device)
+
+
+def _run_grad(heatmap, box_2d, gts, shape, params, scales, want):
+    """The one call.  gts: padded device targets; scales: None (1, 1) or a float64 device tensor [2]; want: (heatmap?, box_2d?).
+    -> (heatmap gradient or None, box_2d gradient or None, skipped [1] i32)"""
+    N, C, H, W = shape
+    dev = heatmap.device
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        gh = _like(heatmap) if want[0] else None
+        gb = _like(box_2d) if want[1] else None
+        skipped = torch.zeros((1,), dtype=torch.int32, device=dev)
+        if N == 0:
+            return gh, gb, skipped
+        Gmax = int(gts[0].shape[1])
+        nbytes = lib.cnl_detection_loss_grad_workspace_bytes(N, Gmax, H, W)
+        ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=dev)
+        _lib.check(lib.cnl_detection_loss_grad_f32(heatmap.data_ptr(), *heatmap.stride(), box_2d.data_ptr(), *box_2d.stride(), N, C, H, W,
+                                                   gts[0].data_ptr(), gts[1].data_ptr(), gts[2].data_ptr(), Gmax, ctypes.byref(params),
+                                                   None if scales is None else scales.data_ptr(),
+                                                   None if gh is None else gh.data_ptr(), *(gh.stride() if gh is not None else (0,) * 4),
+                                                   None if gb is None else gb.data_ptr(), *(gb.stride() if gb is not None else (0,) * 4),
+                                                   skipped.data_ptr(), ws.data_ptr(), nbytes,
+                                                   ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "cnl_detection_loss_grad_f32")
+    return gh, gb, skipped
+
+
+def detection_loss_grad(heatmap, box_2d, targets, stride=4, heatmap_target="cornernet", heatmap_target_params=None, heatmap_loss="cornernet_focal",
+                        box_loss="giou", heatmap_loss_weight=1.0, box_loss_weight=1.0, box_log=False, box_multiplier=1.0, heatmap_scale=1.0,
+                        box_scale=1.0, want=WANT):
+    """The gradient of heatmap_scale * res["heatmap"] + box_scale * res["box_2d"] (res = detection_loss(...) on the same arguments) with respect to
+    the fp32 logits and box values, analytic, float64 rounded once to fp32 (the rule: include/centernet_gfx950.h).  The two loss weights are NOT
+    applied: the gradient of "total" is the one with scales (heatmap_loss_weight, box_loss_weight).  Each scale is a Python number or a 0-dim /
+    1-element float64 tensor on the device (read there).  want: which gradients to compute, a subset of ("heatmap", "box_2d").
+    -> {"heatmap_grad", "box_2d_grad": fp32 of the input's shape (None when not wanted), with the input's strides when it is dense (contiguous or
+    channels-last), else contiguous; "skipped": 0-dim int32}.  One call of cnl_detection_loss_grad_f32, no synchronisation, no atomics: the same
+    bits on every run."""
+    what = "detection_loss_grad"
+    params = loss_params(stride, heatmap_target, heatmap_target_params, heatmap_loss, box_loss, heatmap_loss_weight, box_loss_weight, box_log,
+                         box_multiplier, what)
+    if isinstance(want, str) or not isinstance(want, (tuple, list)) or not want or any(w not in WANT for w in want) or len(set(want)) != len(want):
+        raise ValueError(f"{what}: want must be a non-empty tuple out of {WANT}, got {want!r}")
+    _check_map(heatmap, "heatmap", "C", what)
+    _check_map(box_2d, "box_2d", 4, what)
+    dev = heatmap.device
+    s_heat, s_box = _scale(heatmap_scale, "heatmap_scale", dev, what), _scale(box_scale, "box_scale", dev, what)
+    shape = _check_outputs(heatmap, box_2d, what)
+    gts = _device_targets(targets, shape, params.stride, dev, what)
+    scales = None
+    if isinstance(s_heat, torch.Tensor) or isinstance(s_box, torch.Tensor):
+        with torch.cuda.device(dev):
+            scales = torch.stack([v if isinstance(v, torch.Tensor) else torch.full((), v, dtype=torch.float64, device=dev) for v in (s_heat, s_box)])
+    elif (s_heat, s_box) != (1.0, 1.0):
+        with torch.cuda.device(dev):
+            (scales,) = _upload([np.array([s_heat, s_box], dtype=np.float64)], dev)
+    gh, gb, skipped = _run_grad(heatmap.detach(), box_2d.detach(), gts, shape, params, scales, ("heatmap" in want, "box_2d" in want))
+    return {"heatmap_grad": gh, "box_2d_grad": gb, "skipped": skipped[0]}
+
+
+class _DetectionLossFunction(torch.autograd.Function):
+    """detection_loss with the backward of cnl_detection_loss_grad_f32: one call forward, one call backward."""
+
+    @staticmethod
+    def forward(ctx, heatmap, box_2d, targets, settings):
+        what = "DetectionLoss"
+        params = loss_params(what=what, **settings)
+        shape = _check_outputs(heatmap, box_2d, what)
+        gts = _device_targets(targets, shape, params.stride, heatmap.device, what)          # a host list: padded and uploaded once, kept for the backward
+        out, skipped, _ = _run(heatmap, box_2d, gts, shape, params, False, heatmap.device, what)
+        N = shape[0]
+        ctx.save_for_backward(heatmap, box_2d, *gts)
+        ctx.params, ctx.shape = params, shape
+        per_image, skip = out[:4 * N].view(N, 4), skipped[0]
+        ctx.mark_non_differentiable(per_image, skip)
+        return out[4 * N], out[4 * N + 1], out[4 * N + 2], per_image, skip
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_heatmap, g_box_2d, g_total, _g_rows, _g_skipped):
+        heatmap, box_2d, *gts = ctx.saved_tensors
+        p = ctx.params
+        scales = torch.stack([g_heatmap + g_total * p.heatmap_weight, g_box_2d + g_total * p.box_weight]).to(torch.float64)      # on the device: no synchronisation
+        gh, gb, _ = _run_grad(heatmap, box_2d, tuple(gts), ctx.shape, p, scales, (ctx.needs_input_grad[0], ctx.needs_input_grad[1]))
+        return gh, gb, None, None
+
+
+class DetectionLoss(torch.nn.Module):
+    """The criterion of a training step: DetectionLoss(**settings)(outputs, targets) -> the dict detection_loss returns, bit for bit, where "heatmap",
+    "box_2d" and "total" carry a grad_fn when an output requires grad: criterion(outputs, targets)["total"].backward() reaches the head that produced
+    `outputs` (any torch model on the device).  outputs: the dict of get_encoded_outputs ("heatmap" LOGITS, "box_2d"), fp32; targets as for
+    detection_loss (a host list is padded and uploaded once, and kept for the backward).  `settings`: detection_loss's keyword arguments
+    (model.criterion() fills them from the model).  "per_image" and "skipped" are not differentiable; no double backward.  Under torch.no_grad(),
+    or when no output requires grad, it is detection_loss."""
+
+    def __init__(self, **settings):
+        super().__init__()
+        settings.pop("return_targets", None)
+        loss_params(what="DetectionLoss", **settings)
+        self.settings = settings
+
+    def extra_repr(self):
+        return ", ".join(f"{k}={v!r}" for k, v in self.settings.items())
+
+    def forward(self, outputs, targets):
+        if not isinstance(outputs, dict) or "heatmap" not in outputs or "box_2d" not in outputs:
+            raise ValueError("DetectionLoss: outputs must be the dict of get_encoded_outputs with 'heatmap' and 'box_2d'")
+        heatmap, box_2d = outputs["heatmap"], outputs["box_2d"]
+        needs = torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (heatmap, box_2d))
+        if not needs:
+            return detection_loss(heatmap, box_2d, targets, **self.settings)
+        heat, box, total, per_image, skipped = _DetectionLossFunction.apply(heatmap, box_2d, targets, self.settings)
+        return {"heatmap": heat, "box_2d": box, "total": total, "per_image": per_image, "skipped": skipped}
 
 
 def render_targets(targets, num_classes, height, width, stride=4, heatmap_target="cornernet", heatmap_target_params=None, device=None):

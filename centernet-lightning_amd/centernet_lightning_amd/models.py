@@ -379,6 +379,10 @@ class CenterNet(nn.Module):
         """A LossMeter with this model's loss settings: update(outputs, targets) per batch, get_metrics() at the end of the epoch (loss.py)."""
         return _loss.LossMeter(**self._loss_kwargs(None))
 
+    def criterion(self):
+        """A DetectionLoss with this model's loss settings: criterion(outputs, targets)["total"].backward() for a training step (loss.py)."""
+        return _loss.DetectionLoss(**self._loss_kwargs(None))
+
     def _loss_kwargs(self, stride):
         return dict(self.loss_settings, stride=self.stride if stride is None else stride, box_log=self.box_log, box_multiplier=self.box_multiplier)
 

@@ -1,7 +1,8 @@
 // det_loss.hip — the validation value of the detection losses (reference models/centernet.py:123-200 compute_loss / update_heatmap,
 // losses/heatmap_losses.py, losses/box_losses.py) on the device: Gaussian targets, heatmap loss and the 3x3 centre-sampled box loss of a
 // batch in four launches, the logits read once, no N x C x H x W target tensor unless the caller asks for it.  The rule is stated in
-// include/centernet_gfx950.h and restated in numpy in tests/loss_ref.py.  Forward value only: nothing here computes a gradient.
+// include/centernet_gfx950.h and restated in numpy in tests/loss_ref.py.  The gradient of that value with respect to the logits and the box_2d
+// values (cnl_detection_loss_grad_f32, the second half of this file; tests/loss_grad_ref.py) is analytic: no reid loss, no double backward.
 //
 //   record_kernel    one thread per target slot: box -> (cx, cy, rx, ry, the two fp32 Gaussian denominators, label, state), all float64
 //                    as the reference's host code computes them.  Slots at or beyond count[n] are never read.
@@ -358,6 +359,331 @@ __global__ __launch_bounds__(THREADS) void finish_kernel(const double* __restric
 
 }  // namespace cnl_det_loss
 
+// ================================================================================================================ gradient
+// cnl_detection_loss_grad_f32: d(s_heat heatmap_loss + s_box box_2d_loss) / d(logits, box_2d), the rule of include/centernet_gfx950.h.
+//   record_kernel        as above.
+//   count_kernel         one workgroup: num_dets, num_boxes and skipped of the BATCH (integers: exact in any order), which both gradients divide by.
+//   heat_grad_kernel     the hot path: the forward's tile ownership, staging and register targets; every element's derivative in float64, rounded
+//                        once, no reduction.  The element order follows the GRADIENT's strides (the write stream): channel stride 1 (and, where
+//                        both maps are packed channels-last and 16-byte aligned, four consecutive elements of a tile row per lane: one 16-byte
+//                        load and one 16-byte store), W stride 1, or the plane order with free strides.  The logits are read by their own strides.
+//   box_grad_kernel      a workgroup per 8 x 32 pixel tile of one image, a thread per pixel: the image's counted records whose 3 x 3 sample
+//                        neighbourhood touches the tile are compacted into LDS in slot order with their slot; a thread adds the contribution of
+//                        every staged record that samples its pixel, in slot order, and stores its four values once (0 where none does).
+namespace cnl_det_loss {
+
+constexpr size_t COUNT_BYTES = 16;                 // num_dets, num_boxes (float64)
+
+inline size_t grad_sections_total(int N, int Gmax) { return (size_t)N * Gmax * sizeof(Rec) + COUNT_BYTES; }
+
+__global__ __launch_bounds__(THREADS) void count_kernel(const Rec* __restrict__ rec, const int* __restrict__ count, int N, int Gmax, int H, int W,
+                                                        double* __restrict__ counts, int* __restrict__ skipped) {
+    __shared__ double s_part[WAVES];
+    double dets = 0.0, samples = 0.0, skip = 0.0;             // (integers below 2^53: exact, the order does not matter)
+    const long slots = (long)N * Gmax;
+    for (long i = threadIdx.x; i < slots; i += THREADS) {
+        const int n = (int)(i / Gmax), s = (int)(i - (long)n * Gmax);
+        if (s >= min(max(count[n], 0), Gmax)) continue;
+        const Rec r = rec[i];
+        if (r.state == 0) { skip += 1.0; continue; }
+        dets += 1.0;
+        const int nx = min(r.cx + 1, W - 1) - max(r.cx - 1, 0) + 1, ny = min(r.cy + 1, H - 1) - max(r.cy - 1, 0) + 1;
+        samples += (double)(nx * ny);
+    }
+    dets = block_sum_fixed(dets, s_part);
+    samples = block_sum_fixed(samples, s_part);
+    skip = block_sum_fixed(skip, s_part);
+    if (threadIdx.x == 0) { counts[0] = dets; counts[1] = samples; skipped[0] = (int)skip; }
+}
+
+struct HeatGradArgs {
+    const float* heat; long sn, sc, sh, sw;
+    float* grad; long gn, gc, gh, gw;
+    const Rec* rec;
+    const int* count;
+    const double* counts;                          // num_dets, num_boxes
+    const double* scales;                          // s_heat, s_box; NULL: 1, 1
+    int C, H, W, Gmax, tx;
+    int loss;
+    int alpha_is_2, beta_is_4, beta_is_2;
+    double alpha, beta;
+};
+
+// d(heat_term) / d(logit): p, logsigmoid and log1p(exp(-|x|)) formed as heat_term forms them; the target and the [t == 1] weight are constants
+__device__ __forceinline__ double heat_dterm(const HeatGradArgs& a, float logit, float t) {
+    const double x = (double)logit, td = (double)t;
+    const double e = exp(-fabs(x));
+    const double l1p = log1p(e);
+    const double inv = 1.0 / (1.0 + e);
+    const double p = x >= 0.0 ? inv : e * inv;
+    const double q = 1.0 - p, pq = p * q;                     // dp/dx = p (1 - p)
+    if (a.loss == 0) {
+        const double ls = fmin(x, 0.0) - l1p, lsn = fmin(-x, 0.0) - l1p;      // d ls/dx = 1 - p, d lsn/dx = -p
+        double pos = 0.0;
+        if (t == 1.f) {
+            const double dq = a.alpha_is_2 ? 2.0 * q : a.alpha * pow(q, a.alpha - 1.0);
+            pos = dq * pq * ls - pow_small(q, a.alpha, a.alpha_is_2, 0) * q;
+        }
+        const double dp = a.alpha_is_2 ? 2.0 * p : a.alpha * pow(p, a.alpha - 1.0);
+        const double neg = (pow_small(p, a.alpha, a.alpha_is_2, 0) * p - dp * pq * lsn) * pow_small(1.0 - td, a.beta, 0, a.beta_is_4);
+        return pos + neg;
+    }
+    const double d = td - p, ad = fabs(d);
+    if (d == 0.0) return 0.0;                                 // |t - p|^beta: derivative 0 at t == p
+    const double sg = d > 0.0 ? 1.0 : -1.0;
+    const double ce = fmax(x, 0.0) - x * td + l1p;            // d ce/dx = p - t
+    const double dm = a.beta_is_2 ? 2.0 * ad : a.beta * pow(ad, a.beta - 1.0);
+    return pow_small(ad, a.beta, a.beta_is_2, 0) * (p - td) - sg * (dm * pq) * ce;
+}
+
+// VEC4: LAYOUT_CMINOR with both maps packed channels-last (pixel stride C, everything else a multiple of 4 elements, 16-byte aligned bases)
+template <int LAYOUT, bool VEC4>
+__global__ __launch_bounds__(THREADS) void heat_grad_kernel(const HeatGradArgs a) {
+    constexpr int PER = VEC4 ? 4 : 1;
+    __shared__ Rec s_rec[PASS_SLOTS];
+    __shared__ int s_cnt[WAVES];
+    const int tid = threadIdx.x;
+    const int tiles = a.tx * tiles_y(a.H);
+    const int n = blockIdx.x / tiles, tile = blockIdx.x - n * tiles;
+    const int ty = tile / a.tx, txi = tile - ty * a.tx;
+    const int x0 = txi * TILE_W, y0 = ty * TILE_H, x1 = min(x0 + TILE_W, a.W), y1 = min(y0 + TILE_H, a.H);
+    const int M = min(max(a.count[n], 0), a.Gmax);
+    const Rec* const recs = a.rec + (long)n * a.Gmax;
+    const int passes = (M + PASS_SLOTS - 1) / PASS_SLOTS;
+    const long gw = LAYOUT == LAYOUT_PLANE ? 1 : a.gw, gc = LAYOUT == LAYOUT_CMINOR ? 1 : a.gc;
+    const float* const heat = a.heat + (long)n * a.sn;
+    float* const grad = a.grad + (long)n * a.gn;
+    const double scale = (a.scales ? a.scales[0] : 1.0) / fmax(1.0, a.counts[0]);
+
+    int cnt = passes == 1 ? stage(recs, 0, M, x0, y0, x1, y1, a.W, a.H, s_rec, s_cnt) : 0;
+    const unsigned row = (unsigned)TILE_W * (unsigned)a.C;                   // elements of a full tile row
+    const int steps = VEC4 ? (a.C + 3) / 4 : a.C;                            // the same in every thread: the barriers of a multi-pass step are uniform
+    for (int step = 0; step < steps; ++step) {
+        int x[PER], y, c[PER];
+        bool inside;
+        unsigned j0 = 0;
+        if (VEC4) {                                           // lanes along the 16-byte groups of a tile row, then along y
+            const unsigned g = (unsigned)step * THREADS + (unsigned)tid, per_row = row / 4;
+            const unsigned yy = g / per_row;
+            j0 = (g - yy * per_row) * 4;
+            y = y0 + (int)yy;
+            inside = yy < (unsigned)TILE_H && y < y1 && j0 < (unsigned)(x1 - x0) * (unsigned)a.C;
+#pragma unroll
+            for (int k = 0; k < PER; ++k) {
+                const unsigned xx = (j0 + k) / (unsigned)a.C;
+                x[k] = x0 + (int)xx; c[k] = (int)(j0 + k - xx * (unsigned)a.C);
+            }
+        } else if (LAYOUT == LAYOUT_CMINOR) {                 // lanes along the classes of a pixel, then along x
+            const unsigned e = (unsigned)step * THREADS + (unsigned)tid;
+            const unsigned yy = e / row, j = e - yy * row, xx = j / (unsigned)a.C;
+            y = y0 + (int)yy; x[0] = x0 + (int)xx; c[0] = (int)(j - xx * (unsigned)a.C);
+            inside = x[0] < x1 && y < y1;
+        } else {                                              // lanes along x, then y; one class per step
+            c[0] = step; y = y0 + tid / TILE_W; x[0] = x0 + tid % TILE_W;
+            inside = x[0] < x1 && y < y1;
+        }
+        float logit[PER], t[PER];
+#pragma unroll
+        for (int k = 0; k < PER; ++k) { logit[k] = 0.f; t[k] = 0.f; }
+        if (inside) {                                         // requested before the target's arithmetic
+            if (VEC4) {
+                const float4 v = *reinterpret_cast<const float4*>(heat + (long)y * a.sh + (long)x0 * a.C + (long)j0);
+                logit[0] = v.x; if (PER > 1) { logit[1 % PER] = v.y; logit[2 % PER] = v.z; logit[3 % PER] = v.w; }
+            } else {
+                logit[0] = heat[(long)c[0] * a.sc + (long)y * a.sh + (long)x[0] * a.sw];
+            }
+        }
+        if (passes <= 1) {
+            if (inside) {
+#pragma unroll
+                for (int k = 0; k < PER; ++k) t[k] = target_of(s_rec, cnt, x[k], y, c[k], 0.f);
+            }
+        } else {
+            for (int p = 0; p < passes; ++p) {
+                cnt = stage(recs, p * PASS_SLOTS, M, x0, y0, x1, y1, a.W, a.H, s_rec, s_cnt);
+                if (inside) {
+#pragma unroll
+                    for (int k = 0; k < PER; ++k) t[k] = target_of(s_rec, cnt, x[k], y, c[k], t[k]);
+                }
+            }
+        }
+        if (inside) {
+            float o[PER];
+#pragma unroll
+            for (int k = 0; k < PER; ++k) o[k] = (float)(scale * heat_dterm(a, logit[k], t[k]));
+            if (VEC4) {
+                float4 v;
+                v.x = o[0]; v.y = o[1 % PER]; v.z = o[2 % PER]; v.w = o[3 % PER];
+                *reinterpret_cast<float4*>(grad + (long)y * a.gh + (long)x0 * a.C + (long)j0) = v;
+            } else {
+                grad[(long)c[0] * gc + (long)y * a.gh + (long)x[0] * gw] = o[0];
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- box gradient
+// d max(a, b) / da and d min(a, b) / da as torch's autograd takes them: half on a tie
+__device__ __forceinline__ double d_max(double a, double b) { return a > b ? 1.0 : (a == b ? 0.5 : 0.0); }
+__device__ __forceinline__ double d_min(double a, double b) { return a < b ? 1.0 : (a == b ? 0.5 : 0.0); }
+
+// d(box_term) / d(pred): g <- the four derivatives, float64 on the fp32 boxes; non-differentiable points as torch's autograd takes them
+__device__ __forceinline__ void box_dterm(int kind, const float* pf, const float* tf, double* g) {
+    double p[4], t[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { p[j] = (double)pf[j]; t[j] = (double)tf[j]; }
+    if (kind <= 1) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const double d = p[j] - t[j];
+            const double sg = d > 0.0 ? 1.0 : (d < 0.0 ? -1.0 : 0.0);      // |d|: derivative 0 at 0
+            g[j] = kind == 0 ? sg : (fabs(d) < 1.0 ? d : sg);              // smooth_l1: the quadratic branch for |d| < 1
+        }
+        return;
+    }
+    const double eps = 1e-8;
+    const double w1 = p[2] - p[0], h1 = p[3] - p[1];
+    const double area1 = w1 * h1, area2 = (t[2] - t[0]) * (t[3] - t[1]);
+    const double iwr = fmin(p[2], t[2]) - fmax(p[0], t[0]), ihr = fmin(p[3], t[3]) - fmax(p[1], t[1]);
+    const double iw = fmax(iwr, 0.0), ih = fmax(ihr, 0.0);
+    const double inter = iw * ih;
+    const double uni = area1 + area2 - inter;
+    const double U = uni + eps;
+    const double iou = inter / U;
+    // the loss as a function of (iou, uni, ew, eh, ddx, ddy, w1, h1): its partial derivatives
+    double g_iou = -1.0, g_uni = 0.0, g_ew = 0.0, g_eh = 0.0, g_ddx = 0.0, g_ddy = 0.0, g_w1 = 0.0, g_h1 = 0.0;
+    if (kind >= 3) {
+        const double ew = fmax(p[2], t[2]) - fmin(p[0], t[0]), eh = fmax(p[3], t[3]) - fmin(p[1], t[1]);
+        if (kind == 3) {
+            const double enclosing = ew * eh;
+            const double g_enc = uni / (enclosing * enclosing);
+            g_uni = -1.0 / enclosing;
+            g_ew = g_enc * eh; g_eh = g_enc * ew;
+        } else {
+            const double diagonal = ew * ew + eh * eh;
+            const double ddx = (t[0] + t[2]) / 2.0 - (p[0] + p[2]) / 2.0, ddy = (t[1] + t[3]) / 2.0 - (p[1] + p[3]) / 2.0;
+            const double g_diag = -(ddx * ddx + ddy * ddy) / (diagonal * diagonal);
+            g_ew = g_diag * (2.0 * ew); g_eh = g_diag * (2.0 * eh);
+            g_ddx = 2.0 * ddx / diagonal; g_ddy = 2.0 * ddy / diagonal;
+            if (kind == 5) {
+                const double w2 = t[2] - t[0], h2 = t[3] - t[1];
+                const double hq = h1 + eps, q = w1 / hq;
+                const double angle = (atan(q) - atan(w2 / (h2 + eps))) * 2.0 / 3.141592653589793;
+                const double v = angle * angle;
+                const double r = v / (1.0 - iou + v + eps);               // alpha; the term is r v
+                g_iou = -1.0 + r * r;
+                const double g_q = (2.0 * r - r * r) * (2.0 * angle) * (2.0 / 3.141592653589793) / (1.0 + q * q);
+                g_w1 = g_q / hq; g_h1 = -(g_q * w1) / (hq * hq);
+            }
+        }
+    }
+    const double g_uni_t = g_uni - g_iou * (inter / (U * U));
+    const double g_inter = g_iou / U - g_uni_t;
+    const double g_iw = iwr >= 0.0 ? g_inter * ih : 0.0, g_ih = ihr >= 0.0 ? g_inter * iw : 0.0;      // clamp at 0: passes at >= 0
+    const double ax = g_uni_t * h1, ay = g_uni_t * w1;        // through area1 = w1 h1
+    g[0] = -(g_iw * d_max(p[0], t[0])) - ax - g_ew * d_min(p[0], t[0]) - 0.5 * g_ddx - g_w1;
+    g[1] = -(g_ih * d_max(p[1], t[1])) - ay - g_eh * d_min(p[1], t[1]) - 0.5 * g_ddy - g_h1;
+    g[2] = g_iw * d_min(p[2], t[2]) + ax + g_ew * d_max(p[2], t[2]) - 0.5 * g_ddx + g_w1;
+    g[3] = g_ih * d_min(p[3], t[3]) + ay + g_eh * d_max(p[3], t[3]) - 0.5 * g_ddy + g_h1;
+}
+
+// one pass: the counted records of slots s0 .. s0 + PASS_SLOTS - 1 whose SAMPLE neighbourhood (cx-1..cx+1 x cy-1..cy+1 clipped to the map: a radius-0
+// box still has nine samples, a centre on cx == W samples column W - 1) touches the tile, as (cx, cy, slot, 0), compacted in slot order -> how many
+__device__ __forceinline__ int stage_samples(const Rec* __restrict__ recs, int s0, int M, int x0, int y0, int x1, int y1, int W, int H, int4* s_smp,
+                                             int* s_cnt) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    __syncthreads();                                          // the readers of the previous pass are done
+    const int s = s0 + tid;
+    bool hit = false;
+    int4 v = make_int4(0, 0, 0, 0);
+    if (s < M) {
+        const Rec r = recs[s];
+        v = make_int4(r.cx, r.cy, s, 0);
+        hit = r.state != 0 && max(r.cx - 1, 0) < x1 && min(r.cx + 1, W - 1) >= x0 && max(r.cy - 1, 0) < y1 && min(r.cy + 1, H - 1) >= y0;
+    }
+    const unsigned long long votes = __ballot(hit);
+    if (lane == 0) s_cnt[wave] = __popcll(votes);
+    __syncthreads();
+    int base = 0, total = 0;
+#pragma unroll
+    for (int w = 0; w < WAVES; ++w) {
+        const int c = s_cnt[w];
+        if (w < wave) base += c;
+        total += c;
+    }
+    if (hit) s_smp[base + __popcll(votes & ((1ull << lane) - 1ull))] = v;
+    __syncthreads();
+    return total;
+}
+
+struct BoxGradArgs {
+    const float* box; long sn, sc, sh, sw;
+    float* grad; long gn, gc, gh, gw;
+    const double* gt_boxes;
+    const Rec* rec;
+    const int* count;
+    const double* counts;
+    const double* scales;
+    int H, W, Gmax, tx;
+    int kind, box_log;
+    float mult, stride;
+};
+
+__global__ __launch_bounds__(THREADS) void box_grad_kernel(const BoxGradArgs a) {
+    __shared__ int4 s_smp[PASS_SLOTS];
+    __shared__ int s_cnt[WAVES];
+    const int tid = threadIdx.x;
+    const int tiles = a.tx * tiles_y(a.H);
+    const int n = blockIdx.x / tiles, tile = blockIdx.x - n * tiles;
+    const int ty = tile / a.tx, txi = tile - ty * a.tx;
+    const int x0 = txi * TILE_W, y0 = ty * TILE_H, x1 = min(x0 + TILE_W, a.W), y1 = min(y0 + TILE_H, a.H);
+    const int x = x0 + tid % TILE_W, y = y0 + tid / TILE_W;
+    const bool inside = x < x1 && y < y1;
+    const int M = min(max(a.count[n], 0), a.Gmax);
+    const Rec* const recs = a.rec + (long)n * a.Gmax;
+    const double* const gts = a.gt_boxes + (long)n * a.Gmax * 4;
+    const float* const bp = a.box + (long)n * a.sn + (long)y * a.sh + (long)x * a.sw;
+    const double scale = (a.scales ? a.scales[1] : 1.0) / fmax(1.0, a.counts[1]);
+    const int passes = (M + PASS_SLOTS - 1) / PASS_SLOTS;
+
+    double acc[4] = {0.0, 0.0, 0.0, 0.0}, chain[4] = {0.0, 0.0, 0.0, 0.0};
+    float pred[4] = {0.f, 0.f, 0.f, 0.f};
+    bool touched = false;
+    for (int p = 0; p < passes; ++p) {                        // (uniform: M is the image's)
+        const int cnt = stage_samples(recs, p * PASS_SLOTS, M, x0, y0, x1, y1, a.W, a.H, s_smp, s_cnt);
+        if (!inside) continue;
+        for (int j = 0; j < cnt; ++j) {
+            const int4 r = s_smp[j];                          // the same address in every lane: a broadcast
+            if (abs(x - r.x) > 1 || abs(y - r.y) > 1) continue;
+            if (!touched) {                                   // this pixel's decode and its derivative, once
+                touched = true;
+                cnl::decode_box(bp, a.sc, x, y, a.W, a.H, 0, a.box_log, a.mult, a.stride, pred);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {                 // the decode's own fp32 operations (box_decode.h), for the clamp's side and exp's value
+                    float v = bp[(long)k * a.sc];
+                    if (a.box_log) v = expf(v);
+                    const float m = v * a.mult;
+                    const double side = k < 2 ? -1.0 : 1.0;   // x1 = (cx + 0.5 - g) stride, x2 = (cx + 0.5 + g) stride
+                    chain[k] = m >= 0.f ? side * (double)a.stride * (double)a.mult * (a.box_log ? (double)v : 1.0) : 0.0;
+                }
+            }
+            const double* const b = gts + (long)r.z * 4;
+            const float target[4] = {(float)b[0], (float)b[1], (float)(b[0] + b[2]), (float)(b[1] + b[3])};
+            double g[4];
+            box_dterm(a.kind, pred, target, g);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) acc[k] += g[k] * chain[k];
+        }
+    }
+    if (inside) {
+        float* const o = a.grad + (long)n * a.gn + (long)y * a.gh + (long)x * a.gw;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) o[(long)k * a.gc] = touched ? (float)(scale * acc[k]) : 0.f;
+    }
+}
+
+}  // namespace cnl_det_loss
+
 extern "C" size_t cnl_detection_loss_workspace_bytes(int32_t N, int32_t Gmax, int32_t H, int32_t W) {
     using namespace cnl_det_loss;
     if (N < 0 || N > (1 << 16) || Gmax < 1 || Gmax > MAX_G || H < 1 || H > (1 << 15) || W < 1 || W > (1 << 15)) return 0;
@@ -426,4 +752,86 @@ extern "C" int cnl_detection_loss_f64(const float* heat, int64_t heat_sn, int64_
 
     hipLaunchKernelGGL(finish_kernel, dim3(1), dim3(THREADS), 0, st, part, img, N, tiles, p->heatmap_weight, p->box_weight, per_image, totals, skipped);
     return cnl::check_launch("det_loss finish_kernel");
+}
+
+extern "C" size_t cnl_detection_loss_grad_workspace_bytes(int32_t N, int32_t Gmax, int32_t H, int32_t W) {
+    using namespace cnl_det_loss;
+    if (N < 0 || N > (1 << 16) || Gmax < 1 || Gmax > MAX_G || H < 1 || H > (1 << 15) || W < 1 || W > (1 << 15)) return 0;
+    return grad_sections_total(N, Gmax);
+}
+
+extern "C" int cnl_detection_loss_grad_f32(const float* heat, int64_t heat_sn, int64_t heat_sc, int64_t heat_sh, int64_t heat_sw, const float* box,
+                                           int64_t box_sn, int64_t box_sc, int64_t box_sh, int64_t box_sw, int32_t N, int32_t C, int32_t H, int32_t W,
+                                           const double* gt_boxes, const int64_t* gt_labels, const int32_t* gt_count, int32_t Gmax,
+                                           const cnl_loss_params* p, const double* scales, float* grad_heat, int64_t gh_sn, int64_t gh_sc,
+                                           int64_t gh_sh, int64_t gh_sw, float* grad_box, int64_t gb_sn, int64_t gb_sc, int64_t gb_sh, int64_t gb_sw,
+                                           int32_t* skipped, void* workspace, size_t workspace_bytes, void* stream) {
+    using namespace cnl_det_loss;
+    CNL_REQUIRE(p, CNL_E_BAD_ARG, "cnl_detection_loss_grad_f32: null params");
+    CNL_REQUIRE(N >= 0 && N <= (1 << 16), CNL_E_BAD_ARG, "cnl_detection_loss_grad_f32: N = %d outside 0..2^16", N);
+    CNL_REQUIRE(C >= 1 && C <= (1 << 16), CNL_E_BAD_ARG, "cnl_detection_loss_grad_f32: C = %d outside 1..2^16", C);
+    CNL_REQUIRE(H >= 1 && H <= (1 << 15) && W >= 1 && W <= (1 << 15), CNL_E_BAD_ARG, "cnl_detection_loss_grad_f32: H x W = %d x %d outside 1..2^15", H, W);
+    CNL_REQUIRE(Gmax >= 1 && Gmax <= MAX_G, CNL_E_BAD_ARG, "cnl_detection_loss_grad_f32: Gmax = %d outside 1..%d", Gmax, MAX_G);
+    CNL_REQUIRE(p->target_method >= 0 && p->target_method <= 2, CNL_E_BAD_ARG, "cnl_detection_loss_grad_f32: target_method = %d outside 0..2", p->target_method);
+    CNL_REQUIRE(p->heatmap_loss >= 0 && p->heatmap_loss <= 1, CNL_E_BAD_ARG, "cnl_detection_loss_grad_f32: heatmap_loss = %d outside 0..1", p->heatmap_loss);
+    CNL_REQUIRE(p->box_loss >= 0 && p->box_loss <= 5, CNL_E_BAD_ARG, "cnl_detection_loss_grad_f32: box_loss = %d outside 0..5", p->box_loss);
+    CNL_REQUIRE(p->stride > 0.0 && p->stride < 1e6, CNL_E_BAD_ARG, "cnl_detection_loss_grad_f32: stride = %g must be positive", p->stride);
+    CNL_REQUIRE(p->target_method != 0 || (p->target_param > 0.0 && p->target_param < 1.0), CNL_E_BAD_ARG,
+                "cnl_detection_loss_grad_f32: cornernet min_overlap = %g outside (0, 1)", p->target_param);
+    CNL_REQUIRE(p->target_param == p->target_param && p->hm_alpha == p->hm_alpha && p->hm_beta == p->hm_beta, CNL_E_BAD_ARG,
+                "cnl_detection_loss_grad_f32: a NaN parameter");
+    CNL_REQUIRE(heat && box, CNL_E_BAD_ARG, "cnl_detection_loss_grad_f32: the gradient needs the logits and the box map");
+    if (N == 0) return CNL_OK;
+    CNL_REQUIRE(gt_boxes && gt_labels && gt_count && skipped && workspace, CNL_E_BAD_ARG, "cnl_detection_loss_grad_f32: null pointer");
+    CNL_REQUIRE((((uintptr_t)gt_boxes | (uintptr_t)gt_labels | (uintptr_t)scales) & 7) == 0 && ((uintptr_t)workspace & 15) == 0 &&
+                    (((uintptr_t)heat | (uintptr_t)box | (uintptr_t)grad_heat | (uintptr_t)grad_box | (uintptr_t)gt_count | (uintptr_t)skipped) & 3) == 0,
+                CNL_E_BAD_ARG,
+                "cnl_detection_loss_grad_f32: the float64 / int64 arrays must be 8-byte aligned, the workspace 16-byte aligned, the rest 4-byte aligned");
+    const size_t need = grad_sections_total(N, Gmax);
+    CNL_REQUIRE(workspace_bytes >= need, CNL_E_WORKSPACE, "cnl_detection_loss_grad_f32: workspace of %zu bytes, %zu needed", workspace_bytes, need);
+    const int tiles = tiles_x(W) * tiles_y(H);
+    CNL_REQUIRE((long long)N * tiles < (1ll << 31), CNL_E_UNSUPPORTED, "cnl_detection_loss_grad_f32: %d images x %d tiles exceed the grid", N, tiles);
+    char* const ws = static_cast<char*>(workspace);
+    Rec* const rec = reinterpret_cast<Rec*>(ws);
+    double* const counts = reinterpret_cast<double*>(ws + (size_t)N * Gmax * sizeof(Rec));
+    hipStream_t st = (hipStream_t)stream;
+
+    const long slots = (long)N * Gmax;
+    hipLaunchKernelGGL(record_kernel, dim3((unsigned)((slots + THREADS - 1) / THREADS)), dim3(THREADS), 0, st, gt_boxes,
+                       reinterpret_cast<const long long*>(gt_labels), gt_count, N, Gmax, C, H, W, p->stride, p->target_method, p->target_param, rec);
+    if (int rc = cnl::check_launch("det_loss record_kernel")) return rc;
+    hipLaunchKernelGGL(count_kernel, dim3(1), dim3(THREADS), 0, st, rec, gt_count, N, Gmax, H, W, counts, skipped);
+    if (int rc = cnl::check_launch("det_loss count_kernel")) return rc;
+    const dim3 grid((unsigned)(N * tiles));
+
+    if (grad_heat) {
+        HeatGradArgs a;
+        a.heat = heat; a.sn = heat_sn; a.sc = heat_sc; a.sh = heat_sh; a.sw = heat_sw;
+        a.grad = grad_heat; a.gn = gh_sn; a.gc = gh_sc; a.gh = gh_sh; a.gw = gh_sw;
+        a.rec = rec; a.count = gt_count; a.counts = counts; a.scales = scales;
+        a.C = C; a.H = H; a.W = W; a.Gmax = Gmax; a.tx = tiles_x(W);
+        a.loss = p->heatmap_loss; a.alpha = p->hm_alpha; a.beta = p->hm_beta;
+        a.alpha_is_2 = p->hm_alpha == 2.0; a.beta_is_4 = p->hm_beta == 4.0; a.beta_is_2 = p->hm_beta == 2.0;
+        // the element order follows the gradient's strides; four elements per lane where both maps are packed channels-last rows of whole 16-byte groups
+        auto packed = [&](const float* ptr, int64_t sn, int64_t sc, int64_t sh, int64_t sw) {
+            return sc == 1 && sw == C && sh % 4 == 0 && sn % 4 == 0 && ((uintptr_t)ptr & 15) == 0;
+        };
+        const bool vec4 = ((long long)W * C) % 4 == 0 && packed(heat, heat_sn, heat_sc, heat_sh, heat_sw) && packed(grad_heat, gh_sn, gh_sc, gh_sh, gh_sw);
+        if (vec4) hipLaunchKernelGGL((heat_grad_kernel<LAYOUT_CMINOR, true>), grid, dim3(THREADS), 0, st, a);
+        else if (gh_sc == 1) hipLaunchKernelGGL((heat_grad_kernel<LAYOUT_CMINOR, false>), grid, dim3(THREADS), 0, st, a);
+        else if (gh_sw == 1) hipLaunchKernelGGL((heat_grad_kernel<LAYOUT_PLANE, false>), grid, dim3(THREADS), 0, st, a);
+        else hipLaunchKernelGGL((heat_grad_kernel<LAYOUT_GENERIC, false>), grid, dim3(THREADS), 0, st, a);
+        if (int rc = cnl::check_launch("det_loss heat_grad_kernel")) return rc;
+    }
+    if (grad_box) {
+        BoxGradArgs b;
+        b.box = box; b.sn = box_sn; b.sc = box_sc; b.sh = box_sh; b.sw = box_sw;
+        b.grad = grad_box; b.gn = gb_sn; b.gc = gb_sc; b.gh = gb_sh; b.gw = gb_sw;
+        b.gt_boxes = gt_boxes; b.rec = rec; b.count = gt_count; b.counts = counts; b.scales = scales;
+        b.H = H; b.W = W; b.Gmax = Gmax; b.tx = tiles_x(W);
+        b.kind = p->box_loss; b.box_log = p->box_log; b.mult = p->box_multiplier; b.stride = (float)p->stride;
+        hipLaunchKernelGGL(box_grad_kernel, grid, dim3(THREADS), 0, st, b);
+        if (int rc = cnl::check_launch("det_loss box_grad_kernel")) return rc;
+    }
+    return CNL_OK;
 }

@@ -1011,7 +1011,8 @@ int cnl_boxes_xyxy_to_xywh_f32(const float* boxes, float* out, int64_t n, void* 
 /*
  * The validation value of the detection losses (reference models/centernet.py:123-200 compute_loss / update_heatmap, losses/heatmap_losses.py,
  * losses/box_losses.py; csrc/det_loss.hip): Gaussian target heatmap, heatmap loss and the 3x3 centre-sampled box loss of a batch in one call.
- * Forward value only (validation curves, checkpoint selection, regression checks of converted weights): no gradient, no reid loss.  Every step the
+ * This entry point is the value (validation curves, checkpoint selection, regression checks of converted weights); its gradient with respect to the
+ * logits and the box values is cnl_detection_loss_grad_f32 below.  No reid loss.  Every step the
  * reference does on the host in float64 is float64 here; det_loss.hip is compiled with contraction off.  tests/loss_ref.py restates the rule in numpy.
  *
  * Targets: gt_boxes [N, Gmax, 4] float64 x y w h in INPUT pixels, gt_labels [N, Gmax] int64, gt_count [N] int32 (clamped to 0..Gmax), Gmax <= 1024.
@@ -1065,6 +1066,44 @@ int cnl_detection_loss_f64(const float* heat, int64_t heat_sn, int64_t heat_sc, 
                            const int64_t* gt_labels, const int32_t* gt_count, int32_t Gmax, const cnl_loss_params* p, float* target_map, int64_t t_sn,
                            int64_t t_sc, int64_t t_sh, int64_t t_sw, double* per_image, double* totals, int32_t* skipped, void* workspace,
                            size_t workspace_bytes, void* stream);
+
+/*
+ * The gradient of exactly the function cnl_detection_loss_f64 computes, for a criterion training can call (csrc/det_loss.hip; tests/loss_grad_ref.py
+ * restates it in numpy): grad_heat = d(s_heat heatmap + s_box box_2d) / d heat, grad_box likewise / d box, where
+ *   heatmap = sum of element terms / max(1, num_dets),   box_2d = sum of sample terms / max(1, num_boxes),
+ * num_dets and num_boxes counted over the BATCH, the target map a constant and the [t == 1] weight a constant.  Everything is float64 on the fp32
+ * logits and the fp32 decoded boxes, rounded ONCE to fp32.
+ * Heatmap, every element:  grad_heat[n,c,y,x] = fl32(s_heat / max(1, num_dets) * dterm/dx), with p, ls(x) = logsigmoid(x) and log1p(exp(-|x|)) formed as
+ * the forward forms them (dp/dx = p (1 - p), d ls(x)/dx = 1 - p, d ls(-x)/dx = -p), exponents 2 and 4 by multiplication:
+ *   "cornernet_focal" (alpha 2):  [t == 1] (1 - p)^2 (2 p ls(x) - (1 - p))  +  (1 - t)^hm_beta p^2 (p - 2 (1 - p) ls(-x))
+ *       (any alpha: [t == 1] (alpha (1-p)^(alpha-1) p (1-p) ls(x) - (1-p)^alpha (1-p))  +  (1-t)^hm_beta (p^alpha p - alpha p^(alpha-1) p (1-p) ls(-x)))
+ *   "quality" (beta 2):           (t - p)^2 (p - t)  -  sign(t - p) 2 |t - p| p (1 - p) ce,   ce = max(x, 0) - x t + log1p(exp(-|x|))
+ *       (any beta: |t-p|^beta (p - t) - sign(t-p) beta |t-p|^(beta-1) p (1-p) ce);  exactly 0 at t == p.
+ * Box: for every counted box and each of its up to nine samples, the derivative of the sample's loss with respect to the four box values at that pixel:
+ * through the loss (l1, smooth_l1, iou, giou, diou, ciou on the fp32 decoded box and the fp32 target, eps 1e-8; ciou's alpha is differentiated, as the
+ * reference's autograd does) and through the decode: d x1 / d v = -stride box_multiplier [fl32(v' box_multiplier) >= 0] (exp(v) with box_log, as the
+ * decode's fp32 expf gives it; v' = that exp or v), + for x2, y2.  A pixel sampled by several boxes receives the SUM of their contributions, added in
+ * float64 in slot order (a box samples a pixel at most once):  grad_box[n,j,y,x] = fl32(s_box / max(1, num_boxes) * sum);  a pixel no sample touches
+ * receives exactly 0.
+ * Non-differentiable points follow torch's autograd: the clamps at 0 (decode, intersection) pass the gradient where the clamped value is >= 0;
+ * maximum / minimum give half to each side on a tie;  |d| has derivative 0 at 0;  smooth_l1 takes the quadratic branch for |d| < 1;
+ * |t - p|^beta has derivative 0 at t == p.  A skipped box contributes nothing and is counted in skipped[0], as in the forward.
+ *
+ * heat, box, the targets, p and the limits: as cnl_detection_loss_f64 (heat and box both non-NULL).  scales: DEVICE float64 [2] = (s_heat, s_box), read by
+ * the kernels (no synchronisation for a caller whose scales are computed on the device); NULL: 1, 1.  grad_heat [N, C, H, W] and grad_box [N, 4, H, W],
+ * fp32, each with its own element strides; NULL: not wanted (its launch is skipped).  Every element of a wanted output is written exactly once: no
+ * pre-zeroing, and nothing outside the declared elements or past workspace_bytes is written.  The element order of the heatmap gradient follows
+ * grad_heat's strides (channel stride 1, W stride 1, or neither); where heat and grad_heat are both packed channels-last (pixel stride C, the other
+ * strides and W C multiples of 4, bases 16-byte aligned) a lane moves four consecutive elements per 16-byte access.  The workspace holds at least
+ * cnl_detection_loss_grad_workspace_bytes(N, Gmax, H, W) bytes (0 outside the limits), 16-byte aligned.  At most four launches on `stream` (records,
+ * counts, heatmap gradient, box gradient), no synchronisation, no allocation, no memset, no atomics: the same bits on every run.
+ */
+size_t cnl_detection_loss_grad_workspace_bytes(int32_t N, int32_t Gmax, int32_t H, int32_t W);
+int cnl_detection_loss_grad_f32(const float* heat, int64_t heat_sn, int64_t heat_sc, int64_t heat_sh, int64_t heat_sw, const float* box, int64_t box_sn,
+                                int64_t box_sc, int64_t box_sh, int64_t box_sw, int32_t N, int32_t C, int32_t H, int32_t W, const double* gt_boxes,
+                                const int64_t* gt_labels, const int32_t* gt_count, int32_t Gmax, const cnl_loss_params* p, const double* scales,
+                                float* grad_heat, int64_t gh_sn, int64_t gh_sc, int64_t gh_sh, int64_t gh_sw, float* grad_box, int64_t gb_sn,
+                                int64_t gb_sc, int64_t gb_sh, int64_t gb_sw, int32_t* skipped, void* workspace, size_t workspace_bytes, void* stream);
 
 int cnl_version(void);
 /* sizeof(cnl_conv_params) / sizeof(cnl_decode_params) / sizeof(cnl_deconv_params) (which = 0 / 1 / 2) and sizeof(cnl_loss_params) (which = 4; 3 is
