@@ -96,6 +96,15 @@ class LossParams(Structure):
                 ("heatmap_loss", c_int32), ("box_loss", c_int32), ("box_log", c_int32), ("reserved", c_int32)]
 
 
+class ReidLossParams(Structure):
+    """cnl_reid_loss_params: the rule of one cnl_reid_loss_f64 / cnl_reid_loss_grad_f32 call (48 bytes; cnl_sizeof_params(5))."""
+    _fields_ = [("stride", c_double), ("bn_eps", c_double), ("momentum", c_double), ("ignore_index", c_int64), ("center", c_int32),
+                ("padded_rows", c_int32), ("training", c_int32), ("reserved", c_int32)]
+
+
+_REID_COMMON = [c_void_p, c_int64, c_int64, c_int64, c_int64, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int32,
+                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, POINTER(ReidLossParams)]
+
 _SIGNATURES = {
     "cnl_version": (ctypes.c_int, []),
     "cnl_sizeof_params": (c_size_t, [ctypes.c_int32]),
@@ -166,6 +175,11 @@ _SIGNATURES = {
                                                    c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int32, POINTER(LossParams),
                                                    c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64,
                                                    c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "cnl_reid_loss_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32]),
+    "cnl_reid_loss_f64": (ctypes.c_int, _REID_COMMON + [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "cnl_reid_loss_grad_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32]),
+    "cnl_reid_loss_grad_f32": (ctypes.c_int, _REID_COMMON + [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
+                                                              c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "cnl_stem_conv7x7_u8": (ctypes.c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, POINTER(c_float), POINTER(c_float), c_void_p, c_void_p,
                                            c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "cnl_stem_packed_weight_floats": (c_size_t, []),
@@ -243,7 +257,7 @@ def load():
     if lib.cnl_version() != ABI_VERSION:
         raise HipLibraryError(f"{path} has ABI version {lib.cnl_version()}, this binding expects {ABI_VERSION}: rebuild it "
                               "(__graft_entry__.build())")
-    for which, struct in ((0, ConvParams), (1, DecodeParams), (2, DeconvParams), (4, LossParams)):       # the binding's struct layouts against the library's
+    for which, struct in ((0, ConvParams), (1, DecodeParams), (2, DeconvParams), (4, LossParams), (5, ReidLossParams)):       # the binding's struct layouts against the library's
         if lib.cnl_sizeof_params(which) != ctypes.sizeof(struct):
             raise HipLibraryError(f"{path}: sizeof({struct.__name__}) is {lib.cnl_sizeof_params(which)} in the library, {ctypes.sizeof(struct)} in this binding")
     _lib = lib

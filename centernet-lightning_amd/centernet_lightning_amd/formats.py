@@ -103,6 +103,20 @@ def is_training_only_key(key):
     return any(t in "." + key for t in _TRAINING_ONLY)
 
 
+def reid_classifier_state(ckpt):
+    """The `classifier.*` entries of a reference tracking checkpoint (EmbeddingHead.classifier: classifier.{0,1,3}.*, whatever prefix the head sits
+    under), keyed for loss.ReIDLoss.load_state_dict.  The model loader keeps skipping them (see _TRAINING_ONLY)."""
+    sd = ckpt.get("state_dict", ckpt) if isinstance(ckpt, dict) else ckpt
+    out = {}
+    for k, v in sd.items():
+        head, sep, tail = ("." + k).rpartition(".classifier.")
+        if sep:
+            out["classifier." + tail] = v
+    if not out:
+        raise ValueError("reid_classifier_state: the checkpoint holds no '<head>.classifier.*' entries (not a tracking checkpoint?)")
+    return out
+
+
 def checkpoint_state_dict(ckpt, keep_training_only=False):
     """Lightning `.ckpt` (dict with "state_dict") or a bare state_dict -> tensors keyed like this package's CenterNet:
     wrapper prefixes dropped ("model." of GenericModel inside the LightningModule, models/meta.py:66; "module." of DDP),

@@ -9,7 +9,9 @@ rule is stated in include/centernet_gfx950.h and restated in numpy in tests/loss
 detection_loss_grad() is ONE call of cnl_detection_loss_grad_f32 (at most four launches): the analytic gradient of that value with respect to the
 logits and the box values (tests/loss_grad_ref.py).  DetectionLoss is the criterion training calls: an nn.Module whose "heatmap", "box_2d" and
 "total" carry a grad_fn, so criterion(outputs, targets)["total"].backward() works on the head outputs of any torch model on the device.  fp32 inputs
-only, no double backward, no backward through the conv engine, no reid loss (the reference leaves it out at validation, fairmot.py:87-91).
+only, no double backward, no backward through the conv engine.  The re-ID loss of the tracking model is the second half of this file: reid_loss() /
+reid_loss_grad() (csrc/reid_loss.hip), the ReIDLoss criterion that owns the reference's classifier, and TrackingLoss, which adds it to DetectionLoss's total
+(the reference leaves it out at validation, fairmot.py:87-91: TrackingLoss(...)(outputs, targets, ignore_reid=True)).
 No CPU fallback: a missing device or library raises.
 """
 import ctypes
@@ -459,3 +461,359 @@ class LossMeter:
                              "label outside the classes): the reference's loss is not defined for them")
         images = max(images, 1.0)
         return dict(zip(METRIC_NAMES, (heat / images, box / images, total / images)))
+
+
+# ------------------------------------------------------------------------------------------------------------------------ re-ID loss
+# The tracking model's third loss (reference models/fairmot.py:34-61 EmbeddingHead.compute_loss): the embedding at every box centre through the training-only
+# classifier Linear / BatchNorm1d / ReLU / Linear and a cross entropy over the track identities.  reid_loss() is ONE call of cnl_reid_loss_f64,
+# reid_loss_grad() ONE call of cnl_reid_loss_grad_f32 (csrc/reid_loss.hip; the rule: include/centernet_gfx950.h; in numpy: tests/reid_loss_ref.py).
+MAX_EMB, MAX_TRACK_IDS = 256, 1 << 20
+CENTERS = {"trunc": 0, "round": 1}
+REID_KEYS = ("W1", "gamma", "beta", "running_mean", "running_var", "W2", "b2")
+REID_WANT = ("reid", "W1", "gamma", "beta", "W2", "b2")
+
+
+def reid_params(training=True, stride=4, center="trunc", padded_rows=False, ignore_index=-1, bn_eps=1e-5, momentum=0.1, what="reid_loss"):
+    """The checked cnl_reid_loss_params block of these settings (needs neither a device nor the library)."""
+    if center not in CENTERS:
+        raise ValueError(f"{what}: center must be one of {sorted(CENTERS)}, got {center!r}")
+    if isinstance(ignore_index, bool) or not isinstance(ignore_index, (int, np.integer)):
+        raise ValueError(f"{what}: ignore_index must be an int, got {ignore_index!r}")
+    if momentum is None:
+        raise ValueError(f"{what}: BatchNorm1d with momentum=None (a cumulative average) is not supported")
+    p = _lib.ReidLossParams()
+    p.stride = _number(stride, "stride", what, positive=True)
+    p.bn_eps = _number(bn_eps, "eps", what, positive=True)
+    p.momentum = _number(momentum, "momentum", what)
+    if not 0.0 <= p.momentum <= 1.0:
+        raise ValueError(f"{what}: momentum must lie in 0..1, got {momentum!r}")
+    p.ignore_index, p.center, p.padded_rows, p.training = int(ignore_index), CENTERS[center], 1 if padded_rows else 0, 1 if training else 0
+    return p
+
+
+def _classifier(classifier, what):
+    """A ReIDLoss or a dict of the seven tensors -> (the seven tensors by REID_KEYS, eps, momentum, num_batches_tracked or None), shapes checked."""
+    if isinstance(classifier, ReIDLoss):
+        lin1, bn, _, lin2 = classifier.classifier
+        t = dict(W1=lin1.weight, gamma=bn.weight, beta=bn.bias, running_mean=bn.running_mean, running_var=bn.running_var, W2=lin2.weight, b2=lin2.bias)
+        eps, momentum, steps = bn.eps, bn.momentum, bn.num_batches_tracked
+    elif isinstance(classifier, dict):
+        missing = [k for k in REID_KEYS if k not in classifier]
+        if missing:
+            raise ValueError(f"{what}: the classifier dict lacks {missing}; it holds {REID_KEYS} (and optionally 'eps', 'momentum', 'num_batches_tracked')")
+        t = {k: classifier[k] for k in REID_KEYS}
+        eps, momentum, steps = classifier.get("eps", 1e-5), classifier.get("momentum", 0.1), classifier.get("num_batches_tracked")
+    else:
+        raise ValueError(f"{what}: classifier must be a ReIDLoss or a dict of {REID_KEYS}, got {type(classifier).__name__}")
+    for k, v in t.items():
+        if not isinstance(v, torch.Tensor) or v.dtype != torch.float32:
+            raise ValueError(f"{what}: classifier tensor '{k}' must be a float32 tensor, got {v.dtype if isinstance(v, torch.Tensor) else type(v).__name__}")
+    if t["W1"].dim() != 2 or t["W1"].shape[0] != t["W1"].shape[1] or t["W2"].dim() != 2:
+        raise ValueError(f"{what}: W1 must be [D, D] and W2 [K, D], got {tuple(t['W1'].shape)} and {tuple(t['W2'].shape)}")
+    D, K = int(t["W1"].shape[0]), int(t["W2"].shape[0])
+    for k, shape in (("gamma", (D,)), ("beta", (D,)), ("running_mean", (D,)), ("running_var", (D,)), ("W2", (K, D)), ("b2", (K,))):
+        if tuple(t[k].shape) != shape:
+            raise ValueError(f"{what}: classifier tensor '{k}' must be {list(shape)} beside W1 [{D}, {D}], got {tuple(t[k].shape)}")
+    if not (1 <= D <= MAX_EMB and 2 <= K <= MAX_TRACK_IDS):
+        raise ValueError(f"{what}: D = {D}, K = {K} outside 1..{MAX_EMB}, 2..{MAX_TRACK_IDS}")
+    return t, eps, momentum, steps
+
+
+def _reid_targets(targets, N, H, W, K, stride, center, ignore_index, what):
+    """-> (device or None, (boxes [N,Gmax,4] f64, ids [N,Gmax] i64, count [N] i32) as device tensors or numpy, Gmax)"""
+    padded = None
+    if isinstance(targets, dict):
+        if any(name not in targets for name in ("boxes", "ids", "count")):
+            raise ValueError(f"{what}: device targets need 'boxes' [N,Gmax,4] f64, 'ids' [N,Gmax] i64 and 'count' [N] i32")
+        padded = (targets["boxes"], targets["ids"], targets["count"])
+    elif isinstance(targets, (list, tuple)) and len(targets) == 4 and all(isinstance(t, torch.Tensor) for t in targets):
+        padded = (targets[0], targets[3], targets[2])          # detection_loss's (boxes, labels, count) and the ids as the fourth tensor
+    if padded is not None:
+        boxes, ids, count = padded
+        for name, t, dtype, dims in (("boxes", boxes, torch.float64, 3), ("ids", ids, torch.int64, 2), ("count", count, torch.int32, 1)):
+            if not isinstance(t, torch.Tensor):
+                raise ValueError(f"{what}: targets '{name}' must be a tensor, got {type(t).__name__}")
+            if t.dtype != dtype or t.dim() != dims:
+                raise ValueError(f"{what}: targets '{name}' must be {dtype} with {dims} dimensions, got {t.dtype} {tuple(t.shape)}")
+        Gmax = int(boxes.shape[1])
+        if tuple(boxes.shape) != (N, Gmax, 4) or tuple(ids.shape) != (N, Gmax) or tuple(count.shape) != (N,):
+            raise ValueError(f"{what}: expected target boxes [{N},Gmax,4], ids [{N},Gmax], count [{N}], got {tuple(boxes.shape)}, {tuple(ids.shape)}, "
+                             f"{tuple(count.shape)}")
+        if not 1 <= Gmax <= MAX_PER_IMAGE:
+            raise ValueError(f"{what}: Gmax = {Gmax} boxes per image; 1..{MAX_PER_IMAGE} are supported")
+        _gather.require_hip([boxes, ids, count], what)
+        if ids.device != boxes.device or count.device != boxes.device:
+            raise ValueError(f"{what}: target tensors live on different devices")
+        return boxes.device, (boxes.contiguous(), ids.contiguous(), count.contiguous()), Gmax
+    if not isinstance(targets, (list, tuple)):
+        raise ValueError(f"{what}: targets must be a list of per-image dicts or padded device tensors, got {type(targets).__name__}")
+    if len(targets) != N:
+        raise ValueError(f"{what}: {N} images of outputs against {len(targets)} of targets")
+    images = []
+    for i, d in enumerate(targets):
+        if not isinstance(d, dict) or "boxes" not in d or "ids" not in d:
+            raise ValueError(f"{what}: targets[{i}] must be a dict with 'boxes', 'ids'")
+        try:
+            b = np.asarray(d["boxes"].detach().cpu().numpy() if isinstance(d["boxes"], torch.Tensor) else d["boxes"]).astype(np.float64)
+            ident = np.asarray(d["ids"].detach().cpu().numpy() if isinstance(d["ids"], torch.Tensor) else d["ids"]).astype(np.int64).reshape(-1)
+        except (TypeError, ValueError) as e:
+            raise ValueError(f"{what}: targets[{i}] is not numeric: {e}") from e
+        if b.size == 0:
+            b = b.reshape(0, 4)
+        if b.ndim != 2 or b.shape[1] != 4 or b.shape[0] != ident.shape[0]:
+            raise ValueError(f"{what}: targets[{i}] has boxes {b.shape} and ids {ident.shape}; expected [n, 4] and [n]")
+        if ident.shape[0] > MAX_PER_IMAGE:
+            raise ValueError(f"{what}: targets[{i}] has {ident.shape[0]} boxes; at most {MAX_PER_IMAGE} per image are supported")
+        with np.errstate(all="ignore"):
+            c = (b[:, :2] + b[:, 2:] / 2.0) / float(stride)
+            c = np.rint(c) if center == "round" else np.trunc(c)
+            ok = np.isfinite(b).all(axis=1) & (b[:, 2] >= 0) & (b[:, 3] >= 0) & (c[:, 0] >= 0) & (c[:, 0] <= W - 1) & (c[:, 1] >= 0) & (c[:, 1] <= H - 1) & \
+                (ident >= 0) & (ident < K)
+        bad = np.nonzero(~ok & (ident != ignore_index))[0]
+        if bad.size:
+            j = int(bad[0])
+            raise ValueError(f"{what}: targets[{i}] box {j} = {b[j].tolist()} (id {int(ident[j])}) cannot be a row on a {H} x {W} map with {K} identities at "
+                             f"stride {stride}: non-finite, negative size, centre cell outside the map or id outside 0..{K - 1}")
+        images.append((b, ident))
+    Gmax = max([1] + [len(ident) for (_, ident) in images])
+    boxes, ids, count = np.zeros((N, Gmax, 4), dtype=np.float64), np.zeros((N, Gmax), dtype=np.int64), np.zeros((N,), dtype=np.int32)
+    for i, (b, ident) in enumerate(images):
+        boxes[i, :len(ident)], ids[i, :len(ident)], count[i] = b, ident, len(ident)
+    return None, (boxes, ids, count), Gmax
+
+
+def _reid_inputs(reid, targets, classifier, params, center, what):
+    """Everything one call reads, checked -> (shape (N, D, H, W), K, the seven tensors (detached, dense) by REID_KEYS, num_batches_tracked, device targets)"""
+    _check_map(reid, "reid", "D", what)
+    N, D, H, W = (int(v) for v in reid.shape)
+    t, eps, momentum, steps = classifier
+    if int(t["W1"].shape[0]) != D:
+        raise ValueError(f"{what}: reid has {D} channels, the classifier expects {int(t['W1'].shape[0])}")
+    K = int(t["W2"].shape[0])
+    _check_sizes(N, 1, H, W, what)
+    _gather.require_hip([reid] + list(t.values()), what)
+    dev = reid.device
+    for k, v in t.items():
+        if v.device != dev:
+            raise ValueError(f"{what}: reid on {dev}, classifier tensor '{k}' on {v.device}")
+    g_dev, gts, _ = _reid_targets(targets, N, H, W, K, params.stride, center, params.ignore_index, what)
+    if g_dev is not None and g_dev != dev:
+        raise ValueError(f"{what}: reid on {dev}, targets on {g_dev}")
+    if g_dev is None:
+        with torch.cuda.device(dev):
+            gts = [torch.from_numpy(a).to(dev) for a in gts] if N == 0 else _upload(list(gts), dev)
+    return (N, D, H, W), K, {k: v.detach().contiguous() for k, v in t.items()}, steps, tuple(gts)
+
+
+def _reid_common(reid, shape, K, t, gts, params):
+    N, D, H, W = shape
+    return (reid.data_ptr(), *reid.stride(), N, D, H, W, gts[0].data_ptr(), gts[1].data_ptr(), gts[2].data_ptr(), int(gts[0].shape[1]),
+            *(t[k].data_ptr() for k in REID_KEYS), K, ctypes.byref(params))
+
+
+def _run_reid(reid, shape, K, t, gts, params):
+    """The one call -> (per_row [N, Gmax] f64, total [1] f64, counts [4] i32 (rows, top-1 hits, skipped, stepped), new statistics [2, D] f32)"""
+    N, D, H, W = shape
+    dev = reid.device
+    Gmax = int(gts[0].shape[1])
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        per_row = torch.zeros((N, Gmax), dtype=torch.float64, device=dev) if N == 0 else torch.empty((N, Gmax), dtype=torch.float64, device=dev)
+        total = torch.zeros((1,), dtype=torch.float64, device=dev)
+        counts = torch.zeros((4,), dtype=torch.int32, device=dev)
+        new_stats = torch.stack([t["running_mean"], t["running_var"]])
+        if N == 0:
+            return per_row, total, counts, new_stats
+        nbytes = lib.cnl_reid_loss_workspace_bytes(N, Gmax, D)
+        ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=dev)
+        _lib.check(lib.cnl_reid_loss_f64(*_reid_common(reid, shape, K, t, gts, params), per_row.data_ptr(), total.data_ptr(), counts.data_ptr(),
+                                         new_stats.data_ptr(), ws.data_ptr(), nbytes, ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
+                   "cnl_reid_loss_f64")
+    return per_row, total, counts, new_stats
+
+
+def _run_reid_grad(reid, shape, K, t, gts, params, scale, want):
+    """The one call.  scale: None (1) or a float64 device tensor [1]; want: six flags by REID_WANT -> (six gradients or None, skipped [1] i32)"""
+    N, D, H, W = shape
+    dev = reid.device
+    Gmax = int(gts[0].shape[1])
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        empty = torch.zeros if N == 0 else torch.empty
+        grads = [(_like(reid) if N else torch.zeros_like(reid)) if want[0] else None]
+        grads += [empty(tuple(t[k].shape), dtype=torch.float32, device=dev) if w else None for k, w in zip(REID_WANT[1:], want[1:])]
+        skipped = torch.zeros((1,), dtype=torch.int32, device=dev)
+        if N == 0:
+            return grads, skipped
+        nbytes = lib.cnl_reid_loss_grad_workspace_bytes(N, Gmax, D)
+        ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=dev)
+        ptr = lambda g: None if g is None else g.data_ptr()
+        _lib.check(lib.cnl_reid_loss_grad_f32(*_reid_common(reid, shape, K, t, gts, params), None if scale is None else scale.data_ptr(), ptr(grads[0]),
+                                              *(grads[0].stride() if grads[0] is not None else (0,) * 4), *(ptr(g) for g in grads[1:]),
+                                              skipped.data_ptr(), ws.data_ptr(), nbytes,
+                                              ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "cnl_reid_loss_grad_f32")
+    return grads, skipped
+
+
+def _reid_result(per_row, total, counts):
+    return {"reid": total[0], "per_row": per_row, "num_rows": counts[0], "correct": counts[1], "skipped": counts[2]}
+
+
+def _step_statistics(t_live, steps, new_stats, counts):
+    """The BatchNorm buffers after a training call (t_live: the classifier's own tensors, written in place on the device)."""
+    with torch.no_grad():
+        t_live["running_mean"].copy_(new_stats[0])
+        t_live["running_var"].copy_(new_stats[1])
+        if isinstance(steps, torch.Tensor):
+            steps += counts[3].to(steps.dtype)
+
+
+def reid_loss(reid, targets, classifier, training=True, stride=4, center="trunc", padded_rows=False, ignore_index=-1, update_stats=True):
+    """The reference's EmbeddingHead.compute_loss on the device.  reid [N, D, H, W] fp32 as get_encoded_outputs returns it (any strides).  targets:
+    detection_loss's forms plus the identities: a list of per-image {"boxes" [m, 4] x y w h in input pixels, "ids" [m]} (checked on the host: a box that
+    cannot be a row raises ValueError), or padded device tensors as a dict {"boxes" [N, Gmax, 4] float64, "ids" [N, Gmax] int64, "count" [N] int32} or the
+    tuple (boxes, labels, count, ids) (a bad row is skipped and counted in "skipped").  classifier: a ReIDLoss, or a dict of the seven fp32 tensors
+    W1 [D, D], gamma, beta, running_mean, running_var [D], W2 [K, D], b2 [K] (optionally "eps", "momentum", "num_batches_tracked").
+    center: "trunc" (the reference's cell) or "round" (the cell the decode reads).  padded_rows: the slots beyond count enter the BatchNorm statistics at
+    cell (0, 0), as the reference's zero-padded boxes do.  ignore_index: the identity of a box without one (dropped silently).  training: batch
+    statistics, and with update_stats the running statistics and num_batches_tracked make their step in place; else the running statistics are used.
+    -> {"reid": 0-dim float64, "per_row" [N, Gmax] float64 (0 for rows not in the loss), "num_rows", "correct" (top-1 hits), "skipped": 0-dim int32}.
+    Training with fewer than two rows in the statistics gives 0 and leaves the buffers alone.  No synchronisation."""
+    what = "reid_loss"
+    cls = _classifier(classifier, what)
+    params = reid_params(training, stride, center, padded_rows, ignore_index, cls[1], cls[2], what)
+    shape, K, t, steps, gts = _reid_inputs(reid, targets, cls, params, center, what)
+    per_row, total, counts, new_stats = _run_reid(reid.detach(), shape, K, t, gts, params)
+    if training and update_stats:
+        _step_statistics(cls[0], steps, new_stats, counts)
+    return _reid_result(per_row, total, counts)
+
+
+def reid_loss_grad(reid, targets, classifier, training=True, stride=4, center="trunc", padded_rows=False, ignore_index=-1, scale=1.0, want=REID_WANT):
+    """The gradient of scale * reid_loss(...)["reid"] with respect to the map and the five trainable classifier tensors, analytic, float64 rounded once to
+    fp32 (the rule: include/centernet_gfx950.h).  scale: a Python number or a 0-dim / 1-element float64 tensor on the device (read there).  want: which
+    gradients to compute, a subset of ("reid", "W1", "gamma", "beta", "W2", "b2").
+    -> {"reid_grad" (the map's shape; its strides when it is dense, else contiguous; exactly 0 wherever no row reads), "W1_grad", "gamma_grad",
+    "beta_grad", "W2_grad", "b2_grad" (None when not wanted), "skipped": 0-dim int32}.  The running statistics are never touched.  One call of
+    cnl_reid_loss_grad_f32, no synchronisation, no atomics: the same bits on every run."""
+    what = "reid_loss_grad"
+    if isinstance(want, str) or not isinstance(want, (tuple, list)) or not want or any(w not in REID_WANT for w in want) or len(set(want)) != len(want):
+        raise ValueError(f"{what}: want must be a non-empty tuple out of {REID_WANT}, got {want!r}")
+    cls = _classifier(classifier, what)
+    params = reid_params(training, stride, center, padded_rows, ignore_index, cls[1], cls[2], what)
+    _check_map(reid, "reid", "D", what)
+    s = _scale(scale, "scale", reid.device, what)
+    shape, K, t, _, gts = _reid_inputs(reid, targets, cls, params, center, what)
+    dev = reid.device
+    if isinstance(s, torch.Tensor):
+        s = s.reshape(1)
+    elif s != 1.0:
+        with torch.cuda.device(dev):
+            (s,) = _upload([np.array([s], dtype=np.float64)], dev)
+    else:
+        s = None
+    grads, skipped = _run_reid_grad(reid.detach(), shape, K, t, gts, params, s, tuple(w in want for w in REID_WANT))
+    out = {f"{k}_grad": g for k, g in zip(REID_WANT, grads)}
+    out["skipped"] = skipped[0]
+    return out
+
+
+class _ReIDLossFunction(torch.autograd.Function):
+    """reid_loss with the backward of cnl_reid_loss_grad_f32: one call forward, one call backward."""
+
+    @staticmethod
+    def forward(ctx, reid, W1, gamma, beta, W2, b2, running, gts, params, shape, K):
+        t = dict(W1=W1, gamma=gamma, beta=beta, running_mean=running[0], running_var=running[1], W2=W2, b2=b2)
+        t = {k: v.detach().contiguous() for k, v in t.items()}
+        per_row, total, counts, new_stats = _run_reid(reid.detach(), shape, K, t, gts, params)
+        ctx.save_for_backward(reid, W1, gamma, beta, W2, b2, *gts)
+        # (the running statistics are not saved tensors: a training step writes them in place after this call, and only an eval-mode backward reads them)
+        ctx.running, ctx.params, ctx.shape, ctx.K = running, params, shape, K
+        ctx.mark_non_differentiable(per_row, counts, new_stats)
+        return total, per_row, counts, new_stats
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_total, _g_rows, _g_counts, _g_stats):
+        reid, W1, gamma, beta, W2, b2, *gts = ctx.saved_tensors
+        t = dict(W1=W1, gamma=gamma, beta=beta, running_mean=ctx.running[0], running_var=ctx.running[1], W2=W2, b2=b2)
+        t = {k: v.detach().contiguous() for k, v in t.items()}
+        scale = g_total.detach().to(torch.float64).reshape(1)                 # on the device: no synchronisation
+        grads, _ = _run_reid_grad(reid.detach(), ctx.shape, ctx.K, t, tuple(gts), ctx.params, scale, tuple(ctx.needs_input_grad[:6]))
+        return (*grads, None, None, None, None, None)
+
+
+class ReIDLoss(torch.nn.Module):
+    """The tracking model's re-ID criterion: the reference's EmbeddingHead classifier and loss (models/fairmot.py:20-61).  `classifier` is the reference's
+    nn.Sequential(Linear(D, D, bias=False), BatchNorm1d(D), ReLU, Linear(D, K)) with torch's initialisation, so state_dict() has the reference's keys
+    classifier.{0,1,3}.* (formats.reid_classifier_state takes them out of a reference checkpoint).  The Sequential owns the parameters and buffers; its
+    own forward is never used.  ReIDLoss(...)(outputs, targets) -> reid_loss's dict, where "reid" carries a grad_fn when the map or a parameter requires
+    grad (one call forward, one call backward, only for the inputs that need a gradient).  .train() / .eval() pick batch or running statistics; a
+    training call steps running_mean, running_var and num_batches_tracked.  loss_weight is NOT applied to the value (TrackingLoss applies it to the
+    total).  `settings`: stride, center, padded_rows, ignore_index of reid_loss."""
+
+    def __init__(self, emb_dim=64, max_track_ids=1000, loss_weight=1.0, **settings):
+        super().__init__()
+        unknown = set(settings) - {"stride", "center", "padded_rows", "ignore_index"}
+        if unknown:
+            raise ValueError(f"ReIDLoss: unknown settings {sorted(unknown)}; stride, center, padded_rows and ignore_index are understood")
+        for name, v, hi in (("emb_dim", emb_dim, MAX_EMB), ("max_track_ids", max_track_ids, MAX_TRACK_IDS)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not (2 if name == "max_track_ids" else 1) <= v <= hi:
+                raise ValueError(f"ReIDLoss: {name} must be an int up to {hi}, got {v!r}")
+        reid_params(what="ReIDLoss", **settings)
+        self.emb_dim, self.max_track_ids = int(emb_dim), int(max_track_ids)
+        self.loss_weight = _number(loss_weight, "loss_weight", "ReIDLoss")
+        self.settings = settings
+        self.classifier = torch.nn.Sequential(torch.nn.Linear(self.emb_dim, self.emb_dim, bias=False), torch.nn.BatchNorm1d(self.emb_dim),
+                                              torch.nn.ReLU(inplace=True), torch.nn.Linear(self.emb_dim, self.max_track_ids))
+
+    def extra_repr(self):
+        return ", ".join([f"loss_weight={self.loss_weight!r}"] + [f"{k}={v!r}" for k, v in self.settings.items()])
+
+    def forward(self, outputs, targets):
+        what = "ReIDLoss"
+        if not isinstance(outputs, dict) or "reid" not in outputs:
+            raise ValueError("ReIDLoss: outputs must be the dict of get_encoded_outputs with 'reid'")
+        reid = outputs["reid"]
+        cls = _classifier(self, what)
+        t, _, _, steps = cls
+        trainable = (reid, t["W1"], t["gamma"], t["beta"], t["W2"], t["b2"])
+        needs = torch.is_grad_enabled() and any(isinstance(v, torch.Tensor) and v.requires_grad for v in trainable)
+        if not needs:
+            return reid_loss(reid, targets, self, training=self.training, **self.settings)
+        params = reid_params(self.training, bn_eps=cls[1], momentum=cls[2], what=what, **self.settings)
+        shape, K, _, _, gts = _reid_inputs(reid, targets, cls, params, self.settings.get("center", "trunc"), what)
+        total, per_row, counts, new_stats = _ReIDLossFunction.apply(*trainable, (t["running_mean"], t["running_var"]), gts, params, shape, K)
+        if self.training:
+            _step_statistics(t, steps, new_stats, counts)
+        return _reid_result(per_row, total, counts)
+
+
+class TrackingLoss(torch.nn.Module):
+    """The criterion of a tracking model's training step: TrackingLoss(detection_settings, reid_loss_module)(outputs, targets) ->
+    {"heatmap", "box_2d", "reid", "total", "per_image", "skipped", "per_row", "num_rows", "correct", "reid_skipped"} with
+    total = DetectionLoss's total + loss_weight * reid; "heatmap", "box_2d", "per_image" and "skipped" are DetectionLoss's, bit for bit.  outputs: the
+    dict of get_encoded_outputs with "heatmap", "box_2d" and "reid"; targets: a list of per-image {"boxes", "labels", "ids"}, the dict of padded device
+    tensors {"boxes", "labels", "ids", "count"} or the tuple (boxes, labels, count, ids).  ignore_reid=True at call time leaves the re-ID loss out, as the
+    reference's validation step does (models/fairmot.py:89): "total" is the detection total and "reid" is 0."""
+
+    def __init__(self, detection_settings, reid_loss_module):
+        super().__init__()
+        if not isinstance(reid_loss_module, ReIDLoss):
+            raise ValueError(f"TrackingLoss: reid_loss_module must be a ReIDLoss, got {type(reid_loss_module).__name__}")
+        self.detection = DetectionLoss(**dict(detection_settings or {}))
+        self.reid = reid_loss_module
+
+    def forward(self, outputs, targets, ignore_reid=False):
+        det_targets = targets
+        if isinstance(targets, (list, tuple)) and len(targets) == 4 and all(isinstance(t, torch.Tensor) for t in targets):
+            det_targets = tuple(targets[:3])
+        out = dict(self.detection(outputs, det_targets))
+        if ignore_reid:
+            out["reid"] = torch.zeros((), dtype=torch.float64, device=out["total"].device)
+            return out
+        res = self.reid(outputs, targets)
+        out["reid_skipped"] = res.pop("skipped")
+        out.update(res)
+        out["total"] = out["total"] + self.reid.loss_weight * res["reid"]
+        return out

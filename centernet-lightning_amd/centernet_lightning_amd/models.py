@@ -372,7 +372,8 @@ class CenterNet(nn.Module):
         """The reference's compute_loss (models/centernet.py:123-175) as a validation VALUE: outputs is the dict of get_encoded_outputs (heatmap
         logits), targets the reference's list of per-image {"boxes" x y w h, "labels"} or padded device tensors -> {"heatmap", "box_2d", "total"}
         (0-dim float64 device tensors), "per_image", "skipped" (loss.detection_loss).  Target method, loss functions and weights come from the
-        config, stride / box_log / box_multiplier from the model; the reid loss is left out, as the reference leaves it out at validation."""
+        config, stride / box_log / box_multiplier from the model; the reid loss is left out, as the reference leaves it out at validation
+        (tracking_criterion() is the training criterion with it)."""
         return _loss.detection_loss(outputs["heatmap"], outputs["box_2d"], targets, **self._loss_kwargs(stride))
 
     def loss_meter(self):
@@ -382,6 +383,17 @@ class CenterNet(nn.Module):
     def criterion(self):
         """A DetectionLoss with this model's loss settings: criterion(outputs, targets)["total"].backward() for a training step (loss.py)."""
         return _loss.DetectionLoss(**self._loss_kwargs(None))
+
+    def tracking_criterion(self, max_track_ids=None):
+        """A TrackingLoss for a tracking model: DetectionLoss with this model's settings plus a ReIDLoss built from output_heads.reid.{emb_dim,
+        max_track_ids, loss_weight} (max_track_ids: overrides the config's, e.g. the identity count of the training set).  The ReIDLoss owns the
+        training-only classifier: give its parameters to the optimizer and move it to the device (criterion.to(device))."""
+        if self.task != "tracking":
+            raise ValueError("tracking_criterion() needs a tracking model (task 'tracking' with a 'reid' head); a detection model's criterion is criterion()")
+        cfg = dict(self.config_section["output_heads"].get("reid") or {})
+        ids = cfg.get("max_track_ids", 1000) if max_track_ids is None else max_track_ids
+        reid = _loss.ReIDLoss(int(cfg.get("emb_dim", 64)), int(ids), float(cfg.get("loss_weight", 1.0)), stride=self.stride)
+        return _loss.TrackingLoss(self._loss_kwargs(None), reid)
 
     def _loss_kwargs(self, stride):
         return dict(self.loss_settings, stride=self.stride if stride is None else stride, box_log=self.box_log, box_multiplier=self.box_multiplier)

@@ -34,10 +34,10 @@ int cu_count(int dev, int* n_cu) {
 
 extern "C" int cnl_version(void) { return CNL_ABI_VERSION; }
 extern "C" int cnl_absmax_stride(void) { return CNL_ABSMAX_STRIDE; }
-// sizeof of the parameter structs as THIS library was compiled (0 conv, 1 decode, 2 deconv, 4 loss; 3 is unused): a binder checks its own struct layout against it
+// sizeof of the parameter structs as THIS library was compiled (0 conv, 1 decode, 2 deconv, 4 loss, 5 re-ID loss; 3 is unused): a binder checks its own struct layout against it
 extern "C" size_t cnl_sizeof_params(int32_t which) {
     return which == 0 ? sizeof(cnl_conv_params) : which == 1 ? sizeof(cnl_decode_params) : which == 2 ? sizeof(cnl_deconv_params) :
-           which == 4 ? sizeof(cnl_loss_params) : 0;
+           which == 4 ? sizeof(cnl_loss_params) : which == 5 ? sizeof(cnl_reid_loss_params) : 0;
 }
 
 extern "C" size_t cnl_last_error(char* buf, size_t n) {

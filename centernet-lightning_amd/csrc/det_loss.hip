@@ -2,7 +2,7 @@
 // losses/heatmap_losses.py, losses/box_losses.py) on the device: Gaussian targets, heatmap loss and the 3x3 centre-sampled box loss of a
 // batch in four launches, the logits read once, no N x C x H x W target tensor unless the caller asks for it.  The rule is stated in
 // include/centernet_gfx950.h and restated in numpy in tests/loss_ref.py.  The gradient of that value with respect to the logits and the box_2d
-// values (cnl_detection_loss_grad_f32, the second half of this file; tests/loss_grad_ref.py) is analytic: no reid loss, no double backward.
+// values (cnl_detection_loss_grad_f32, the second half of this file; tests/loss_grad_ref.py) is analytic: no double backward (the re-ID loss of the tracking model is csrc/reid_loss.hip).
 //
 //   record_kernel    one thread per target slot: box -> (cx, cy, rx, ry, the two fp32 Gaussian denominators, label, state), all float64
 //                    as the reference's host code computes them.  Slots at or beyond count[n] are never read.

@@ -1012,7 +1012,7 @@ int cnl_boxes_xyxy_to_xywh_f32(const float* boxes, float* out, int64_t n, void* 
  * The validation value of the detection losses (reference models/centernet.py:123-200 compute_loss / update_heatmap, losses/heatmap_losses.py,
  * losses/box_losses.py; csrc/det_loss.hip): Gaussian target heatmap, heatmap loss and the 3x3 centre-sampled box loss of a batch in one call.
  * This entry point is the value (validation curves, checkpoint selection, regression checks of converted weights); its gradient with respect to the
- * logits and the box values is cnl_detection_loss_grad_f32 below.  No reid loss.  Every step the
+ * logits and the box values is cnl_detection_loss_grad_f32 below; the tracking model's third loss, the re-ID loss, is cnl_reid_loss_f64 further down.  Every step the
  * reference does on the host in float64 is float64 here; det_loss.hip is compiled with contraction off.  tests/loss_ref.py restates the rule in numpy.
  *
  * Targets: gt_boxes [N, Gmax, 4] float64 x y w h in INPUT pixels, gt_labels [N, Gmax] int64, gt_count [N] int32 (clamped to 0..Gmax), Gmax <= 1024.
@@ -1105,8 +1105,77 @@ int cnl_detection_loss_grad_f32(const float* heat, int64_t heat_sn, int64_t heat
                                 float* grad_heat, int64_t gh_sn, int64_t gh_sc, int64_t gh_sh, int64_t gh_sw, float* grad_box, int64_t gb_sn,
                                 int64_t gb_sc, int64_t gb_sh, int64_t gb_sw, int32_t* skipped, void* workspace, size_t workspace_bytes, void* stream);
 
+/*
+ * The re-ID loss of the tracking model (reference models/fairmot.py:34-61 EmbeddingHead.compute_loss; csrc/reid_loss.hip; tests/reid_loss_ref.py restates
+ * the rule in numpy): the embedding at every box centre goes through the training-only classifier Linear(D, D, no bias) / BatchNorm1d(D) / ReLU /
+ * Linear(D, K) and a cross entropy over the K track identities.  Value and analytic gradient, float64 on the fp32 values, every summation order fixed:
+ * no atomics, no memset, the same bits on every run.  The R x K logits (R = N Gmax) are never written to memory.
+ *
+ * Inputs: reid [N, D, H, W] fp32 with the element strides of its logical axes (n, c, y, x); gt_boxes [N, Gmax, 4] float64 x y w h in INPUT pixels,
+ * gt_ids [N, Gmax] int64, gt_count [N] int32 (clamped to 0..Gmax); the classifier, fp32, dense: W1 [D, D], gamma / beta / running_mean / running_var [D],
+ * W2 [K, D], b2 [K].
+ * Rows: row r = (n, g), taken in (n, g) order.  A LIVE row has g < gt_count[n], finite box numbers, w >= 0, h >= 0, 0 <= id < K, and its cell inside the
+ * map: c = (b.x + b.w / 2) / stride, x = trunc(c) (center 0, the reference's .long()) or rint(c) (center 1: the peak cell of the detection loss's record
+ * rule), y likewise, 0 <= x <= W - 1, 0 <= y <= H - 1.  A row with g < gt_count[n] and id == ignore_index is dropped silently; any other row with
+ * g < gt_count[n] that is not live is skipped and counted.  STAT rows (those the BatchNorm statistics are taken over): the live rows, and with
+ * padded_rows = 1 also every slot g >= gt_count[n], which reads cell (0, 0) of its image and enters the statistics but not the loss (what the
+ * reference's zero-padded boxes and mask do).  R_s stat rows, M live rows.
+ * Forward, float64:  e_r = the D values at the cell;  h_j = sum_i W1[j, i] e_i by fused multiply-add, i ascending;
+ *   training = 1: mean_j = (sum over the stat rows, ascending r, of h_j) / R_s, var_j = (sum, ascending r, of (h_j - mean_j)^2) / R_s;
+ *     new_stats = fl32((1 - momentum) running + momentum (mean, var R_s / (R_s - 1)));   training = 0: mean, var = the running statistics;
+ *   a_j = (h_j - mean_j) / sqrt(var_j + bn_eps) * gamma_j + beta_j;  z_j = max(a_j, 0);
+ *   logit_k = b2_k, then fma(z_j, W2[k, j], logit_k) for j ascending;
+ *   log-sum-exp over tiles of 64 identities, tiles ascending, with a running (m, s): in a tile t = its maximum, m' = max(m, t); 16 partial sums, partial q
+ *     = exp(logit - m') of identities 4q .. 4q + 3 of the tile added in ascending order (0 beyond K); the 16 partials folded by a butterfly (partners at
+ *     distance 1, 2, 4, 8); s = s exp(m - m') + that sum, m = m';  lse_r = m + log(s);  ce_r = lse_r - logit_id;  top-1: the first of the largest logits;
+ *   total = (sum of ce_r over the live rows, ascending r) / (M + 1e-8).
+ * training = 1 with R_s < 2: total 0, per_row 0, every gradient 0, new_stats = the running statistics, counts[3] = 0 (torch raises there; a batch without
+ * identities must not stop a run).
+ * Results of cnl_reid_loss_f64: per_row [N, Gmax] float64 (ce_r, 0 for rows not in the loss; every element written), total [1] float64, counts [4] int32 =
+ * (M, top-1 hits, skipped rows, 1 when the running statistics made a step), new_stats [2, D] fp32 (NULL: not wanted).  The running statistics themselves
+ * are never written.
+ *
+ * cnl_reid_loss_grad_f32: d(scale total) / d(reid, W1, gamma, beta, W2, b2), float64 rounded ONCE to fp32.  scale: DEVICE float64 [1], read by the
+ * kernels; NULL: 1.  With p_k = exp(logit_k - lse_r):  g[r, k] = scale (p_k - [k == id_r]) / (M + 1e-8) on live rows;
+ *   grad_W2[k, j] = sum over the live rows, ascending r, of g[r, k] z[r, j];  grad_b2[k] = that sum of g[r, k];  dz[r, j] = sum_k g[r, k] W2[k, j], k ascending;
+ *   da = dz where z > 0, else 0 (the ReLU's derivative is 0 at a <= 0);  grad_beta_j = sum da, grad_gamma_j = sum da xhat (live rows, ascending r),
+ *   xhat = (h - mean) / sqrt(var + bn_eps);  dxhat = da gamma;
+ *   training = 1: dh = (R_s dxhat - sum dxhat - xhat sum(dxhat xhat)) / (R_s sqrt(var + bn_eps)) on EVERY stat row (a padded row has dxhat = 0 but
+ *   receives a gradient through the batch statistics);  training = 0: dh = dxhat / sqrt(var + bn_eps);
+ *   grad_W1[j, i] = sum over the stat rows, ascending r, of dh[r, j] e[r, i];  de[r, i] = sum_j W1[j, i] dh[r, j], j ascending;
+ *   grad_reid [N, D, H, W] with its own strides: a cell receives the sum of its stat rows' de in (n, g) order (several boxes can share a cell, padded rows
+ *   all share (0, 0)); every other element is exactly 0; every element is stored exactly once by the workgroup that owns its 8 x 32 pixel tile.
+ * Any gradient pointer may be NULL (not wanted; its launches are skipped).  skipped [1] int32 (NULL: not wanted).
+ *
+ * Limits (CNL_E_BAD_ARG outside them): 1 <= D <= 256, 2 <= K <= 2^20, Gmax <= 1024, N <= 2^16, H, W <= 2^15.  The workspace holds at least
+ * cnl_reid_loss_workspace_bytes / cnl_reid_loss_grad_workspace_bytes (N, Gmax, D) bytes (0 outside the limits) and is 16-byte aligned; float64 / int64
+ * arrays are 8-byte aligned.  Launches on `stream` only, no synchronisation, no allocation.  The struct's size is cnl_sizeof_params(5).
+ */
+typedef struct cnl_reid_loss_params {
+    double stride;             /* output stride of the map (box centres are divided by it) */
+    double bn_eps;             /* BatchNorm1d.eps */
+    double momentum;           /* BatchNorm1d.momentum (a number) */
+    int64_t ignore_index;      /* identity of a box without one: the row is dropped silently */
+    int32_t center;            /* 0 trunc, 1 round */
+    int32_t padded_rows;       /* 1: slots beyond gt_count are stat rows at cell (0, 0) */
+    int32_t training;          /* 1: batch statistics; 0: running statistics */
+    int32_t reserved;          /* 0 */
+} cnl_reid_loss_params;
+size_t cnl_reid_loss_workspace_bytes(int32_t N, int32_t Gmax, int32_t D);
+int cnl_reid_loss_f64(const float* reid, int64_t sn, int64_t sc, int64_t sh, int64_t sw, int32_t N, int32_t D, int32_t H, int32_t W, const double* gt_boxes,
+                      const int64_t* gt_ids, const int32_t* gt_count, int32_t Gmax, const float* W1, const float* gamma, const float* beta,
+                      const float* running_mean, const float* running_var, const float* W2, const float* b2, int32_t K, const cnl_reid_loss_params* p,
+                      double* per_row, double* total, int32_t* counts, float* new_stats, void* workspace, size_t workspace_bytes, void* stream);
+size_t cnl_reid_loss_grad_workspace_bytes(int32_t N, int32_t Gmax, int32_t D);
+int cnl_reid_loss_grad_f32(const float* reid, int64_t sn, int64_t sc, int64_t sh, int64_t sw, int32_t N, int32_t D, int32_t H, int32_t W,
+                           const double* gt_boxes, const int64_t* gt_ids, const int32_t* gt_count, int32_t Gmax, const float* W1, const float* gamma,
+                           const float* beta, const float* running_mean, const float* running_var, const float* W2, const float* b2, int32_t K,
+                           const cnl_reid_loss_params* p, const double* scale, float* grad_reid, int64_t gn, int64_t gc, int64_t gh, int64_t gw,
+                           float* grad_W1, float* grad_gamma, float* grad_beta, float* grad_W2, float* grad_b2, int32_t* skipped, void* workspace,
+                           size_t workspace_bytes, void* stream);
+
 int cnl_version(void);
-/* sizeof(cnl_conv_params) / sizeof(cnl_decode_params) / sizeof(cnl_deconv_params) (which = 0 / 1 / 2) and sizeof(cnl_loss_params) (which = 4; 3 is
+/* sizeof(cnl_conv_params) / sizeof(cnl_decode_params) / sizeof(cnl_deconv_params) (which = 0 / 1 / 2), sizeof(cnl_loss_params) (which = 4) and sizeof(cnl_reid_loss_params) (which = 5; 3 is
  * unused; else 0) as the library was compiled — the structs grow at the end between ABI
  * versions: a binder (ctypes, cgo, JNI ...) compares its own struct's size before the first call (ABI v12). */
 size_t cnl_sizeof_params(int32_t which);
