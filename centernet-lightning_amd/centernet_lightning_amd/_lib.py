@@ -102,6 +102,15 @@ class ReidLossParams(Structure):
                 ("padded_rows", c_int32), ("training", c_int32), ("reserved", c_int32)]
 
 
+class AugmentPlacement(Structure):
+    """cnl_augment_placement: one placement of an augmentation plan (96 bytes): a window of a source frame, where it goes in the canvas,
+    whether it is mirrored, and its Q12 colour matrix."""
+    _fields_ = [("frame", c_int32), ("x0", c_int32), ("y0", c_int32), ("w", c_int32), ("h", c_int32), ("dx0", c_int32), ("dy0", c_int32),
+                ("dw", c_int32), ("dh", c_int32), ("flip", c_int32), ("colour", c_int32 * 12), ("reserved", c_int32 * 2)]
+
+
+assert ctypes.sizeof(LetterboxFrame) == 40 and ctypes.sizeof(AugmentPlacement) == 96
+
 _REID_COMMON = [c_void_p, c_int64, c_int64, c_int64, c_int64, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int32,
                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, POINTER(ReidLossParams)]
 
@@ -180,6 +189,10 @@ _SIGNATURES = {
     "cnl_reid_loss_grad_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32]),
     "cnl_reid_loss_grad_f32": (ctypes.c_int, _REID_COMMON + [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
                                                               c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "cnl_augment_u8": (ctypes.c_int, [c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_uint32, c_uint32,
+                                      c_void_p]),
+    "cnl_augment_boxes_f64": (ctypes.c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p,
+                                             c_void_p, c_void_p, c_void_p, c_int32, c_double, c_double, c_void_p]),
     "cnl_stem_conv7x7_u8": (ctypes.c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, POINTER(c_float), POINTER(c_float), c_void_p, c_void_p,
                                            c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "cnl_stem_packed_weight_floats": (c_size_t, []),

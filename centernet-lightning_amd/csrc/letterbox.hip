@@ -36,84 +36,13 @@
 //   Measured rates and what limits them: DESIGN.md §12, §15.
 #include <algorithm>
 #include <cstdlib>
-#include "cnl_common.h"
+#include "letterbox_sampling.h"   // the sampling rule itself (shared with augment.hip): axis_coef, the table entries, PackedSource, sample_group
 
 #pragma clang fp contract(off)   // OpenCV rounds (dx + 0.5) * scale and the subtraction separately
 
 namespace cnl_letterbox {
 
-constexpr int LB_THREADS = 256;
-constexpr int LB_ROWS = 8;           // canvas rows per workgroup (the two letterbox entries)
-constexpr int LB_TILE_GROUPS = 256;  // 4-pixel groups per column tile (1024 canvas columns)
-
-typedef unsigned short u16_unaligned __attribute__((aligned(1)));
-typedef unsigned long long u64_unaligned __attribute__((aligned(1)));
-// the frames' pointers come out of the table, so the compiler cannot tell their address space: name it (global_load, not flat_load)
-typedef const __attribute__((address_space(1))) unsigned char* gbytes;
-typedef const __attribute__((address_space(1))) u16_unaligned* gpairs;
-typedef const __attribute__((address_space(1))) u64_unaligned* gwords;
 static_assert(sizeof(cnl_yuv420_frame) == 72, "cnl_yuv420_frame is 72 bytes");
-
-// resize_bilinear_u8_kernel's coefficient rule for one axis position
-__device__ __forceinline__ void axis_coef(int d, double scale, int& s, float& f) {
-    f = (float)(((double)d + 0.5) * scale - 0.5);
-    s = (int)floorf(f);
-    f -= (float)s;
-}
-
-// packed C-channel bytes (cnl_letterbox_frame, 40 bytes); the column table keeps the byte offset of the left tap within a row
-template <int CH>
-struct PackedSource {
-    static constexpr int C = CH;
-    typedef cnl_letterbox_frame Frame;
-    struct Params {};
-    struct Taps {
-        unsigned long long t0[4], t1[4];         // per pixel, upper / lower source row; bytes 0..C-1: left tap, C..2C-1: right tap
-    };
-    const Frame& f;
-    const gbytes src;
-    const int row_bytes;                         // bytes of a source row that belong to the frame (row_stride may be larger)
-    const bool wide;
-
-    __device__ __forceinline__ PackedSource(const Frame& f, const Params&) : f(f), src((gbytes)f.src), row_bytes(f.w * C), wide(row_bytes >= 8) {}
-    static __device__ __forceinline__ int column(int sx) { return sx * C; }
-
-    // a border pixel (c4[p].x < 0) reads its row's first bytes; the caller drops them
-    __device__ __forceinline__ void load(int y0, int y1, const int2 (&c4)[4], Taps& t) const {
-        const gbytes r0 = src + (size_t)y0 * f.row_stride;
-        const gbytes r1 = src + (size_t)y1 * f.row_stride;
-        if (wide) {
-#pragma unroll
-            for (int p = 0; p < 4; ++p) {
-                const int x0 = max(c4[p].x, 0), o = min(x0, row_bytes - 8);
-                t.t0[p] = *(gwords)(r0 + o);
-                t.t1[p] = *(gwords)(r1 + o);
-            }
-#pragma unroll
-            for (int p = 0; p < 4; ++p) {
-                const int x0 = max(c4[p].x, 0), sh = (x0 - min(x0, row_bytes - 8)) * 8;
-                t.t0[p] >>= sh;
-                t.t1[p] >>= sh;
-            }
-        } else {
-            for (int p = 0; p < 4; ++p) {
-                const int x0 = max(c4[p].x, 0);
-                t.t0[p] = t.t1[p] = 0;
-                for (int b = 0; b < 2 * C && x0 + b < row_bytes; ++b) {
-                    t.t0[p] |= (unsigned long long)r0[x0 + b] << (8 * b);
-                    t.t1[p] |= (unsigned long long)r1[x0 + b] << (8 * b);
-                }
-            }
-        }
-    }
-    // at the last column the right tap's bytes are zeros shifted in: its weight a1 is 0 there
-    __device__ __forceinline__ void taps(const Taps& t, int p, unsigned (&v)[4]) const {
-        v[0] = (unsigned)t.t0[p];
-        v[1] = (unsigned)(t.t0[p] >> (8 * C));
-        v[2] = (unsigned)t.t1[p];
-        v[3] = (unsigned)(t.t1[p] >> (8 * C));
-    }
-};
 
 // YUV 4:2:0 planes (cnl_yuv420_frame, 72 bytes): the record's window (x0, y0, h, w) lies inside the frame, and chroma is addressed in
 // FRAME coordinates; the column table keeps the window column of the left tap
@@ -193,35 +122,14 @@ __global__ __launch_bounds__(LB_THREADS) void letterbox_kernel(const typename So
     const int x_begin = g_begin * 4, n_cols = n_groups * 4;
     const int row_begin = rblk * ROWS, n_rows = min(ROWS, height - row_begin);
 
-    // OpenCV: inv_scale = dsize / ssize (double), scale = 1 / inv_scale
-    const double scale_x = 1.0 / ((double)f.new_w / (double)f.w), scale_y = 1.0 / ((double)f.new_h / (double)f.h);
+    const double scale_x = axis_scale(f.new_w, f.w), scale_y = axis_scale(f.new_h, f.h);
     for (int i = threadIdx.x; i < n_cols; i += LB_THREADS) {
         const int dx = x_begin + i - f.pad_left;
-        int2 e = make_int2(-1, 0);
-        if (dx >= 0 && dx < f.new_w) {
-            int sx;
-            float fx;
-            axis_coef(dx, scale_x, sx, fx);
-            if (sx < 0) { fx = 0.f; sx = 0; }
-            if (sx >= f.w - 1) { fx = 0.f; sx = f.w - 1; }
-            const int a0 = (short)__float2int_rn((1.f - fx) * 2048.f), a1 = (short)__float2int_rn(fx * 2048.f);
-            e = make_int2(Source::column(sx), (a0 & 0xffff) | (a1 << 16));
-        }
-        col[i] = e;
+        col[i] = dx >= 0 && dx < f.new_w ? column_entry<Source>(dx, scale_x, f.w) : make_int2(-1, 0);
     }
     if ((int)threadIdx.x < n_rows) {
         const int dy = row_begin + (int)threadIdx.x - f.pad_top;
-        int4 e = make_int4(-1, 0, 0, 0);
-        if (dy >= 0 && dy < f.new_h) {
-            int sy;
-            float fy;
-            axis_coef(dy, scale_y, sy, fy);       // fy is not clamped: the two source rows are clipped to the frame (window) instead
-            e.x = min(max(sy, 0), f.h - 1);
-            e.y = min(max(sy + 1, 0), f.h - 1);
-            e.z = (short)__float2int_rn((1.f - fy) * 2048.f);
-            e.w = (short)__float2int_rn(fy * 2048.f);
-        }
-        row[threadIdx.x] = e;
+        row[threadIdx.x] = dy >= 0 && dy < f.new_h ? row_entry(dy, scale_y, f.h) : make_int4(-1, 0, 0, 0);
     }
     __syncthreads();
 
@@ -237,32 +145,9 @@ __global__ __launch_bounds__(LB_THREADS) void letterbox_kernel(const typename So
         if (rc.x >= 0) {
             const int4 c01 = reinterpret_cast<const int4*>(col)[g * 2], c23 = reinterpret_cast<const int4*>(col)[g * 2 + 1];
             const int2 c4[4] = {make_int2(c01.x, c01.y), make_int2(c01.z, c01.w), make_int2(c23.x, c23.y), make_int2(c23.z, c23.w)};
-            typename Source::Taps loaded;
-            source.load(rc.x, rc.y, c4, loaded);
-#pragma unroll
-            for (int p = 0; p < 4; ++p) {
-                const int a0 = (short)(c4[p].y & 0xffff), a1 = c4[p].y >> 16;
-                unsigned t[4];
-                source.taps(loaded, p, t);
-                unsigned v4 = 0;
-#pragma unroll
-                for (int c = 0; c < C; ++c) {
-                    const int d0 = (int)((t[0] >> (8 * c)) & 255u) * a0 + (int)((t[1] >> (8 * c)) & 255u) * a1;
-                    const int d1 = (int)((t[2] >> (8 * c)) & 255u) * a0 + (int)((t[3] >> (8 * c)) & 255u) * a1;
-                    const int v = (((rc.z * (d0 >> 4)) >> 16) + ((rc.w * (d1 >> 4)) >> 16) + 2) >> 2;
-                    v4 |= (unsigned)min(max(v, 0), 255) << (8 * c);
-                }
-                if (c4[p].x >= 0) px[p] = v4;
-            }
+            sample_group(source, rc, c4, px);
         }
-        unsigned* dst = reinterpret_cast<unsigned*>(canvas + ((size_t)(row_begin + r) * width + (size_t)(g_begin + g) * 4) * C);
-#pragma unroll
-        for (int k = 0; k < C; ++k) {            // word k of the group: byte 4k + b = channel (4k + b) % C of pixel (4k + b) / C
-            unsigned v = 0;
-#pragma unroll
-            for (int b = 0; b < 4; ++b) v |= ((px[(4 * k + b) / C] >> (8 * ((4 * k + b) % C))) & 255u) << (8 * b);
-            dst[k] = v;
-        }
+        store_group<C>(reinterpret_cast<unsigned*>(canvas + ((size_t)(row_begin + r) * width + (size_t)(g_begin + g) * 4) * C), px);
     }
 }
 

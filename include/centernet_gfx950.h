@@ -1174,6 +1174,74 @@ int cnl_reid_loss_grad_f32(const float* reid, int64_t sn, int64_t sc, int64_t sh
                            float* grad_W1, float* grad_gamma, float* grad_beta, float* grad_W2, float* grad_b2, int32_t* skipped, void* workspace,
                            size_t workspace_bytes, void* stream);
 
+/*
+ * Training augmentation of a batch: the reference's albumentations Compose (HorizontalFlip, RandomResizedCrop, ColorJitter, Cutout:
+ * datasets/builder.py::parse_transforms, one image at a time on the host) and a batch-level mosaic (datasets/transforms.py declares
+ * Mosaic.__call__ with an empty body) as TWO launches that are a deterministic function of a PLAN.  All randomness is drawn on the host into
+ * the plan; nothing below is random, nothing goes to the host, no atomics: the same plan gives the same bytes on every run.
+ *
+ * The plan of N canvases of height x width (new entry points and records only: the ABI version does not change):
+ *   places   device array of N * 4 placement records (four slots per canvas), 96 bytes each, 8-byte aligned:
+ *     offset  0  int32 frame            index of the source frame, 0..F-1
+ *     offset  4  int32 x0, y0, w, h     the source window inside that frame: w, h >= 1, x0, y0 >= 0, x0 + w <= frame w, y0 + h <= frame h
+ *     offset 20  int32 dx0, dy0, dw, dh the destination rectangle inside the canvas: dx0 % 4 == 0, dw % 4 == 0, dw >= 4, dh >= 1
+ *     offset 36  int32 flip             != 0: mirrored left-right inside the rectangle
+ *     offset 40  int32 colour[12]       Q12 colour matrix: colour[3c + k] (|.| <= 32767) weighs source channel k in channel c; colour[9 + c]
+ *                                       (|.| <= 2^21) is channel c's offset, already multiplied by 4096.  Identity: 4096 at 0, 4, 8, else 0.
+ *     offset 88  int32 reserved[2]      0
+ *   n_place  N int32 in device memory: the live slots of canvas n are 0 .. n_place[n] - 1.  The kernels clamp it to 0..max_place, and
+ *            max_place (1..4, a host argument: the largest n_place of the plan) is what the host can check.
+ *   holes    N * 16 slots of four int32 (x0, y0, w, h) in canvas pixels, 16-byte aligned, or NULL for no holes; w <= 0 or h <= 0 marks a dead
+ *            slot.  Holes may overlap each other and the canvas edge (x0, y0 may be negative); they are clipped to the canvas.
+ * The rectangles of one canvas should be disjoint; where two overlap, the lower slot wins.  A DEGENERATE record — frame outside 0..F-1, a
+ * window that is empty or leaves its frame, a rectangle that is empty, misaligned or leaves the canvas — is not a fault: it paints nothing
+ * (cnl_augment_u8) and carries no boxes (cnl_augment_boxes_f64, which cannot see frame sizes and judges frame, w, h, dw, dh only).
+ *
+ * cnl_augment_u8.  frames: device array of F WHOLE-FRAME cnl_letterbox_frame records of 3-channel packed frames (only src, h, w and
+ * row_stride are read).  out: [N, height, width, 3] u8, 4-byte aligned, height in 1..32768, width in 4..32768 a multiple of 4; every byte is
+ * written exactly once in one launch (no memset before it).  The value of canvas pixel (y, x), byte c = bits 8c..8c+7 of a word:
+ *   inside the rectangle of placement p, at dy = y - dy0, dx = x - dx0: the cv2 INTER_LINEAR resize of the window (h, w) -> (dh, dw) at
+ *     (dy, dx') with dx' = flip ? dw - 1 - dx : dx, in exactly the arithmetic of cnl_letterbox_bilinear_u8 (cnl_resize_bilinear_u8's 8-bit
+ *     fixed-point rule, the taps clipped to the window as cnl_crop_boxes_u8 clips them), giving R, G, B; then for c in 0..2, in 32-bit integers,
+ *     >> an arithmetic shift (floor):
+ *         out_c = clamp((colour[3c] * R + colour[3c + 1] * G + colour[3c + 2] * B + colour[9 + c] + 2048) >> 12, 0, 255)
+ *   in no rectangle: fill_rgba
+ *   in a hole: hole_fill_rgba, overriding both.
+ * A placement with flip = 0, the identity matrix and no hole is therefore bit for bit what cnl_letterbox_bilinear_u8 writes for the record
+ * (h, w, new_h = dh, new_w = dw, pad_top = dy0, pad_left = dx0) on the sliced frame.  YUV sources are not taken.
+ *
+ * cnl_augment_boxes_f64.  The targets in the padded forms of cnl_detection_loss_f64: boxes [F, Gmax, 4] f64 (x, y, w, h: top-left corner and
+ * size in the SOURCE frame's pixels), labels [F, Gmax] i64, ids [F, Gmax] i64 (optional, given together with out_ids), count [F] i32 (clamped
+ * to 0..Gmax).  Outputs: out_boxes [N, Gout, 4] f64 in CANVAS pixels, out_labels / out_ids [N, Gout] i64, out_count [N] i32, with
+ * Gout >= max_place * Gmax.  For canvas n, placements in slot order and, within a placement, boxes j < count[frame] in source order; every step
+ * is ONE float64 operation in the order written (no fused multiply-add):
+ *     sx = dw / w, sy = dh / h                                  (the int32 values converted to double)
+ *     u1 = (x - x0) * sx, u2 = ((x + bw) - x0) * sx;  v1 = (y - y0) * sy, v2 = ((y + bh) - y0) * sy
+ *     flip != 0: t = dw - u2, u2 = dw - u1, u1 = t
+ *     full = (u2 - u1) * (v2 - v1)
+ *     cu1 = min(max(u1, 0), dw), cu2 = min(max(u2, 0), dw), cv1 = min(max(v1, 0), dh), cv2 = min(max(v2, 0), dh)
+ *     cw = cu2 - cu1, ch = cv2 - cv1, area = cw * ch
+ * The box is KEPT iff x, y, bw, bh, u1, u2, v1, v2 and full are all finite, cw > 0, ch > 0, area >= min_area (albumentations'
+ * BboxParams(min_area); the reference uses 1), area >= min_visibility * full, and its label is >= 0.  A kept box is written as
+ * (dx0 + cu1, dy0 + cv1, cw, ch) with its label and id.  Kept boxes are compacted STABLY (slot order, then source order) into slots
+ * 0 .. out_count[n] - 1; every slot beyond is exactly zero (boxes, labels, ids).  Holes do not touch boxes (as in albumentations).
+ *
+ * Both: N, F in 0..65535; N == 0 is a no-op.  CNL_E_BAD_ARG with a message for everything the host can see, before anything is launched.
+ */
+typedef struct cnl_augment_placement {
+    int32_t frame;
+    int32_t x0, y0, w, h;
+    int32_t dx0, dy0, dw, dh;
+    int32_t flip;
+    int32_t colour[12];
+    int32_t reserved[2];
+} cnl_augment_placement;
+int cnl_augment_u8(const void* frames, int32_t F, const void* places, const int32_t* n_place, int32_t max_place, const int32_t* holes, uint8_t* out,
+                   int32_t N, int32_t height, int32_t width, uint32_t fill_rgba, uint32_t hole_fill_rgba, void* stream);
+int cnl_augment_boxes_f64(const void* places, const int32_t* n_place, int32_t max_place, int32_t N, int32_t F, const double* boxes,
+                          const int64_t* labels, const int64_t* ids, const int32_t* count, int32_t Gmax, double* out_boxes, int64_t* out_labels,
+                          int64_t* out_ids, int32_t* out_count, int32_t Gout, double min_area, double min_visibility, void* stream);
+
 int cnl_version(void);
 /* sizeof(cnl_conv_params) / sizeof(cnl_decode_params) / sizeof(cnl_deconv_params) (which = 0 / 1 / 2), sizeof(cnl_loss_params) (which = 4) and sizeof(cnl_reid_loss_params) (which = 5; 3 is
  * unused; else 0) as the library was compiled — the structs grow at the end between ABI
