@@ -19,6 +19,7 @@ from .coco_eval import CocoEvaluator
 from .mot_eval import MotEvaluator, evaluate_mot_tracking_sequence
 from .loss import (DetectionLoss, LossMeter, ReIDLoss, TrackingLoss, detection_loss, detection_loss_grad, reid_loss, reid_loss_grad, render_targets)
 from .augment import AugmentPlan, TrainAugment, augment_batch, sample_augment
+from .warp import TrainWarp, WarpPlan, affine_matrix, sample_warp, warp_batch, warp_inverse
 from .export import TraceableCenterNet, export_onnx, export_torchscript
 
 __all__ = ["CenterNet", "build_centernet", "load_config", "DetectionOutput", "TrackingOutput", "decode",
@@ -29,4 +30,5 @@ __all__ = ["CenterNet", "build_centernet", "load_config", "DetectionOutput", "Tr
            "draw_detections", "DEFAULT_PALETTE", "rgb_to_yuv", "flip_merge", "mirror_append_uint8", "CocoEvaluator",
            "MotEvaluator", "evaluate_mot_tracking_sequence", "LossMeter", "detection_loss", "render_targets", "DetectionLoss",
            "detection_loss_grad", "reid_loss", "reid_loss_grad", "ReIDLoss", "TrackingLoss",
-           "augment_batch", "sample_augment", "AugmentPlan", "TrainAugment"]
+           "augment_batch", "sample_augment", "AugmentPlan", "TrainAugment",
+           "warp_batch", "sample_warp", "WarpPlan", "TrainWarp", "affine_matrix", "warp_inverse"]

@@ -109,7 +109,15 @@ class AugmentPlacement(Structure):
                 ("dw", c_int32), ("dh", c_int32), ("flip", c_int32), ("colour", c_int32 * 12), ("reserved", c_int32 * 2)]
 
 
-assert ctypes.sizeof(LetterboxFrame) == 40 and ctypes.sizeof(AugmentPlacement) == 96
+class WarpPlacement(Structure):
+    """cnl_warp_placement: one placement of an affine augmentation plan (192 bytes): the clip window in a source frame, where it goes in the
+    canvas, its Q12 colour matrix, the Q20 inverse map (canvas pixel -> source pixel index) and the float64 forward map."""
+    _fields_ = [("frame", c_int32), ("x0", c_int32), ("y0", c_int32), ("w", c_int32), ("h", c_int32), ("dx0", c_int32), ("dy0", c_int32),
+                ("dw", c_int32), ("dh", c_int32), ("reserved0", c_int32), ("colour", c_int32 * 12), ("inv", c_int64 * 6), ("fwd", c_double * 6),
+                ("reserved", c_int32 * 2)]
+
+
+assert ctypes.sizeof(LetterboxFrame) == 40 and ctypes.sizeof(AugmentPlacement) == 96 and ctypes.sizeof(WarpPlacement) == 192
 
 _REID_COMMON = [c_void_p, c_int64, c_int64, c_int64, c_int64, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int32,
                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, POINTER(ReidLossParams)]
@@ -193,6 +201,10 @@ _SIGNATURES = {
                                       c_void_p]),
     "cnl_augment_boxes_f64": (ctypes.c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p,
                                              c_void_p, c_void_p, c_void_p, c_int32, c_double, c_double, c_void_p]),
+    "cnl_augment_warp_u8": (ctypes.c_int, [c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_uint32, c_uint32,
+                                           c_uint32, c_void_p]),
+    "cnl_augment_warp_boxes_f64": (ctypes.c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
+                                                  c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_double, c_double, c_void_p]),
     "cnl_stem_conv7x7_u8": (ctypes.c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, POINTER(c_float), POINTER(c_float), c_void_p, c_void_p,
                                            c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "cnl_stem_packed_weight_floats": (c_size_t, []),

@@ -10,7 +10,8 @@ Python).  The rules are stated in include/centernet_gfx950.h and restated in num
 
 Two stated deviations from albumentations' ColorJitter, so that the whole jitter is ONE integer 3 x 4 matrix per pixel and needs no reduction
 over the image (what DALI's ColorTwist does): contrast pivots on the constant `contrast_center` instead of the image's mean, and hue turns in
-YIQ instead of HSV.  Rotation, shear (Affine), RandomCrop / SmallestMaxSize, MixUp and YUV sources are out of scope.
+YIQ instead of HSV.  Rotation, shear (Affine) and RandomCrop / SmallestMaxSize are warp.py's (a rule and a kernel of their own; this module's
+behaviour is unchanged); MixUp and YUV sources are out of scope.
 """
 import ctypes
 import dataclasses
@@ -384,9 +385,15 @@ def augment_batch(frames, plan, targets=None, fill=(0, 0, 0), hole_fill=(0, 0, 0
     then source order; slots beyond count are zero.  Holes do not touch boxes.  out: optionally a dict of the caller's own buffers to
     write into, by the names "canvas", "boxes", "labels", "ids", "count" (a training loop reuses them; every element is written).
     One pinned upload, two launches, no device sync."""
-    what = "augment_batch"
-    if not isinstance(plan, AugmentPlan):
-        raise ValueError(f"{what}: plan must be an AugmentPlan, got {type(plan).__name__}")
+    return _batch("augment_batch", AugmentPlan, 12, "cnl_augment_u8", "cnl_augment_boxes_f64", (fill, hole_fill), frames, plan, targets, min_area, min_visibility,
+                  out)
+
+
+def _batch(what, plan_type, record_words, image_entry, boxes_entry, fills, frames, plan, targets, min_area, min_visibility, out):
+    """The host path of augment_batch and warp.warp_batch: a plan of `plan_type` whose records are record_words int64 words, the image
+    entry (which takes the colour words of `fills` in order) and the box entry."""
+    if not isinstance(plan, plan_type):
+        raise ValueError(f"{what}: plan must be {'an' if plan_type.__name__[0] in 'AEIOU' else 'a'} {plan_type.__name__}, got {type(plan).__name__}")
     plan.check()
     for name, v in (("min_area", min_area), ("min_visibility", min_visibility)):
         if isinstance(v, bool) or not isinstance(v, (int, float)) or math.isnan(v):
@@ -399,7 +406,7 @@ def augment_batch(frames, plan, targets=None, fill=(0, 0, 0), hole_fill=(0, 0, 0
         raise ValueError(f"{what}: frames must have 3 channels, got {src.C}")
     if list(src.sizes) != list(plan.sizes):
         raise ValueError(f"{what}: the plan was drawn for frames of sizes {plan.sizes}, got {list(src.sizes)}")
-    word, hole_word = _frames.fill_word(fill, 3), _frames.fill_word(hole_fill, 3)
+    words = [_frames.fill_word(f, 3) for f in fills]
     max_place = plan.max_place
 
     host = None                                  # a list of targets travels in the same upload
@@ -415,9 +422,9 @@ def augment_batch(frames, plan, targets=None, fill=(0, 0, 0), hole_fill=(0, 0, 0
         raise ValueError(f"{what}: {max_place} placements x Gmax = {Gmax} boxes give Gout = {max_place * Gmax}; at most {MAX_PER_IMAGE} per image "
                          "are supported")
 
-    # [F x 5] frame records | (pad to 16 bytes) | [N x 4 x 12] placements | [N x 16 x 2] holes | n_place | boxes | labels | ids | count, in int64 words
+    # [F x 5] frame records | (pad to 16 bytes) | [N x 4 x record_words] placements | [N x 16 x 2] holes | n_place | boxes | labels | ids | count, in int64 words
     o_place = F * 5 + (F * 5) % 2
-    o_holes = o_place + N * MAX_PLACE * 12
+    o_holes = o_place + N * MAX_PLACE * record_words
     o_np = o_holes + N * MAX_HOLES * 2
     o_boxes = o_np + (N + 1) // 2
     o_labels = o_ids = o_count = end = o_boxes
@@ -428,7 +435,7 @@ def augment_batch(frames, plan, targets=None, fill=(0, 0, 0), hole_fill=(0, 0, 0
         end = o_count + (F + 1) // 2
     windows = src.whole()
     buf = _gather.pack_records(windows, *src.records(windows), tail_words=end - F * 5)
-    plan.pack(buf[o_place:o_holes].view(np.int32).reshape(N * MAX_PLACE, 24), buf[o_holes:o_np].view(np.int32).reshape(N * MAX_HOLES, 4),
+    plan.pack(buf[o_place:o_holes].view(np.int32).reshape(N * MAX_PLACE, 2 * record_words), buf[o_holes:o_np].view(np.int32).reshape(N * MAX_HOLES, 4),
               buf[o_np:o_boxes].view(np.int32)[:N])
     if host is not None:
         buf[o_boxes:o_labels].view(np.float64)[:] = host[0].reshape(-1)
@@ -443,8 +450,8 @@ def augment_batch(frames, plan, targets=None, fill=(0, 0, 0), hole_fill=(0, 0, 0
         canvas = _out(out, "canvas", torch.uint8, (N, plan.height, plan.width, 3), dev, what)
         stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         places, n_place = d[o_place:o_holes], d[o_np:o_boxes]
-        _lib.check(lib.cnl_augment_u8(d.data_ptr(), F, places.data_ptr(), n_place.data_ptr(), max_place, d[o_holes:o_np].data_ptr(), canvas.data_ptr(), N,
-                                      plan.height, plan.width, word, hole_word, stream), "cnl_augment_u8")
+        _lib.check(getattr(lib, image_entry)(d.data_ptr(), F, places.data_ptr(), n_place.data_ptr(), max_place, d[o_holes:o_np].data_ptr(), canvas.data_ptr(),
+                                             N, plan.height, plan.width, *words, stream), image_entry)
         if targets is None:
             return canvas, None
         if host is not None:
@@ -457,10 +464,10 @@ def augment_batch(frames, plan, targets=None, fill=(0, 0, 0), hole_fill=(0, 0, 0
                "count": _out(out, "count", torch.int32, (N,), dev, what)}
         if with_ids:
             res["ids"] = _out(out, "ids", torch.int64, (N, Gout), dev, what)
-        _lib.check(lib.cnl_augment_boxes_f64(places.data_ptr(), n_place.data_ptr(), max_place, N, F, t_boxes.data_ptr(), t_labels.data_ptr(),
+        _lib.check(getattr(lib, boxes_entry)(places.data_ptr(), n_place.data_ptr(), max_place, N, F, t_boxes.data_ptr(), t_labels.data_ptr(),
                                              t_ids.data_ptr() if with_ids else None, t_count.data_ptr(), Gmax, res["boxes"].data_ptr(),
                                              res["labels"].data_ptr(), res["ids"].data_ptr() if with_ids else None, res["count"].data_ptr(), Gout,
-                                             float(min_area), float(min_visibility), stream), "cnl_augment_boxes_f64")
+                                             float(min_area), float(min_visibility), stream), boxes_entry)
     return canvas, res
 
 
@@ -479,6 +486,43 @@ def _frame_sizes(frames):
 
 _SETTINGS = ("mosaic", "scale", "ratio", "flip", "brightness", "contrast", "saturation", "hue", "contrast_center", "cutout", "crop")
 _IGNORED = ("Normalize",)                        # the stem and preprocess_uint8 normalise
+
+
+def _config_items(transforms, unsupported):
+    """The reference's YAML transform list in its forms ([{name, params}], `init_args` for `params`, or a {name: params} mapping)
+    -> [(name, params dict)]."""
+    if unsupported not in ("raise", "skip"):
+        raise ValueError(f"unsupported must be 'raise' or 'skip', got {unsupported!r}")
+    if isinstance(transforms, dict):
+        return [(name, dict(params or {})) for name, params in transforms.items()]
+    items = []
+    for t in transforms or []:
+        if not isinstance(t, dict) or "name" not in t:
+            raise ValueError(f"a transform must be a mapping with 'name', got {t!r}")
+        items.append((t["name"], dict(t.get("params", t.get("init_args")) or {})))
+    return items
+
+
+def _read_common(name, params, settings, size):
+    """One transform that TrainAugment and warp.TrainWarp read alike, into `settings` (and `size`, the canvas it names) -> whether it was one."""
+    if name == "HorizontalFlip":
+        settings["flip"] = float(params.get("p", 0.5))
+    elif name in ("RandomResizedCrop", "Resize"):
+        size.clear()
+        size.update({k: int(params[k]) for k in ("height", "width") if k in params})
+        settings["crop"] = name == "RandomResizedCrop"
+        if name == "RandomResizedCrop":
+            settings["scale"] = tuple(params.get("scale", (0.08, 1.0)))
+            settings["ratio"] = tuple(params.get("ratio", (3 / 4, 4 / 3)))
+    elif name == "ColorJitter":
+        for k in ("brightness", "contrast", "saturation", "hue"):
+            v = params.get(k, 0.0)
+            settings[k] = tuple(v) if isinstance(v, (list, tuple)) else v
+    elif name == "Cutout":
+        settings["cutout"] = (int(params.get("num_holes", 8)), int(params.get("max_h_size", 8)), int(params.get("max_w_size", 8)))
+    elif name not in _IGNORED:
+        return False
+    return True
 
 
 class TrainAugment:
@@ -512,36 +556,11 @@ class TrainAugment:
         Cutout.{num_holes, max_h_size, max_w_size}; Resize.{height, width} -> crop=False; Normalize is accepted and ignored (the stem and
         preprocess_uint8 normalise).  Any other name (Affine, RandomCrop, ...) raises ValueError naming it, or with unsupported="skip" is
         listed in .skipped.  `height` / `width` override the size the list names."""
-        if unsupported not in ("raise", "skip"):
-            raise ValueError(f"unsupported must be 'raise' or 'skip', got {unsupported!r}")
-        if isinstance(transforms, dict):
-            items = [(name, params) for name, params in transforms.items()]
-        else:
-            items = []
-            for t in transforms or []:
-                if not isinstance(t, dict) or "name" not in t:
-                    raise ValueError(f"a transform must be a mapping with 'name', got {t!r}")
-                items.append((t["name"], t.get("params", t.get("init_args"))))
         settings, skipped, size = {"flip": 0.0, "crop": False}, [], {}
-        for name, params in items:
-            params = dict(params or {})
-            if name == "HorizontalFlip":
-                settings["flip"] = float(params.get("p", 0.5))
-            elif name in ("RandomResizedCrop", "Resize"):
-                size = {k: int(params[k]) for k in ("height", "width") if k in params}
-                settings["crop"] = name == "RandomResizedCrop"
-                if name == "RandomResizedCrop":
-                    settings["scale"] = tuple(params.get("scale", (0.08, 1.0)))
-                    settings["ratio"] = tuple(params.get("ratio", (3 / 4, 4 / 3)))
-            elif name == "ColorJitter":
-                for k in ("brightness", "contrast", "saturation", "hue"):
-                    v = params.get(k, 0.0)
-                    settings[k] = tuple(v) if isinstance(v, (list, tuple)) else v
-            elif name == "Cutout":
-                settings["cutout"] = (int(params.get("num_holes", 8)), int(params.get("max_h_size", 8)), int(params.get("max_w_size", 8)))
-            elif name in _IGNORED:
+        for name, params in _config_items(transforms, unsupported):
+            if _read_common(name, params, settings, size):
                 continue
-            elif unsupported == "skip":
+            if unsupported == "skip":
                 skipped.append(name)
             else:
                 raise ValueError(f"TrainAugment.from_config: transform {name!r} is not supported (HorizontalFlip, RandomResizedCrop, ColorJitter, "

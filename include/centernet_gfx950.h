@@ -1242,6 +1242,74 @@ int cnl_augment_boxes_f64(const void* places, const int32_t* n_place, int32_t ma
                           const int64_t* labels, const int64_t* ids, const int32_t* count, int32_t Gmax, double* out_boxes, int64_t* out_labels,
                           int64_t* out_ids, int32_t* out_count, int32_t Gout, double min_area, double min_visibility, void* stream);
 
+/*
+ * Affine training augmentation: the geometric transforms of the reference's training lists that are not separable — albumentations' Affine
+ * (scale, rotate, shear, translate), and with it RandomResizedCrop / RandomCrop / SmallestMaxSize and HorizontalFlip — composed by the host
+ * into ONE affine map per placement, so that every canvas pixel is resampled ONCE.  The plan, n_place, max_place, holes, the canvas, the
+ * limits, the degenerate-record rule and the no-op N == 0 are those of cnl_augment_u8 / cnl_augment_boxes_f64 above; the record differs
+ * (new entry points and a new record only: the ABI version does not change):
+ *   places   device array of N * 4 warp records, 192 bytes each, 8-byte aligned:
+ *     offset   0  int32  frame
+ *     offset   4  int32  x0, y0, w, h      the CLIP window in the source frame (the whole frame: 0, 0, frame w, frame h); bounds as above
+ *     offset  20  int32  dx0, dy0, dw, dh  the destination rectangle; bounds as above
+ *     offset  36  int32  reserved0         0
+ *     offset  40  int32  colour[12]        the Q12 matrix of cnl_augment_placement, same bounds
+ *     offset  88  int64  inv[6]            Q20 inverse map: canvas pixel (dx, dy) of the rectangle -> source pixel INDEX
+ *     offset 136  double fwd[6]            forward map: continuous source-frame coordinates -> continuous rectangle coordinates
+ *     offset 184  int32  reserved[2]       0
+ * A mirror is not a field: the host folds it into both maps.  A record is also DEGENERATE (paints nothing, carries no boxes) when
+ * |inv[0]|, |inv[1]|, |inv[3]| or |inv[4]| > 2^30 or |inv[2]| or |inv[5]| > 2^44.
+ *
+ * cnl_augment_warp_u8.  cnl_augment_u8's arguments with warp records and border_rgba, the colour of everything outside the clip window.
+ * Inside the rectangle of placement p, at dx = x - dx0, dy = y - dy0, all in exact integers (>> an arithmetic shift: floor):
+ *     X  = inv[0]*dx + inv[1]*dy + inv[2]        Y  = inv[3]*dx + inv[4]*dy + inv[5]        (int64)
+ *     sx = X >> 20,  sy = Y >> 20
+ *     a1 = (X >> 9) & 2047, a0 = 2048 - a1       b1 = (Y >> 9) & 2047, b0 = 2048 - b1
+ *     tap(i, j), i, j in {0, 1}: channel c of frame pixel (sx + i, sy + j) if x0 <= sx+i < x0+w and y0 <= sy+j < y0+h, else byte c of border_rgba
+ *     t = tap(0,0)*a0 + tap(1,0)*a1              u = tap(0,1)*a0 + tap(1,1)*a1
+ *     v = (t*b0 + u*b1 + 2^21) >> 22             (fits int32; 0..255 without a clamp)
+ * giving (R, G, B) = v; then cnl_augment_u8's colour step, unchanged — so the border is jittered too, as albumentations' ColorJitter after
+ * Affine does.  In no rectangle: fill_rgba; in a hole: hole_fill_rgba; where rectangles overlap the lower slot wins.  Every canvas byte is
+ * written exactly once in one launch.  This rule is deliberately NOT cv2.warpAffine's (5-bit weights from a 10-bit table of rounded
+ * coordinates) and NOT the letterbox rule (cv2 INTER_LINEAR resize with separable float-derived weights): it is the cheapest exact-integer
+ * rule a rotated gather admits.  Consequences: an identity or integer-translation map copies source bytes exactly; quarter turns and mirrors
+ * are exact permutations.  No frame byte outside [row start, row start + 3 * frame w) of a frame row is read, and a pixel whose four taps
+ * all lie outside the window reads nothing.
+ *
+ * The host rule warp_inverse(fwd) -> inv, in float64, each operation rounded on its own, in the order written:
+ *     det = fwd[0]*fwd[4] - fwd[1]*fwd[3];  A00 = fwd[4]/det, A01 = -fwd[1]/det, A10 = -fwd[3]/det, A11 = fwd[0]/det  (the 2 x 2 adjugate)
+ *     A02 = -(A00*fwd[2] + A01*fwd[5]),  A12 = -(A10*fwd[2] + A11*fwd[5])
+ *     inv[0,1,3,4] = rint(A_ij * 2^20)
+ *     inv[2] = rint((((0.5*A00 + 0.5*A01) + A02) - 0.5) * 2^20),  inv[5] = rint((((0.5*A10 + 0.5*A11) + A12) - 0.5) * 2^20)
+ * the pixel-centre convention: pixel k covers [k, k + 1).  A singular or non-finite map, or one outside the bounds above, is refused.
+ *
+ * cnl_augment_warp_boxes_f64.  cnl_augment_boxes_f64's arguments with warp records.  Every step is ONE float64 operation in the order
+ * written (no fused multiply-add):
+ *     corners (X, Y) in the order a = (x, y), b = (x+bw, y), c = (x, y+bh), d = (x+bw, y+bh)
+ *     u_k = (fwd[0]*X + fwd[1]*Y) + fwd[2],   v_k = (fwd[3]*X + fwd[4]*Y) + fwd[5]
+ *     u1 = min(min(min(u_a, u_b), u_c), u_d), u2 = the same with max;  v1, v2 likewise
+ * the enclosing box (albumentations' rotate_method="largest_box"); from full = (u2 - u1)*(v2 - v1) on it is cnl_augment_boxes_f64's rule
+ * exactly (clip to [0, dw] x [0, dh]; KEPT iff x, y, bw, bh, every u_k and v_k and full are finite, cw > 0, ch > 0, area >= min_area,
+ * area >= min_visibility * full, label >= 0; written as (dx0 + cu1, dy0 + cv1, cw, ch); compacted STABLY; every slot beyond is zero).  This
+ * entry judges a record by frame, w, h, dw, dh and the bounds of inv.
+ */
+typedef struct cnl_warp_placement {
+    int32_t frame;
+    int32_t x0, y0, w, h;
+    int32_t dx0, dy0, dw, dh;
+    int32_t reserved0;
+    int32_t colour[12];
+    int64_t inv[6];
+    double fwd[6];
+    int32_t reserved[2];
+} cnl_warp_placement;
+int cnl_augment_warp_u8(const void* frames, int32_t F, const void* places, const int32_t* n_place, int32_t max_place, const int32_t* holes,
+                        uint8_t* out, int32_t N, int32_t height, int32_t width, uint32_t fill_rgba, uint32_t hole_fill_rgba, uint32_t border_rgba,
+                        void* stream);
+int cnl_augment_warp_boxes_f64(const void* places, const int32_t* n_place, int32_t max_place, int32_t N, int32_t F, const double* boxes,
+                               const int64_t* labels, const int64_t* ids, const int32_t* count, int32_t Gmax, double* out_boxes, int64_t* out_labels,
+                               int64_t* out_ids, int32_t* out_count, int32_t Gout, double min_area, double min_visibility, void* stream);
+
 int cnl_version(void);
 /* sizeof(cnl_conv_params) / sizeof(cnl_decode_params) / sizeof(cnl_deconv_params) (which = 0 / 1 / 2), sizeof(cnl_loss_params) (which = 4) and sizeof(cnl_reid_loss_params) (which = 5; 3 is
  * unused; else 0) as the library was compiled — the structs grow at the end between ABI
