@@ -87,68 +87,125 @@ def settings_from_config(output_heads=None, **gen_b):
     return out
 
 
-def _bad_boxes(boxes, labels, stride, C, H, W):
-    """Indices of the boxes the kernel would skip (the record rule of include/centernet_gfx950.h, in numpy float64)."""
-    with np.errstate(all="ignore"):
-        b = boxes / float(stride)
-        cx, cy = np.rint(b[:, 0] + b[:, 2] / 2), np.rint(b[:, 1] + b[:, 3] / 2)
-        ok = np.isfinite(b).all(axis=1) & (b[:, 2] >= 0) & (b[:, 3] >= 0) & (cx >= 0) & (cx <= W) & (cy >= 0) & (cy <= H) & (labels >= 0) & (labels < C)
-    return np.nonzero(~ok)[0]
+def _is_padded(targets, n_tensors):
+    """Is this the padded device form: a dict, or a tuple / list of n_tensors tensors?"""
+    return isinstance(targets, dict) or (isinstance(targets, (list, tuple)) and len(targets) == n_tensors and all(isinstance(t, torch.Tensor) for t in targets))
 
 
-def _targets(targets, N, C, H, W, stride, what):
-    """-> (device or None, (boxes [N,Gmax,4] f64, labels [N,Gmax] i64, count [N] i32) as device tensors or numpy, Gmax)"""
-    if isinstance(targets, dict) or (isinstance(targets, (list, tuple)) and len(targets) == 3 and all(isinstance(t, torch.Tensor) for t in targets)):
-        if isinstance(targets, dict):
-            if any(name not in targets for name in ("boxes", "labels", "count")):
-                raise ValueError(f"{what}: device targets need 'boxes' [N,Gmax,4] f64, 'labels' [N,Gmax] i64 and 'count' [N] i32")
-            targets = (targets["boxes"], targets["labels"], targets["count"])
-        boxes, labels, count = targets
-        for name, t, dtype, dims in (("boxes", boxes, torch.float64, 3), ("labels", labels, torch.int64, 2), ("count", count, torch.int32, 1)):
+def _padded_targets(targets, N, field, row_ok, what, cannot):
+    """targets: the dict of padded device tensors {"boxes", field, "count"}, or a list of per-image {"boxes" [m, 4], field [m]}, which is checked here:
+    row_ok(boxes [m, 4] f64, second [m] i64) -> the mask of the boxes the kernel would take; any other box raises with cannot(its second value).
+    -> (device or None, (boxes [N,Gmax,4] f64, second [N,Gmax] i64, count [N] i32) as device tensors or numpy, Gmax)"""
+    if isinstance(targets, dict):
+        if any(name not in targets for name in ("boxes", field, "count")):
+            raise ValueError(f"{what}: device targets need 'boxes' [N,Gmax,4] f64, '{field}' [N,Gmax] i64 and 'count' [N] i32")
+        boxes, second, count = targets["boxes"], targets[field], targets["count"]
+        for name, t, dtype, dims in (("boxes", boxes, torch.float64, 3), (field, second, torch.int64, 2), ("count", count, torch.int32, 1)):
             if not isinstance(t, torch.Tensor):
                 raise ValueError(f"{what}: targets '{name}' must be a tensor, got {type(t).__name__}")
             if t.dtype != dtype or t.dim() != dims:
                 raise ValueError(f"{what}: targets '{name}' must be {dtype} with {dims} dimensions, got {t.dtype} {tuple(t.shape)}")
         Gmax = int(boxes.shape[1])
-        if tuple(boxes.shape) != (N, Gmax, 4) or tuple(labels.shape) != (N, Gmax) or tuple(count.shape) != (N,):
-            raise ValueError(f"{what}: expected target boxes [{N},Gmax,4], labels [{N},Gmax], count [{N}], got {tuple(boxes.shape)}, "
-                             f"{tuple(labels.shape)}, {tuple(count.shape)}")
+        if tuple(boxes.shape) != (N, Gmax, 4) or tuple(second.shape) != (N, Gmax) or tuple(count.shape) != (N,):
+            raise ValueError(f"{what}: expected target boxes [{N},Gmax,4], {field} [{N},Gmax], count [{N}], got {tuple(boxes.shape)}, "
+                             f"{tuple(second.shape)}, {tuple(count.shape)}")
         if not 1 <= Gmax <= MAX_PER_IMAGE:
             raise ValueError(f"{what}: Gmax = {Gmax} boxes per image; 1..{MAX_PER_IMAGE} are supported")
-        _gather.require_hip([boxes, labels, count], what)
-        if labels.device != boxes.device or count.device != boxes.device:
+        _gather.require_hip([boxes, second, count], what)
+        if second.device != boxes.device or count.device != boxes.device:
             raise ValueError(f"{what}: target tensors live on different devices")
-        return boxes.device, (boxes.contiguous(), labels.contiguous(), count.contiguous()), Gmax
+        return boxes.device, (boxes.contiguous(), second.contiguous(), count.contiguous()), Gmax
     if not isinstance(targets, (list, tuple)):
         raise ValueError(f"{what}: targets must be a list of per-image dicts or padded device tensors, got {type(targets).__name__}")
     if len(targets) != N:
         raise ValueError(f"{what}: {N} images of outputs against {len(targets)} of targets")
     images = []
     for i, d in enumerate(targets):
-        if not isinstance(d, dict) or "boxes" not in d or "labels" not in d:
-            raise ValueError(f"{what}: targets[{i}] must be a dict with 'boxes', 'labels'")
+        if not isinstance(d, dict) or "boxes" not in d or field not in d:
+            raise ValueError(f"{what}: targets[{i}] must be a dict with 'boxes', '{field}'")
         try:
-            b = np.asarray(d["boxes"].detach().cpu().numpy() if isinstance(d["boxes"], torch.Tensor) else d["boxes"]).astype(np.float64)
-            lab = np.asarray(d["labels"].detach().cpu().numpy() if isinstance(d["labels"], torch.Tensor) else d["labels"]).astype(np.int64).reshape(-1)
+            b, sec = d["boxes"], d[field]
+            b = np.asarray(b.detach().cpu().numpy() if isinstance(b, torch.Tensor) else b).astype(np.float64)
+            sec = np.asarray(sec.detach().cpu().numpy() if isinstance(sec, torch.Tensor) else sec).astype(np.int64).reshape(-1)
         except (TypeError, ValueError) as e:
             raise ValueError(f"{what}: targets[{i}] is not numeric: {e}") from e
         if b.size == 0:
             b = b.reshape(0, 4)
-        if b.ndim != 2 or b.shape[1] != 4 or b.shape[0] != lab.shape[0]:
-            raise ValueError(f"{what}: targets[{i}] has boxes {b.shape} and labels {lab.shape}; expected [n, 4] and [n]")
-        if lab.shape[0] > MAX_PER_IMAGE:
-            raise ValueError(f"{what}: targets[{i}] has {lab.shape[0]} boxes; at most {MAX_PER_IMAGE} per image are supported")
-        bad = _bad_boxes(b, lab, stride, C, H, W)
+        if b.ndim != 2 or b.shape[1] != 4 or b.shape[0] != sec.shape[0]:
+            raise ValueError(f"{what}: targets[{i}] has boxes {b.shape} and {field} {sec.shape}; expected [n, 4] and [n]")
+        if sec.shape[0] > MAX_PER_IMAGE:
+            raise ValueError(f"{what}: targets[{i}] has {sec.shape[0]} boxes; at most {MAX_PER_IMAGE} per image are supported")
+        bad = np.nonzero(~row_ok(b, sec))[0]
         if bad.size:
             j = int(bad[0])
-            raise ValueError(f"{what}: targets[{i}] box {j} = {b[j].tolist()} (label {int(lab[j])}) cannot be a target on a {H} x {W} map of {C} "
-                             f"classes at stride {stride}: non-finite, negative size, centre outside the map or label outside 0..{C - 1}")
-        images.append((b, lab))
-    Gmax = max([1] + [len(lab) for (_, lab) in images])
-    boxes, labels, count = np.zeros((N, Gmax, 4), dtype=np.float64), np.zeros((N, Gmax), dtype=np.int64), np.zeros((N,), dtype=np.int32)
-    for i, (b, lab) in enumerate(images):
-        boxes[i, :len(lab)], labels[i, :len(lab)], count[i] = b, lab, len(lab)
-    return None, (boxes, labels, count), Gmax
+            raise ValueError(f"{what}: targets[{i}] box {j} = {b[j].tolist()} {cannot(int(sec[j]))}")
+        images.append((b, sec))
+    Gmax = max([1] + [len(sec) for (_, sec) in images])
+    boxes, second, count = np.zeros((N, Gmax, 4), dtype=np.float64), np.zeros((N, Gmax), dtype=np.int64), np.zeros((N,), dtype=np.int32)
+    for i, (b, sec) in enumerate(images):
+        boxes[i, :len(sec)], second[i, :len(sec)], count[i] = b, sec, len(sec)
+    return None, (boxes, second, count), Gmax
+
+
+def _targets(targets, N, C, H, W, stride, what):
+    """detection_loss's targets through _padded_targets: the tuple (boxes, labels, count) is the dict's other spelling"""
+    if not isinstance(targets, dict) and _is_padded(targets, 3):
+        targets = {"boxes": targets[0], "labels": targets[1], "count": targets[2]}
+
+    def row_ok(boxes, labels):             # the record rule of include/centernet_gfx950.h, in numpy float64
+        with np.errstate(all="ignore"):
+            b = boxes / float(stride)
+            cx, cy = np.rint(b[:, 0] + b[:, 2] / 2), np.rint(b[:, 1] + b[:, 3] / 2)
+            return np.isfinite(b).all(axis=1) & (b[:, 2] >= 0) & (b[:, 3] >= 0) & (cx >= 0) & (cx <= W) & (cy >= 0) & (cy <= H) & (labels >= 0) & (labels < C)
+
+    return _padded_targets(targets, N, "labels", row_ok, what,
+                           lambda label: f"(label {label}) cannot be a target on a {H} x {W} map of {C} classes at stride {stride}: non-finite, negative "
+                                         f"size, centre outside the map or label outside 0..{C - 1}")
+
+
+def _same_device(g_dev, dev, what, outputs="outputs"):
+    if g_dev is not None and g_dev != dev:
+        raise ValueError(f"{what}: {outputs} on {dev}, targets on {g_dev}")
+
+
+def _on_device(g_dev, gts, N, dev, what, outputs="outputs"):
+    """_padded_targets's result on the outputs' device: device tensors must live there, host arrays go up in one copy."""
+    _same_device(g_dev, dev, what, outputs)
+    if g_dev is None:
+        with torch.cuda.device(dev):
+            gts = [torch.from_numpy(a).to(dev) for a in gts] if N == 0 else _upload(list(gts), dev)      # (an empty batch: nothing to stage)
+    return tuple(gts)
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def _map_args(t):
+    """The pointer and the four strides of a map, or NULL and zeros"""
+    return (None, 0, 0, 0, 0) if t is None else (t.data_ptr(), *t.stride())
+
+
+def _call(name, workspace_bytes, dev, *args):
+    """One entry point on dev's current stream, inside the caller's `with torch.cuda.device(dev)`: args are its arguments up to the workspace,
+    workspace_bytes = (the name of its size query, the query's arguments)."""
+    lib = _lib.load()
+    nbytes = getattr(lib, workspace_bytes[0])(*workspace_bytes[1:])
+    ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=dev)
+    _lib.check(getattr(lib, name)(*args, ws.data_ptr(), nbytes, ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), name)
+
+
+def _check_want(want, allowed, what):
+    """-> a flag per name of `allowed`"""
+    if isinstance(want, str) or not isinstance(want, (tuple, list)) or not want or any(w not in allowed for w in want) or len(set(want)) != len(want):
+        raise ValueError(f"{what}: want must be a non-empty tuple out of {allowed}, got {want!r}")
+    return tuple(w in want for w in allowed)
+
+
+def _outputs(outputs, keys, who):
+    if not isinstance(outputs, dict) or any(k not in outputs for k in keys):
+        raise ValueError(f"{who}: outputs must be the dict of get_encoded_outputs with {' and '.join(repr(k) for k in keys)}")
+    return [outputs[k] for k in keys]
 
 
 def _check_map(t, name, channels, what):
@@ -186,26 +243,17 @@ def _run(heatmap, box_2d, targets, shape, params, want_targets, dev, what):
         if not torch.cuda.is_available():
             raise RuntimeError(f"{what} runs on HIP devices only (no CPU fallback)")
         dev = torch.device("cuda", torch.cuda.current_device())
-    if g_dev is not None and g_dev != dev:
-        raise ValueError(f"{what}: outputs on {dev}, targets on {g_dev}")
-    lib = _lib.load()
+    _same_device(g_dev, dev, what)
     with torch.cuda.device(dev):
         out = torch.zeros((N * 4 + 3,), dtype=torch.float64, device=dev)
         skipped = torch.zeros((1,), dtype=torch.int32, device=dev)
         tmap = torch.empty((N, C, H, W), dtype=torch.float32, device=dev, memory_format=torch.channels_last) if want_targets else None
-        if N == 0:
-            return out, skipped, tmap
-        if g_dev is None:
-            gts = _upload(list(gts), dev)
-        nbytes = lib.cnl_detection_loss_workspace_bytes(N, Gmax, H, W)
-        ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=dev)
-        hs, bs = (heatmap.stride(), box_2d.stride()) if heatmap is not None else ((0,) * 4, (0,) * 4)
-        ts = tmap.stride() if tmap is not None else (0,) * 4
-        _lib.check(lib.cnl_detection_loss_f64(None if heatmap is None else heatmap.data_ptr(), *hs, None if box_2d is None else box_2d.data_ptr(), *bs,
-                                              N, C, H, W, gts[0].data_ptr(), gts[1].data_ptr(), gts[2].data_ptr(), Gmax, ctypes.byref(params),
-                                              None if tmap is None else tmap.data_ptr(), *ts, out.data_ptr(), out.data_ptr() + 8 * 4 * N,
-                                              skipped.data_ptr(), ws.data_ptr(), nbytes,
-                                              ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "cnl_detection_loss_f64")
+        if N:
+            if g_dev is None:
+                gts = _upload(list(gts), dev)
+            _call("cnl_detection_loss_f64", ("cnl_detection_loss_workspace_bytes", N, Gmax, H, W), dev, *_map_args(heatmap), *_map_args(box_2d),
+                  N, C, H, W, gts[0].data_ptr(), gts[1].data_ptr(), gts[2].data_ptr(), Gmax, ctypes.byref(params), *_map_args(tmap),
+                  out.data_ptr(), out.data_ptr() + 8 * 4 * N, skipped.data_ptr())
     return out, skipped, tmap
 
 
@@ -236,12 +284,7 @@ def _device_targets(targets, shape, stride, dev, what):
     """targets in either form -> the padded (boxes, labels, count) device tensors of one call; a host list is checked, padded and uploaded in one copy."""
     N, C, H, W = shape
     g_dev, gts, _ = _targets(targets, N, C, H, W, stride, what)
-    if g_dev is not None and g_dev != dev:
-        raise ValueError(f"{what}: outputs on {dev}, targets on {g_dev}")
-    if g_dev is None:
-        with torch.cuda.device(dev):
-            gts = [torch.from_numpy(a).to(dev) for a in gts] if N == 0 else _upload(list(gts), dev)      # (an empty batch: nothing to stage)
-    return tuple(gts)
+    return _on_device(g_dev, gts, N, dev, what)
 
 
 def _scale(value, name, dev, what):
@@ -253,6 +296,19 @@ def _scale(value, name, dev, what):
             raise ValueError(f"{what}: {name} on {value.device}, outputs on {dev}")
         return value.detach().reshape(())
     return _number(value, name, what)
+
+
+def _scale_arg(values, dev):
+    """The checked scales of one call (_scale) -> what the entry point reads: None (all 1) or a float64 device tensor [len(values)]"""
+    on_device = any(isinstance(v, torch.Tensor) for v in values)
+    if not on_device and all(v == 1.0 for v in values):
+        return None
+    if on_device and len(values) == 1:
+        return values[0].reshape(1)
+    with torch.cuda.device(dev):
+        if on_device:
+            return torch.stack([v if isinstance(v, torch.Tensor) else torch.full((), v, dtype=torch.float64, device=dev) for v in values])
+        return _upload([np.array(values, dtype=np.float64)], dev)[0]
 
 
 def _like(t):
@@ -267,23 +323,15 @@ def _run_grad(heatmap, box_2d, gts, shape, params, scales, want):
     -> (heatmap gradient or None, box_2d gradient or None, skipped [1] i32)"""
     N, C, H, W = shape
     dev = heatmap.device
-    lib = _lib.load()
     with torch.cuda.device(dev):
         gh = _like(heatmap) if want[0] else None
         gb = _like(box_2d) if want[1] else None
         skipped = torch.zeros((1,), dtype=torch.int32, device=dev)
-        if N == 0:
-            return gh, gb, skipped
-        Gmax = int(gts[0].shape[1])
-        nbytes = lib.cnl_detection_loss_grad_workspace_bytes(N, Gmax, H, W)
-        ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=dev)
-        _lib.check(lib.cnl_detection_loss_grad_f32(heatmap.data_ptr(), *heatmap.stride(), box_2d.data_ptr(), *box_2d.stride(), N, C, H, W,
-                                                   gts[0].data_ptr(), gts[1].data_ptr(), gts[2].data_ptr(), Gmax, ctypes.byref(params),
-                                                   None if scales is None else scales.data_ptr(),
-                                                   None if gh is None else gh.data_ptr(), *(gh.stride() if gh is not None else (0,) * 4),
-                                                   None if gb is None else gb.data_ptr(), *(gb.stride() if gb is not None else (0,) * 4),
-                                                   skipped.data_ptr(), ws.data_ptr(), nbytes,
-                                                   ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "cnl_detection_loss_grad_f32")
+        if N:
+            Gmax = int(gts[0].shape[1])
+            _call("cnl_detection_loss_grad_f32", ("cnl_detection_loss_grad_workspace_bytes", N, Gmax, H, W), dev, *_map_args(heatmap),
+                  *_map_args(box_2d), N, C, H, W, gts[0].data_ptr(), gts[1].data_ptr(), gts[2].data_ptr(), Gmax, ctypes.byref(params), _ptr(scales),
+                  *_map_args(gh), *_map_args(gb), skipped.data_ptr())
     return gh, gb, skipped
 
 
@@ -300,22 +348,14 @@ def detection_loss_grad(heatmap, box_2d, targets, stride=4, heatmap_target="corn
     what = "detection_loss_grad"
     params = loss_params(stride, heatmap_target, heatmap_target_params, heatmap_loss, box_loss, heatmap_loss_weight, box_loss_weight, box_log,
                          box_multiplier, what)
-    if isinstance(want, str) or not isinstance(want, (tuple, list)) or not want or any(w not in WANT for w in want) or len(set(want)) != len(want):
-        raise ValueError(f"{what}: want must be a non-empty tuple out of {WANT}, got {want!r}")
+    want = _check_want(want, WANT, what)
     _check_map(heatmap, "heatmap", "C", what)
     _check_map(box_2d, "box_2d", 4, what)
     dev = heatmap.device
     s_heat, s_box = _scale(heatmap_scale, "heatmap_scale", dev, what), _scale(box_scale, "box_scale", dev, what)
     shape = _check_outputs(heatmap, box_2d, what)
     gts = _device_targets(targets, shape, params.stride, dev, what)
-    scales = None
-    if isinstance(s_heat, torch.Tensor) or isinstance(s_box, torch.Tensor):
-        with torch.cuda.device(dev):
-            scales = torch.stack([v if isinstance(v, torch.Tensor) else torch.full((), v, dtype=torch.float64, device=dev) for v in (s_heat, s_box)])
-    elif (s_heat, s_box) != (1.0, 1.0):
-        with torch.cuda.device(dev):
-            (scales,) = _upload([np.array([s_heat, s_box], dtype=np.float64)], dev)
-    gh, gb, skipped = _run_grad(heatmap.detach(), box_2d.detach(), gts, shape, params, scales, ("heatmap" in want, "box_2d" in want))
+    gh, gb, skipped = _run_grad(heatmap.detach(), box_2d.detach(), gts, shape, params, _scale_arg((s_heat, s_box), dev), want)
     return {"heatmap_grad": gh, "box_2d_grad": gb, "skipped": skipped[0]}
 
 
@@ -364,9 +404,7 @@ class DetectionLoss(torch.nn.Module):
         return ", ".join(f"{k}={v!r}" for k, v in self.settings.items())
 
     def forward(self, outputs, targets):
-        if not isinstance(outputs, dict) or "heatmap" not in outputs or "box_2d" not in outputs:
-            raise ValueError("DetectionLoss: outputs must be the dict of get_encoded_outputs with 'heatmap' and 'box_2d'")
-        heatmap, box_2d = outputs["heatmap"], outputs["box_2d"]
+        heatmap, box_2d = _outputs(outputs, ("heatmap", "box_2d"), "DetectionLoss")
         needs = torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (heatmap, box_2d))
         if not needs:
             return detection_loss(heatmap, box_2d, targets, **self.settings)
@@ -382,8 +420,7 @@ def render_targets(targets, num_classes, height, width, stride=4, heatmap_target
     for name, v in (("num_classes", num_classes), ("height", height), ("width", width)):
         if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
             raise ValueError(f"{what}: {name} must be an int, got {v!r}")
-    is_padded = isinstance(targets, dict) or (isinstance(targets, (list, tuple)) and len(targets) == 3 and all(isinstance(t, torch.Tensor) for t in targets))
-    if is_padded:
+    if _is_padded(targets, 3):
         first = targets["boxes"] if isinstance(targets, dict) and "boxes" in targets else targets[0] if not isinstance(targets, dict) else None
         N = int(first.shape[0]) if isinstance(first, torch.Tensor) and first.dim() else 0
     elif isinstance(targets, (list, tuple)):
@@ -419,10 +456,9 @@ class LossMeter:
 
     def update(self, outputs, targets):
         """outputs: the dict of get_encoded_outputs ("heatmap" logits, "box_2d").  One call of detection_loss, no synchronisation."""
-        if not isinstance(outputs, dict) or "heatmap" not in outputs or "box_2d" not in outputs:
-            raise ValueError("LossMeter.update: outputs must be the dict of get_encoded_outputs with 'heatmap' and 'box_2d'")
-        res = detection_loss(outputs["heatmap"], outputs["box_2d"], targets, **self.settings)
-        n = int(outputs["heatmap"].shape[0])
+        heatmap, box_2d = _outputs(outputs, ("heatmap", "box_2d"), "LossMeter.update")
+        res = detection_loss(heatmap, box_2d, targets, **self.settings)
+        n = int(heatmap.shape[0])
         step = torch.stack([res["heatmap"] * n, res["box_2d"] * n, res["total"] * n, res["total"].new_tensor(float(n)), res["skipped"].to(torch.float64)])
         if self._acc is None:
             self._acc = step
@@ -521,65 +557,19 @@ def _classifier(classifier, what):
 
 def _reid_targets(targets, N, H, W, K, stride, center, ignore_index, what):
     """-> (device or None, (boxes [N,Gmax,4] f64, ids [N,Gmax] i64, count [N] i32) as device tensors or numpy, Gmax)"""
-    padded = None
-    if isinstance(targets, dict):
-        if any(name not in targets for name in ("boxes", "ids", "count")):
-            raise ValueError(f"{what}: device targets need 'boxes' [N,Gmax,4] f64, 'ids' [N,Gmax] i64 and 'count' [N] i32")
-        padded = (targets["boxes"], targets["ids"], targets["count"])
-    elif isinstance(targets, (list, tuple)) and len(targets) == 4 and all(isinstance(t, torch.Tensor) for t in targets):
-        padded = (targets[0], targets[3], targets[2])          # detection_loss's (boxes, labels, count) and the ids as the fourth tensor
-    if padded is not None:
-        boxes, ids, count = padded
-        for name, t, dtype, dims in (("boxes", boxes, torch.float64, 3), ("ids", ids, torch.int64, 2), ("count", count, torch.int32, 1)):
-            if not isinstance(t, torch.Tensor):
-                raise ValueError(f"{what}: targets '{name}' must be a tensor, got {type(t).__name__}")
-            if t.dtype != dtype or t.dim() != dims:
-                raise ValueError(f"{what}: targets '{name}' must be {dtype} with {dims} dimensions, got {t.dtype} {tuple(t.shape)}")
-        Gmax = int(boxes.shape[1])
-        if tuple(boxes.shape) != (N, Gmax, 4) or tuple(ids.shape) != (N, Gmax) or tuple(count.shape) != (N,):
-            raise ValueError(f"{what}: expected target boxes [{N},Gmax,4], ids [{N},Gmax], count [{N}], got {tuple(boxes.shape)}, {tuple(ids.shape)}, "
-                             f"{tuple(count.shape)}")
-        if not 1 <= Gmax <= MAX_PER_IMAGE:
-            raise ValueError(f"{what}: Gmax = {Gmax} boxes per image; 1..{MAX_PER_IMAGE} are supported")
-        _gather.require_hip([boxes, ids, count], what)
-        if ids.device != boxes.device or count.device != boxes.device:
-            raise ValueError(f"{what}: target tensors live on different devices")
-        return boxes.device, (boxes.contiguous(), ids.contiguous(), count.contiguous()), Gmax
-    if not isinstance(targets, (list, tuple)):
-        raise ValueError(f"{what}: targets must be a list of per-image dicts or padded device tensors, got {type(targets).__name__}")
-    if len(targets) != N:
-        raise ValueError(f"{what}: {N} images of outputs against {len(targets)} of targets")
-    images = []
-    for i, d in enumerate(targets):
-        if not isinstance(d, dict) or "boxes" not in d or "ids" not in d:
-            raise ValueError(f"{what}: targets[{i}] must be a dict with 'boxes', 'ids'")
-        try:
-            b = np.asarray(d["boxes"].detach().cpu().numpy() if isinstance(d["boxes"], torch.Tensor) else d["boxes"]).astype(np.float64)
-            ident = np.asarray(d["ids"].detach().cpu().numpy() if isinstance(d["ids"], torch.Tensor) else d["ids"]).astype(np.int64).reshape(-1)
-        except (TypeError, ValueError) as e:
-            raise ValueError(f"{what}: targets[{i}] is not numeric: {e}") from e
-        if b.size == 0:
-            b = b.reshape(0, 4)
-        if b.ndim != 2 or b.shape[1] != 4 or b.shape[0] != ident.shape[0]:
-            raise ValueError(f"{what}: targets[{i}] has boxes {b.shape} and ids {ident.shape}; expected [n, 4] and [n]")
-        if ident.shape[0] > MAX_PER_IMAGE:
-            raise ValueError(f"{what}: targets[{i}] has {ident.shape[0]} boxes; at most {MAX_PER_IMAGE} per image are supported")
+    if not isinstance(targets, dict) and _is_padded(targets, 4):
+        targets = {"boxes": targets[0], "ids": targets[3], "count": targets[2]}      # detection_loss's (boxes, labels, count) and the ids as the fourth tensor
+
+    def row_ok(b, ident):                  # the row rule of include/centernet_gfx950.h; a box without identity is never a bad one
         with np.errstate(all="ignore"):
             c = (b[:, :2] + b[:, 2:] / 2.0) / float(stride)
             c = np.rint(c) if center == "round" else np.trunc(c)
-            ok = np.isfinite(b).all(axis=1) & (b[:, 2] >= 0) & (b[:, 3] >= 0) & (c[:, 0] >= 0) & (c[:, 0] <= W - 1) & (c[:, 1] >= 0) & (c[:, 1] <= H - 1) & \
-                (ident >= 0) & (ident < K)
-        bad = np.nonzero(~ok & (ident != ignore_index))[0]
-        if bad.size:
-            j = int(bad[0])
-            raise ValueError(f"{what}: targets[{i}] box {j} = {b[j].tolist()} (id {int(ident[j])}) cannot be a row on a {H} x {W} map with {K} identities at "
-                             f"stride {stride}: non-finite, negative size, centre cell outside the map or id outside 0..{K - 1}")
-        images.append((b, ident))
-    Gmax = max([1] + [len(ident) for (_, ident) in images])
-    boxes, ids, count = np.zeros((N, Gmax, 4), dtype=np.float64), np.zeros((N, Gmax), dtype=np.int64), np.zeros((N,), dtype=np.int32)
-    for i, (b, ident) in enumerate(images):
-        boxes[i, :len(ident)], ids[i, :len(ident)], count[i] = b, ident, len(ident)
-    return None, (boxes, ids, count), Gmax
+            return (np.isfinite(b).all(axis=1) & (b[:, 2] >= 0) & (b[:, 3] >= 0) & (c[:, 0] >= 0) & (c[:, 0] <= W - 1) & (c[:, 1] >= 0) & (c[:, 1] <= H - 1) &
+                    (ident >= 0) & (ident < K)) | (ident == ignore_index)
+
+    return _padded_targets(targets, N, "ids", row_ok, what,
+                           lambda ident: f"(id {ident}) cannot be a row on a {H} x {W} map with {K} identities at stride {stride}: non-finite, negative size, "
+                                         f"centre cell outside the map or id outside 0..{K - 1}")
 
 
 def _reid_inputs(reid, targets, classifier, params, center, what):
@@ -597,12 +587,7 @@ def _reid_inputs(reid, targets, classifier, params, center, what):
         if v.device != dev:
             raise ValueError(f"{what}: reid on {dev}, classifier tensor '{k}' on {v.device}")
     g_dev, gts, _ = _reid_targets(targets, N, H, W, K, params.stride, center, params.ignore_index, what)
-    if g_dev is not None and g_dev != dev:
-        raise ValueError(f"{what}: reid on {dev}, targets on {g_dev}")
-    if g_dev is None:
-        with torch.cuda.device(dev):
-            gts = [torch.from_numpy(a).to(dev) for a in gts] if N == 0 else _upload(list(gts), dev)
-    return (N, D, H, W), K, {k: v.detach().contiguous() for k, v in t.items()}, steps, tuple(gts)
+    return (N, D, H, W), K, {k: v.detach().contiguous() for k, v in t.items()}, steps, _on_device(g_dev, gts, N, dev, what, "reid")
 
 
 def _reid_common(reid, shape, K, t, gts, params):
@@ -616,19 +601,14 @@ def _run_reid(reid, shape, K, t, gts, params):
     N, D, H, W = shape
     dev = reid.device
     Gmax = int(gts[0].shape[1])
-    lib = _lib.load()
     with torch.cuda.device(dev):
         per_row = torch.zeros((N, Gmax), dtype=torch.float64, device=dev) if N == 0 else torch.empty((N, Gmax), dtype=torch.float64, device=dev)
         total = torch.zeros((1,), dtype=torch.float64, device=dev)
         counts = torch.zeros((4,), dtype=torch.int32, device=dev)
         new_stats = torch.stack([t["running_mean"], t["running_var"]])
-        if N == 0:
-            return per_row, total, counts, new_stats
-        nbytes = lib.cnl_reid_loss_workspace_bytes(N, Gmax, D)
-        ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=dev)
-        _lib.check(lib.cnl_reid_loss_f64(*_reid_common(reid, shape, K, t, gts, params), per_row.data_ptr(), total.data_ptr(), counts.data_ptr(),
-                                         new_stats.data_ptr(), ws.data_ptr(), nbytes, ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
-                   "cnl_reid_loss_f64")
+        if N:
+            _call("cnl_reid_loss_f64", ("cnl_reid_loss_workspace_bytes", N, Gmax, D), dev, *_reid_common(reid, shape, K, t, gts, params),
+                  per_row.data_ptr(), total.data_ptr(), counts.data_ptr(), new_stats.data_ptr())
     return per_row, total, counts, new_stats
 
 
@@ -636,22 +616,14 @@ def _run_reid_grad(reid, shape, K, t, gts, params, scale, want):
     """The one call.  scale: None (1) or a float64 device tensor [1]; want: six flags by REID_WANT -> (six gradients or None, skipped [1] i32)"""
     N, D, H, W = shape
     dev = reid.device
-    Gmax = int(gts[0].shape[1])
-    lib = _lib.load()
     with torch.cuda.device(dev):
         empty = torch.zeros if N == 0 else torch.empty
         grads = [(_like(reid) if N else torch.zeros_like(reid)) if want[0] else None]
         grads += [empty(tuple(t[k].shape), dtype=torch.float32, device=dev) if w else None for k, w in zip(REID_WANT[1:], want[1:])]
         skipped = torch.zeros((1,), dtype=torch.int32, device=dev)
-        if N == 0:
-            return grads, skipped
-        nbytes = lib.cnl_reid_loss_grad_workspace_bytes(N, Gmax, D)
-        ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=dev)
-        ptr = lambda g: None if g is None else g.data_ptr()
-        _lib.check(lib.cnl_reid_loss_grad_f32(*_reid_common(reid, shape, K, t, gts, params), None if scale is None else scale.data_ptr(), ptr(grads[0]),
-                                              *(grads[0].stride() if grads[0] is not None else (0,) * 4), *(ptr(g) for g in grads[1:]),
-                                              skipped.data_ptr(), ws.data_ptr(), nbytes,
-                                              ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "cnl_reid_loss_grad_f32")
+        if N:
+            _call("cnl_reid_loss_grad_f32", ("cnl_reid_loss_grad_workspace_bytes", N, int(gts[0].shape[1]), D), dev,
+                  *_reid_common(reid, shape, K, t, gts, params), _ptr(scale), *_map_args(grads[0]), *(_ptr(g) for g in grads[1:]), skipped.data_ptr())
     return grads, skipped
 
 
@@ -697,22 +669,13 @@ def reid_loss_grad(reid, targets, classifier, training=True, stride=4, center="t
     "beta_grad", "W2_grad", "b2_grad" (None when not wanted), "skipped": 0-dim int32}.  The running statistics are never touched.  One call of
     cnl_reid_loss_grad_f32, no synchronisation, no atomics: the same bits on every run."""
     what = "reid_loss_grad"
-    if isinstance(want, str) or not isinstance(want, (tuple, list)) or not want or any(w not in REID_WANT for w in want) or len(set(want)) != len(want):
-        raise ValueError(f"{what}: want must be a non-empty tuple out of {REID_WANT}, got {want!r}")
+    want = _check_want(want, REID_WANT, what)
     cls = _classifier(classifier, what)
     params = reid_params(training, stride, center, padded_rows, ignore_index, cls[1], cls[2], what)
     _check_map(reid, "reid", "D", what)
     s = _scale(scale, "scale", reid.device, what)
     shape, K, t, _, gts = _reid_inputs(reid, targets, cls, params, center, what)
-    dev = reid.device
-    if isinstance(s, torch.Tensor):
-        s = s.reshape(1)
-    elif s != 1.0:
-        with torch.cuda.device(dev):
-            (s,) = _upload([np.array([s], dtype=np.float64)], dev)
-    else:
-        s = None
-    grads, skipped = _run_reid_grad(reid.detach(), shape, K, t, gts, params, s, tuple(w in want for w in REID_WANT))
+    grads, skipped = _run_reid_grad(reid.detach(), shape, K, t, gts, params, _scale_arg((s,), reid.device), want)
     out = {f"{k}_grad": g for k, g in zip(REID_WANT, grads)}
     out["skipped"] = skipped[0]
     return out
@@ -772,9 +735,7 @@ class ReIDLoss(torch.nn.Module):
 
     def forward(self, outputs, targets):
         what = "ReIDLoss"
-        if not isinstance(outputs, dict) or "reid" not in outputs:
-            raise ValueError("ReIDLoss: outputs must be the dict of get_encoded_outputs with 'reid'")
-        reid = outputs["reid"]
+        (reid,) = _outputs(outputs, ("reid",), what)
         cls = _classifier(self, what)
         t, _, _, steps = cls
         trainable = (reid, t["W1"], t["gamma"], t["beta"], t["W2"], t["b2"])
@@ -805,9 +766,7 @@ class TrackingLoss(torch.nn.Module):
         self.reid = reid_loss_module
 
     def forward(self, outputs, targets, ignore_reid=False):
-        det_targets = targets
-        if isinstance(targets, (list, tuple)) and len(targets) == 4 and all(isinstance(t, torch.Tensor) for t in targets):
-            det_targets = tuple(targets[:3])
+        det_targets = tuple(targets[:3]) if not isinstance(targets, dict) and _is_padded(targets, 4) else targets
         out = dict(self.detection(outputs, det_targets))
         if ignore_reid:
             out["reid"] = torch.zeros((), dtype=torch.float64, device=out["total"].device)

@@ -6,19 +6,19 @@
 //
 //   record_kernel    one thread per target slot: box -> (cx, cy, rx, ry, the two fp32 Gaussian denominators, label, state), all float64
 //                    as the reference's host code computes them.  Slots at or beyond count[n] are never read.
-//   heatmap_kernel   the hot path.  A workgroup owns a TILE_H x TILE_W tile of pixels of one image over ALL classes.  It compacts the
-//                    image's records whose window touches the tile into LDS in slot order (ballot + popcount prefix, PASS_SLOTS slots per
-//                    pass; an image of at most PASS_SLOTS boxes is staged once), reads each logit exactly once, forms the element's target
-//                    in registers (the maximum over the staged records of its class), and adds the element's float64 loss term to a
-//                    per-thread sum in element order; the workgroup folds its 256 sums in a fixed tree into ONE float64 partial.
-//                    Three element orders: channel stride 1 (the engine's channels-last maps: lanes along the classes of a pixel, then
-//                    along x), W stride 1 (planes: lanes along x, then y, classes outermost), and the plane order with free strides.
+//   heatmap_kernel   the hot path.  A workgroup owns a tile of pixels of one image over ALL classes (loss_common.h: Tile).  It stages the
+//                    image's records whose window touches the tile in LDS in slot order (stage, over loss_common.h's stage_pass; an image
+//                    of at most PASS_SLOTS boxes is staged once), reads each logit exactly once, forms the element's target in registers
+//                    (the maximum over the staged records of its class), and adds the element's float64 loss term to a per-thread sum in
+//                    element order; the workgroup folds its 256 sums in a fixed tree into ONE float64 partial.  Three element orders
+//                    (loss_common.h: element): channel stride 1 (the engine's channels-last maps), W stride 1 (planes, classes outermost),
+//                    and the plane order with free strides.
 //   sample_kernel    one workgroup per image: the up to nine box samples of every counted record, decoded by the decode's own device
 //                    function (box_decode.h), the loss per sample in float64, summed per thread in slot order and folded in a fixed tree.
 //   finish_kernel    one workgroup: a wave per image folds the image's tile partials (lane stripes in index order, then a fixed tree) into
 //                    its row; thread 0 then adds the rows in image order into the three totals.
 // No floating-point atomics, no atomics at all: an image's row is a function of that image alone.  Nothing here synchronises the device.
-#include "cnl_common.h"
+#include "loss_common.h"
 
 #pragma clang fp contract(off)   // one rounding per operation
 
@@ -26,12 +26,10 @@
 
 namespace cnl_det_loss {
 
-constexpr int THREADS = 256, WAVES = THREADS / 64;
-constexpr int TILE_W = 32, TILE_H = 8;             // TILE_W * TILE_H == THREADS: every thread of a tile makes the same number of element steps
-constexpr int PASS_SLOTS = 256;                    // target slots staged per pass (one per thread)
-constexpr int MAX_G = 1024;                        // boxes per image
+using namespace cnl_loss;
+
+constexpr int MAX_C = 1 << 16;
 constexpr int RADIUS_CAP = 1 << 24;                // window radii beyond any map are clamped here (the Gaussian's width is not)
-static_assert(TILE_W * TILE_H == THREADS && PASS_SLOTS == THREADS, "one element / one slot per thread and step");
 
 struct alignas(16) Rec {
     int cx, cy, rx, ry;
@@ -40,11 +38,6 @@ struct alignas(16) Rec {
     int state;                 // 0 skipped, 1 counted
 };
 static_assert(sizeof(Rec) == 32, "record layout");
-
-enum { LAYOUT_CMINOR = 0, LAYOUT_PLANE = 1, LAYOUT_GENERIC = 2 };
-
-__host__ __device__ inline int tiles_x(int W) { return (W + TILE_W - 1) / TILE_W; }
-__host__ __device__ inline int tiles_y(int H) { return (H + TILE_H - 1) / TILE_H; }
 
 struct Sections {              // the workspace: records | tile partials | per-image sample results
     size_t rec, part, img, total;
@@ -110,61 +103,28 @@ __global__ __launch_bounds__(THREADS) void record_kernel(const double* __restric
 }
 
 // ---------------------------------------------------------------------------------------------------------------- heatmap
-struct HeatArgs {
-    const float* heat; long sn, sc, sh, sw;        // NULL: targets only
-    float* tmap; long tn, tc, th, tw;              // NULL: never written
+struct HeatArgs {                                  // of heatmap_kernel (the value) and heat_grad_kernel (its gradient)
+    const float* heat; long sn, sc, sh, sw;        // NULL (value only): targets only
+    float* out; long on, oc, oh, ow;               // the value: the target map, NULL: never written; the gradient: the heatmap gradient
     const Rec* rec;
     const int* count;
-    double* part;
+    double* part;                                  // the value: a float64 partial per tile
+    const double* counts;                          // the gradient: num_dets, num_boxes
+    const double* scales;                          // the gradient: s_heat, s_box; NULL: 1, 1
     int C, H, W, Gmax, tx;
     int loss;                                      // 0 cornernet_focal, 1 quality
     int alpha_is_2, beta_is_4, beta_is_2;
     double alpha, beta;
 };
 
-__device__ __forceinline__ double wave_sum_fixed(double v) {      // the same tree in every lane, every run
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-// sum over the workgroup in a fixed order; valid in thread 0
-__device__ __forceinline__ double block_sum_fixed(double v, double* s_part) {
-    v = wave_sum_fixed(v);
-    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double s = s_part[0];
-#pragma unroll
-    for (int w = 1; w < WAVES; ++w) s += s_part[w];
-    __syncthreads();
-    return s;
-}
-
 // one pass: the records of slots s0 .. s0 + PASS_SLOTS - 1 whose window touches the tile, compacted into s_rec in slot order -> how many
-__device__ __forceinline__ int stage(const Rec* __restrict__ recs, int s0, int M, int x0, int y0, int x1, int y1, int W, int H, Rec* s_rec,
-                                     int* s_cnt) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    __syncthreads();                                          // the readers of the previous pass are done
-    const int s = s0 + tid;
-    bool hit = false;
-    Rec r;
-    if (s < M) {
+__device__ __forceinline__ int stage(const Rec* __restrict__ recs, int s0, int M, const Tile& t, Rec* s_rec, int* s_cnt) {
+    const int x0 = t.x0, y0 = t.y0, x1 = t.x1, y1 = t.y1;
+    return stage_pass(s0, M, s_rec, s_cnt, [=](int s, Rec& r) {
         r = recs[s];
         // (a centre ON cx == W or cy == H still renders the part of its window that lies inside the map, as the reference's slices do)
-        hit = r.state != 0 && r.cx - r.rx < x1 && r.cx + r.rx >= x0 && r.cy - r.ry < y1 && r.cy + r.ry >= y0;
-    }
-    const unsigned long long votes = __ballot(hit);
-    if (lane == 0) s_cnt[wave] = __popcll(votes);
-    __syncthreads();
-    int base = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < WAVES; ++w) {
-        const int c = s_cnt[w];
-        if (w < wave) base += c;
-        total += c;
-    }
-    if (hit) s_rec[base + __popcll(votes & ((1ull << lane) - 1ull))] = r;
-    __syncthreads();
-    return total;
+        return r.state != 0 && r.cx - r.rx < x1 && r.cx + r.rx >= x0 && r.cy - r.ry < y1 && r.cy + r.ry >= y0;
+    });
 }
 
 __device__ __forceinline__ float target_of(const Rec* s_rec, int cnt, int x, int y, int c, float t) {
@@ -181,18 +141,48 @@ __device__ __forceinline__ float target_of(const Rec* s_rec, int cnt, int x, int
     return t;
 }
 
+// t[k] <- the target of element (x[k], y, c[k]) over all M records of the image (0 where !inside).  A single pass was staged once before the
+// element loop (cnt) and stays; several passes are restaged here, by every thread of the workgroup (stage_pass's barriers).
+template <int PER>
+__device__ __forceinline__ void targets_of(const Rec* __restrict__ recs, int M, int passes, const Tile& tile, Rec* s_rec, int* s_cnt, int& cnt, bool inside,
+                                           const int (&x)[PER], int y, const int (&c)[PER], float (&t)[PER]) {
+#pragma unroll
+    for (int k = 0; k < PER; ++k) t[k] = 0.f;
+    if (passes <= 1) {
+        if (inside) {
+#pragma unroll
+            for (int k = 0; k < PER; ++k) t[k] = target_of(s_rec, cnt, x[k], y, c[k], 0.f);
+        }
+    } else {
+        for (int p = 0; p < passes; ++p) {
+            cnt = stage(recs, p * PASS_SLOTS, M, tile, s_rec, s_cnt);
+            if (inside) {
+#pragma unroll
+                for (int k = 0; k < PER; ++k) t[k] = target_of(s_rec, cnt, x[k], y, c[k], t[k]);
+            }
+        }
+    }
+}
+
 __device__ __forceinline__ double pow_small(double v, double e, int is2, int is4) {
     if (is2) return v * v;
     if (is4) { const double v2 = v * v; return v2 * v2; }
     return pow(v, e);
 }
 
-__device__ __forceinline__ double heat_term(const HeatArgs& a, float logit, float t) {
-    const double x = (double)logit, td = (double)t;
+// p = 1 / (1 + exp(-x)) without the overflow, and log1p(exp(-|x|))
+struct Sigmoid { double p, l1p; };
+__device__ __forceinline__ Sigmoid sigmoid_of(double x) {
     const double e = exp(-fabs(x));
     const double l1p = log1p(e);
     const double inv = 1.0 / (1.0 + e);
-    const double p = x >= 0.0 ? inv : e * inv;               // 1 / (1 + exp(-x)) without the overflow
+    return {x >= 0.0 ? inv : e * inv, l1p};
+}
+
+__device__ __forceinline__ double heat_term(const HeatArgs& a, float logit, float t) {
+    const double x = (double)logit, td = (double)t;
+    const Sigmoid s = sigmoid_of(x);
+    const double p = s.p, l1p = s.l1p;
     if (a.loss == 0) {
         const double pos = t == 1.f ? -pow_small(1.0 - p, a.alpha, a.alpha_is_2, 0) * (fmin(x, 0.0) - l1p) : 0.0;
         const double neg = -pow_small(p, a.alpha, a.alpha_is_2, 0) * (fmin(-x, 0.0) - l1p) * pow_small(1.0 - td, a.beta, 0, a.beta_is_4);
@@ -206,50 +196,31 @@ __global__ __launch_bounds__(THREADS) void heatmap_kernel(const HeatArgs a) {
     __shared__ Rec s_rec[PASS_SLOTS];
     __shared__ int s_cnt[WAVES];
     __shared__ double s_part[WAVES];
-    const int tid = threadIdx.x;
-    const int tiles = a.tx * tiles_y(a.H);
-    const int n = blockIdx.x / tiles, tile = blockIdx.x - n * tiles;
-    const int ty = tile / a.tx, txi = tile - ty * a.tx;
-    const int x0 = txi * TILE_W, y0 = ty * TILE_H, x1 = min(x0 + TILE_W, a.W), y1 = min(y0 + TILE_H, a.H);
-    const int M = min(max(a.count[n], 0), a.Gmax);
-    const Rec* const recs = a.rec + (long)n * a.Gmax;
+    const Tile tile(blockIdx.x, a.tx, a.H, a.W);
+    const int M = min(max(a.count[tile.n], 0), a.Gmax);
+    const Rec* const recs = a.rec + (long)tile.n * a.Gmax;
     const int passes = (M + PASS_SLOTS - 1) / PASS_SLOTS;
     const long sw = LAYOUT == LAYOUT_PLANE ? 1 : a.sw, sc = LAYOUT == LAYOUT_CMINOR ? 1 : a.sc;
-    const float* const heat = a.heat ? a.heat + (long)n * a.sn : nullptr;
-    float* const tmap = a.tmap ? a.tmap + (long)n * a.tn : nullptr;
+    const float* const heat = a.heat ? a.heat + (long)tile.n * a.sn : nullptr;
+    float* const tmap = a.out ? a.out + (long)tile.n * a.on : nullptr;
 
-    int cnt = passes == 1 ? stage(recs, 0, M, x0, y0, x1, y1, a.W, a.H, s_rec, s_cnt) : 0;
+    int cnt = passes == 1 ? stage(recs, 0, M, tile, s_rec, s_cnt) : 0;
     double acc = 0.0;
-    const unsigned row = (unsigned)TILE_W * (unsigned)a.C;
-    // THREADS * C elements, THREADS per step: the trip count is C in every thread, so the barriers of a multi-pass step are uniform
     for (int step = 0; step < a.C; ++step) {
-        int x, y, c;
-        if (LAYOUT == LAYOUT_CMINOR) {                        // lanes along the classes of a pixel, then along x
-            const unsigned e = (unsigned)step * THREADS + (unsigned)tid;
-            const unsigned yy = e / row, j = e - yy * row, xx = j / (unsigned)a.C;
-            y = y0 + (int)yy; x = x0 + (int)xx; c = (int)(j - xx * (unsigned)a.C);
-        } else {                                              // lanes along x, then y; one class per step
-            c = step; y = y0 + tid / TILE_W; x = x0 + tid % TILE_W;
-        }
-        const bool inside = x < x1 && y < y1;
+        const Elem e = element(LAYOUT == LAYOUT_CMINOR, tile, step, a.C);
+        const int x[1] = {e.x}, c[1] = {e.c}, y = e.y;
+        const bool inside = tile.holds(e.x, y);
         float logit = 0.f;
-        if (inside && heat) logit = heat[(long)c * sc + (long)y * a.sh + (long)x * sw];      // requested before the target's arithmetic
-        float t = 0.f;
-        if (passes <= 1) {
-            if (inside) t = target_of(s_rec, cnt, x, y, c, 0.f);
-        } else {
-            for (int p = 0; p < passes; ++p) {
-                cnt = stage(recs, p * PASS_SLOTS, M, x0, y0, x1, y1, a.W, a.H, s_rec, s_cnt);
-                if (inside) t = target_of(s_rec, cnt, x, y, c, t);
-            }
-        }
+        if (inside && heat) logit = heat[(long)e.c * sc + (long)y * a.sh + (long)e.x * sw];      // requested before the target's arithmetic
+        float t[1];
+        targets_of(recs, M, passes, tile, s_rec, s_cnt, cnt, inside, x, y, c, t);
         if (inside) {
-            if (tmap) tmap[(long)c * a.tc + (long)y * a.th + (long)x * a.tw] = t;
-            if (heat) acc += heat_term(a, logit, t);
+            if (tmap) tmap[(long)e.c * a.oc + (long)y * a.oh + (long)e.x * a.ow] = t[0];
+            if (heat) acc += heat_term(a, logit, t[0]);
         }
     }
     const double total = block_sum_fixed(acc, s_part);
-    if (tid == 0) a.part[blockIdx.x] = total;
+    if (threadIdx.x == 0) a.part[blockIdx.x] = total;
 }
 
 // ---------------------------------------------------------------------------------------------------------------- box samples
@@ -363,13 +334,13 @@ __global__ __launch_bounds__(THREADS) void finish_kernel(const double* __restric
 // cnl_detection_loss_grad_f32: d(s_heat heatmap_loss + s_box box_2d_loss) / d(logits, box_2d), the rule of include/centernet_gfx950.h.
 //   record_kernel        as above.
 //   count_kernel         one workgroup: num_dets, num_boxes and skipped of the BATCH (integers: exact in any order), which both gradients divide by.
-//   heat_grad_kernel     the hot path: the forward's tile ownership, staging and register targets; every element's derivative in float64, rounded
-//                        once, no reduction.  The element order follows the GRADIENT's strides (the write stream): channel stride 1 (and, where
+//   heat_grad_kernel     the hot path: the forward's tile ownership, staging and register targets (Tile, targets_of); every element's derivative in
+//                        float64, rounded once, no reduction.  The element order follows the GRADIENT's strides (the write stream): channel stride 1 (and, where
 //                        both maps are packed channels-last and 16-byte aligned, four consecutive elements of a tile row per lane: one 16-byte
 //                        load and one 16-byte store), W stride 1, or the plane order with free strides.  The logits are read by their own strides.
-//   box_grad_kernel      a workgroup per 8 x 32 pixel tile of one image, a thread per pixel: the image's counted records whose 3 x 3 sample
-//                        neighbourhood touches the tile are compacted into LDS in slot order with their slot; a thread adds the contribution of
-//                        every staged record that samples its pixel, in slot order, and stores its four values once (0 where none does).
+//   box_grad_kernel      a workgroup per tile of one image, a thread per pixel: the image's counted records whose 3 x 3 sample neighbourhood
+//                        touches the tile are staged (stage_pass) in slot order with their slot; a thread adds the contribution of every staged
+//                        record that samples its pixel, in slot order, and stores its four values once (0 where none does).
 namespace cnl_det_loss {
 
 constexpr size_t COUNT_BYTES = 16;                 // num_dets, num_boxes (float64)
@@ -396,26 +367,11 @@ __global__ __launch_bounds__(THREADS) void count_kernel(const Rec* __restrict__ 
     if (threadIdx.x == 0) { counts[0] = dets; counts[1] = samples; skipped[0] = (int)skip; }
 }
 
-struct HeatGradArgs {
-    const float* heat; long sn, sc, sh, sw;
-    float* grad; long gn, gc, gh, gw;
-    const Rec* rec;
-    const int* count;
-    const double* counts;                          // num_dets, num_boxes
-    const double* scales;                          // s_heat, s_box; NULL: 1, 1
-    int C, H, W, Gmax, tx;
-    int loss;
-    int alpha_is_2, beta_is_4, beta_is_2;
-    double alpha, beta;
-};
-
-// d(heat_term) / d(logit): p, logsigmoid and log1p(exp(-|x|)) formed as heat_term forms them; the target and the [t == 1] weight are constants
-__device__ __forceinline__ double heat_dterm(const HeatGradArgs& a, float logit, float t) {
+// d(heat_term) / d(logit): p and log1p(exp(-|x|)) are heat_term's (sigmoid_of); the target and the [t == 1] weight are constants
+__device__ __forceinline__ double heat_dterm(const HeatArgs& a, float logit, float t) {
     const double x = (double)logit, td = (double)t;
-    const double e = exp(-fabs(x));
-    const double l1p = log1p(e);
-    const double inv = 1.0 / (1.0 + e);
-    const double p = x >= 0.0 ? inv : e * inv;
+    const Sigmoid s = sigmoid_of(x);
+    const double p = s.p, l1p = s.l1p;
     const double q = 1.0 - p, pq = p * q;                     // dp/dx = p (1 - p)
     if (a.loss == 0) {
         const double ls = fmin(x, 0.0) - l1p, lsn = fmin(-x, 0.0) - l1p;      // d ls/dx = 1 - p, d lsn/dx = -p
@@ -438,32 +394,29 @@ __device__ __forceinline__ double heat_dterm(const HeatGradArgs& a, float logit,
 
 // VEC4: LAYOUT_CMINOR with both maps packed channels-last (pixel stride C, everything else a multiple of 4 elements, 16-byte aligned bases)
 template <int LAYOUT, bool VEC4>
-__global__ __launch_bounds__(THREADS) void heat_grad_kernel(const HeatGradArgs a) {
+__global__ __launch_bounds__(THREADS) void heat_grad_kernel(const HeatArgs a) {
     constexpr int PER = VEC4 ? 4 : 1;
     __shared__ Rec s_rec[PASS_SLOTS];
     __shared__ int s_cnt[WAVES];
     const int tid = threadIdx.x;
-    const int tiles = a.tx * tiles_y(a.H);
-    const int n = blockIdx.x / tiles, tile = blockIdx.x - n * tiles;
-    const int ty = tile / a.tx, txi = tile - ty * a.tx;
-    const int x0 = txi * TILE_W, y0 = ty * TILE_H, x1 = min(x0 + TILE_W, a.W), y1 = min(y0 + TILE_H, a.H);
-    const int M = min(max(a.count[n], 0), a.Gmax);
-    const Rec* const recs = a.rec + (long)n * a.Gmax;
-    const int passes = (M + PASS_SLOTS - 1) / PASS_SLOTS;
-    const long gw = LAYOUT == LAYOUT_PLANE ? 1 : a.gw, gc = LAYOUT == LAYOUT_CMINOR ? 1 : a.gc;
-    const float* const heat = a.heat + (long)n * a.sn;
-    float* const grad = a.grad + (long)n * a.gn;
+    const Tile tile(blockIdx.x, a.tx, a.H, a.W);
+    const int x0 = tile.x0, y0 = tile.y0, x1 = tile.x1, y1 = tile.y1;
+    const long gw = LAYOUT == LAYOUT_PLANE ? 1 : a.ow, gc = LAYOUT == LAYOUT_CMINOR ? 1 : a.oc;
+    const float* const heat = a.heat + (long)tile.n * a.sn;
+    float* const grad = a.out + (long)tile.n * a.on;
     const double scale = (a.scales ? a.scales[0] : 1.0) / fmax(1.0, a.counts[0]);
 
-    int cnt = passes == 1 ? stage(recs, 0, M, x0, y0, x1, y1, a.W, a.H, s_rec, s_cnt) : 0;
-    const unsigned row = (unsigned)TILE_W * (unsigned)a.C;                   // elements of a full tile row
+    const int M = min(max(a.count[tile.n], 0), a.Gmax);
+    const Rec* const recs = a.rec + (long)tile.n * a.Gmax;
+    const int passes = (M + PASS_SLOTS - 1) / PASS_SLOTS;
+    int cnt = passes == 1 ? stage(recs, 0, M, tile, s_rec, s_cnt) : 0;
     const int steps = VEC4 ? (a.C + 3) / 4 : a.C;                            // the same in every thread: the barriers of a multi-pass step are uniform
     for (int step = 0; step < steps; ++step) {
         int x[PER], y, c[PER];
         bool inside;
         unsigned j0 = 0;
         if (VEC4) {                                           // lanes along the 16-byte groups of a tile row, then along y
-            const unsigned g = (unsigned)step * THREADS + (unsigned)tid, per_row = row / 4;
+            const unsigned g = (unsigned)step * THREADS + (unsigned)tid, per_row = (unsigned)TILE_W * (unsigned)a.C / 4;
             const unsigned yy = g / per_row;
             j0 = (g - yy * per_row) * 4;
             y = y0 + (int)yy;
@@ -473,18 +426,14 @@ __global__ __launch_bounds__(THREADS) void heat_grad_kernel(const HeatGradArgs a
                 const unsigned xx = (j0 + k) / (unsigned)a.C;
                 x[k] = x0 + (int)xx; c[k] = (int)(j0 + k - xx * (unsigned)a.C);
             }
-        } else if (LAYOUT == LAYOUT_CMINOR) {                 // lanes along the classes of a pixel, then along x
-            const unsigned e = (unsigned)step * THREADS + (unsigned)tid;
-            const unsigned yy = e / row, j = e - yy * row, xx = j / (unsigned)a.C;
-            y = y0 + (int)yy; x[0] = x0 + (int)xx; c[0] = (int)(j - xx * (unsigned)a.C);
-            inside = x[0] < x1 && y < y1;
-        } else {                                              // lanes along x, then y; one class per step
-            c[0] = step; y = y0 + tid / TILE_W; x[0] = x0 + tid % TILE_W;
-            inside = x[0] < x1 && y < y1;
+        } else {
+            const Elem e = element(LAYOUT == LAYOUT_CMINOR, tile, step, a.C);
+            x[0] = e.x; y = e.y; c[0] = e.c;
+            inside = tile.holds(e.x, y);
         }
         float logit[PER], t[PER];
 #pragma unroll
-        for (int k = 0; k < PER; ++k) { logit[k] = 0.f; t[k] = 0.f; }
+        for (int k = 0; k < PER; ++k) logit[k] = 0.f;
         if (inside) {                                         // requested before the target's arithmetic
             if (VEC4) {
                 const float4 v = *reinterpret_cast<const float4*>(heat + (long)y * a.sh + (long)x0 * a.C + (long)j0);
@@ -493,20 +442,7 @@ __global__ __launch_bounds__(THREADS) void heat_grad_kernel(const HeatGradArgs a
                 logit[0] = heat[(long)c[0] * a.sc + (long)y * a.sh + (long)x[0] * a.sw];
             }
         }
-        if (passes <= 1) {
-            if (inside) {
-#pragma unroll
-                for (int k = 0; k < PER; ++k) t[k] = target_of(s_rec, cnt, x[k], y, c[k], 0.f);
-            }
-        } else {
-            for (int p = 0; p < passes; ++p) {
-                cnt = stage(recs, p * PASS_SLOTS, M, x0, y0, x1, y1, a.W, a.H, s_rec, s_cnt);
-                if (inside) {
-#pragma unroll
-                    for (int k = 0; k < PER; ++k) t[k] = target_of(s_rec, cnt, x[k], y, c[k], t[k]);
-                }
-            }
-        }
+        targets_of(recs, M, passes, tile, s_rec, s_cnt, cnt, inside, x, y, c, t);
         if (inside) {
             float o[PER];
 #pragma unroll
@@ -514,9 +450,9 @@ __global__ __launch_bounds__(THREADS) void heat_grad_kernel(const HeatGradArgs a
             if (VEC4) {
                 float4 v;
                 v.x = o[0]; v.y = o[1 % PER]; v.z = o[2 % PER]; v.w = o[3 % PER];
-                *reinterpret_cast<float4*>(grad + (long)y * a.gh + (long)x0 * a.C + (long)j0) = v;
+                *reinterpret_cast<float4*>(grad + (long)y * a.oh + (long)x0 * a.C + (long)j0) = v;
             } else {
-                grad[(long)c[0] * gc + (long)y * a.gh + (long)x[0] * gw] = o[0];
+                grad[(long)c[0] * gc + (long)y * a.oh + (long)x[0] * gw] = o[0];
             }
         }
     }
@@ -587,35 +523,6 @@ __device__ __forceinline__ void box_dterm(int kind, const float* pf, const float
     g[3] = g_ih * d_min(p[3], t[3]) + ay + g_eh * d_max(p[3], t[3]) - 0.5 * g_ddy + g_h1;
 }
 
-// one pass: the counted records of slots s0 .. s0 + PASS_SLOTS - 1 whose SAMPLE neighbourhood (cx-1..cx+1 x cy-1..cy+1 clipped to the map: a radius-0
-// box still has nine samples, a centre on cx == W samples column W - 1) touches the tile, as (cx, cy, slot, 0), compacted in slot order -> how many
-__device__ __forceinline__ int stage_samples(const Rec* __restrict__ recs, int s0, int M, int x0, int y0, int x1, int y1, int W, int H, int4* s_smp,
-                                             int* s_cnt) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    __syncthreads();                                          // the readers of the previous pass are done
-    const int s = s0 + tid;
-    bool hit = false;
-    int4 v = make_int4(0, 0, 0, 0);
-    if (s < M) {
-        const Rec r = recs[s];
-        v = make_int4(r.cx, r.cy, s, 0);
-        hit = r.state != 0 && max(r.cx - 1, 0) < x1 && min(r.cx + 1, W - 1) >= x0 && max(r.cy - 1, 0) < y1 && min(r.cy + 1, H - 1) >= y0;
-    }
-    const unsigned long long votes = __ballot(hit);
-    if (lane == 0) s_cnt[wave] = __popcll(votes);
-    __syncthreads();
-    int base = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < WAVES; ++w) {
-        const int c = s_cnt[w];
-        if (w < wave) base += c;
-        total += c;
-    }
-    if (hit) s_smp[base + __popcll(votes & ((1ull << lane) - 1ull))] = v;
-    __syncthreads();
-    return total;
-}
-
 struct BoxGradArgs {
     const float* box; long sn, sc, sh, sw;
     float* grad; long gn, gc, gh, gw;
@@ -633,12 +540,10 @@ __global__ __launch_bounds__(THREADS) void box_grad_kernel(const BoxGradArgs a) 
     __shared__ int4 s_smp[PASS_SLOTS];
     __shared__ int s_cnt[WAVES];
     const int tid = threadIdx.x;
-    const int tiles = a.tx * tiles_y(a.H);
-    const int n = blockIdx.x / tiles, tile = blockIdx.x - n * tiles;
-    const int ty = tile / a.tx, txi = tile - ty * a.tx;
-    const int x0 = txi * TILE_W, y0 = ty * TILE_H, x1 = min(x0 + TILE_W, a.W), y1 = min(y0 + TILE_H, a.H);
+    const Tile tile(blockIdx.x, a.tx, a.H, a.W);
+    const int n = tile.n, x0 = tile.x0, y0 = tile.y0, x1 = tile.x1, y1 = tile.y1;
     const int x = x0 + tid % TILE_W, y = y0 + tid / TILE_W;
-    const bool inside = x < x1 && y < y1;
+    const bool inside = tile.holds(x, y);
     const int M = min(max(a.count[n], 0), a.Gmax);
     const Rec* const recs = a.rec + (long)n * a.Gmax;
     const double* const gts = a.gt_boxes + (long)n * a.Gmax * 4;
@@ -650,7 +555,13 @@ __global__ __launch_bounds__(THREADS) void box_grad_kernel(const BoxGradArgs a) 
     float pred[4] = {0.f, 0.f, 0.f, 0.f};
     bool touched = false;
     for (int p = 0; p < passes; ++p) {                        // (uniform: M is the image's)
-        const int cnt = stage_samples(recs, p * PASS_SLOTS, M, x0, y0, x1, y1, a.W, a.H, s_smp, s_cnt);
+        // the counted records whose SAMPLE neighbourhood (cx-1..cx+1 x cy-1..cy+1 clipped to the map: a radius-0 box still has nine samples, a
+        // centre on cx == W samples column W - 1) touches the tile, as (cx, cy, slot, 0)
+        const int cnt = stage_pass(p * PASS_SLOTS, M, s_smp, s_cnt, [&](int s, int4& v) {
+            const Rec r = recs[s];
+            v = make_int4(r.cx, r.cy, s, 0);
+            return r.state != 0 && max(r.cx - 1, 0) < x1 && min(r.cx + 1, a.W - 1) >= x0 && max(r.cy - 1, 0) < y1 && min(r.cy + 1, a.H - 1) >= y0;
+        });
         if (!inside) continue;
         for (int j = 0; j < cnt; ++j) {
             const int4 r = s_smp[j];                          // the same address in every lane: a broadcast
@@ -682,12 +593,53 @@ __global__ __launch_bounds__(THREADS) void box_grad_kernel(const BoxGradArgs a) 
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------- host
+struct Call {                                      // what both entry points take
+    const float* heat; int64_t sn, sc, sh, sw;
+    const float* box;
+    int N, C, H, W, Gmax;
+    const double* gt_boxes; const int64_t* gt_labels; const int32_t* gt_count;
+    const cnl_loss_params* p;
+};
+
+// the checks both entry points make before an empty batch returns
+inline int check_call(const Call& c, const char* who) {
+    const cnl_loss_params* const p = c.p;
+    CNL_REQUIRE(p, CNL_E_BAD_ARG, "%s: null params", who);
+    if (int rc = check_dims(who, c.N, c.H, c.W, c.Gmax)) return rc;
+    CNL_REQUIRE(c.C >= 1 && c.C <= MAX_C, CNL_E_BAD_ARG, "%s: C = %d outside 1..2^16", who, c.C);
+    CNL_REQUIRE(p->target_method >= 0 && p->target_method <= 2, CNL_E_BAD_ARG, "%s: target_method = %d outside 0..2", who, p->target_method);
+    CNL_REQUIRE(p->heatmap_loss >= 0 && p->heatmap_loss <= 1, CNL_E_BAD_ARG, "%s: heatmap_loss = %d outside 0..1", who, p->heatmap_loss);
+    CNL_REQUIRE(p->box_loss >= 0 && p->box_loss <= 5, CNL_E_BAD_ARG, "%s: box_loss = %d outside 0..5", who, p->box_loss);
+    if (int rc = check_stride(who, p->stride)) return rc;
+    CNL_REQUIRE(p->target_method != 0 || (p->target_param > 0.0 && p->target_param < 1.0), CNL_E_BAD_ARG, "%s: cornernet min_overlap = %g outside (0, 1)",
+                who, p->target_param);
+    CNL_REQUIRE(p->target_param == p->target_param && p->hm_alpha == p->hm_alpha && p->hm_beta == p->hm_beta, CNL_E_BAD_ARG, "%s: a NaN parameter", who);
+    return CNL_OK;
+}
+
+inline int launch_records(const Call& c, Rec* rec, hipStream_t st) {
+    const long slots = (long)c.N * c.Gmax;
+    hipLaunchKernelGGL(record_kernel, dim3((unsigned)((slots + THREADS - 1) / THREADS)), dim3(THREADS), 0, st, c.gt_boxes,
+                       reinterpret_cast<const long long*>(c.gt_labels), c.gt_count, c.N, c.Gmax, c.C, c.H, c.W, c.p->stride, c.p->target_method,
+                       c.p->target_param, rec);
+    return cnl::check_launch("det_loss record_kernel");
+}
+
+inline void fill(HeatArgs& a, const Call& c, const Rec* rec) {
+    const cnl_loss_params* const p = c.p;
+    a.heat = c.heat; a.sn = c.sn; a.sc = c.sc; a.sh = c.sh; a.sw = c.sw;
+    a.rec = rec; a.count = c.gt_count; a.part = nullptr; a.counts = a.scales = nullptr;
+    a.C = c.C; a.H = c.H; a.W = c.W; a.Gmax = c.Gmax; a.tx = tiles_x(c.W);
+    a.loss = p->heatmap_loss; a.alpha = p->hm_alpha; a.beta = p->hm_beta;
+    a.alpha_is_2 = p->hm_alpha == 2.0; a.beta_is_4 = p->hm_beta == 4.0; a.beta_is_2 = p->hm_beta == 2.0;
+}
+
 }  // namespace cnl_det_loss
 
 extern "C" size_t cnl_detection_loss_workspace_bytes(int32_t N, int32_t Gmax, int32_t H, int32_t W) {
     using namespace cnl_det_loss;
-    if (N < 0 || N > (1 << 16) || Gmax < 1 || Gmax > MAX_G || H < 1 || H > (1 << 15) || W < 1 || W > (1 << 15)) return 0;
-    return sections(N, Gmax, H, W).total;
+    return dims_in_range(N, Gmax, H, W) ? sections(N, Gmax, H, W).total : 0;
 }
 
 extern "C" int cnl_detection_loss_f64(const float* heat, int64_t heat_sn, int64_t heat_sc, int64_t heat_sh, int64_t heat_sw, const float* box,
@@ -696,48 +648,30 @@ extern "C" int cnl_detection_loss_f64(const float* heat, int64_t heat_sn, int64_
                                       const cnl_loss_params* p, float* target_map, int64_t t_sn, int64_t t_sc, int64_t t_sh, int64_t t_sw,
                                       double* per_image, double* totals, int32_t* skipped, void* workspace, size_t workspace_bytes, void* stream) {
     using namespace cnl_det_loss;
-    CNL_REQUIRE(p, CNL_E_BAD_ARG, "cnl_detection_loss_f64: null params");
-    CNL_REQUIRE(N >= 0 && N <= (1 << 16), CNL_E_BAD_ARG, "cnl_detection_loss_f64: N = %d outside 0..2^16", N);
-    CNL_REQUIRE(C >= 1 && C <= (1 << 16), CNL_E_BAD_ARG, "cnl_detection_loss_f64: C = %d outside 1..2^16", C);
-    CNL_REQUIRE(H >= 1 && H <= (1 << 15) && W >= 1 && W <= (1 << 15), CNL_E_BAD_ARG, "cnl_detection_loss_f64: H x W = %d x %d outside 1..2^15", H, W);
-    CNL_REQUIRE(Gmax >= 1 && Gmax <= MAX_G, CNL_E_BAD_ARG, "cnl_detection_loss_f64: Gmax = %d outside 1..%d", Gmax, MAX_G);
-    CNL_REQUIRE(p->target_method >= 0 && p->target_method <= 2, CNL_E_BAD_ARG, "cnl_detection_loss_f64: target_method = %d outside 0..2", p->target_method);
-    CNL_REQUIRE(p->heatmap_loss >= 0 && p->heatmap_loss <= 1, CNL_E_BAD_ARG, "cnl_detection_loss_f64: heatmap_loss = %d outside 0..1", p->heatmap_loss);
-    CNL_REQUIRE(p->box_loss >= 0 && p->box_loss <= 5, CNL_E_BAD_ARG, "cnl_detection_loss_f64: box_loss = %d outside 0..5", p->box_loss);
-    CNL_REQUIRE(p->stride > 0.0 && p->stride < 1e6, CNL_E_BAD_ARG, "cnl_detection_loss_f64: stride = %g must be positive", p->stride);
-    CNL_REQUIRE(p->target_method != 0 || (p->target_param > 0.0 && p->target_param < 1.0), CNL_E_BAD_ARG,
-                "cnl_detection_loss_f64: cornernet min_overlap = %g outside (0, 1)", p->target_param);
-    CNL_REQUIRE(p->target_param == p->target_param && p->hm_alpha == p->hm_alpha && p->hm_beta == p->hm_beta, CNL_E_BAD_ARG,
-                "cnl_detection_loss_f64: a NaN parameter");
-    CNL_REQUIRE((heat != nullptr) == (box != nullptr), CNL_E_BAD_ARG, "cnl_detection_loss_f64: heat and box come together (both NULL: targets only)");
-    CNL_REQUIRE(heat || target_map, CNL_E_BAD_ARG, "cnl_detection_loss_f64: neither logits nor a target map: nothing to do");
+    const char* const who = "cnl_detection_loss_f64";
+    const Call c{heat, heat_sn, heat_sc, heat_sh, heat_sw, box, N, C, H, W, Gmax, gt_boxes, gt_labels, gt_count, p};
+    if (int rc = check_call(c, who)) return rc;
+    CNL_REQUIRE((heat != nullptr) == (box != nullptr), CNL_E_BAD_ARG, "%s: heat and box come together (both NULL: targets only)", who);
+    CNL_REQUIRE(heat || target_map, CNL_E_BAD_ARG, "%s: neither logits nor a target map: nothing to do", who);
     if (N == 0) return CNL_OK;
-    CNL_REQUIRE(gt_boxes && gt_labels && gt_count && per_image && totals && skipped && workspace, CNL_E_BAD_ARG, "cnl_detection_loss_f64: null pointer");
-    CNL_REQUIRE((((uintptr_t)gt_boxes | (uintptr_t)gt_labels | (uintptr_t)per_image | (uintptr_t)totals) & 7) == 0 && ((uintptr_t)workspace & 15) == 0 &&
-                    (((uintptr_t)heat | (uintptr_t)box | (uintptr_t)target_map | (uintptr_t)gt_count | (uintptr_t)skipped) & 3) == 0, CNL_E_BAD_ARG,
-                "cnl_detection_loss_f64: the float64 / int64 arrays must be 8-byte aligned, the workspace 16-byte aligned, the rest 4-byte aligned");
+    CNL_REQUIRE(gt_boxes && gt_labels && gt_count && per_image && totals && skipped && workspace, CNL_E_BAD_ARG, "%s: null pointer", who);
+    if (int rc = check_aligned(who, {gt_boxes, gt_labels, per_image, totals}, workspace, {heat, box, target_map, gt_count, skipped})) return rc;
     const Sections sec = sections(N, Gmax, H, W);
-    CNL_REQUIRE(workspace_bytes >= sec.total, CNL_E_WORKSPACE, "cnl_detection_loss_f64: workspace of %zu bytes, %zu needed", workspace_bytes, sec.total);
-    const int tiles = tiles_x(W) * tiles_y(H);
-    CNL_REQUIRE((long long)N * tiles < (1ll << 31), CNL_E_UNSUPPORTED, "cnl_detection_loss_f64: %d images x %d tiles exceed the grid", N, tiles);
+    if (int rc = check_workspace(who, workspace_bytes, sec.total)) return rc;
+    int tiles;
+    if (int rc = check_tile_grid(who, N, H, W, tiles)) return rc;
     char* const ws = static_cast<char*>(workspace);
     Rec* const rec = reinterpret_cast<Rec*>(ws + sec.rec);
     double* const part = reinterpret_cast<double*>(ws + sec.part);
     double* const img = reinterpret_cast<double*>(ws + sec.img);
     hipStream_t st = (hipStream_t)stream;
 
-    const long slots = (long)N * Gmax;
-    hipLaunchKernelGGL(record_kernel, dim3((unsigned)((slots + THREADS - 1) / THREADS)), dim3(THREADS), 0, st, gt_boxes,
-                       reinterpret_cast<const long long*>(gt_labels), gt_count, N, Gmax, C, H, W, p->stride, p->target_method, p->target_param, rec);
-    if (int rc = cnl::check_launch("det_loss record_kernel")) return rc;
+    if (int rc = launch_records(c, rec, st)) return rc;
 
     HeatArgs a;
-    a.heat = heat; a.sn = heat_sn; a.sc = heat_sc; a.sh = heat_sh; a.sw = heat_sw;
-    a.tmap = target_map; a.tn = t_sn; a.tc = t_sc; a.th = t_sh; a.tw = t_sw;
-    a.rec = rec; a.count = gt_count; a.part = part;
-    a.C = C; a.H = H; a.W = W; a.Gmax = Gmax; a.tx = tiles_x(W);
-    a.loss = p->heatmap_loss; a.alpha = p->hm_alpha; a.beta = p->hm_beta;
-    a.alpha_is_2 = p->hm_alpha == 2.0; a.beta_is_4 = p->hm_beta == 4.0; a.beta_is_2 = p->hm_beta == 2.0;
+    fill(a, c, rec);
+    a.out = target_map; a.on = t_sn; a.oc = t_sc; a.oh = t_sh; a.ow = t_sw;
+    a.part = part;
     const dim3 grid((unsigned)(N * tiles));
     // with logits their layout picks the element order; a targets-only launch follows the target map's
     const int64_t l_sc = heat ? heat_sc : t_sc, l_sw = heat ? heat_sw : t_sw;
@@ -756,8 +690,7 @@ extern "C" int cnl_detection_loss_f64(const float* heat, int64_t heat_sn, int64_
 
 extern "C" size_t cnl_detection_loss_grad_workspace_bytes(int32_t N, int32_t Gmax, int32_t H, int32_t W) {
     using namespace cnl_det_loss;
-    if (N < 0 || N > (1 << 16) || Gmax < 1 || Gmax > MAX_G || H < 1 || H > (1 << 15) || W < 1 || W > (1 << 15)) return 0;
-    return grad_sections_total(N, Gmax);
+    return dims_in_range(N, Gmax, H, W) ? grad_sections_total(N, Gmax) : 0;
 }
 
 extern "C" int cnl_detection_loss_grad_f32(const float* heat, int64_t heat_sn, int64_t heat_sc, int64_t heat_sh, int64_t heat_sw, const float* box,
@@ -767,51 +700,31 @@ extern "C" int cnl_detection_loss_grad_f32(const float* heat, int64_t heat_sn, i
                                            int64_t gh_sh, int64_t gh_sw, float* grad_box, int64_t gb_sn, int64_t gb_sc, int64_t gb_sh, int64_t gb_sw,
                                            int32_t* skipped, void* workspace, size_t workspace_bytes, void* stream) {
     using namespace cnl_det_loss;
-    CNL_REQUIRE(p, CNL_E_BAD_ARG, "cnl_detection_loss_grad_f32: null params");
-    CNL_REQUIRE(N >= 0 && N <= (1 << 16), CNL_E_BAD_ARG, "cnl_detection_loss_grad_f32: N = %d outside 0..2^16", N);
-    CNL_REQUIRE(C >= 1 && C <= (1 << 16), CNL_E_BAD_ARG, "cnl_detection_loss_grad_f32: C = %d outside 1..2^16", C);
-    CNL_REQUIRE(H >= 1 && H <= (1 << 15) && W >= 1 && W <= (1 << 15), CNL_E_BAD_ARG, "cnl_detection_loss_grad_f32: H x W = %d x %d outside 1..2^15", H, W);
-    CNL_REQUIRE(Gmax >= 1 && Gmax <= MAX_G, CNL_E_BAD_ARG, "cnl_detection_loss_grad_f32: Gmax = %d outside 1..%d", Gmax, MAX_G);
-    CNL_REQUIRE(p->target_method >= 0 && p->target_method <= 2, CNL_E_BAD_ARG, "cnl_detection_loss_grad_f32: target_method = %d outside 0..2", p->target_method);
-    CNL_REQUIRE(p->heatmap_loss >= 0 && p->heatmap_loss <= 1, CNL_E_BAD_ARG, "cnl_detection_loss_grad_f32: heatmap_loss = %d outside 0..1", p->heatmap_loss);
-    CNL_REQUIRE(p->box_loss >= 0 && p->box_loss <= 5, CNL_E_BAD_ARG, "cnl_detection_loss_grad_f32: box_loss = %d outside 0..5", p->box_loss);
-    CNL_REQUIRE(p->stride > 0.0 && p->stride < 1e6, CNL_E_BAD_ARG, "cnl_detection_loss_grad_f32: stride = %g must be positive", p->stride);
-    CNL_REQUIRE(p->target_method != 0 || (p->target_param > 0.0 && p->target_param < 1.0), CNL_E_BAD_ARG,
-                "cnl_detection_loss_grad_f32: cornernet min_overlap = %g outside (0, 1)", p->target_param);
-    CNL_REQUIRE(p->target_param == p->target_param && p->hm_alpha == p->hm_alpha && p->hm_beta == p->hm_beta, CNL_E_BAD_ARG,
-                "cnl_detection_loss_grad_f32: a NaN parameter");
-    CNL_REQUIRE(heat && box, CNL_E_BAD_ARG, "cnl_detection_loss_grad_f32: the gradient needs the logits and the box map");
+    const char* const who = "cnl_detection_loss_grad_f32";
+    const Call c{heat, heat_sn, heat_sc, heat_sh, heat_sw, box, N, C, H, W, Gmax, gt_boxes, gt_labels, gt_count, p};
+    if (int rc = check_call(c, who)) return rc;
+    CNL_REQUIRE(heat && box, CNL_E_BAD_ARG, "%s: the gradient needs the logits and the box map", who);
     if (N == 0) return CNL_OK;
-    CNL_REQUIRE(gt_boxes && gt_labels && gt_count && skipped && workspace, CNL_E_BAD_ARG, "cnl_detection_loss_grad_f32: null pointer");
-    CNL_REQUIRE((((uintptr_t)gt_boxes | (uintptr_t)gt_labels | (uintptr_t)scales) & 7) == 0 && ((uintptr_t)workspace & 15) == 0 &&
-                    (((uintptr_t)heat | (uintptr_t)box | (uintptr_t)grad_heat | (uintptr_t)grad_box | (uintptr_t)gt_count | (uintptr_t)skipped) & 3) == 0,
-                CNL_E_BAD_ARG,
-                "cnl_detection_loss_grad_f32: the float64 / int64 arrays must be 8-byte aligned, the workspace 16-byte aligned, the rest 4-byte aligned");
-    const size_t need = grad_sections_total(N, Gmax);
-    CNL_REQUIRE(workspace_bytes >= need, CNL_E_WORKSPACE, "cnl_detection_loss_grad_f32: workspace of %zu bytes, %zu needed", workspace_bytes, need);
-    const int tiles = tiles_x(W) * tiles_y(H);
-    CNL_REQUIRE((long long)N * tiles < (1ll << 31), CNL_E_UNSUPPORTED, "cnl_detection_loss_grad_f32: %d images x %d tiles exceed the grid", N, tiles);
+    CNL_REQUIRE(gt_boxes && gt_labels && gt_count && skipped && workspace, CNL_E_BAD_ARG, "%s: null pointer", who);
+    if (int rc = check_aligned(who, {gt_boxes, gt_labels, scales}, workspace, {heat, box, grad_heat, grad_box, gt_count, skipped})) return rc;
+    if (int rc = check_workspace(who, workspace_bytes, grad_sections_total(N, Gmax))) return rc;
+    int tiles;
+    if (int rc = check_tile_grid(who, N, H, W, tiles)) return rc;
     char* const ws = static_cast<char*>(workspace);
     Rec* const rec = reinterpret_cast<Rec*>(ws);
     double* const counts = reinterpret_cast<double*>(ws + (size_t)N * Gmax * sizeof(Rec));
     hipStream_t st = (hipStream_t)stream;
 
-    const long slots = (long)N * Gmax;
-    hipLaunchKernelGGL(record_kernel, dim3((unsigned)((slots + THREADS - 1) / THREADS)), dim3(THREADS), 0, st, gt_boxes,
-                       reinterpret_cast<const long long*>(gt_labels), gt_count, N, Gmax, C, H, W, p->stride, p->target_method, p->target_param, rec);
-    if (int rc = cnl::check_launch("det_loss record_kernel")) return rc;
+    if (int rc = launch_records(c, rec, st)) return rc;
     hipLaunchKernelGGL(count_kernel, dim3(1), dim3(THREADS), 0, st, rec, gt_count, N, Gmax, H, W, counts, skipped);
     if (int rc = cnl::check_launch("det_loss count_kernel")) return rc;
     const dim3 grid((unsigned)(N * tiles));
 
     if (grad_heat) {
-        HeatGradArgs a;
-        a.heat = heat; a.sn = heat_sn; a.sc = heat_sc; a.sh = heat_sh; a.sw = heat_sw;
-        a.grad = grad_heat; a.gn = gh_sn; a.gc = gh_sc; a.gh = gh_sh; a.gw = gh_sw;
-        a.rec = rec; a.count = gt_count; a.counts = counts; a.scales = scales;
-        a.C = C; a.H = H; a.W = W; a.Gmax = Gmax; a.tx = tiles_x(W);
-        a.loss = p->heatmap_loss; a.alpha = p->hm_alpha; a.beta = p->hm_beta;
-        a.alpha_is_2 = p->hm_alpha == 2.0; a.beta_is_4 = p->hm_beta == 4.0; a.beta_is_2 = p->hm_beta == 2.0;
+        HeatArgs a;
+        fill(a, c, rec);
+        a.out = grad_heat; a.on = gh_sn; a.oc = gh_sc; a.oh = gh_sh; a.ow = gh_sw;
+        a.counts = counts; a.scales = scales;
         // the element order follows the gradient's strides; four elements per lane where both maps are packed channels-last rows of whole 16-byte groups
         auto packed = [&](const float* ptr, int64_t sn, int64_t sc, int64_t sh, int64_t sw) {
             return sc == 1 && sw == C && sh % 4 == 0 && sn % 4 == 0 && ((uintptr_t)ptr & 15) == 0;

@@ -19,22 +19,21 @@
 //   dw2_kernel       by identity tile, walking all live rows in order: dW2[k, j] = sum_r g[r, k] Z[r, j], db2[k] = sum_r g[r, k]; stored once.
 //   bn_grad_kernel   dbeta, dgamma and the two sums of the BatchNorm backward, over the live rows in order.      dh_kernel   dH of every stat row.
 //   dw1_kernel       a workgroup per 16 x 16 tile of dW1 = sum_r dH[r, j] E[r, i], stat rows in order.           de_kernel   dE[r, i] = sum_j W1[j, i] dH[r, j].
-//   scatter_kernel   a workgroup owns an 8 x 32 pixel tile of one image over all D channels: the image's stat rows whose cell lies in the tile are
-//                    compacted into LDS in slot order; every element is stored exactly once: the sum of its rows' dE in slot order, or 0.
+//   scatter_kernel   a workgroup owns a tile of one image over all D channels (loss_common.h: Tile, element): the image's stat rows whose cell lies in
+//                    the tile are staged in LDS in slot order (stage_pass); every element is stored exactly once: the sum of its rows' dE in slot order, or 0.
 // Nothing here synchronises the device.
-#include "cnl_common.h"
+#include "loss_common.h"
 
 #pragma clang fp contract(off)   // one rounding per operation; the products' accumulation is an explicit fma()
 
 namespace cnl_reid_loss {
 
-constexpr int THREADS = 256, WAVES = THREADS / 64;
-constexpr int MAX_G = 1024, MAX_D = 256, MAX_K = 1 << 20;
+using namespace cnl_loss;
+
+constexpr int MAX_D = 256, MAX_K = 1 << 20;
 constexpr int RB = 32, KT = 64, DC = 32;           // rows per block, identities per tile, features per staged chunk
 constexpr int ZS_LD = RB + 2, WS_LD = KT + 2;      // LDS row pitches (doubles): 16-byte aligned pairs, rows on different banks
 constexpr int FJ = 16, TR = 128;                   // column sums: features per workgroup, rows per tile
-constexpr int TILE_W = 32, TILE_H = 8, PASS_SLOTS = 256;
-static_assert(TILE_W * TILE_H == THREADS && PASS_SLOTS == THREADS, "one pixel / one slot per thread");
 
 struct alignas(16) Row { int state, x, y, id; };   // state: 0 none, 1 statistics only, 2 live
 enum { H_NSTAT = 0, H_NLIVE = 1, H_SKIPPED = 2, H_DEGENERATE = 3, H_M = 4, H_INTS = 8 };
@@ -602,61 +601,34 @@ struct ScatterArgs {
 __global__ __launch_bounds__(THREADS) void scatter_kernel(const ScatterArgs a) {
     __shared__ int4 s_hit[PASS_SLOTS];             // x, y, slot
     __shared__ int s_cnt[WAVES];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int tiles = a.tx * ((a.H + TILE_H - 1) / TILE_H);
-    const int n = blockIdx.x / tiles, tile = blockIdx.x - n * tiles;
-    const int ty = tile / a.tx, txi = tile - ty * a.tx;
-    const int x0 = txi * TILE_W, y0 = ty * TILE_H, x1 = min(x0 + TILE_W, a.W), y1 = min(y0 + TILE_H, a.H);
-    const Row* const rows = a.rows + (long)n * a.Gmax;
-    const double* const dE = a.dE + (long)n * a.Gmax * a.D;
-    float* const grad = a.grad + (long)n * a.gn;
+    const Tile tile(blockIdx.x, a.tx, a.H, a.W);
+    const Row* const rows = a.rows + (long)tile.n * a.Gmax;
+    const double* const dE = a.dE + (long)tile.n * a.Gmax * a.D;
+    float* const grad = a.grad + (long)tile.n * a.gn;
     const int passes = (a.Gmax + PASS_SLOTS - 1) / PASS_SLOTS;
-    const unsigned row_elems = (unsigned)TILE_W * (unsigned)a.D;
+    int cnt = 0;
     // THREADS * D elements, THREADS per step: the trip count is D in every thread, so the barriers are uniform
     for (int step = 0; step < a.D; ++step) {
-        int x, y, c;
-        if (a.cminor) {
-            const unsigned e = (unsigned)step * THREADS + (unsigned)tid;
-            const unsigned yy = e / row_elems, j = e - yy * row_elems, xx = j / (unsigned)a.D;
-            y = y0 + (int)yy; x = x0 + (int)xx; c = (int)(j - xx * (unsigned)a.D);
-        } else {
-            c = step; y = y0 + tid / TILE_W; x = x0 + tid % TILE_W;
-        }
-        const bool inside = x < x1 && y < y1;
+        const Elem e = element(a.cminor, tile, step, a.D);
+        const bool inside = tile.holds(e.x, e.y);
         double sum = 0.0;
         bool touched = false;
         for (int p = 0; p < passes; ++p) {
-            int cnt = 0;
-            if (p > 0 || step == 0 || passes > 1) {           // a single pass is staged once and stays
-                __syncthreads();
-                const int s = p * PASS_SLOTS + tid;
-                bool hit = false;
-                int4 v = make_int4(0, 0, 0, 0);
-                if (s < a.Gmax) {
+            if (passes > 1 || step == 0) {                    // a single pass is staged once and stays
+                cnt = stage_pass(p * PASS_SLOTS, a.Gmax, s_hit, s_cnt, [&](int s, int4& v) {
                     const Row r = rows[s];
                     v = make_int4(r.x, r.y, s, 0);
-                    hit = r.state >= 1 && r.x >= x0 && r.x < x1 && r.y >= y0 && r.y < y1;
-                }
-                const unsigned long long votes = __ballot(hit);
-                if (lane == 0) s_cnt[wave] = __popcll(votes);
-                __syncthreads();
-                int base = 0;
-#pragma unroll
-                for (int w = 0; w < WAVES; ++w)
-                    if (w < wave) base += s_cnt[w];
-                if (hit) s_hit[base + __popcll(votes & ((1ull << lane) - 1ull))] = v;
-                __syncthreads();
+                    return r.state >= 1 && r.x >= tile.x0 && r.x < tile.x1 && r.y >= tile.y0 && r.y < tile.y1;
+                });
             }
-#pragma unroll
-            for (int w = 0; w < WAVES; ++w) cnt += s_cnt[w];
             if (inside) {
                 for (int q = 0; q < cnt; ++q) {               // slot order
                     const int4 h = s_hit[q];
-                    if (h.x == x && h.y == y) { sum += dE[(long)h.z * a.D + c]; touched = true; }
+                    if (h.x == e.x && h.y == e.y) { sum += dE[(long)h.z * a.D + e.c]; touched = true; }
                 }
             }
         }
-        if (inside) grad[(long)c * a.gc + (long)y * a.gh + (long)x * a.gw] = touched ? (float)sum : 0.f;
+        if (inside) grad[(long)e.c * a.gc + (long)e.y * a.gh + (long)e.x * a.gw] = touched ? (float)sum : 0.f;
     }
 }
 
@@ -671,12 +643,10 @@ struct Call {
 
 inline int check_call(const Call& c, const char* who) {
     CNL_REQUIRE(c.p, CNL_E_BAD_ARG, "%s: null params", who);
-    CNL_REQUIRE(c.N >= 0 && c.N <= (1 << 16), CNL_E_BAD_ARG, "%s: N = %d outside 0..2^16", who, c.N);
+    if (int rc = check_dims(who, c.N, c.H, c.W, c.Gmax)) return rc;
     CNL_REQUIRE(c.D >= 1 && c.D <= MAX_D, CNL_E_BAD_ARG, "%s: D = %d outside 1..%d", who, c.D, MAX_D);
     CNL_REQUIRE(c.K >= 2 && c.K <= MAX_K, CNL_E_BAD_ARG, "%s: K = %d outside 2..2^20", who, c.K);
-    CNL_REQUIRE(c.H >= 1 && c.H <= (1 << 15) && c.W >= 1 && c.W <= (1 << 15), CNL_E_BAD_ARG, "%s: H x W = %d x %d outside 1..2^15", who, c.H, c.W);
-    CNL_REQUIRE(c.Gmax >= 1 && c.Gmax <= MAX_G, CNL_E_BAD_ARG, "%s: Gmax = %d outside 1..%d", who, c.Gmax, MAX_G);
-    CNL_REQUIRE(c.p->stride > 0.0 && c.p->stride < 1e6, CNL_E_BAD_ARG, "%s: stride = %g must be positive", who, c.p->stride);
+    if (int rc = check_stride(who, c.p->stride)) return rc;
     CNL_REQUIRE(c.p->bn_eps > 0.0 && c.p->bn_eps < 1e6, CNL_E_BAD_ARG, "%s: bn_eps = %g must be positive", who, c.p->bn_eps);
     CNL_REQUIRE(c.p->momentum >= 0.0 && c.p->momentum <= 1.0, CNL_E_BAD_ARG, "%s: momentum = %g outside 0..1", who, c.p->momentum);
     CNL_REQUIRE((c.p->center == 0 || c.p->center == 1) && (c.p->padded_rows == 0 || c.p->padded_rows == 1) && (c.p->training == 0 || c.p->training == 1),
@@ -684,11 +654,7 @@ inline int check_call(const Call& c, const char* who) {
     if (c.N == 0) return CNL_OK;
     CNL_REQUIRE(c.reid && c.boxes && c.ids && c.count && c.W1 && c.gamma && c.beta && c.running_mean && c.running_var && c.W2 && c.b2, CNL_E_BAD_ARG,
                 "%s: null pointer", who);
-    CNL_REQUIRE((((uintptr_t)c.boxes | (uintptr_t)c.ids) & 7) == 0 &&
-                    (((uintptr_t)c.reid | (uintptr_t)c.count | (uintptr_t)c.W1 | (uintptr_t)c.gamma | (uintptr_t)c.beta | (uintptr_t)c.running_mean |
-                      (uintptr_t)c.running_var | (uintptr_t)c.W2 | (uintptr_t)c.b2) & 3) == 0,
-                CNL_E_BAD_ARG, "%s: the float64 / int64 arrays must be 8-byte aligned, the rest 4-byte aligned", who);
-    return CNL_OK;
+    return check_aligned(who, {c.boxes, c.ids}, nullptr, {c.reid, c.count, c.W1, c.gamma, c.beta, c.running_mean, c.running_var, c.W2, c.b2});
 }
 
 inline unsigned blocks_for(long n) { return (unsigned)((n + THREADS - 1) / THREADS); }
@@ -733,8 +699,7 @@ inline int forward(const Call& c, char* ws, const Sections& sec, double* per_row
 
 static size_t reid_ws_bytes(int32_t N, int32_t Gmax, int32_t D, bool grad) {
     using namespace cnl_reid_loss;
-    if (N < 0 || N > (1 << 16) || Gmax < 1 || Gmax > MAX_G || D < 1 || D > MAX_D) return 0;
-    return sections((long)N * Gmax, D, grad).total;
+    return slots_in_range(N, Gmax) && D >= 1 && D <= MAX_D ? sections((long)N * Gmax, D, grad).total : 0;
 }
 
 extern "C" size_t cnl_reid_loss_workspace_bytes(int32_t N, int32_t Gmax, int32_t D) { return reid_ws_bytes(N, Gmax, D, false); }
@@ -751,12 +716,11 @@ extern "C" int cnl_reid_loss_f64(const float* reid, int64_t sn, int64_t sc, int6
     if (int rc = check_call(c, who)) return rc;
     if (N == 0) return CNL_OK;
     CNL_REQUIRE(per_row && total && counts && workspace, CNL_E_BAD_ARG, "%s: null pointer", who);
-    CNL_REQUIRE((((uintptr_t)per_row | (uintptr_t)total) & 7) == 0 && ((uintptr_t)workspace & 15) == 0 && (((uintptr_t)counts | (uintptr_t)new_stats) & 3) == 0,
-                CNL_E_BAD_ARG, "%s: per_row and total must be 8-byte aligned, the workspace 16-byte aligned, the rest 4-byte aligned", who);
+    if (int rc = check_aligned(who, {per_row, total}, workspace, {counts, new_stats})) return rc;
     const long R = (long)N * Gmax;
     CNL_REQUIRE(R < (1l << 31) / MAX_D, CNL_E_UNSUPPORTED, "%s: %ld rows exceed the grid", who, R);
     const Sections sec = sections(R, D, false);
-    CNL_REQUIRE(workspace_bytes >= sec.total, CNL_E_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, sec.total);
+    if (int rc = check_workspace(who, workspace_bytes, sec.total)) return rc;
     char* const ws = static_cast<char*>(workspace);
     hipStream_t st = (hipStream_t)stream;
     if (int rc = forward(c, ws, sec, per_row, new_stats, nullptr, st)) return rc;
@@ -777,16 +741,13 @@ extern "C" int cnl_reid_loss_grad_f32(const float* reid, int64_t sn, int64_t sc,
     if (int rc = check_call(c, who)) return rc;
     if (N == 0) return CNL_OK;      // (the parameter gradients of an empty batch are the caller's zeros)
     CNL_REQUIRE(workspace, CNL_E_BAD_ARG, "%s: null pointer", who);
-    CNL_REQUIRE(((uintptr_t)scale & 7) == 0 && ((uintptr_t)workspace & 15) == 0 &&
-                    (((uintptr_t)grad_reid | (uintptr_t)grad_W1 | (uintptr_t)grad_gamma | (uintptr_t)grad_beta | (uintptr_t)grad_W2 | (uintptr_t)grad_b2 |
-                      (uintptr_t)skipped) & 3) == 0,
-                CNL_E_BAD_ARG, "%s: scale must be 8-byte aligned, the workspace 16-byte aligned, the rest 4-byte aligned", who);
+    if (int rc = check_aligned(who, {scale}, workspace, {grad_reid, grad_W1, grad_gamma, grad_beta, grad_W2, grad_b2, skipped})) return rc;
     const long R = (long)N * Gmax;
     CNL_REQUIRE(R < (1l << 31) / MAX_D, CNL_E_UNSUPPORTED, "%s: %ld rows exceed the grid", who, R);
-    const int tx = (W + TILE_W - 1) / TILE_W, tiles = tx * ((H + TILE_H - 1) / TILE_H);
-    CNL_REQUIRE((long long)N * tiles < (1ll << 31), CNL_E_UNSUPPORTED, "%s: %d images x %d tiles exceed the grid", who, N, tiles);
+    int tiles;
+    if (int rc = check_tile_grid(who, N, H, W, tiles)) return rc;
     const Sections sec = sections(R, D, true);
-    CNL_REQUIRE(workspace_bytes >= sec.total, CNL_E_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, sec.total);
+    if (int rc = check_workspace(who, workspace_bytes, sec.total)) return rc;
     char* const ws = static_cast<char*>(workspace);
     hipStream_t st = (hipStream_t)stream;
     if (int rc = forward(c, ws, sec, nullptr, nullptr, skipped, st)) return rc;
@@ -833,7 +794,7 @@ extern "C" int cnl_reid_loss_grad_f32(const float* reid, int64_t sn, int64_t sc,
         if (int rc = cnl::check_launch("reid_loss de_kernel")) return rc;
         ScatterArgs a;
         a.grad = grad_reid; a.gn = gn; a.gc = gc; a.gh = gh; a.gw = gw;
-        a.rows = rows; a.dE = dE; a.D = D; a.H = H; a.W = W; a.Gmax = Gmax; a.tx = tx; a.cminor = gc == 1;
+        a.rows = rows; a.dE = dE; a.D = D; a.H = H; a.W = W; a.Gmax = Gmax; a.tx = tiles_x(W); a.cminor = gc == 1;
         hipLaunchKernelGGL(scatter_kernel, dim3((unsigned)(N * tiles)), dim3(THREADS), 0, st, a);
         if (int rc = cnl::check_launch("reid_loss scatter_kernel")) return rc;
     }

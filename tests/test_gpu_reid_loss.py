@@ -10,7 +10,9 @@ default.
 Shapes: N = 3, H x W = 12 x 16, Gmax = 5, counts (5, 0, 3); D in 64 (two staged chunks of 32 features), 8, 20 (a partial chunk); K in 37 (a partial tile of
 64 identities) and 2 * 64 + 3; two boxes in one cell, one box in cell (0, 0) (beside the padded rows with padded_rows), one in the last cell; both
 padded_rows modes, both centre modes (box 3's centre truncs and rounds to different cells), training and eval.  big_case() runs every loop of the kernels more
-than once: N = 3, Gmax = 300, counts (300, 40, 0), D in 96 and 160 (the 4- and 8-chunk forms of dz_kernel / dw2_kernel), K = 2 * 64 + 3."""
+than once: N = 3, Gmax = 300, counts (300, 40, 0), D in 96 and 160 (the 4- and 8-chunk forms of dz_kernel / dw2_kernel), K = 2 * 64 + 3; once more as
+contiguous NCHW (the scatter's plane order with two staging passes).  seam_case(): one 16 x 40 image (2 x 2 tiles of 8 x 32), D = 8, Gmax = 8, a row on
+each side of the tile seams (x = 31 | 32, y = 7 | 8) and in the four map corners: the edges of the scatter's staging predicate."""
 import copy
 import ctypes
 import functools
@@ -193,6 +195,73 @@ def test_many_rows_and_wide_embeddings(D, padded, training):
     check_against_ref(value, d, grads, want, want_grad, training, f"many rows D{D} padded={padded} training={training}")
     for a, b in zip(*runs):
         assert same_bits(a, b)
+
+
+def test_plane_order_with_two_scatter_passes():
+    """big_case(96) (Gmax = 300: two staging passes of the scatter) with the map and its gradient contiguous NCHW: the scatter walks the tile in plane
+    order and restages both passes in every step.  The restatement's bound, and the bits of the channels-last run of the same inputs."""
+    D, padded, training = 96, True, True
+    want, want_grad = big_expected(D, padded, training)
+    assert want["num_rows"] == 333 and want["skipped"] == 3
+    reid, boxes, ids, count, cls = big_case(D)
+    assert boxes.shape[1] == 300 > 256                        # more slots than one pass stages
+    gts = device_targets(boxes, ids, count)
+    kw = dict(training=training, stride=STRIDE, padded_rows=padded)
+    runs = []
+    for fmt in (torch.contiguous_format, torch.channels_last):
+        x, d = torch.from_numpy(reid).cuda().contiguous(memory_format=fmt), device_cls(cls)
+        d["num_batches_tracked"] = torch.tensor(3, dtype=torch.int64, device="cuda")
+        grads = cl.reid_loss_grad(x, gts, d, **kw)
+        value = cl.reid_loss(x, gts, d, **kw)
+        assert grads["reid_grad"].stride() == x.stride()
+        runs.append((value, d, grads))
+    value, d, grads = runs[0]
+    assert grads["reid_grad"].is_contiguous() and grads["reid_grad"].stride(3) == 1 and runs[1][2]["reid_grad"].stride(1) == 1
+    check_against_ref(value, d, grads, want, want_grad, training, "plane order, two scatter passes")
+    for k in ref.GRADS:
+        assert same_bits(grads[k + "_grad"], runs[1][2][k + "_grad"]), k
+    assert same_bits(value["per_row"], runs[1][0]["per_row"]) and same_bits(value["reid"], runs[1][0]["reid"])
+
+
+SEAM_H, SEAM_W, SEAM_D, SEAM_K = 16, 40, 8, 37
+SEAM_CELLS = [(31, 7), (32, 7), (31, 8), (32, 8), (0, 0), (SEAM_W - 1, 0), (0, SEAM_H - 1), (SEAM_W - 1, SEAM_H - 1)]      # the 8 x 32 tiles meet at x = 31 | 32, y = 7 | 8
+
+
+@functools.lru_cache(maxsize=None)
+def seam_case():
+    """One image, Gmax = 8: a row in each of the four cells around the tiles' common corner and in the four corners of the map.  -> as case(), and the
+    restatement's value and gradient"""
+    rng = np.random.default_rng(31)
+    boxes = boxes_at(np.asarray(SEAM_CELLS, np.float64) + 0.5, rng.uniform(1.0, 4.0, (len(SEAM_CELLS), 2)))[None]
+    ids = rng.choice(SEAM_K, len(SEAM_CELLS), replace=False).astype(np.int64)[None]
+    count = np.array([len(SEAM_CELLS)], np.int32)
+    reid = rng.normal(0.0, 1.0, (1, SEAM_D, SEAM_H, SEAM_W)).astype(np.float32)
+    D, K = SEAM_D, SEAM_K
+    cls = dict(W1=rng.normal(0, 1 / np.sqrt(D), (D, D)), gamma=rng.uniform(0.5, 1.5, D), beta=rng.normal(0, 0.3, D), running_mean=rng.normal(0, 0.2, D),
+               running_var=rng.uniform(0.5, 1.5, D), W2=rng.normal(0, 2 / np.sqrt(D), (K, D)), b2=rng.normal(0, 0.5, K))
+    cls = {k: v.astype(np.float32) for k, v in cls.items()}
+    kw = dict(training=True, stride=STRIDE)
+    return (reid, boxes, ids, count, cls), ref.reid_loss(reid, boxes, ids, count, cls, **kw), ref.reid_loss_grad(reid, boxes, ids, count, cls, **kw)
+
+
+@pytest.mark.parametrize("fmt", [torch.channels_last, torch.contiguous_format], ids=["nhwc", "nchw"])
+def test_rows_on_both_sides_of_the_tile_seams_and_in_the_map_corners(fmt):
+    """The scatter stages a row in the tile whose rectangle holds its cell (x0 <= x < x1, y0 <= y < y1): a row on either side of a seam, or in a corner
+    of the map, belongs to exactly one tile, and every other element of the gradient is exactly +0."""
+    (reid, boxes, ids, count, cls), want, want_grad = seam_case()
+    assert want["num_rows"] == len(SEAM_CELLS) and want["skipped"] == 0
+    assert sorted(zip(*np.nonzero(want_grad["read"][0])[::-1])) == sorted(SEAM_CELLS)
+    assert {(x // 32, y // 8) for x, y in SEAM_CELLS} == {(0, 0), (1, 0), (0, 1), (1, 1)}
+    for (x, y) in SEAM_CELLS:                                 # every planted row carries a gradient
+        assert (want_grad["reid"][0, :, y, x] != 0).any(), (x, y)
+    x, d = torch.from_numpy(reid).cuda().contiguous(memory_format=fmt), device_cls(cls)
+    d["num_batches_tracked"] = torch.tensor(3, dtype=torch.int64, device="cuda")
+    gts = device_targets(boxes, ids, count)
+    grads = cl.reid_loss_grad(x, gts, d, training=True, stride=STRIDE)
+    value = cl.reid_loss(x, gts, d, training=True, stride=STRIDE)
+    check_against_ref(value, d, grads, want, want_grad, True, "tile seams and map corners")
+    g = grads["reid_grad"].cpu().numpy()
+    assert np.array_equal((g != 0).any(axis=1), want_grad["read"])
 
 
 def test_rules_skipped_ignored_and_cells():
