@@ -67,6 +67,24 @@ def upload(buf, dev) -> torch.Tensor:
     return host.to(dev, non_blocking=True)
 
 
+def upload_parts(parts, dev):
+    """numpy arrays (int64 / float64 / int32 / float32) -> device tensors of the same dtype and shape, through ONE pinned staging buffer and
+    one asynchronous copy (call under torch.cuda.device(dev))."""
+    import numpy as np
+    words = [-(-p.nbytes // 8) for p in parts]
+    buf = np.zeros((max(sum(words), 1),), dtype=np.int64)
+    at = 0
+    for p, w in zip(parts, words):
+        buf[at:at + w].view(np.uint8)[:p.nbytes] = np.ascontiguousarray(p).reshape(-1).view(np.uint8)
+        at += w
+    dev_buf = upload(buf, dev)
+    out, at = [], 0
+    for p, w in zip(parts, words):
+        out.append(dev_buf[at:at + w].view(getattr(torch, p.dtype.name))[:p.size].view(p.shape))
+        at += w
+    return out
+
+
 def gather(dev, windows, plain, height: int, width: int, C: int, word: int, planes=None, coef=None, merge_records=None,
            frame_first_view=None) -> Gathered:
     """One pinned upload and one launch for the V windows [(frame, y0, x0, h, w, new_h, new_w, pad_top, pad_left)].
@@ -100,7 +118,7 @@ def gather(dev, windows, plain, height: int, width: int, C: int, word: int, plan
                        yuv_table=d[:o_plain].view(V, 9) if planes is not None else None,
                        merge_table=d[o_merge:o_first].view(torch.int32).view(V, 8) if merge_records is not None else None,
                        first_view=d[o_first:].view(torch.int32)[:n_first] if merge_records is not None else None)
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        stream = _lib.stream(dev)
         # the two entry points differ in one argument: the six colour integers where the packed one takes C
         entry, table, c = (("cnl_letterbox_yuv420_u8", out.yuv_table, (ctypes.c_int32 * 6)(*coef)) if planes is not None else
                            ("cnl_letterbox_bilinear_u8", out.table, C))

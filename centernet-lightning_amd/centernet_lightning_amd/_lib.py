@@ -305,6 +305,12 @@ def check(rc, what=""):
     raise RuntimeError(msg)
 
 
+def stream(device):
+    """The hipStream_t argument of an entry point: the device's current torch stream."""
+    import torch
+    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
 def absmax_stride():
     """Floats between the per-image slots of an x_absmax / y_absmax array (one 128-byte line per image: include/centernet_gfx950.h)."""
     return load().cnl_absmax_stride()

@@ -13,14 +13,13 @@ over the image (what DALI's ColorTwist does): contrast pivots on the constant `c
 YIQ instead of HSV.  Rotation, shear (Affine) and RandomCrop / SmallestMaxSize are warp.py's (a rule and a kernel of their own; this module's
 behaviour is unchanged); MixUp and YUV sources are out of scope.
 """
-import ctypes
 import dataclasses
 import math
 
 import numpy as np
 import torch
 
-from . import _frames, _gather, _lib
+from . import _frames, _gather, _lib, _targets
 from .loss import MAX_PER_IMAGE, MAX_SIDE
 
 MAX_PLACE, MAX_HOLES = 4, 16                      # placement and hole slots per canvas (csrc/augment.hip)
@@ -29,6 +28,7 @@ MAX_ENTRY, MAX_OFFSET = 32767, 1 << 21            # bounds of the nine matrix en
 IDENTITY_Q12 = np.array([Q12, 0, 0, 0, Q12, 0, 0, 0, Q12, 0, 0, 0], dtype=np.int32)
 BRIGHTNESS, CONTRAST, SATURATION, HUE = 0, 1, 2, 3
 
+_COLUMNS = _targets.columns(("labels", "int64"), ("ids", "int64"))          # of the targets; the ids are optional
 _LUMA = np.array([0.299, 0.587, 0.114], dtype=np.float64)
 _YIQ = np.array([[0.299, 0.587, 0.114], [0.5959, -0.2746, -0.3213], [0.2115, -0.5227, 0.3112]], dtype=np.float64)
 
@@ -61,33 +61,24 @@ def colour_matrix(brightness=1.0, contrast=1.0, saturation=1.0, hue=0.0, order=(
     return q
 
 
-@dataclasses.dataclass
-class AugmentPlan:
-    """What augment_batch does to a batch of F frames, as numpy arrays (N canvases; slot p of canvas n is live when p < n_place[n]):
-    sizes [(h, w)] of the F frames; n_place [N] int32 (1..4); frame [N, 4] int32; window [N, 4, 4] int32 (x0, y0, w, h) in the frame;
-    dest [N, 4, 4] int32 (dx0, dy0, dw, dh) in the canvas; flip [N, 4] int32; colour [N, 4, 12] int32 (colour_matrix); holes
-    [N, 16, 4] int32 (x0, y0, w, h) in canvas pixels, w == 0 marking a dead slot.  The plan is the interface: build one by hand with
-    AugmentPlan.empty and fill its arrays, then check()."""
-    sizes: list
-    height: int
-    width: int
-    n_place: np.ndarray
-    frame: np.ndarray
-    window: np.ndarray
-    dest: np.ndarray
-    flip: np.ndarray
-    colour: np.ndarray
-    holes: np.ndarray
+_HEAD = (("n_place", np.int32, ()), ("frame", np.int32, (MAX_PLACE,)), ("window", np.int32, (MAX_PLACE, 4)), ("dest", np.int32, (MAX_PLACE, 4)))
+_TAIL = (("colour", np.int32, (MAX_PLACE, 12)), ("holes", np.int32, (MAX_HOLES, 4)))
+
+
+class _Plan:
+    """What AugmentPlan and warp.WarpPlan share.  A plan class is a dataclass of sizes, height, width and the arrays of its _FIELDS
+    [(name, dtype, shape of one canvas)], and names what a slot starts as where that is not zero (_INITIAL), the int64 words of one
+    placement record (RECORD_WORDS) and its two library entry points (IMAGE_ENTRY, BOXES_ENTRY)."""
 
     @classmethod
     def empty(cls, sizes, height, width, N=None):
-        """A plan of N canvases (default: one per frame) with no live placement yet, identity colours and no holes."""
+        """A plan of N canvases (default: one per frame) with no live placement yet, identity maps and colours and no holes."""
         sizes = [(int(h), int(w)) for (h, w) in sizes]
         N = len(sizes) if N is None else int(N)
-        colour = np.empty((N, MAX_PLACE, 12), dtype=np.int32)
-        colour[...] = IDENTITY_Q12
-        return cls(sizes, int(height), int(width), np.zeros(N, np.int32), np.zeros((N, MAX_PLACE), np.int32), np.zeros((N, MAX_PLACE, 4), np.int32),
-                   np.zeros((N, MAX_PLACE, 4), np.int32), np.zeros((N, MAX_PLACE), np.int32), colour, np.zeros((N, MAX_HOLES, 4), np.int32))
+        arrays = {name: np.zeros((N,) + shape, dtype) for name, dtype, shape in cls._FIELDS}
+        for name, value in cls._INITIAL.items():
+            arrays[name][...] = value
+        return cls(sizes, int(height), int(width), **arrays)
 
     def __len__(self):
         return int(self.n_place.shape[0])
@@ -99,19 +90,17 @@ class AugmentPlan:
     def single(self, n):
         """The plan of canvas n alone (same frames)."""
         s = slice(n, n + 1)
-        return AugmentPlan(self.sizes, self.height, self.width, self.n_place[s].copy(), self.frame[s].copy(), self.window[s].copy(),
-                           self.dest[s].copy(), self.flip[s].copy(), self.colour[s].copy(), self.holes[s].copy())
+        return type(self)(self.sizes, self.height, self.width, **{name: getattr(self, name)[s].copy() for name, _, _ in self._FIELDS})
 
     def check(self):
         """Every bound of the plan; ValueError naming the canvas and placement otherwise.  -> self"""
         N, H, W, F = len(self), self.height, self.width, len(self.sizes)
         if not (1 <= H <= MAX_SIDE and 4 <= W <= MAX_SIDE and W % 4 == 0):
             raise ValueError(f"plan: canvas {H} x {W} needs sides of at most {MAX_SIDE} and a width that is a positive multiple of 4")
-        for name, shape in (("n_place", (N,)), ("frame", (N, MAX_PLACE)), ("window", (N, MAX_PLACE, 4)), ("dest", (N, MAX_PLACE, 4)),
-                            ("flip", (N, MAX_PLACE)), ("colour", (N, MAX_PLACE, 12)), ("holes", (N, MAX_HOLES, 4))):
+        for name, dtype, shape in self._FIELDS:
             a = getattr(self, name)
-            if not isinstance(a, np.ndarray) or a.dtype != np.int32 or a.shape != shape:
-                raise ValueError(f"plan: {name} must be an int32 array of shape {list(shape)}")
+            if not isinstance(a, np.ndarray) or a.dtype != dtype or a.shape != (N,) + shape:
+                raise ValueError(f"plan: {name} must be {'an' if dtype != np.float64 else 'a'} {np.dtype(dtype).name} array of shape {[N] + list(shape)}")
         for (h, w) in self.sizes:
             if h < 1 or w < 1:
                 raise ValueError(f"plan: frame size {h} x {w}")
@@ -141,9 +130,7 @@ class AugmentPlan:
         if at:
             raise ValueError(f"plan: canvas {at[0]} placement {at[1]}: rectangle (dx0 {dx0[at]}, dy0 {dy0[at]}, dw {dw[at]}, dh {dh[at]}) needs dx0 and dw "
                              f"multiples of 4, dh >= 1, inside the {H} x {W} canvas")
-        at = first((self.flip != 0) & (self.flip != 1))
-        if at:
-            raise ValueError(f"plan: canvas {at[0]} placement {at[1]}: flip must be 0 or 1")
+        self._check_geometry(first)
         c = np.abs(self.colour.astype(np.int64))
         at = first((c[..., :9].max(axis=-1) > MAX_ENTRY) | (c[..., 9:].max(axis=-1) > MAX_OFFSET))
         if at:
@@ -162,16 +149,48 @@ class AugmentPlan:
         return self
 
     def pack(self, places, holes, n_place):
-        """Fill the upload's views: places [N * 4, 24] int32 (cnl_augment_placement records, zeroed), holes [N * 16, 4] int32, n_place [N]."""
+        """Fill the upload's views: places [N * 4, 2 * RECORD_WORDS] int32 (the placement records, zeroed), holes [N * 16, 4] int32, n_place [N].
+        -> the records as [N, 4, 2 * RECORD_WORDS], for the words a plan class adds."""
         N = len(self)
-        rec = places.reshape(N, MAX_PLACE, 24)
+        rec = places.reshape(N, MAX_PLACE, 2 * self.RECORD_WORDS)
         rec[:, :, 0] = self.frame
         rec[:, :, 1:5] = self.window
         rec[:, :, 5:9] = self.dest
-        rec[:, :, 9] = self.flip
         rec[:, :, 10:22] = self.colour
         holes.reshape(N, MAX_HOLES, 4)[:] = self.holes
         n_place[:] = self.n_place
+        return rec
+
+
+@dataclasses.dataclass
+class AugmentPlan(_Plan):
+    """What augment_batch does to a batch of F frames, as numpy arrays (N canvases; slot p of canvas n is live when p < n_place[n]):
+    sizes [(h, w)] of the F frames; n_place [N] int32 (1..4); frame [N, 4] int32; window [N, 4, 4] int32 (x0, y0, w, h) in the frame;
+    dest [N, 4, 4] int32 (dx0, dy0, dw, dh) in the canvas; flip [N, 4] int32; colour [N, 4, 12] int32 (colour_matrix); holes
+    [N, 16, 4] int32 (x0, y0, w, h) in canvas pixels, w == 0 marking a dead slot.  The plan is the interface: build one by hand with
+    AugmentPlan.empty and fill its arrays, then check()."""
+    sizes: list
+    height: int
+    width: int
+    n_place: np.ndarray
+    frame: np.ndarray
+    window: np.ndarray
+    dest: np.ndarray
+    flip: np.ndarray
+    colour: np.ndarray
+    holes: np.ndarray
+
+    _FIELDS = _HEAD + (("flip", np.int32, (MAX_PLACE,)),) + _TAIL
+    _INITIAL = {"colour": IDENTITY_Q12}
+    RECORD_WORDS, IMAGE_ENTRY, BOXES_ENTRY = 12, "cnl_augment_u8", "cnl_augment_boxes_f64"          # cnl_augment_placement: 96 bytes
+
+    def _check_geometry(self, first):
+        at = first((self.flip != 0) & (self.flip != 1))
+        if at:
+            raise ValueError(f"plan: canvas {at[0]} placement {at[1]}: flip must be 0 or 1")
+
+    def pack(self, places, holes, n_place):
+        super().pack(places, holes, n_place)[:, :, 9] = self.flip
 
 
 # ----------------------------------------------------------------------------- drawing a plan
@@ -294,73 +313,6 @@ def sample_augment(sizes, height, width, rng, *, mosaic=0.0, scale=(0.08, 1.0), 
 
 
 # ----------------------------------------------------------------------------- the call
-def _list_targets(targets, F, what):
-    """A list of per-image {"boxes" [n, 4] (x, y, w, h), "labels" [n][, "ids" [n]]} -> numpy (boxes [F, Gmax, 4] f64, labels, ids or None,
-    count [F] i32).  Nothing is judged here: the kernel's keep rule drops what cannot be a target."""
-    if len(targets) != F:
-        raise ValueError(f"{what}: {F} frames against {len(targets)} targets")
-    with_ids = [isinstance(d, dict) and "ids" in d for d in targets]
-    if any(with_ids) and not all(with_ids):
-        raise ValueError(f"{what}: either every target has 'ids' or none has")
-    images = []
-    for i, d in enumerate(targets):
-        if not isinstance(d, dict) or "boxes" not in d or "labels" not in d:
-            raise ValueError(f"{what}: targets[{i}] must be a dict with 'boxes', 'labels'")
-        try:
-            cols = [np.asarray(d[k].detach().cpu().numpy() if isinstance(d[k], torch.Tensor) else d[k]) for k in ("boxes", "labels") + (("ids",) if with_ids[i] else ())]
-            b = cols[0].astype(np.float64)
-            rest = [c.astype(np.int64).reshape(-1) for c in cols[1:]]
-        except (TypeError, ValueError) as e:
-            raise ValueError(f"{what}: targets[{i}] is not numeric: {e}") from e
-        if b.size == 0:
-            b = b.reshape(0, 4)
-        if b.ndim != 2 or b.shape[1] != 4 or any(c.shape[0] != b.shape[0] for c in rest):
-            raise ValueError(f"{what}: targets[{i}] has boxes {b.shape} against {[c.shape for c in rest]}; expected [n, 4] and [n]")
-        images.append((b, rest))
-    Gmax = max([1] + [b.shape[0] for (b, _) in images])
-    boxes, labels, count = np.zeros((F, Gmax, 4), np.float64), np.zeros((F, Gmax), np.int64), np.zeros((F,), np.int32)
-    ids = np.zeros((F, Gmax), np.int64) if all(with_ids) and F else None
-    for i, (b, rest) in enumerate(images):
-        m = b.shape[0]
-        boxes[i, :m], labels[i, :m], count[i] = b, rest[0], m
-        if ids is not None:
-            ids[i, :m] = rest[1]
-    return boxes, labels, ids, count
-
-
-def _device_targets(targets, F, dev, what):
-    """The padded device forms of loss.py: a dict {"boxes", "labels", "count"[, "ids"]} or a tuple (boxes, labels, count[, ids])."""
-    if isinstance(targets, dict):
-        if any(name not in targets for name in ("boxes", "labels", "count")):
-            raise ValueError(f"{what}: device targets need 'boxes' [F,Gmax,4] f64, 'labels' [F,Gmax] i64 and 'count' [F] i32")
-        boxes, labels, count, ids = targets["boxes"], targets["labels"], targets["count"], targets.get("ids")
-    else:
-        boxes, labels, count = targets[:3]
-        ids = targets[3] if len(targets) == 4 else None
-    Gmax = int(boxes.shape[1]) if isinstance(boxes, torch.Tensor) and boxes.dim() == 3 else -1
-    out = []
-    for name, t, dtype, shape in (("boxes", boxes, torch.float64, (F, Gmax, 4)), ("labels", labels, torch.int64, (F, Gmax)),
-                                  ("ids", ids, torch.int64, (F, Gmax)), ("count", count, torch.int32, (F,))):
-        if t is None and name == "ids":
-            out.append(None)
-            continue
-        if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != shape:
-            raise ValueError(f"{what}: targets '{name}' must be a {dtype} tensor of shape {list(shape)} (Gmax >= 1), got "
-                             f"{(t.dtype, tuple(t.shape)) if isinstance(t, torch.Tensor) else type(t).__name__}")
-        _gather.require_hip([t], what)
-        if t.device != dev:
-            raise ValueError(f"{what}: targets '{name}' lives on {t.device}, the frames on {dev}")
-        out.append(t.contiguous())
-    if Gmax < 1:
-        raise ValueError(f"{what}: Gmax = {Gmax}")
-    return out[0], out[1], out[2], out[3], Gmax
-
-
-def _is_padded(targets):
-    return isinstance(targets, dict) or (isinstance(targets, (list, tuple)) and len(targets) in (3, 4) and
-                                         all(isinstance(t, torch.Tensor) for t in targets))
-
-
 def _out(out, name, dtype, shape, dev, what):
     """The caller's buffer for one result (out[name]: a contiguous tensor of exactly that type, shape and device), or a fresh one."""
     t = out.get(name) if out else None
@@ -385,13 +337,12 @@ def augment_batch(frames, plan, targets=None, fill=(0, 0, 0), hole_fill=(0, 0, 0
     then source order; slots beyond count are zero.  Holes do not touch boxes.  out: optionally a dict of the caller's own buffers to
     write into, by the names "canvas", "boxes", "labels", "ids", "count" (a training loop reuses them; every element is written).
     One pinned upload, two launches, no device sync."""
-    return _batch("augment_batch", AugmentPlan, 12, "cnl_augment_u8", "cnl_augment_boxes_f64", (fill, hole_fill), frames, plan, targets, min_area, min_visibility,
-                  out)
+    return _batch("augment_batch", AugmentPlan, (fill, hole_fill), frames, plan, targets, min_area, min_visibility, out)
 
 
-def _batch(what, plan_type, record_words, image_entry, boxes_entry, fills, frames, plan, targets, min_area, min_visibility, out):
-    """The host path of augment_batch and warp.warp_batch: a plan of `plan_type` whose records are record_words int64 words, the image
-    entry (which takes the colour words of `fills` in order) and the box entry."""
+def _batch(what, plan_type, fills, frames, plan, targets, min_area, min_visibility, out):
+    """The host path of augment_batch and warp.warp_batch: a plan of `plan_type`, which names its record words, its image entry (which
+    takes the colour words of `fills` in order) and its box entry."""
     if not isinstance(plan, plan_type):
         raise ValueError(f"{what}: plan must be {'an' if plan_type.__name__[0] in 'AEIOU' else 'a'} {plan_type.__name__}, got {type(plan).__name__}")
     plan.check()
@@ -409,22 +360,21 @@ def _batch(what, plan_type, record_words, image_entry, boxes_entry, fills, frame
     words = [_frames.fill_word(f, 3) for f in fills]
     max_place = plan.max_place
 
-    host = None                                  # a list of targets travels in the same upload
-    if targets is not None and not _is_padded(targets):
-        if not isinstance(targets, (list, tuple)):
-            raise ValueError(f"{what}: targets must be a list of per-image dicts or padded device tensors, got {type(targets).__name__}")
-        host = _list_targets(targets, F, what)
-        Gmax, with_ids = host[0].shape[1], host[2] is not None
-    elif targets is not None:
-        t_boxes, t_labels, t_ids, t_count, Gmax = _device_targets(targets, F, dev, what)
-        with_ids = t_ids is not None
-    if targets is not None and max_place * Gmax > MAX_PER_IMAGE:
-        raise ValueError(f"{what}: {max_place} placements x Gmax = {Gmax} boxes give Gout = {max_place * Gmax}; at most {MAX_PER_IMAGE} per image "
-                         "are supported")
+    host = None                                  # a list of targets travels in the same upload; nothing in it is judged: the kernel's keep rule does that
+    if targets is not None:
+        if _targets.is_padded(targets, (3, 4)):
+            t, Gmax, _ = _targets.read_padded(targets, F, _COLUMNS, what, optional=("ids",), device=dev)
+        else:
+            t, Gmax = _targets.read_list(targets, F, _COLUMNS, what, against="frames", optional=("ids",))
+            host = t
+        with_ids = t["ids"] is not None
+        if max_place * Gmax > MAX_PER_IMAGE:
+            raise ValueError(f"{what}: {max_place} placements x Gmax = {Gmax} boxes give Gout = {max_place * Gmax}; at most {MAX_PER_IMAGE} per image "
+                             "are supported")
 
-    # [F x 5] frame records | (pad to 16 bytes) | [N x 4 x record_words] placements | [N x 16 x 2] holes | n_place | boxes | labels | ids | count, in int64 words
+    # [F x 5] frame records | (pad to 16 bytes) | [N x 4 x RECORD_WORDS] placements | [N x 16 x 2] holes | n_place | boxes | labels | ids | count, in int64 words
     o_place = F * 5 + (F * 5) % 2
-    o_holes = o_place + N * MAX_PLACE * record_words
+    o_holes = o_place + N * MAX_PLACE * plan.RECORD_WORDS
     o_np = o_holes + N * MAX_HOLES * 2
     o_boxes = o_np + (N + 1) // 2
     o_labels = o_ids = o_count = end = o_boxes
@@ -435,39 +385,37 @@ def _batch(what, plan_type, record_words, image_entry, boxes_entry, fills, frame
         end = o_count + (F + 1) // 2
     windows = src.whole()
     buf = _gather.pack_records(windows, *src.records(windows), tail_words=end - F * 5)
-    plan.pack(buf[o_place:o_holes].view(np.int32).reshape(N * MAX_PLACE, 2 * record_words), buf[o_holes:o_np].view(np.int32).reshape(N * MAX_HOLES, 4),
+    plan.pack(buf[o_place:o_holes].view(np.int32).reshape(N * MAX_PLACE, 2 * plan.RECORD_WORDS), buf[o_holes:o_np].view(np.int32).reshape(N * MAX_HOLES, 4),
               buf[o_np:o_boxes].view(np.int32)[:N])
     if host is not None:
-        buf[o_boxes:o_labels].view(np.float64)[:] = host[0].reshape(-1)
-        buf[o_labels:o_ids] = host[1].reshape(-1)
+        buf[o_boxes:o_labels].view(np.float64)[:] = t["boxes"].reshape(-1)
+        buf[o_labels:o_ids] = t["labels"].reshape(-1)
         if with_ids:
-            buf[o_ids:o_count] = host[2].reshape(-1)
-        buf[o_count:end].view(np.int32)[:F] = host[3]
+            buf[o_ids:o_count] = t["ids"].reshape(-1)
+        buf[o_count:end].view(np.int32)[:F] = t["count"]
 
     lib = _lib.load()
     with torch.cuda.device(dev):
         d = _gather.upload(buf, dev)
         canvas = _out(out, "canvas", torch.uint8, (N, plan.height, plan.width, 3), dev, what)
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        stream = _lib.stream(dev)
         places, n_place = d[o_place:o_holes], d[o_np:o_boxes]
-        _lib.check(getattr(lib, image_entry)(d.data_ptr(), F, places.data_ptr(), n_place.data_ptr(), max_place, d[o_holes:o_np].data_ptr(), canvas.data_ptr(),
-                                             N, plan.height, plan.width, *words, stream), image_entry)
+        _lib.check(getattr(lib, plan.IMAGE_ENTRY)(d.data_ptr(), F, places.data_ptr(), n_place.data_ptr(), max_place, d[o_holes:o_np].data_ptr(),
+                                                  canvas.data_ptr(), N, plan.height, plan.width, *words, stream), plan.IMAGE_ENTRY)
         if targets is None:
             return canvas, None
         if host is not None:
-            t_boxes = d[o_boxes:o_labels].view(torch.float64).view(F, Gmax, 4)
-            t_labels = d[o_labels:o_ids].view(F, Gmax)
-            t_ids = d[o_ids:o_count].view(F, Gmax) if with_ids else None
-            t_count = d[o_count:end].view(torch.int32)[:F]
+            t = {"boxes": d[o_boxes:o_labels].view(torch.float64).view(F, Gmax, 4), "labels": d[o_labels:o_ids].view(F, Gmax),
+                 "ids": d[o_ids:o_count].view(F, Gmax) if with_ids else None, "count": d[o_count:end].view(torch.int32)[:F]}
         Gout = max_place * Gmax
         res = {"boxes": _out(out, "boxes", torch.float64, (N, Gout, 4), dev, what), "labels": _out(out, "labels", torch.int64, (N, Gout), dev, what),
                "count": _out(out, "count", torch.int32, (N,), dev, what)}
         if with_ids:
             res["ids"] = _out(out, "ids", torch.int64, (N, Gout), dev, what)
-        _lib.check(getattr(lib, boxes_entry)(places.data_ptr(), n_place.data_ptr(), max_place, N, F, t_boxes.data_ptr(), t_labels.data_ptr(),
-                                             t_ids.data_ptr() if with_ids else None, t_count.data_ptr(), Gmax, res["boxes"].data_ptr(),
-                                             res["labels"].data_ptr(), res["ids"].data_ptr() if with_ids else None, res["count"].data_ptr(), Gout,
-                                             float(min_area), float(min_visibility), stream), boxes_entry)
+        _lib.check(getattr(lib, plan.BOXES_ENTRY)(places.data_ptr(), n_place.data_ptr(), max_place, N, F, t["boxes"].data_ptr(), t["labels"].data_ptr(),
+                                                  t["ids"].data_ptr() if with_ids else None, t["count"].data_ptr(), Gmax, res["boxes"].data_ptr(),
+                                                  res["labels"].data_ptr(), res["ids"].data_ptr() if with_ids else None, res["count"].data_ptr(), Gout,
+                                                  float(min_area), float(min_visibility), stream), plan.BOXES_ENTRY)
     return canvas, res
 
 
@@ -484,7 +432,6 @@ def _frame_sizes(frames):
     return sizes
 
 
-_SETTINGS = ("mosaic", "scale", "ratio", "flip", "brightness", "contrast", "saturation", "hue", "contrast_center", "cutout", "crop")
 _IGNORED = ("Normalize",)                        # the stem and preprocess_uint8 normalise
 
 
@@ -503,14 +450,15 @@ def _config_items(transforms, unsupported):
     return items
 
 
-def _read_common(name, params, settings, size):
-    """One transform that TrainAugment and warp.TrainWarp read alike, into `settings` (and `size`, the canvas it names) -> whether it was one."""
+def _read_common(name, params, settings, size, resized):
+    """One transform that TrainAugment and warp.TrainWarp read alike, into `settings` (and `size`, the canvas it names; `resized`: what crop
+    is for a RandomResizedCrop) -> whether it was one."""
     if name == "HorizontalFlip":
         settings["flip"] = float(params.get("p", 0.5))
     elif name in ("RandomResizedCrop", "Resize"):
         size.clear()
         size.update({k: int(params[k]) for k in ("height", "width") if k in params})
-        settings["crop"] = name == "RandomResizedCrop"
+        settings["crop"] = resized if name == "RandomResizedCrop" else False
         if name == "RandomResizedCrop":
             settings["scale"] = tuple(params.get("scale", (0.08, 1.0)))
             settings["ratio"] = tuple(params.get("ratio", (3 / 4, 4 / 3)))
@@ -525,50 +473,74 @@ def _read_common(name, params, settings, size):
     return True
 
 
-class TrainAugment:
-    """The training transform of a run: callable as (frames, targets) -> (canvas, targets).  Owns a numpy Generator (`seed`); every
-    call draws a fresh plan with sample_augment(**settings) (kept as .last_plan) and runs augment_batch."""
+class _Transform:
+    """What TrainAugment and warp.TrainWarp share: the training transform of a run, callable as (frames, targets) -> (canvas, targets).  It owns
+    a numpy Generator (`seed`); every call draws a fresh plan with its sampler (kept as .last_plan) and runs its batch call.  A transform
+    class names its sampler and the settings that takes (_sample, _SETTINGS), its batch call (_run), what crop is for a RandomResizedCrop
+    (_RESIZED), the transforms that name the canvas size and the ones it reads (_SIZED, _SUPPORTED, for the messages) and how it reads a
+    transform _read_common does not know (_read_other); its own __init__ states which colours its batch call takes."""
+    _RESIZED = True
 
-    def __init__(self, height, width, seed=0, fill=(0, 0, 0), hole_fill=(0, 0, 0), min_area=1.0, min_visibility=0.0, **settings):
-        unknown = [k for k in settings if k not in _SETTINGS]
+    def _setup(self, height, width, seed, fills, min_area, min_visibility, settings):
+        unknown = [k for k in settings if k not in self._SETTINGS]
         if unknown:
-            raise ValueError(f"TrainAugment: unknown settings {unknown}; sample_augment takes {list(_SETTINGS)}")
+            raise ValueError(f"{type(self).__name__}: unknown settings {unknown}; {self._sample.__name__} takes {list(self._SETTINGS)}")
         self.height, self.width, self.settings = int(height), int(width), dict(settings)
-        self.fill, self.hole_fill, self.min_area, self.min_visibility = fill, hole_fill, min_area, min_visibility
+        for name, colour in fills.items():          # .fill, .hole_fill (and .border): read again at every call
+            setattr(self, name, colour)
+        self._fills, self.min_area, self.min_visibility = tuple(fills), min_area, min_visibility
         self.rng = np.random.default_rng(seed)
         self.skipped, self.last_plan = [], None
-        sample_augment([(self.height, self.width)], self.height, self.width, np.random.default_rng(0), **self.settings)    # bad settings fail here
+        self._sample([(self.height, self.width)], self.height, self.width, np.random.default_rng(0), **self.settings)      # bad settings fail here
 
     def __repr__(self):
-        return f"TrainAugment({self.height}, {self.width}, {', '.join(f'{k}={v!r}' for k, v in self.settings.items())})"
+        return f"{type(self).__name__}({self.height}, {self.width}, {', '.join(f'{k}={v!r}' for k, v in self.settings.items())})"
 
     def __call__(self, frames, targets=None):
         if not isinstance(frames, torch.Tensor):
             frames = list(frames)
-        self.last_plan = sample_augment(_frame_sizes(frames), self.height, self.width, self.rng, **self.settings)
-        return augment_batch(frames, self.last_plan, targets, fill=self.fill, hole_fill=self.hole_fill, min_area=self.min_area,
-                             min_visibility=self.min_visibility)
+        self.last_plan = self._sample(_frame_sizes(frames), self.height, self.width, self.rng, **self.settings)
+        return self._run(frames, self.last_plan, targets, min_area=self.min_area, min_visibility=self.min_visibility,
+                         **{k: getattr(self, k) for k in self._fills})
+
+    @staticmethod
+    def _read_other(name, params, settings, size):
+        """A transform _read_common does not know, read into settings and size -> None, or what to add to its name in the refusal."""
+        return ""
 
     @classmethod
     def from_config(cls, transforms, height=None, width=None, unsupported="raise", **kwargs):
-        """The reference's YAML transform list ([{name, params}], `init_args` for `params` and a {name: params} mapping are read too):
-        HorizontalFlip.p -> flip; RandomResizedCrop.{height, width, scale, ratio}; ColorJitter.{brightness, contrast, saturation, hue};
-        Cutout.{num_holes, max_h_size, max_w_size}; Resize.{height, width} -> crop=False; Normalize is accepted and ignored (the stem and
-        preprocess_uint8 normalise).  Any other name (Affine, RandomCrop, ...) raises ValueError naming it, or with unsupported="skip" is
-        listed in .skipped.  `height` / `width` override the size the list names."""
+        """The reference's YAML transform list ([{name, params}], `init_args` for `params` and a {name: params} mapping are read too), read as
+        the class states.  Any name it does not read raises ValueError naming it, or with unsupported="skip" is listed in .skipped.
+        `height` / `width` override the size the list names."""
         settings, skipped, size = {"flip": 0.0, "crop": False}, [], {}
         for name, params in _config_items(transforms, unsupported):
-            if _read_common(name, params, settings, size):
+            if _read_common(name, params, settings, size, cls._RESIZED):
                 continue
-            if unsupported == "skip":
-                skipped.append(name)
-            else:
-                raise ValueError(f"TrainAugment.from_config: transform {name!r} is not supported (HorizontalFlip, RandomResizedCrop, ColorJitter, "
-                                 "Cutout, Resize and Normalize are)")
+            detail = cls._read_other(name, params, settings, size)
+            if detail is None:
+                continue
+            if unsupported != "skip":
+                raise ValueError(f"{cls.__name__}.from_config: transform {name!r}{detail} is not supported ({cls._SUPPORTED} are)")
+            skipped.append(name)
         height = size.get("height") if height is None else height
         width = size.get("width") if width is None else width
         if height is None or width is None:
-            raise ValueError("TrainAugment.from_config: no RandomResizedCrop / Resize names the canvas size; give height and width")
+            raise ValueError(f"{cls.__name__}.from_config: no {cls._SIZED} names the canvas size; give height and width")
         out = cls(height, width, **kwargs, **settings)
         out.skipped = skipped
         return out
+
+
+class TrainAugment(_Transform):
+    """The training transform of a run: callable as (frames, targets) -> (canvas, targets).  Owns a numpy Generator (`seed`); every
+    call draws a fresh plan with sample_augment(**settings) (kept as .last_plan) and runs augment_batch.
+    from_config reads HorizontalFlip.p -> flip; RandomResizedCrop.{height, width, scale, ratio}; ColorJitter.{brightness, contrast, saturation,
+    hue}; Cutout.{num_holes, max_h_size, max_w_size}; Resize.{height, width} -> crop=False; Normalize is accepted and ignored (the stem and
+    preprocess_uint8 normalise).  Any other name (Affine, RandomCrop, ...) is not supported."""
+    _sample, _run = staticmethod(sample_augment), staticmethod(augment_batch)
+    _SETTINGS = ("mosaic", "scale", "ratio", "flip", "brightness", "contrast", "saturation", "hue", "contrast_center", "cutout", "crop")
+    _SIZED, _SUPPORTED = "RandomResizedCrop / Resize", "HorizontalFlip, RandomResizedCrop, ColorJitter, Cutout, Resize and Normalize"
+
+    def __init__(self, height, width, seed=0, fill=(0, 0, 0), hole_fill=(0, 0, 0), min_area=1.0, min_visibility=0.0, **settings):
+        self._setup(height, width, seed, dict(fill=fill, hole_fill=hole_fill), min_area, min_visibility, settings)

@@ -7,16 +7,16 @@ two stable device sorts, runs ONE launch (cnl_coco_accumulate_f64) and downloads
 the records the reference builds (no crowds), stated in include/centernet_gfx950.h and restated in numpy in tests/coco_eval_ref.py; the
 two agree bit for bit.  No CPU fallback: a missing device or library raises.
 """
-import ctypes
-
-import numpy as np
 import torch
 
 from . import _gather, _lib
+from . import _targets as _t
 
 METRIC_NAMES = ("mAP", "AP50", "AP75", "AP_small", "AP_medium", "AP_large", "AR1", "AR10", "mAR", "AR_small", "AR_medium", "AR_large")
 MAX_PER_IMAGE = 1024          # detections (k) and ground truths (Gmax) per image: csrc/coco_eval.hip keeps an image in LDS
 T, R, A, M = 10, 101, 4, 3    # thresholds, recall points, area ranges, maxDets
+_DETECTIONS = _t.columns(("scores", "float32"), ("labels", "int64"), boxes="float32")       # the predictions, in either form
+_DETECTIONS_COUNT64 = _DETECTIONS[:-1] + (_DETECTIONS[-1]._replace(torch=torch.int64),)        # gather_detection2d's count may be int64
 _RECORD = (("score", torch.float32), ("label", torch.int64), ("rank", torch.int32), ("matched", torch.int64), ("ignored", torch.int64))
 
 
@@ -30,75 +30,6 @@ def summarize(precision, recall):
               mean(precision[:, :, :, 2, 2]), mean(precision[:, :, :, 3, 2]), mean(recall[:, :, 0, 0]), mean(recall[:, :, 0, 1]),
               mean(recall[:, :, 0, 2]), mean(recall[:, :, 1, 2]), mean(recall[:, :, 2, 2]), mean(recall[:, :, 3, 2]))
     return dict(zip(METRIC_NAMES, values))
-
-
-def _upload(parts, dev):
-    """numpy arrays (int64 / float64 / int32) -> device tensors of the same dtype and shape, through ONE pinned staging buffer and one
-    asynchronous copy (call under torch.cuda.device(dev))."""
-    words = [-(-p.nbytes // 8) for p in parts]
-    buf = np.zeros((max(sum(words), 1),), dtype=np.int64)
-    at = 0
-    for p, w in zip(parts, words):
-        buf[at:at + w].view(np.uint8)[:p.nbytes] = np.ascontiguousarray(p).reshape(-1).view(np.uint8)
-        at += w
-    dev_buf = _gather.upload(buf, dev)
-    out, at = [], 0
-    for p, w in zip(parts, words):
-        out.append(dev_buf[at:at + w].view(getattr(torch, p.dtype.name))[:p.size].view(p.shape))
-        at += w
-    return out
-
-
-def _as_numpy(x, dtype, what):
-    if isinstance(x, torch.Tensor):
-        x = x.detach().cpu().numpy()
-    try:
-        return np.asarray(x).astype(dtype, copy=False)
-    except (TypeError, ValueError) as e:
-        raise ValueError(f"CocoEvaluator.update: {what} is not numeric: {e}") from e
-
-
-def _per_image(items, what, with_scores):
-    """The reference's per-image dicts -> [(boxes [n, 4] xywh, labels [n] int64[, scores [n] float32])] as numpy."""
-    out = []
-    for i, d in enumerate(items):
-        if not isinstance(d, dict) or "boxes" not in d or "labels" not in d or (with_scores and "scores" not in d):
-            raise ValueError(f"CocoEvaluator.update: {what}[{i}] must be a dict with 'boxes', 'labels'" + (", 'scores'" if with_scores else ""))
-        boxes = _as_numpy(d["boxes"], np.float32 if with_scores else np.float64, f"{what}[{i}]['boxes']")
-        if boxes.size == 0:
-            boxes = boxes.reshape(0, 4)
-        labels = _as_numpy(d["labels"], np.int64, f"{what}[{i}]['labels']").reshape(-1)
-        if boxes.ndim != 2 or boxes.shape[1] != 4 or boxes.shape[0] != labels.shape[0]:
-            raise ValueError(f"CocoEvaluator.update: {what}[{i}] has boxes {boxes.shape} and labels {labels.shape}; expected [n, 4] and [n]")
-        rec = (boxes, labels)
-        if with_scores:
-            scores = _as_numpy(d["scores"], np.float32, f"{what}[{i}]['scores']").reshape(-1)
-            if scores.shape[0] != labels.shape[0]:
-                raise ValueError(f"CocoEvaluator.update: {what}[{i}] has {scores.shape[0]} scores for {labels.shape[0]} labels")
-            rec += (scores,)
-        if labels.shape[0] > MAX_PER_IMAGE:
-            raise ValueError(f"CocoEvaluator.update: {what}[{i}] has {labels.shape[0]} boxes; at most {MAX_PER_IMAGE} per image are supported")
-        out.append(rec)
-    return out
-
-
-def _check_tensors(named, what):
-    """[(name, tensor, dtype, dimensions)]: a malformed call is a ValueError wherever its tensors live, so this runs before _one_device."""
-    for name, t, dtype, dims in named:
-        if not isinstance(t, torch.Tensor):
-            raise ValueError(f"CocoEvaluator.update: {what} '{name}' must be a tensor, got {type(t).__name__}")
-        if t.dtype != dtype or t.dim() != dims:
-            raise ValueError(f"CocoEvaluator.update: {what} '{name}' must be {dtype} with {dims} dimensions, got {t.dtype} {tuple(t.shape)}")
-
-
-def _one_device(named, what):
-    """All on one HIP device (RuntimeError for a CPU tensor: no CPU fallback) -> that device."""
-    _gather.require_hip([t for (_, t, _, _) in named], "CocoEvaluator.update")
-    dev = named[0][1].device
-    for name, t, _, _ in named:
-        if t.device != dev:
-            raise ValueError(f"CocoEvaluator.update: {what} tensors live on different devices ({dev}, {t.device})")
-    return dev
 
 
 class CocoEvaluator:
@@ -187,72 +118,33 @@ class CocoEvaluator:
 
     # ------------------------------------------------------------------ update
     def _detections(self, preds):
-        """-> (boxes [N,k,4] f32 xyxy, scores, labels, count or None, N, k) as device tensors, or as numpy for the list form."""
+        """-> (device or None, (boxes [N,k,4] f32 xyxy, scores, labels, count or None) as device tensors, or as numpy for the list form, N, k)"""
+        what = "CocoEvaluator.update"
         if isinstance(preds, dict):
-            boxes = preds.get("bboxes", preds.get("boxes"))
+            boxes, count = preds.get("bboxes", preds.get("boxes")), preds.get("count")
             if boxes is None or "scores" not in preds or "labels" not in preds:
-                raise ValueError("CocoEvaluator.update: the detections need 'bboxes' (or 'boxes'), 'scores' and 'labels'")
-            named = [("bboxes", boxes, torch.float32, 3), ("scores", preds["scores"], torch.float32, 2), ("labels", preds["labels"], torch.int64, 2)]
-            count = preds.get("count")
-            if count is not None:
-                if not isinstance(count, torch.Tensor) or count.dtype not in (torch.int32, torch.int64) or count.dim() != 1:
-                    raise ValueError("CocoEvaluator.update: 'count' must be an int32 / int64 [N] tensor")
-                named.append(("count", count, count.dtype, 1))
-            _check_tensors(named, "detections")
-            N, k = int(boxes.shape[0]), int(boxes.shape[1])
-            if boxes.shape[2] != 4 or tuple(preds["scores"].shape) != (N, k) or tuple(preds["labels"].shape) != (N, k) or \
-                    (count is not None and count.shape[0] != N):
-                raise ValueError(f"CocoEvaluator.update: expected bboxes [N,k,4], scores [N,k], labels [N,k] (count [N]), got {tuple(boxes.shape)}, "
-                                 f"{tuple(preds['scores'].shape)}, {tuple(preds['labels'].shape)}" + (f", {tuple(count.shape)}" if count is not None else ""))
-            if not 1 <= k <= MAX_PER_IMAGE:
-                raise ValueError(f"CocoEvaluator.update: k = {k} detections per image; 1..{MAX_PER_IMAGE} are supported")
-            dev = _one_device(named, "detections")
-            if count is not None and count.dtype != torch.int32:
-                count = count.to(torch.int32)
-            return dev, (boxes.contiguous(), preds["scores"].contiguous(), preds["labels"].contiguous(),
-                         None if count is None else count.contiguous()), N, k
+                raise ValueError(f"{what}: the detections need 'bboxes' (or 'boxes'), 'scores' and 'labels'")
+            if count is not None and (not isinstance(count, torch.Tensor) or count.dtype not in (torch.int32, torch.int64) or count.dim() != 1):
+                raise ValueError(f"{what}: 'count' must be an int32 / int64 [N] tensor")
+            narrow = count is not None and count.dtype != torch.int32          # an int64 count is read as it is and made int32 once all is checked
+            spec = _DETECTIONS_COUNT64 if narrow else _DETECTIONS
+            t, k, dev = _t.read_padded({"boxes": boxes, "scores": preds["scores"], "labels": preds["labels"], "count": count}, None, spec, what,
+                                       arg="detections", one="detection", dim="k", optional=("count",), cap=MAX_PER_IMAGE)
+            return dev, (t["boxes"], t["scores"], t["labels"], t["count"].to(torch.int32) if narrow else t["count"]), int(boxes.shape[0]), k
         if not isinstance(preds, (list, tuple)):
-            raise ValueError(f"CocoEvaluator.update: detections must be the device dict of gather_detection2d or a list of per-image dicts, "
-                             f"got {type(preds).__name__}")
-        images = _per_image(preds, "preds", True)
-        N, k = len(images), max([1] + [len(lab) for (_, lab, _) in images])
-        boxes, scores = np.zeros((N, k, 4), dtype=np.float32), np.zeros((N, k), dtype=np.float32)
-        labels, count = np.zeros((N, k), dtype=np.int64), np.zeros((N,), dtype=np.int32)
-        for i, (b, lab, s) in enumerate(images):
-            n = len(lab)
-            boxes[i, :n, :2] = b[:, :2]
-            boxes[i, :n, 2:] = b[:, :2] + b[:, 2:]       # fp32: the kernel's w = x2 - x1 gives w back only when x + w is exact
-            scores[i, :n], labels[i, :n], count[i] = s, lab, n
-        return None, (boxes, scores, labels, count), N, k
+            raise ValueError(f"{what}: detections must be the device dict of gather_detection2d or a list of per-image dicts, got {type(preds).__name__}")
+        t, k = _t.read_list(preds, None, _DETECTIONS, what, arg="preds", cap=MAX_PER_IMAGE)
+        t["boxes"][..., 2:] += t["boxes"][..., :2]       # x y w h -> corners in fp32: the kernel's w = x2 - x1 gives w back only when x + w is exact
+        return None, (t["boxes"], t["scores"], t["labels"], t["count"]), len(preds), k
 
     def _targets(self, targets, N):
         """-> (device or None, (boxes [N,Gmax,4] f64 xywh, labels [N,Gmax] i64, count [N] i32), Gmax)"""
-        if isinstance(targets, dict) or (isinstance(targets, (list, tuple)) and len(targets) == 3 and all(isinstance(t, torch.Tensor) for t in targets)):
-            if isinstance(targets, dict):
-                if any(name not in targets for name in ("boxes", "labels", "count")):
-                    raise ValueError("CocoEvaluator.update: device targets need 'boxes' [N,Gmax,4] f64, 'labels' [N,Gmax] i64 and 'count' [N] i32")
-                targets = (targets["boxes"], targets["labels"], targets["count"])
-            boxes, labels, count = targets
-            named = [("boxes", boxes, torch.float64, 3), ("labels", labels, torch.int64, 2), ("count", count, torch.int32, 1)]
-            _check_tensors(named, "targets")
-            Gmax = int(boxes.shape[1])
-            if tuple(boxes.shape) != (N, Gmax, 4) or tuple(labels.shape) != (N, Gmax) or tuple(count.shape) != (N,):
-                raise ValueError(f"CocoEvaluator.update: expected target boxes [{N},Gmax,4], labels [{N},Gmax], count [{N}], got "
-                                 f"{tuple(boxes.shape)}, {tuple(labels.shape)}, {tuple(count.shape)}")
-            if not 1 <= Gmax <= MAX_PER_IMAGE:
-                raise ValueError(f"CocoEvaluator.update: Gmax = {Gmax} ground truths per image; 1..{MAX_PER_IMAGE} are supported")
-            dev = _one_device(named, "targets")
-            return dev, (boxes.contiguous(), labels.contiguous(), count.contiguous()), Gmax
-        if not isinstance(targets, (list, tuple)):
-            raise ValueError(f"CocoEvaluator.update: targets must be a list of per-image dicts or padded device tensors, got {type(targets).__name__}")
-        if len(targets) != N:
-            raise ValueError(f"CocoEvaluator.update: {N} images of detections against {len(targets)} of targets")
-        images = _per_image(targets, "targets", False)
-        Gmax = max([1] + [len(lab) for (_, lab) in images])
-        boxes, labels, count = np.zeros((N, Gmax, 4), dtype=np.float64), np.zeros((N, Gmax), dtype=np.int64), np.zeros((N,), dtype=np.int32)
-        for i, (b, lab) in enumerate(images):
-            boxes[i, :len(lab)], labels[i, :len(lab)], count[i] = b, lab, len(lab)
-        return None, (boxes, labels, count), Gmax
+        what = "CocoEvaluator.update"
+        if _t.is_padded(targets):
+            t, Gmax, dev = _t.read_padded(targets, N, _t.LABELS, what, cap=MAX_PER_IMAGE)
+        else:
+            (t, Gmax), dev = _t.read_list(targets, N, _t.LABELS, what, against="detections", cap=MAX_PER_IMAGE), None
+        return dev, (t["boxes"], t["labels"], t["count"]), Gmax
 
     def update(self, preds, targets):
         """One batch.  preds: the device dict of gather_detection2d / detect_frames / detect_tiled as it is — "bboxes" (or "boxes")
@@ -279,7 +171,7 @@ class CocoEvaluator:
         with torch.cuda.device(self.device):
             host = (list(dets) if d_dev is None else []) + (list(gts) if g_dev is None else [])
             if host:                                        # everything that came as numpy goes up in one copy
-                up = _upload(host, self.device)
+                up = _gather.upload_parts(host, self.device)
                 if d_dev is None:
                     dets, up = up[:4], up[4:]
                 if g_dev is None:
@@ -292,7 +184,7 @@ class CocoEvaluator:
             _lib.check(lib.cnl_coco_match_f64(boxes.data_ptr(), scores.data_ptr(), labels.data_ptr(), None if count is None else count.data_ptr(),
                                               gts[0].data_ptr(), gts[1].data_ptr(), gts[2].data_ptr(), N, k, Gmax, self.num_classes,
                                               buf["rank"].data_ptr() + 4 * at, buf["matched"].data_ptr() + 8 * at, buf["ignored"].data_ptr() + 8 * at,
-                                              self._npig.data_ptr(), ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)),
+                                              self._npig.data_ptr(), _lib.stream(self.device)),
                        "cnl_coco_match_f64")
         self._n += N * k
         self.num_images += N
@@ -320,7 +212,7 @@ class CocoEvaluator:
             n_pr = T * R * K * A * M
             _lib.check(lib.cnl_coco_accumulate_f64(rank.data_ptr(), matched.data_ptr(), ignored.data_ptr(), first.data_ptr(), self._npig.data_ptr(),
                                                    n, K, out.data_ptr(), out.data_ptr() + 8 * n_pr,
-                                                   ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "cnl_coco_accumulate_f64")
+                                                   _lib.stream(dev)), "cnl_coco_accumulate_f64")
             host = out.cpu().numpy()
         self.precision = host[:n_pr].reshape(T, R, K, A, M)
         self.recall = host[n_pr:].reshape(T, K, A, M)

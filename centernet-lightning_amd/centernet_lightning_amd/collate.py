@@ -9,8 +9,6 @@ order of the gathered buffer.  world_size == 1 is a no-op, like the reference (e
 `torch.distributed` backend "nccl" is RCCL on ROCm (xGMI within the node); the gloo backend is used by the
 CPU tests of the protocol.  Pack / unpack are HIP kernels (cnl_pack_detections_f32 / cnl_unpack_detections_f32).
 """
-import ctypes
-
 import torch
 import torch.distributed as dist
 
@@ -25,10 +23,6 @@ def shard_range(n_total: int, rank: int, world_size: int):
         raise ValueError(f"global batch {n_total} is not divisible by world size {world_size}")
     per = n_total // world_size
     return rank * per, (rank + 1) * per
-
-
-def _stream(device):
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
 def pack_detections(dets: dict, out: torch.Tensor = None) -> torch.Tensor:
@@ -49,7 +43,7 @@ def pack_detections(dets: dict, out: torch.Tensor = None) -> torch.Tensor:
             raise ValueError(f"pack_detections: out must be a contiguous float32 [{N},{k},{RECORD_FIELDS + E}] tensor")
         _lib.check(lib.cnl_pack_detections_f32(boxes.data_ptr(), scores.data_ptr(), labels.data_ptr(),
                                                emb.data_ptr() if emb is not None else None, rec.data_ptr(), N, k, E,
-                                               _stream(boxes.device)), "cnl_pack_detections_f32")
+                                               _lib.stream(boxes.device)), "cnl_pack_detections_f32")
     return rec
 
 
@@ -67,7 +61,7 @@ def unpack_detections(rec: torch.Tensor, box_key="bboxes") -> dict:
         labels = torch.empty((N, k), device=dev, dtype=torch.int64)
         emb = torch.empty((N, k, E), device=dev, dtype=torch.float32) if E else None
         _lib.check(lib.cnl_unpack_detections_f32(rec.data_ptr(), boxes.data_ptr(), scores.data_ptr(), labels.data_ptr(),
-                                                 emb.data_ptr() if emb is not None else None, N, k, E, _stream(dev)),
+                                                 emb.data_ptr() if emb is not None else None, N, k, E, _lib.stream(dev)),
                    "cnl_unpack_detections_f32")
     out = {box_key: boxes, "labels": labels, "scores": scores}
     if E:

@@ -67,7 +67,7 @@ def crop_detections(frames, bboxes, size=(128, 64), scores=None, score_threshold
         crops = torch.empty((N, k, ch, cw, C), device=dev, dtype=torch.uint8)
         out_windows = torch.empty((N, k, 4), device=dev, dtype=torch.int32)
         records = torch.empty((max(N * k, 1) * words,), device=dev, dtype=torch.int64)
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        stream = _lib.stream(dev)
         _lib.check(lib.cnl_crop_boxes_u8(table.data_ptr(), bboxes.data_ptr(), scores.data_ptr() if scores is not None else None,
                                          float(score_threshold) if scores is not None else 0.0, count.data_ptr() if count is not None else None,
                                          N, k, C, coef, float(pad), int(bool(keep_aspect)), records.data_ptr(), out_windows.data_ptr(),

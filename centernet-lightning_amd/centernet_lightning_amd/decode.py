@@ -22,10 +22,6 @@ def _require_cuda_f32(name, t, ndim=4):
         raise ValueError(f"{name}: expected float32 with {ndim} dims, got {t.dtype} {tuple(t.shape)}")
 
 
-def _stream(device):
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
 def decode(heatmap, box_2d, reid=None, num_detections=100, nms_kernel=3, normalize_boxes=False, box_log=False,
            box_multiplier=1.0, stride=4):
     """Fused pseudo-NMS + top-k + gathers.  Returns dict(scores [N,k] f32, indices [N,k] i64, labels [N,k] i64,
@@ -79,7 +75,7 @@ def decode(heatmap, box_2d, reid=None, num_detections=100, nms_kernel=3, normali
         p.box_multiplier, p.stride = float(box_multiplier), float(stride)
         p.scores, p.indices, p.labels, p.boxes = base + o_sc, base + o_idx, base + o_lab, base + o_box
         p.workspace, p.workspace_bytes = ws.data_ptr(), ws_bytes
-        _lib.check(lib.cnl_decode_f32(ctypes.byref(p), _stream(dev)), "cnl_decode_f32")
+        _lib.check(lib.cnl_decode_f32(ctypes.byref(p), _lib.stream(dev)), "cnl_decode_f32")
     finally:
         if switch:
             torch.cuda.set_device(prev)
@@ -105,7 +101,7 @@ def gather_boxes(box_2d, indices, normalize_boxes=False, box_log=False, box_mult
         sn, sc, sh, sw = box_2d.stride()
         _lib.check(lib.cnl_gather_boxes_f32(box_2d.data_ptr(), sn, sc, sh, sw, idx.data_ptr(), boxes.data_ptr(), N, H, W, k,
                                             int(bool(normalize_boxes)), int(bool(box_log)), float(box_multiplier), float(stride),
-                                            _stream(box_2d.device)), "cnl_gather_boxes_f32")
+                                            _lib.stream(box_2d.device)), "cnl_gather_boxes_f32")
     return boxes
 
 
@@ -122,5 +118,5 @@ def gather_embeddings(reid, indices):
         emb = torch.empty((N, k, E), device=reid.device, dtype=torch.float32)
         sn, sc, sh, sw = reid.stride()
         _lib.check(lib.cnl_gather_embeddings_f32(reid.data_ptr(), sn, sc, sh, sw, idx.data_ptr(), emb.data_ptr(), N, E, H, W, k,
-                                                 _stream(reid.device)), "cnl_gather_embeddings_f32")
+                                                 _lib.stream(reid.device)), "cnl_gather_embeddings_f32")
     return emb

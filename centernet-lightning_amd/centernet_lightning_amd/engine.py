@@ -122,7 +122,7 @@ class _Layer:
         n = lib.cnl_winograd_weight_floats(self.cin, self.cout)
         with torch.cuda.device(w.device):
             self.u = torch.empty((n,), device=w.device, dtype=torch.float32)
-            stream = ctypes.c_void_p(torch.cuda.current_stream(w.device).cuda_stream)
+            stream = _lib.stream(w.device)
             _lib.check(lib.cnl_winograd_transform_weights_f32(w.data_ptr(), self.u.data_ptr(), self.cin, self.cout, stream),
                        "cnl_winograd_transform_weights_f32")
 
@@ -138,7 +138,7 @@ def _layer_split_w(self):
         else:
             with torch.cuda.device(self.w.device):
                 buf = torch.empty((n,), device=self.w.device, dtype=torch.float32)
-                stream = ctypes.c_void_p(torch.cuda.current_stream(self.w.device).cuda_stream)
+                stream = _lib.stream(self.w.device)
                 _lib.check(lib.cnl_conv_split_weights_f32(self.w.data_ptr(), buf.data_ptr(), self.cin, self.cout, self.kh, self.kw, stream),
                            "cnl_conv_split_weights_f32")
                 torch.cuda.current_stream(self.w.device).synchronize()      # (as up_rows: one buffer for the plans of every stream)
@@ -158,7 +158,7 @@ def _layer_up2(self):
         lib = _lib.load()
         with torch.cuda.device(self.w.device):
             self._up2 = torch.empty((lib.cnl_up2_weight_floats(self.cin, self.cout),), device=self.w.device, dtype=torch.float32)
-            stream = ctypes.c_void_p(torch.cuda.current_stream(self.w.device).cuda_stream)
+            stream = _lib.stream(self.w.device)
             _lib.check(lib.cnl_up2_pack_weights_f32(self.w.data_ptr(), self._up2.data_ptr(), self.cin, self.cout, stream), "cnl_up2_pack_weights_f32")
             self.up2_wmax = self._up2.abs().max().reshape(1).contiguous()
     return self._up2
@@ -175,7 +175,7 @@ def _layer_up_rows(self):
         else:
             with torch.cuda.device(self.w.device):
                 buf = torch.empty((n,), device=self.w.device, dtype=torch.float32)
-                stream = ctypes.c_void_p(torch.cuda.current_stream(self.w.device).cuda_stream)
+                stream = _lib.stream(self.w.device)
                 _lib.check(lib.cnl_winograd_transform_weights_up_f32(self.w.data_ptr(), buf.data_ptr(), self.cin, self.cout, stream),
                            "cnl_winograd_transform_weights_up_f32")
                 torch.cuda.current_stream(self.w.device).synchronize()      # built once, on whichever stream's plan asks first; plans of other streams read it too
@@ -319,7 +319,7 @@ class PackedWeights:
         with torch.cuda.device(device):
             self.stem_packed = torch.empty((lib.cnl_stem_packed_weight_floats(),), device=device, dtype=torch.float32)
             _lib.check(lib.cnl_stem_pack_weights_f32(self.stem.w.data_ptr(), self.stem_packed.data_ptr(),
-                                                     ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)),
+                                                     _lib.stream(device)),
                        "cnl_stem_pack_weights_f32")
         self.blocks = []
         self.bottleneck = bool(getattr(bb, "bottleneck", False))
@@ -1189,7 +1189,7 @@ class Plan:
             with torch.cuda.device(outl.w.device):
                 fw = torch.empty(((p_last.Cout + 63) // 64 * 64, 4), device=outl.w.device, dtype=torch.float32)
                 _lib.check(self.lib.cnl_fused_out_pack_weights_f32(outl.w.data_ptr(), fw.data_ptr(), outl.cin, outl.cout,
-                                                                   ctypes.c_void_p(torch.cuda.current_stream(outl.w.device).cuda_stream)),
+                                                                   _lib.stream(outl.w.device)),
                            "cnl_fused_out_pack_weights_f32")
                 torch.cuda.current_stream(outl.w.device).synchronize()      # (as up_rows / split_w: built once, read by the plans of every stream — ADVICE r5)
             outl._fuse_w = fw
@@ -1212,7 +1212,7 @@ class Plan:
         (channels_last, zero-copy; precedent models/meta.py:97-98)."""
         self._norm = norm
         lib = self.lib
-        stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        stream = _lib.stream(self.device)
         outs = OrderedDict()
         oh, ow = self.out_hw
         for name, (p, c) in self.out_params.items():

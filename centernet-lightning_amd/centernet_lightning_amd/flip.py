@@ -15,18 +15,12 @@ with p(c) = c, except that box_2d (left, top, right, bottom) swaps its channels 
 (a + b.flip(-1)[:, perm]) * 0.5 in torch bit for bit.  box_2d is averaged as the raw head output, before the decode's exp / multiplier /
 clamp: with box_log that is an average of logarithms, i.e. a geometric mean of the box sizes.
 """
-import ctypes
-
 import torch
 
 from . import _lib
 
 SWAP_LR = ("box_2d",)          # the maps whose channels 0 and 2 trade places under a mirror
 _HIP_ONLY = "the flip test runs on HIP devices only: move the tensors to 'cuda' (no CPU fallback)"
-
-
-def _stream(device):
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
 def mirror_append_uint8(canvas: torch.Tensor) -> torch.Tensor:
@@ -46,7 +40,7 @@ def mirror_append_uint8(canvas: torch.Tensor) -> torch.Tensor:
         # forwards of N would also pay every launch of the plan twice at half the work).  Nothing forces it: a plan's head outputs are
         # fresh tensors per call (engine.Plan.run), only its intermediate activations live in the plan's arena.
         out = torch.empty((2 * N, H, W, C), device=canvas.device, dtype=torch.uint8)
-        _lib.check(lib.cnl_mirror_append_u8(canvas.data_ptr(), out.data_ptr(), N, H, W, C, _stream(canvas.device)), "cnl_mirror_append_u8")
+        _lib.check(lib.cnl_mirror_append_u8(canvas.data_ptr(), out.data_ptr(), N, H, W, C, _lib.stream(canvas.device)), "cnl_mirror_append_u8")
     return out
 
 
@@ -107,7 +101,7 @@ def flip_merge(outputs, N: int):
                 rec.d_sn, rec.d_sc, rec.d_sh, rec.d_sw = out.stride()
                 rec.C, rec.swap_lr = C, int(name in SWAP_LR)
                 merged.append(out)
-            _lib.check(lib.cnl_flip_merge_f32(table, len(group), N, H, W, _stream(dev)), "cnl_flip_merge_f32")
+            _lib.check(lib.cnl_flip_merge_f32(table, len(group), N, H, W, _lib.stream(dev)), "cnl_flip_merge_f32")
     if isinstance(outputs, dict):
         return type(outputs)(zip(names, merged))
     return type(outputs)(*merged)

@@ -11,7 +11,6 @@ Only the box conversion is device work (cnl_boxes_xyxy_to_xywh_f32); the rest is
 the reference's so that its evaluators (pycocotools / TrackEval) read the same bytes.  COCO box metrics need neither these records
 nor pycocotools: coco_eval.CocoEvaluator computes them on the device from the detections as decoded.
 """
-import ctypes
 import json
 
 import numpy as np
@@ -29,7 +28,7 @@ def boxes_xyxy_to_xywh(boxes: torch.Tensor) -> torch.Tensor:
     b = boxes.contiguous()
     out = torch.empty_like(b)
     with torch.cuda.device(b.device):
-        stream = ctypes.c_void_p(torch.cuda.current_stream(b.device).cuda_stream)
+        stream = _lib.stream(b.device)
         _lib.check(_lib.load().cnl_boxes_xyxy_to_xywh_f32(b.data_ptr(), out.data_ptr(), b.numel() // 4, stream), "cnl_boxes_xyxy_to_xywh_f32")
     return out
 

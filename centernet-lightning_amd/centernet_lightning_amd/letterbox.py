@@ -4,7 +4,6 @@ The reference validates with keep-aspect resize + pad (configs/centernet.yaml va
 original_height / original_width) one image at a time on the host.  Here the geometry is host arithmetic on tensor SHAPES (no device
 sync), the pixels are one launch of cnl_letterbox_bilinear_u8 and the boxes one launch of cnl_unletterbox_boxes_f32.
 """
-import ctypes
 from typing import List, Tuple
 
 import torch
@@ -92,7 +91,7 @@ def unletterbox_(bboxes: torch.Tensor, geom: LetterboxGeometry, clip: bool = Tru
     lib = _lib.load()
     with torch.cuda.device(bboxes.device):
         _lib.check(lib.cnl_unletterbox_boxes_f32(bboxes.data_ptr(), geom.table.data_ptr(), bboxes.shape[0], bboxes.shape[1], int(bool(clip)),
-                                                 ctypes.c_void_p(torch.cuda.current_stream(bboxes.device).cuda_stream)), "cnl_unletterbox_boxes_f32")
+                                                 _lib.stream(bboxes.device)), "cnl_unletterbox_boxes_f32")
     return bboxes
 
 

@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from . import _gather, _lib
-from .coco_eval import _upload
+from . import _targets as _t
 
 MAX_PER_IMAGE = 1024          # boxes per image (csrc/det_loss.hip)
 MAX_CLASSES, MAX_SIDE, MAX_IMAGES = 1 << 16, 1 << 15, 1 << 16
@@ -87,80 +87,27 @@ def settings_from_config(output_heads=None, **gen_b):
     return out
 
 
-def _is_padded(targets, n_tensors):
-    """Is this the padded device form: a dict, or a tuple / list of n_tensors tensors?"""
-    return isinstance(targets, dict) or (isinstance(targets, (list, tuple)) and len(targets) == n_tensors and all(isinstance(t, torch.Tensor) for t in targets))
-
-
-def _padded_targets(targets, N, field, row_ok, what, cannot):
-    """targets: the dict of padded device tensors {"boxes", field, "count"}, or a list of per-image {"boxes" [m, 4], field [m]}, which is checked here:
-    row_ok(boxes [m, 4] f64, second [m] i64) -> the mask of the boxes the kernel would take; any other box raises with cannot(its second value).
-    -> (device or None, (boxes [N,Gmax,4] f64, second [N,Gmax] i64, count [N] i32) as device tensors or numpy, Gmax)"""
-    if isinstance(targets, dict):
-        if any(name not in targets for name in ("boxes", field, "count")):
-            raise ValueError(f"{what}: device targets need 'boxes' [N,Gmax,4] f64, '{field}' [N,Gmax] i64 and 'count' [N] i32")
-        boxes, second, count = targets["boxes"], targets[field], targets["count"]
-        for name, t, dtype, dims in (("boxes", boxes, torch.float64, 3), (field, second, torch.int64, 2), ("count", count, torch.int32, 1)):
-            if not isinstance(t, torch.Tensor):
-                raise ValueError(f"{what}: targets '{name}' must be a tensor, got {type(t).__name__}")
-            if t.dtype != dtype or t.dim() != dims:
-                raise ValueError(f"{what}: targets '{name}' must be {dtype} with {dims} dimensions, got {t.dtype} {tuple(t.shape)}")
-        Gmax = int(boxes.shape[1])
-        if tuple(boxes.shape) != (N, Gmax, 4) or tuple(second.shape) != (N, Gmax) or tuple(count.shape) != (N,):
-            raise ValueError(f"{what}: expected target boxes [{N},Gmax,4], {field} [{N},Gmax], count [{N}], got {tuple(boxes.shape)}, "
-                             f"{tuple(second.shape)}, {tuple(count.shape)}")
-        if not 1 <= Gmax <= MAX_PER_IMAGE:
-            raise ValueError(f"{what}: Gmax = {Gmax} boxes per image; 1..{MAX_PER_IMAGE} are supported")
-        _gather.require_hip([boxes, second, count], what)
-        if second.device != boxes.device or count.device != boxes.device:
-            raise ValueError(f"{what}: target tensors live on different devices")
-        return boxes.device, (boxes.contiguous(), second.contiguous(), count.contiguous()), Gmax
-    if not isinstance(targets, (list, tuple)):
-        raise ValueError(f"{what}: targets must be a list of per-image dicts or padded device tensors, got {type(targets).__name__}")
-    if len(targets) != N:
-        raise ValueError(f"{what}: {N} images of outputs against {len(targets)} of targets")
-    images = []
-    for i, d in enumerate(targets):
-        if not isinstance(d, dict) or "boxes" not in d or field not in d:
-            raise ValueError(f"{what}: targets[{i}] must be a dict with 'boxes', '{field}'")
-        try:
-            b, sec = d["boxes"], d[field]
-            b = np.asarray(b.detach().cpu().numpy() if isinstance(b, torch.Tensor) else b).astype(np.float64)
-            sec = np.asarray(sec.detach().cpu().numpy() if isinstance(sec, torch.Tensor) else sec).astype(np.int64).reshape(-1)
-        except (TypeError, ValueError) as e:
-            raise ValueError(f"{what}: targets[{i}] is not numeric: {e}") from e
-        if b.size == 0:
-            b = b.reshape(0, 4)
-        if b.ndim != 2 or b.shape[1] != 4 or b.shape[0] != sec.shape[0]:
-            raise ValueError(f"{what}: targets[{i}] has boxes {b.shape} and {field} {sec.shape}; expected [n, 4] and [n]")
-        if sec.shape[0] > MAX_PER_IMAGE:
-            raise ValueError(f"{what}: targets[{i}] has {sec.shape[0]} boxes; at most {MAX_PER_IMAGE} per image are supported")
-        bad = np.nonzero(~row_ok(b, sec))[0]
-        if bad.size:
-            j = int(bad[0])
-            raise ValueError(f"{what}: targets[{i}] box {j} = {b[j].tolist()} {cannot(int(sec[j]))}")
-        images.append((b, sec))
-    Gmax = max([1] + [len(sec) for (_, sec) in images])
-    boxes, second, count = np.zeros((N, Gmax, 4), dtype=np.float64), np.zeros((N, Gmax), dtype=np.int64), np.zeros((N,), dtype=np.int32)
-    for i, (b, sec) in enumerate(images):
-        boxes[i, :len(sec)], second[i, :len(sec)], count[i] = b, sec, len(sec)
-    return None, (boxes, second, count), Gmax
+def _read(targets, N, spec, length, row_ok, cannot, what):
+    """targets in either form (_targets.py) -> (device or None, (boxes [N,Gmax,4] f64, the column [N,Gmax] i64, count [N] i32) as device tensors or
+    numpy, Gmax).  The padded form is a dict or a tuple of `length` tensors; only the list form is judged by row_ok / cannot."""
+    if isinstance(targets, dict) or _t.is_padded(targets, (length,)):
+        t, Gmax, dev = _t.read_padded(targets, N, spec, what, cap=MAX_PER_IMAGE)
+    else:
+        (t, Gmax), dev = _t.read_list(targets, N, spec, what, cap=MAX_PER_IMAGE, row_ok=row_ok, cannot=cannot), None
+    return dev, (t["boxes"], t[spec[1].name], t["count"]), Gmax
 
 
 def _targets(targets, N, C, H, W, stride, what):
-    """detection_loss's targets through _padded_targets: the tuple (boxes, labels, count) is the dict's other spelling"""
-    if not isinstance(targets, dict) and _is_padded(targets, 3):
-        targets = {"boxes": targets[0], "labels": targets[1], "count": targets[2]}
-
+    """detection_loss's targets: the list, the dict {"boxes", "labels", "count"} or the tuple (boxes, labels, count)"""
     def row_ok(boxes, labels):             # the record rule of include/centernet_gfx950.h, in numpy float64
         with np.errstate(all="ignore"):
             b = boxes / float(stride)
             cx, cy = np.rint(b[:, 0] + b[:, 2] / 2), np.rint(b[:, 1] + b[:, 3] / 2)
             return np.isfinite(b).all(axis=1) & (b[:, 2] >= 0) & (b[:, 3] >= 0) & (cx >= 0) & (cx <= W) & (cy >= 0) & (cy <= H) & (labels >= 0) & (labels < C)
 
-    return _padded_targets(targets, N, "labels", row_ok, what,
-                           lambda label: f"(label {label}) cannot be a target on a {H} x {W} map of {C} classes at stride {stride}: non-finite, negative "
-                                         f"size, centre outside the map or label outside 0..{C - 1}")
+    return _read(targets, N, _t.LABELS, 3, row_ok,
+                 lambda label: f"(label {label}) cannot be a target on a {H} x {W} map of {C} classes at stride {stride}: non-finite, negative "
+                               f"size, centre outside the map or label outside 0..{C - 1}", what)
 
 
 def _same_device(g_dev, dev, what, outputs="outputs"):
@@ -169,11 +116,11 @@ def _same_device(g_dev, dev, what, outputs="outputs"):
 
 
 def _on_device(g_dev, gts, N, dev, what, outputs="outputs"):
-    """_padded_targets's result on the outputs' device: device tensors must live there, host arrays go up in one copy."""
+    """_read's result on the outputs' device: device tensors must live there, host arrays go up in one copy."""
     _same_device(g_dev, dev, what, outputs)
     if g_dev is None:
         with torch.cuda.device(dev):
-            gts = [torch.from_numpy(a).to(dev) for a in gts] if N == 0 else _upload(list(gts), dev)      # (an empty batch: nothing to stage)
+            gts = [torch.from_numpy(a).to(dev) for a in gts] if N == 0 else _gather.upload_parts(list(gts), dev)      # (an empty batch: nothing to stage)
     return tuple(gts)
 
 
@@ -192,7 +139,7 @@ def _call(name, workspace_bytes, dev, *args):
     lib = _lib.load()
     nbytes = getattr(lib, workspace_bytes[0])(*workspace_bytes[1:])
     ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=dev)
-    _lib.check(getattr(lib, name)(*args, ws.data_ptr(), nbytes, ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), name)
+    _lib.check(getattr(lib, name)(*args, ws.data_ptr(), nbytes, _lib.stream(dev)), name)
 
 
 def _check_want(want, allowed, what):
@@ -250,7 +197,7 @@ def _run(heatmap, box_2d, targets, shape, params, want_targets, dev, what):
         tmap = torch.empty((N, C, H, W), dtype=torch.float32, device=dev, memory_format=torch.channels_last) if want_targets else None
         if N:
             if g_dev is None:
-                gts = _upload(list(gts), dev)
+                gts = _gather.upload_parts(list(gts), dev)
             _call("cnl_detection_loss_f64", ("cnl_detection_loss_workspace_bytes", N, Gmax, H, W), dev, *_map_args(heatmap), *_map_args(box_2d),
                   N, C, H, W, gts[0].data_ptr(), gts[1].data_ptr(), gts[2].data_ptr(), Gmax, ctypes.byref(params), *_map_args(tmap),
                   out.data_ptr(), out.data_ptr() + 8 * 4 * N, skipped.data_ptr())
@@ -308,7 +255,7 @@ def _scale_arg(values, dev):
     with torch.cuda.device(dev):
         if on_device:
             return torch.stack([v if isinstance(v, torch.Tensor) else torch.full((), v, dtype=torch.float64, device=dev) for v in values])
-        return _upload([np.array(values, dtype=np.float64)], dev)[0]
+        return _gather.upload_parts([np.array(values, dtype=np.float64)], dev)[0]
 
 
 def _like(t):
@@ -420,7 +367,7 @@ def render_targets(targets, num_classes, height, width, stride=4, heatmap_target
     for name, v in (("num_classes", num_classes), ("height", height), ("width", width)):
         if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
             raise ValueError(f"{what}: {name} must be an int, got {v!r}")
-    if _is_padded(targets, 3):
+    if _t.is_padded(targets):
         first = targets["boxes"] if isinstance(targets, dict) and "boxes" in targets else targets[0] if not isinstance(targets, dict) else None
         N = int(first.shape[0]) if isinstance(first, torch.Tensor) and first.dim() else 0
     elif isinstance(targets, (list, tuple)):
@@ -556,10 +503,8 @@ def _classifier(classifier, what):
 
 
 def _reid_targets(targets, N, H, W, K, stride, center, ignore_index, what):
-    """-> (device or None, (boxes [N,Gmax,4] f64, ids [N,Gmax] i64, count [N] i32) as device tensors or numpy, Gmax)"""
-    if not isinstance(targets, dict) and _is_padded(targets, 4):
-        targets = {"boxes": targets[0], "ids": targets[3], "count": targets[2]}      # detection_loss's (boxes, labels, count) and the ids as the fourth tensor
-
+    """reid_loss's targets: the list, the dict {"boxes", "ids", "count"} or the tuple (boxes, labels, count, ids), whose labels are not read
+    -> (device or None, (boxes [N,Gmax,4] f64, ids [N,Gmax] i64, count [N] i32) as device tensors or numpy, Gmax)"""
     def row_ok(b, ident):                  # the row rule of include/centernet_gfx950.h; a box without identity is never a bad one
         with np.errstate(all="ignore"):
             c = (b[:, :2] + b[:, 2:] / 2.0) / float(stride)
@@ -567,9 +512,9 @@ def _reid_targets(targets, N, H, W, K, stride, center, ignore_index, what):
             return (np.isfinite(b).all(axis=1) & (b[:, 2] >= 0) & (b[:, 3] >= 0) & (c[:, 0] >= 0) & (c[:, 0] <= W - 1) & (c[:, 1] >= 0) & (c[:, 1] <= H - 1) &
                     (ident >= 0) & (ident < K)) | (ident == ignore_index)
 
-    return _padded_targets(targets, N, "ids", row_ok, what,
-                           lambda ident: f"(id {ident}) cannot be a row on a {H} x {W} map with {K} identities at stride {stride}: non-finite, negative size, "
-                                         f"centre cell outside the map or id outside 0..{K - 1}")
+    return _read(targets, N, _t.IDS, 4, row_ok,
+                 lambda ident: f"(id {ident}) cannot be a row on a {H} x {W} map with {K} identities at stride {stride}: non-finite, negative size, "
+                               f"centre cell outside the map or id outside 0..{K - 1}", what)
 
 
 def _reid_inputs(reid, targets, classifier, params, center, what):
@@ -766,7 +711,7 @@ class TrackingLoss(torch.nn.Module):
         self.reid = reid_loss_module
 
     def forward(self, outputs, targets, ignore_reid=False):
-        det_targets = tuple(targets[:3]) if not isinstance(targets, dict) and _is_padded(targets, 4) else targets
+        det_targets = tuple(targets[:3]) if not isinstance(targets, dict) and _t.is_padded(targets, (4,)) else targets
         out = dict(self.detection(outputs, det_targets))
         if ignore_reid:
             out["reid"] = torch.zeros((), dtype=torch.float64, device=out["total"].device)

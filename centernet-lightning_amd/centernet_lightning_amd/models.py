@@ -186,7 +186,7 @@ class CenterNet(nn.Module):
             _lib.check(lib.cnl_normalize_u8_nhwc_f32(images.data_ptr(), out.data_ptr(), N, H, W,
                                                      m.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
                                                      r.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
-                                                     ctypes.c_void_p(torch.cuda.current_stream(images.device).cuda_stream)),
+                                                     _lib.stream(images.device)),
                        "cnl_normalize_u8_nhwc_f32")
         return out.permute(0, 3, 1, 2)
 
@@ -211,7 +211,7 @@ class CenterNet(nn.Module):
         with torch.cuda.device(images.device):
             out = torch.empty((N, int(height), int(width), C), device=images.device, dtype=torch.uint8)
             _lib.check(lib.cnl_resize_bilinear_u8(images.data_ptr(), out.data_ptr(), N, H, W, int(height), int(width), C,
-                                                  ctypes.c_void_p(torch.cuda.current_stream(images.device).cuda_stream)), "cnl_resize_bilinear_u8")
+                                                  _lib.stream(images.device)), "cnl_resize_bilinear_u8")
         return out
 
     def forward_uint8(self, images: torch.Tensor, resize=None, mean=IMAGENET_MEAN, std=IMAGENET_STD, flip_test: bool = False):

@@ -14,8 +14,7 @@ import ctypes
 import numpy as np
 import torch
 
-from . import _lib
-from .coco_eval import _upload
+from . import _gather, _lib
 
 ALPHA = np.arange(0.05, 0.99, 0.05)        # TrackEval's HOTA.array_labels: 19 float64 values
 MAX_SHORT, MAX_LONG = 1024, 4096           # objects of a frame on its smaller / larger side (the solver's LDS)
@@ -182,8 +181,8 @@ def run(arrays, scalars, device, alloc=_Plain):
     S = scalars["S"]
     names = list(_lib.MotTables.POINTERS)
     with torch.cuda.device(device):
-        stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-        up = dict(zip(names + ["alpha"], _upload([arrays[n] for n in names] + [ALPHA], device)))
+        stream = _lib.stream(device)
+        up = dict(zip(names + ["alpha"], _gather.upload_parts([arrays[n] for n in names] + [ALPHA], device)))
         tab = _lib.MotTables(**{n: up[n].data_ptr() for n in names}, **scalars)
         ref = ctypes.byref(tab)
         sim = alloc(8 * scalars["sim_total"], 8, device, "sim")

@@ -14,7 +14,6 @@ by tests/overlay_ref.py.
 DEFAULT_PALETTE is a fixed table of 20 distinct RGB colours (Sasha Trubetskoy's list of visually distinct colours, without its white
 and black, which are the usual text colours): label l is drawn in entry l mod 20.
 """
-import ctypes
 import functools
 
 import numpy as np
@@ -129,7 +128,7 @@ def draw_detections(frames, bboxes, labels=None, scores=None, score_threshold=No
     with torch.cuda.device(dev):
         table = _gather.upload(buf, dev)
         records = torch.empty((N * k * 8,), device=dev, dtype=torch.int64)      # 64 bytes per slot
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        stream = _lib.stream(dev)
 
         def ptr(t):
             return t.data_ptr() if t is not None else None

@@ -5,7 +5,6 @@ The geometry is host arithmetic on tensor SHAPES (no device sync).  The tile gat
 is a record whose src points inside a frame and whose resize is 1:1 (the kernel then returns the source bytes); the optional full-frame
 view is the plain letterbox record.  The merge is cnl_merge_tiles_f32 (csrc/tile_merge.hip; the rule: include/centernet_gfx950.h).
 """
-import ctypes
 from typing import List, Tuple
 
 import torch
@@ -194,6 +193,6 @@ def merge_tiles(bboxes: torch.Tensor, scores: torch.Tensor, labels: torch.Tensor
                                            geom.first_view.data_ptr(), N, V, k, max_detections, max_candidates, float(score_threshold),
                                            float(match_threshold), METRICS[match_metric], int(bool(class_aware)), out_boxes.data_ptr(),
                                            out_scores.data_ptr(), out_labels.data_ptr(), out_source.data_ptr(), out_count.data_ptr(),
-                                           ws_ptr, ws_bytes, ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
+                                           ws_ptr, ws_bytes, _lib.stream(dev)),
                    "cnl_merge_tiles_f32")
     return {"bboxes": out_boxes, "scores": out_scores, "labels": out_labels, "source": out_source, "count": out_count}

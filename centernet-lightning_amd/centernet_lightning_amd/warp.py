@@ -98,7 +98,7 @@ def affine_matrix(fh, fw, scale=(1.0, 1.0), rotate=0.0, shear=(0.0, 0.0), transl
 
 
 @dataclasses.dataclass
-class WarpPlan:
+class WarpPlan(_augment._Plan):
     """What warp_batch does to a batch of F frames, as numpy arrays (N canvases; slot p of canvas n is live when p < n_place[n]): AugmentPlan's
     fields with two maps in place of the flip bit.  sizes [(h, w)] of the F frames; n_place [N] int32 (1..4); frame [N, 4] int32; window
     [N, 4, 4] int32 (x0, y0, w, h): the CLIP window in the frame, outside which everything is the border colour (the whole frame:
@@ -117,75 +117,16 @@ class WarpPlan:
     colour: np.ndarray
     holes: np.ndarray
 
-    _FIELDS = (("n_place", np.int32, ()), ("frame", np.int32, (MAX_PLACE,)), ("window", np.int32, (MAX_PLACE, 4)), ("dest", np.int32, (MAX_PLACE, 4)),
-               ("fwd", np.float64, (MAX_PLACE, 6)), ("inv", np.int64, (MAX_PLACE, 6)), ("colour", np.int32, (MAX_PLACE, 12)),
-               ("holes", np.int32, (MAX_HOLES, 4)))
-
-    @classmethod
-    def empty(cls, sizes, height, width, N=None):
-        """A plan of N canvases (default: one per frame) with no live placement yet, identity maps and colours and no holes."""
-        sizes = [(int(h), int(w)) for (h, w) in sizes]
-        N = len(sizes) if N is None else int(N)
-        arrays = {name: np.zeros((N,) + shape, dtype) for name, dtype, shape in cls._FIELDS}
-        arrays["colour"][...] = IDENTITY_Q12
-        arrays["fwd"][...] = (1.0, 0.0, 0.0, 0.0, 1.0, 0.0)
-        arrays["inv"][...] = (Q20, 0, 0, 0, Q20, 0)
-        return cls(sizes, int(height), int(width), **arrays)
-
-    def __len__(self):
-        return int(self.n_place.shape[0])
-
-    @property
-    def max_place(self):
-        return int(self.n_place.max()) if len(self) else 1
+    _FIELDS = _augment._HEAD + (("fwd", np.float64, (MAX_PLACE, 6)), ("inv", np.int64, (MAX_PLACE, 6))) + _augment._TAIL
+    _INITIAL = {"colour": IDENTITY_Q12, "fwd": (1.0, 0.0, 0.0, 0.0, 1.0, 0.0), "inv": (Q20, 0, 0, 0, Q20, 0)}
+    RECORD_WORDS, IMAGE_ENTRY, BOXES_ENTRY = RECORD_WORDS, "cnl_augment_warp_u8", "cnl_augment_warp_boxes_f64"
 
     def set_map(self, n, p, fwd):
         """fwd and inv = warp_inverse(fwd) of slot p of canvas n."""
         self.fwd[n, p] = _six(fwd, "fwd")
         self.inv[n, p] = warp_inverse(fwd)
 
-    def single(self, n):
-        """The plan of canvas n alone (same frames)."""
-        s = slice(n, n + 1)
-        return WarpPlan(self.sizes, self.height, self.width, **{name: getattr(self, name)[s].copy() for name, _, _ in self._FIELDS})
-
-    def check(self):
-        """Every bound of the plan; ValueError naming the canvas and placement otherwise.  -> self"""
-        N, H, W, F = len(self), self.height, self.width, len(self.sizes)
-        if not (1 <= H <= MAX_SIDE and 4 <= W <= MAX_SIDE and W % 4 == 0):
-            raise ValueError(f"plan: canvas {H} x {W} needs sides of at most {MAX_SIDE} and a width that is a positive multiple of 4")
-        for name, dtype, shape in self._FIELDS:
-            a = getattr(self, name)
-            if not isinstance(a, np.ndarray) or a.dtype != dtype or a.shape != (N,) + shape:
-                raise ValueError(f"plan: {name} must be {'an' if dtype != np.float64 else 'a'} {np.dtype(dtype).name} array of shape {[N] + list(shape)}")
-        for (h, w) in self.sizes:
-            if h < 1 or w < 1:
-                raise ValueError(f"plan: frame size {h} x {w}")
-        k = self.n_place.astype(np.int64)
-        bad = np.nonzero((k < 1) | (k > MAX_PLACE))[0]
-        if bad.size:
-            raise ValueError(f"plan: canvas {int(bad[0])} has {int(k[bad[0]])} placements; 1..{MAX_PLACE} are supported")
-        live = np.arange(MAX_PLACE)[None, :] < k[:, None]
-
-        def first(mask):
-            at = np.argwhere(mask & live)
-            return (int(at[0, 0]), int(at[0, 1])) if at.size else None
-
-        frame = self.frame.astype(np.int64)
-        at = first((frame < 0) | (frame >= F))
-        if at:
-            raise ValueError(f"plan: canvas {at[0]} placement {at[1]}: frame {int(frame[at])} outside 0..{F - 1}")
-        size = np.asarray(self.sizes, dtype=np.int64).reshape(F, 2)[np.where(live, frame, 0)]            # [N, 4, (h, w)]
-        x0, y0, w, h = (self.window[..., i].astype(np.int64) for i in range(4))
-        at = first((w < 1) | (h < 1) | (x0 < 0) | (y0 < 0) | (x0 + w > size[..., 1]) | (y0 + h > size[..., 0]))
-        if at:
-            raise ValueError(f"plan: canvas {at[0]} placement {at[1]}: window (x0 {x0[at]}, y0 {y0[at]}, w {w[at]}, h {h[at]}) is empty or leaves its "
-                             f"{size[at][0]} x {size[at][1]} frame")
-        dx0, dy0, dw, dh = (self.dest[..., i].astype(np.int64) for i in range(4))
-        at = first((dw < 4) | (dh < 1) | (dx0 < 0) | (dy0 < 0) | (dx0 % 4 != 0) | (dw % 4 != 0) | (dx0 + dw > W) | (dy0 + dh > H))
-        if at:
-            raise ValueError(f"plan: canvas {at[0]} placement {at[1]}: rectangle (dx0 {dx0[at]}, dy0 {dy0[at]}, dw {dw[at]}, dh {dh[at]}) needs dx0 and dw "
-                             f"multiples of 4, dh >= 1, inside the {H} x {W} canvas")
+    def _check_geometry(self, first):
         at = first(~np.isfinite(self.fwd).all(axis=-1))
         if at:
             raise ValueError(f"plan: canvas {at[0]} placement {at[1]}: forward map {self.fwd[at].tolist()} is not finite")
@@ -195,35 +136,11 @@ class WarpPlan:
         if at:
             raise ValueError(f"plan: canvas {at[0]} placement {at[1]}: inverse map {self.inv[at].tolist()} outside +-2^30 (entries 0, 1, 3, 4) / "
                              "+-2^44 (entries 2, 5)")
-        c = np.abs(self.colour.astype(np.int64))
-        at = first((c[..., :9].max(axis=-1) > MAX_ENTRY) | (c[..., 9:].max(axis=-1) > MAX_OFFSET))
-        if at:
-            raise ValueError(f"plan: canvas {at[0]} placement {at[1]}: colour matrix outside +-{MAX_ENTRY} (entries) / +-{MAX_OFFSET} (offsets)")
-        for p in range(1, MAX_PLACE):
-            for q_ in range(p):
-                both = live[:, p] & (dx0[:, p] < dx0[:, q_] + dw[:, q_]) & (dx0[:, q_] < dx0[:, p] + dw[:, p]) & \
-                    (dy0[:, p] < dy0[:, q_] + dh[:, q_]) & (dy0[:, q_] < dy0[:, p] + dh[:, p])
-                if both.any():
-                    raise ValueError(f"plan: canvas {int(np.nonzero(both)[0][0])} placement {p}: its rectangle overlaps placement {q_}'s")
-        hl = self.holes.astype(np.int64)
-        at = np.argwhere((hl[..., 2] < 0) | (hl[..., 3] < 0) | (hl[..., 2:] > MAX_SIDE).any(axis=-1) | (np.abs(hl[..., :2]) > MAX_SIDE).any(axis=-1))
-        if at.size:
-            n, j = int(at[0, 0]), int(at[0, 1])
-            raise ValueError(f"plan: canvas {n} hole {j} = {hl[n, j].tolist()} needs 0 <= w, h <= {MAX_SIDE} and |x0|, |y0| <= {MAX_SIDE}")
-        return self
 
     def pack(self, places, holes, n_place):
-        """Fill the upload's views: places [N * 4, 48] int32 (cnl_warp_placement records, zeroed), holes [N * 16, 4] int32, n_place [N]."""
-        N = len(self)
-        rec = places.reshape(N, MAX_PLACE, 2 * RECORD_WORDS)
-        rec[:, :, 0] = self.frame
-        rec[:, :, 1:5] = self.window
-        rec[:, :, 5:9] = self.dest
-        rec[:, :, 10:22] = self.colour
-        rec[:, :, 22:34] = np.ascontiguousarray(self.inv).view(np.int32).reshape(N, MAX_PLACE, 12)
-        rec[:, :, 34:46] = np.ascontiguousarray(self.fwd).view(np.int32).reshape(N, MAX_PLACE, 12)
-        holes.reshape(N, MAX_HOLES, 4)[:] = self.holes
-        n_place[:] = self.n_place
+        rec = super().pack(places, holes, n_place)
+        rec[:, :, 22:34] = np.ascontiguousarray(self.inv).view(np.int32).reshape(len(self), MAX_PLACE, 12)
+        rec[:, :, 34:46] = np.ascontiguousarray(self.fwd).view(np.int32).reshape(len(self), MAX_PLACE, 12)
 
 
 # ----------------------------------------------------------------------------- drawing a plan
@@ -339,12 +256,9 @@ def warp_batch(frames, plan, targets=None, fill=(0, 0, 0), hole_fill=(0, 0, 0), 
     through the placement's colour matrix, as albumentations' ColorJitter after Affine jitters the border).  A box comes out as the
     enclosing box of its four mapped corners, clipped to the placement's rectangle and kept by augment_batch's rule.  One pinned upload,
     two launches (cnl_augment_warp_u8, cnl_augment_warp_boxes_f64), no device sync."""
-    return _augment._batch("warp_batch", WarpPlan, RECORD_WORDS, "cnl_augment_warp_u8", "cnl_augment_warp_boxes_f64", (fill, hole_fill, border), frames, plan,
-                           targets, min_area, min_visibility, out)
+    return _augment._batch("warp_batch", WarpPlan, (fill, hole_fill, border), frames, plan, targets, min_area, min_visibility, out)
 
 
-_SETTINGS = ("affine_scale", "rotate", "shear", "translate_percent", "translate_px", "keep_ratio", "affine_p", "crop", "smallest_max_size", "mosaic", "scale",
-             "ratio", "flip", "brightness", "contrast", "saturation", "hue", "contrast_center", "cutout")
 _AFFINE = {"scale": "affine_scale", "rotate": "rotate", "shear": "shear", "translate_percent": "translate_percent", "translate_px": "translate_px",
            "keep_ratio": "keep_ratio", "p": "affine_p"}
 
@@ -356,62 +270,34 @@ def _plain(v):
     return tuple(v) if isinstance(v, list) else v
 
 
-class TrainWarp:
+class TrainWarp(_augment._Transform):
     """TrainAugment with the affine transforms: callable as (frames, targets) -> (canvas, targets).  Owns a numpy Generator (`seed`); every
-    call draws a fresh plan with sample_warp(**settings) (kept as .last_plan) and runs warp_batch."""
+    call draws a fresh plan with sample_warp(**settings) (kept as .last_plan) and runs warp_batch.
+    from_config reads what TrainAugment.from_config reads (HorizontalFlip, RandomResizedCrop, Resize, ColorJitter, Cutout, Normalize), plus
+    Affine.{scale, rotate, shear, translate_percent, translate_px, keep_ratio, p}; SmallestMaxSize.max_size -> smallest_max_size;
+    RandomCrop.{height, width} -> crop="random" and the canvas size.  Any other name (MotionBlur, TrivialAugmentWide's photometric members,
+    ...) and any other Affine parameter is not supported."""
+    _sample, _run, _RESIZED = staticmethod(sample_warp), staticmethod(warp_batch), "resized"
+    _SETTINGS = ("affine_scale", "rotate", "shear", "translate_percent", "translate_px", "keep_ratio", "affine_p", "crop", "smallest_max_size", "mosaic",
+                 "scale", "ratio", "flip", "brightness", "contrast", "saturation", "hue", "contrast_center", "cutout")
+    _SIZED = "RandomResizedCrop / RandomCrop / Resize"
+    _SUPPORTED = "Affine, SmallestMaxSize, RandomCrop, HorizontalFlip, RandomResizedCrop, ColorJitter, Cutout, Resize and Normalize"
 
     def __init__(self, height, width, seed=0, fill=(0, 0, 0), hole_fill=(0, 0, 0), border=(0, 0, 0), min_area=1.0, min_visibility=0.0, **settings):
-        unknown = [k for k in settings if k not in _SETTINGS]
-        if unknown:
-            raise ValueError(f"TrainWarp: unknown settings {unknown}; sample_warp takes {list(_SETTINGS)}")
-        self.height, self.width, self.settings = int(height), int(width), dict(settings)
-        self.fill, self.hole_fill, self.border, self.min_area, self.min_visibility = fill, hole_fill, border, min_area, min_visibility
-        self.rng = np.random.default_rng(seed)
-        self.skipped, self.last_plan = [], None
-        sample_warp([(self.height, self.width)], self.height, self.width, np.random.default_rng(0), **self.settings)      # bad settings fail here
+        self._setup(height, width, seed, dict(fill=fill, hole_fill=hole_fill, border=border), min_area, min_visibility, settings)
 
-    def __repr__(self):
-        return f"TrainWarp({self.height}, {self.width}, {', '.join(f'{k}={v!r}' for k, v in self.settings.items())})"
-
-    def __call__(self, frames, targets=None):
-        import torch
-        if not isinstance(frames, torch.Tensor):
-            frames = list(frames)
-        self.last_plan = sample_warp(_augment._frame_sizes(frames), self.height, self.width, self.rng, **self.settings)
-        return warp_batch(frames, self.last_plan, targets, fill=self.fill, hole_fill=self.hole_fill, border=self.border, min_area=self.min_area,
-                          min_visibility=self.min_visibility)
-
-    @classmethod
-    def from_config(cls, transforms, height=None, width=None, unsupported="raise", **kwargs):
-        """The reference's YAML transform list in the forms TrainAugment.from_config reads, and what it reads (HorizontalFlip,
-        RandomResizedCrop, Resize, ColorJitter, Cutout, Normalize), plus Affine.{scale, rotate, shear, translate_percent, translate_px,
-        keep_ratio, p}; SmallestMaxSize.max_size -> smallest_max_size; RandomCrop.{height, width} -> crop="random" and the canvas size.
-        Any other name (MotionBlur, TrivialAugmentWide's photometric members, ...) and any other Affine parameter raises ValueError naming
-        it, or with unsupported="skip" is listed in .skipped."""
-        settings, skipped, size = {"flip": 0.0, "crop": False}, [], {}
-        for name, params in _augment._config_items(transforms, unsupported):
-            if _augment._read_common(name, params, settings, size):
-                if settings["crop"] is True:
-                    settings["crop"] = "resized"
-                continue
-            other = sorted(set(params) - set(_AFFINE)) if name == "Affine" else []
-            if name == "Affine" and not other:
-                settings.update({_AFFINE[k]: _plain(v) for k, v in params.items()})
-            elif name == "SmallestMaxSize" and "max_size" in params:
-                settings["smallest_max_size"] = int(params["max_size"])
-            elif name == "RandomCrop":
-                size.clear()
-                size.update({k: int(params[k]) for k in ("height", "width") if k in params})
-                settings["crop"] = "random"
-            elif unsupported == "skip":
-                skipped.append(name)
-            else:
-                raise ValueError(f"TrainWarp.from_config: transform {name!r}{f' with {other}' if other else ''} is not supported (Affine, SmallestMaxSize, "
-                                 "RandomCrop, HorizontalFlip, RandomResizedCrop, ColorJitter, Cutout, Resize and Normalize are)")
-        height = size.get("height") if height is None else height
-        width = size.get("width") if width is None else width
-        if height is None or width is None:
-            raise ValueError("TrainWarp.from_config: no RandomResizedCrop / RandomCrop / Resize names the canvas size; give height and width")
-        out = cls(height, width, **kwargs, **settings)
-        out.skipped = skipped
-        return out
+    @staticmethod
+    def _read_other(name, params, settings, size):
+        other = sorted(set(params) - set(_AFFINE)) if name == "Affine" else []
+        if name == "Affine" and not other:
+            settings.update({_AFFINE[k]: _plain(v) for k, v in params.items()})
+            return None
+        if name == "SmallestMaxSize" and "max_size" in params:
+            settings["smallest_max_size"] = int(params["max_size"])
+            return None
+        if name == "RandomCrop":
+            size.clear()
+            size.update({k: int(params[k]) for k in ("height", "width") if k in params})
+            settings["crop"] = "random"
+            return None
+        return f" with {other}" if other else ""
