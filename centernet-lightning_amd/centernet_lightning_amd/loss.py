@@ -115,12 +115,15 @@ def _same_device(g_dev, dev, what, outputs="outputs"):
         raise ValueError(f"{what}: {outputs} on {dev}, targets on {g_dev}")
 
 
-def _on_device(g_dev, gts, N, dev, what, outputs="outputs"):
-    """_read's result on the outputs' device: device tensors must live there, host arrays go up in one copy."""
+def _on_device(g_dev, gts, N, dev, what, outputs="outputs", keep=False):
+    """_read's result on the outputs' device: device tensors must live there, host arrays go up in one copy.  keep: the result is saved for a
+    backward, so the caller's own device tensors are copied (a loop that refills its target buffers before the backward runs changes nothing)."""
     _same_device(g_dev, dev, what, outputs)
     if g_dev is None:
         with torch.cuda.device(dev):
             gts = [torch.from_numpy(a).to(dev) for a in gts] if N == 0 else _gather.upload_parts(list(gts), dev)      # (an empty batch: nothing to stage)
+    elif keep:
+        gts = [t.clone() for t in gts]
     return tuple(gts)
 
 
@@ -227,11 +230,11 @@ def detection_loss(heatmap, box_2d, targets, stride=4, heatmap_target="cornernet
 WANT = ("heatmap", "box_2d")
 
 
-def _device_targets(targets, shape, stride, dev, what):
+def _device_targets(targets, shape, stride, dev, what, keep=False):
     """targets in either form -> the padded (boxes, labels, count) device tensors of one call; a host list is checked, padded and uploaded in one copy."""
     N, C, H, W = shape
     g_dev, gts, _ = _targets(targets, N, C, H, W, stride, what)
-    return _on_device(g_dev, gts, N, dev, what)
+    return _on_device(g_dev, gts, N, dev, what, keep=keep)
 
 
 def _scale(value, name, dev, what):
@@ -314,7 +317,8 @@ class _DetectionLossFunction(torch.autograd.Function):
         what = "DetectionLoss"
         params = loss_params(what=what, **settings)
         shape = _check_outputs(heatmap, box_2d, what)
-        gts = _device_targets(targets, shape, params.stride, heatmap.device, what)          # a host list: padded and uploaded once, kept for the backward
+        # a host list: padded and uploaded once, kept for the backward; the caller's device tensors: copied, so that the backward reads this call's targets
+        gts = _device_targets(targets, shape, params.stride, heatmap.device, what, keep=True)
         out, skipped, _ = _run(heatmap, box_2d, gts, shape, params, False, heatmap.device, what)
         N = shape[0]
         ctx.save_for_backward(heatmap, box_2d, *gts)
@@ -337,7 +341,8 @@ class DetectionLoss(torch.nn.Module):
     """The criterion of a training step: DetectionLoss(**settings)(outputs, targets) -> the dict detection_loss returns, bit for bit, where "heatmap",
     "box_2d" and "total" carry a grad_fn when an output requires grad: criterion(outputs, targets)["total"].backward() reaches the head that produced
     `outputs` (any torch model on the device).  outputs: the dict of get_encoded_outputs ("heatmap" LOGITS, "box_2d"), fp32; targets as for
-    detection_loss (a host list is padded and uploaded once, and kept for the backward).  `settings`: detection_loss's keyword arguments
+    detection_loss (a host list is padded and uploaded once, and kept for the backward; padded device tensors are copied for the backward, so the caller
+    may refill them, as a loop that reuses augment_batch's out= buffers does, before it runs).  `settings`: detection_loss's keyword arguments
     (model.criterion() fills them from the model).  "per_image" and "skipped" are not differentiable; no double backward.  Under torch.no_grad(),
     or when no output requires grad, it is detection_loss."""
 
@@ -517,8 +522,9 @@ def _reid_targets(targets, N, H, W, K, stride, center, ignore_index, what):
                                f"centre cell outside the map or id outside 0..{K - 1}", what)
 
 
-def _reid_inputs(reid, targets, classifier, params, center, what):
-    """Everything one call reads, checked -> (shape (N, D, H, W), K, the seven tensors (detached, dense) by REID_KEYS, num_batches_tracked, device targets)"""
+def _reid_inputs(reid, targets, classifier, params, center, what, keep=False):
+    """Everything one call reads, checked -> (shape (N, D, H, W), K, the seven tensors (detached, dense) by REID_KEYS, num_batches_tracked, device targets;
+    keep: copies of the caller's own, see _on_device)"""
     _check_map(reid, "reid", "D", what)
     N, D, H, W = (int(v) for v in reid.shape)
     t, eps, momentum, steps = classifier
@@ -532,7 +538,7 @@ def _reid_inputs(reid, targets, classifier, params, center, what):
         if v.device != dev:
             raise ValueError(f"{what}: reid on {dev}, classifier tensor '{k}' on {v.device}")
     g_dev, gts, _ = _reid_targets(targets, N, H, W, K, params.stride, center, params.ignore_index, what)
-    return (N, D, H, W), K, {k: v.detach().contiguous() for k, v in t.items()}, steps, _on_device(g_dev, gts, N, dev, what, "reid")
+    return (N, D, H, W), K, {k: v.detach().contiguous() for k, v in t.items()}, steps, _on_device(g_dev, gts, N, dev, what, "reid", keep=keep)
 
 
 def _reid_common(reid, shape, K, t, gts, params):
@@ -656,9 +662,10 @@ class ReIDLoss(torch.nn.Module):
     nn.Sequential(Linear(D, D, bias=False), BatchNorm1d(D), ReLU, Linear(D, K)) with torch's initialisation, so state_dict() has the reference's keys
     classifier.{0,1,3}.* (formats.reid_classifier_state takes them out of a reference checkpoint).  The Sequential owns the parameters and buffers; its
     own forward is never used.  ReIDLoss(...)(outputs, targets) -> reid_loss's dict, where "reid" carries a grad_fn when the map or a parameter requires
-    grad (one call forward, one call backward, only for the inputs that need a gradient).  .train() / .eval() pick batch or running statistics; a
-    training call steps running_mean, running_var and num_batches_tracked.  loss_weight is NOT applied to the value (TrackingLoss applies it to the
-    total).  `settings`: stride, center, padded_rows, ignore_index of reid_loss."""
+    grad (one call forward, one call backward, only for the inputs that need a gradient; the backward reads its own copy of padded device targets, so
+    the caller may refill them before it runs).  .train() / .eval() pick batch or running statistics; a training call steps running_mean, running_var
+    and num_batches_tracked.  loss_weight is NOT applied to the value (TrackingLoss applies it to the total).  `settings`: stride, center, padded_rows,
+    ignore_index of reid_loss."""
 
     def __init__(self, emb_dim=64, max_track_ids=1000, loss_weight=1.0, **settings):
         super().__init__()
@@ -688,7 +695,7 @@ class ReIDLoss(torch.nn.Module):
         if not needs:
             return reid_loss(reid, targets, self, training=self.training, **self.settings)
         params = reid_params(self.training, bn_eps=cls[1], momentum=cls[2], what=what, **self.settings)
-        shape, K, _, _, gts = _reid_inputs(reid, targets, cls, params, self.settings.get("center", "trunc"), what)
+        shape, K, _, _, gts = _reid_inputs(reid, targets, cls, params, self.settings.get("center", "trunc"), what, keep=True)
         total, per_row, counts, new_stats = _ReIDLossFunction.apply(*trainable, (t["running_mean"], t["running_var"]), gts, params, shape, K)
         if self.training:
             _step_statistics(t, steps, new_stats, counts)

@@ -31,6 +31,7 @@ pytestmark = pytest.mark.gpu
 STRIDE = 4
 K_TILE = 64
 C_ORDER = 1e-12
+VALUE_RTOL = 1e-8                                            # of the float64 value and its per-row terms
 N, H, W, GMAX = 3, 12, 16, 5
 COUNTS = (5, 0, 3)
 SHAPES = [(64, 37), (64, 2 * K_TILE + 3), (8, 37), (20, 37)]
@@ -152,8 +153,8 @@ def run(D, K, padded, center, training, fmt=torch.channels_last, reid_t=None):
 
 
 def check_against_ref(value, d, grads, want, want_grad, training, what):
-    np.testing.assert_allclose(float(value["reid"]), want["reid"], rtol=1e-8, err_msg=what)
-    np.testing.assert_allclose(value["per_row"].cpu().numpy(), want["per_row"], rtol=1e-8, atol=0, err_msg=what)
+    np.testing.assert_allclose(float(value["reid"]), want["reid"], rtol=VALUE_RTOL, err_msg=what)
+    np.testing.assert_allclose(value["per_row"].cpu().numpy(), want["per_row"], rtol=VALUE_RTOL, atol=0, err_msg=what)
     assert (int(value["num_rows"]), int(value["correct"]), int(value["skipped"])) == (want["num_rows"], want["correct"], want["skipped"]), what
     within(d["running_mean"].cpu().numpy(), want["running_mean64"], what + " running_mean")
     within(d["running_var"].cpu().numpy(), want["running_var64"], what + " running_var")
