@@ -62,7 +62,9 @@ class KernelOptions:
                        10^7 breaks the path's 1e-4, and nothing in the kernels notices.  With the option every fp16-split launch's input is inspected before it runs
                        (per image: the maximum over all channels of each 8 x 8-pixel tile; the smallest non-zero tile maximum against the image maximum) and a
                        SplitRangeError names the launch when the ratio exceeds 10^5 — the caller then uses algo="f32" for that model.  A full extra pass per launch
-                       and a host synchronisation: a diagnostic, not a production setting
+                       and a host synchronisation: a diagnostic, not a production setting.  NaN / Inf are refused the same way, with the launch and the image
+                       named: in the fp32 network input ahead of the stem and in every inspected input (without the option a non-finite image runs through —
+                       its own outputs are unspecified, often finite behind a ReLU; no other image changes: DESIGN.md §6)
       split_small      for small batches (default off): launches whose output is too small to fill the chip (one image: the
                        16x16 .. 64x64 maps) run as direct convs with the reduction split over several workgroups per output tile and a
                        fixed-order reduce (cnl_conv_params.splitk).  The choice then depends on the batch size, so results are no longer
@@ -454,7 +456,8 @@ class _VBuf:
 
 
 class SplitRangeError(RuntimeError):
-    """KernelOptions(check_range=True): an input of a fp16-split launch spans more than SPLIT_RANGE_LIMIT between an image's maximum and its weakest 8 x 8 tile."""
+    """KernelOptions(check_range=True): an input of a fp16-split launch spans more than SPLIT_RANGE_LIMIT between an image's maximum and its weakest 8 x 8 tile,
+    or it (or the fp32 network input) holds a NaN or an Inf."""
 
 
 SPLIT_RANGE_LIMIT = 1e5
@@ -1223,6 +1226,8 @@ class Plan:
             self.absmax.zero_()                                # the producers fold max |y| into these with atomic max
         for L in self.launches:
             if self.options.check_range:
+                if L.fn == "stem" and x.dtype == torch.float32:        # (uint8 frames hold no NaN / Inf)
+                    self._raise_nonfinite(L, [x])
                 self._check_split_range(L)
             rc = self.launch(L, x, stream)
             if rc != 0:
@@ -1248,8 +1253,9 @@ class Plan:
                 x2, h2, w2, c2, ldx2 = L.aux[:5]
                 off = (x2 - self.arena.data_ptr()) // 4
                 views.append(self.arena.as_strided((p.N, h2, w2, c2), (h2 * w2 * ldx2, w2 * ldx2, ldx2, 1), self.arena.storage_offset() + off))
+            self._raise_nonfinite(L, views)
             # both sources share one scale per image: the weakest tile of either against the larger of the two maxima
-            top = torch.stack([v.abs().amax(dim=(1, 2, 3)) for v in views]).amax(0)
+            top =torch.stack([v.abs().amax(dim=(1, 2, 3)) for v in views]).amax(0)
             rs = []
             for v in views:
                 vmax = v.abs().amax(dim=(1, 2, 3))
@@ -1265,9 +1271,24 @@ class Plan:
             split = L.fn is lib.cnl_conv3x3_up2_nhwc_f32
         if not split:
             return
-        self._raise_range(L, split_range_ratio(self.input_view(p)))
+        view = self.input_view(p)
+        self._raise_nonfinite(L, [view])
+        self._raise_range(L, split_range_ratio(view))
+
+    def _raise_nonfinite(self, L, views):
+        """views: tensors with the image as their first dimension.  A NaN or an Inf in any of them is refused, the first such image named."""
+        bad = torch.stack([(~torch.isfinite(v)).flatten(1).any(dim=1) for v in views]).any(dim=0)
+        if bool(bad.any()):
+            n = int(torch.nonzero(bad)[0])
+            raise SplitRangeError(f"{L.what}: image {n} of the batch holds a non-finite value (NaN or Inf) in this launch's input: its own outputs are unspecified "
+                                  f"from here on — they may even come out finite, since ReLU is an IEEE maximum; the other images are unaffected (DESIGN.md §6)")
 
     def _raise_range(self, L, ratio):
+        finite = torch.isfinite(ratio)
+        if not bool(finite.all()):
+            n = int(torch.nonzero(~finite)[0])
+            raise SplitRangeError(f"{L.what}: image {n} of the batch has a non-finite range ratio ({float(ratio[n])}): its input holds values the split arithmetic "
+                                  f"cannot represent (include/centernet_gfx950.h, x_absmax)")
         worst = float(ratio.max())
         if worst > SPLIT_RANGE_LIMIT:
             n = int(ratio.argmax())

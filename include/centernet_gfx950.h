@@ -132,6 +132,14 @@ typedef struct cnl_conv_params {
      * matrix core's error level, at 1e6 the error is 2-6e-5 of the LOCAL output magnitude (inside the path's 1e-4), beyond that pass
      * CNL_ALGO_F32 (tests/test_gpu_conv.py::test_split_arithmetic_with_an_outlier_inside_one_image).  WITHOUT x_absmax a launch of the fp16-split kernels takes at most 1024 images (4096 up
      * to ABI v9: the private scratch of the own pass is strided like every maxima array now); more return CNL_E_UNSUPPORTED.
+     * NON-FINITE VALUES (every entry point of this header that takes a batch of activations — the convs, the stems, the pointwise kernel, the
+     * deconv, the elementwise and sampling launches, the folded out_conv and its reduce): NaN or Inf in image n — in x, the residual, a second
+     * source, or in image n's x_absmax line — leave image n's OWN outputs and its max |y| line unspecified.  They may even come out finite and
+     * plausible: ReLU is an IEEE maximum (fmaxf(NaN, 0) = 0), and a maximum of 0, Inf or NaN takes scale 1.  They NEVER change a bit of another
+     * image's outputs, of its max |y| line, or of its rows of splitk_scratch / fuse_part, whatever tile, block row or work item the images
+     * share (tests/test_gpu_nonfinite.py: NaN, +-Inf and overflowing values in one image ahead of every launch of every plan form).  Nothing
+     * here reports them: engine.KernelOptions(check_range=True) is the way to find them (it refuses NaN / Inf in the fp32 network input and in
+     * every fp16-split launch's input with the launch and the image named).
      *                                                                        */
     const float* x_absmax;
     float* y_absmax;
@@ -796,7 +804,15 @@ int cnl_decode_f32(const cnl_decode_params* p, void* stream);
  *   *strip   rows of the map per workgroup
  *   *topk    where the top-k keeps an image's score keys: 0 sixteen registers per thread (H*W <= 16384), 1 LDS (<= 24576),
  *            2 forty-eight registers (<= 49152 and H*W % 4 == 0), 3 their upper halves in LDS (<= 49152), 4 memory only.
- * Every combination computes the same bytes.                                                                                            */
+ * Every combination computes the same bytes for finite heat values.
+ * NON-FINITE VALUES in image n's heat, box or reid leave image n's own outputs unspecified and never change another image's outputs.
+ * Whatever the values: image n's indices lie in [0, H*W) and are pairwise distinct, its labels lie in [0, C), and all N*k (x 4, x E)
+ * output elements are written once — the gathers and crops behind the decode stay inside their buffers — and the top-k terminates (it
+ * orders unsigned integer keys: every bit pattern, NaN included, has one; a positive NaN sorts above +inf, a negative one below -inf).
+ * What is NOT the same in every combination is which class a pixel keeps when NaN stands beside other values: each stage-1 kernel gives a
+ * thread its own subset of the classes, takes the subset's first class unconditionally and a later one only if it compares greater
+ * (never, with a NaN on either side), and merges the subsets by another comparison; and heat * mask is NaN for a +-inf that is no peak
+ * (tests/test_gpu_nonfinite.py: NaN, +-inf and a mix of them in one image of three, every stage-1 kernel and key storage).                */
 int cnl_decode_forms(const cnl_decode_params* p, int32_t* stage1, int32_t* vec, int32_t* strip, int32_t* topk);
 
 /*

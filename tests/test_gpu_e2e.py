@@ -669,6 +669,59 @@ def test_check_range_guard_for_the_split_arithmetic():
     plan._check_split_range = prev
 
 
+def test_check_range_guard_refuses_non_finite_activations():
+    """KernelOptions(check_range=True) refuses NaN / Inf: a NaN pixel and an Inf pixel in image 1 of 2 of the fp32 network input are refused
+    ahead of the stem with the launch and image 1 named; a NaN planted in image 1 of an inspected launch's input (through a hook, as above) likewise, at that
+    launch; the finite batch passes and gives the bytes of the unguarded forward; with the option off the poisoned batch runs as before — nothing is raised,
+    and image 0 keeps the bits it has in the finite batch."""
+    from centernet_lightning_amd import engine as E
+    model, sd = build("resnet34_simple.yaml")
+    xi = recipes.images(99, (2, 3, 128, 128)).cuda()
+    plain = [t.clone() for t in model(xi)]
+    bad = {}
+    for name, v in (("nan", float("nan")), ("inf", float("inf")), ("-inf", float("-inf"))):
+        bad[name] = xi.clone()
+        bad[name][1, 2, 77, 5] = v
+    off = {name: [t.clone() for t in model(xb)] for name, xb in bad.items()}               # option off: runs through
+    for name, outs in off.items():
+        assert all(torch.equal(a[0], b[0]) for a, b in zip(outs, plain)), name            # ... and image 0 keeps its bits
+    model.set_kernel_options(check_range=True)
+    guarded = model(xi)
+    assert all(torch.equal(a, b) for a, b in zip(plain, guarded))
+    for name, xb in bad.items():
+        with pytest.raises(E.SplitRangeError, match=r"^stem7x7\S*: image 1 of the batch holds a non-finite value"):
+            model(xb)
+    # ... and in image 0 the error names image 0
+    x0 = xi.clone()
+    x0[0, 0, 0, 0] = float("nan")
+    with pytest.raises(E.SplitRangeError, match="image 0 of the batch holds a non-finite value"):
+        model(x0)
+    plan = model._engine.plan_for(xi, sigmoid=True)
+    L = next(l for l in plan.launches if isinstance(l.args, E.ConvParams) and l.args.x_absmax and l.fn is plan.lib.cnl_conv3x3_winograd_f32)
+    prev = plan._check_split_range
+    for v in (float("nan"), float("inf")):
+        def check(launch, v=v):
+            if launch is L:
+                plan.input_view(L.args)[1, -1, -1, -1] = v
+            return prev(launch)
+        plan._check_split_range = check
+        with pytest.raises(E.SplitRangeError) as err:
+            model(xi)
+        assert str(err.value).startswith(L.what + ": image 1 of the batch holds a non-finite value"), str(err.value)
+    plan._check_split_range = prev
+    # the ratio itself: a non-finite ratio is refused with its image named, whatever produced it
+    with pytest.raises(E.SplitRangeError, match="image 1 of the batch has a non-finite range ratio"):
+        plan._raise_range(L, torch.tensor([1.0, float("nan")], device="cuda"))
+    with pytest.raises(E.SplitRangeError, match="image 0 of the batch has a non-finite range ratio"):
+        plan._raise_range(L, torch.tensor([float("inf"), 2.0], device="cuda"))
+    plan._raise_range(L, torch.tensor([1.0, 2.0], device="cuda"))
+    assert all(torch.equal(a, b) for a, b in zip(plain, model(xi)))                        # the guarded finite batch still passes
+    model.set_kernel_options(check_range=False)
+    assert all(torch.equal(a, b) for a, b in zip(plain, model(xi)))
+    for name, xb in bad.items():
+        assert all(torch.equal(a[0], b[0]) for a, b in zip(model(xb), plain)), name
+
+
 def test_odd_width_input_runs_the_2d_winograd_kernels_end_to_end():
     """since round 5 no launch of the default C1 / C2 / C4 plans takes the 2-D F(2x2,3x3) split kernels (csrc/winograd5.hip / winograd6.hip) — they
     remain what AUTO takes on maps of ODD width with long channel loops, where the row kernels' two-pixel tiles do not apply.  Inputs are multiples of 32

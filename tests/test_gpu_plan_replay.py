@@ -166,9 +166,10 @@ FOOTPRINT_PLANS = list(SMALL_PLANS) + ["neck_simple_deconv4_separable", "neck_fp
                                        "neck_fpn_deconv_weighted", "neck_ida_bilinear_weighted", "neck_bifpn_nearest"]
 
 
-def build_plan(name):
-    """-> (model, sd, plan, x, norm): the model of PLANS[name] with synthetic weights, its structured input, and the plan a forward of that input uses."""
-    cfg, N, H, W, opts, mutate, u8 = PLANS[name] if name in PLANS else SMALL_PLANS[name]
+def build_plan(name, spec=None):
+    """-> (model, sd, plan, x, norm): the model of PLANS[name] with synthetic weights, its structured input, and the plan a forward of that input uses.
+    spec: a tuple like the PLANS entries, for a variant of an entry at another batch or frame size (tests/test_gpu_nonfinite.py)."""
+    cfg, N, H, W, opts, mutate, u8 = spec if spec is not None else PLANS[name] if name in PLANS else SMALL_PLANS[name]
     torch.manual_seed(0)
     if isinstance(cfg, str):
         model = cl.build_centernet(os.path.join(CONFIGS, cfg))
