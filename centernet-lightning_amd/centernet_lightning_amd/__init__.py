@@ -9,8 +9,8 @@ from .models import CenterNet, DetectionOutput, TrackingOutput, build_centernet
 from .collate import (Collator, all_gather_records, collate_detections, pack_detections, shard_range, unpack_detections)
 from .tracker import Tracker, TrackerBank, Track, TrackState, build_tracker, match_with_threshold
 from . import decode, formats
-from .letterbox import LetterboxGeometry, letterbox_geometry, letterbox_yuv420
-from .tiles import TileGeometry, merge_tiles, tile_grid, tile_uint8, tile_yuv420
+from .letterbox import LetterboxGeometry, letterbox_geometry, letterbox_yuv420, multiscale_sizes
+from .tiles import TileGeometry, merge_soft, merge_tiles, tile_grid, tile_uint8, tile_yuv420
 from .yuv import rgb_to_yuv, split_planes, yuv_coefficients
 from .crops import crop_detections
 from .overlay import DEFAULT_PALETTE, draw_detections
@@ -31,4 +31,4 @@ __all__ = ["CenterNet", "build_centernet", "load_config", "DetectionOutput", "Tr
            "MotEvaluator", "evaluate_mot_tracking_sequence", "LossMeter", "detection_loss", "render_targets", "DetectionLoss",
            "detection_loss_grad", "reid_loss", "reid_loss_grad", "ReIDLoss", "TrackingLoss",
            "augment_batch", "sample_augment", "AugmentPlan", "TrainAugment",
-           "warp_batch", "sample_warp", "WarpPlan", "TrainWarp", "affine_matrix", "warp_inverse"]
+           "warp_batch", "sample_warp", "WarpPlan", "TrainWarp", "affine_matrix", "warp_inverse", "merge_soft", "multiscale_sizes"]

@@ -35,6 +35,32 @@ def letterbox_geometry(h: int, w: int, height: int, width: int) -> Tuple[int, in
     return new_h, new_w, (height - new_h) // 2, (width - new_w) // 2
 
 
+MAX_SCALES = 8          # the engine keeps up to 8 plans, one per input shape
+
+
+def multiscale_sizes(height: int, width: int, scales) -> List[Tuple[int, int]]:
+    """The canvases of a multi-scale test: [(h_s, w_s)] with h_s = 32 * max(1, floor(height * s / 32 + 0.5)) and w_s likewise, in the
+    order of `scales` (1 to 8 finite positive numbers).  Two scales that give the same canvas are a ValueError, like any other bad value."""
+    import math
+    for name, v in (("height", height), ("width", width)):
+        if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+            raise ValueError(f"multiscale_sizes: {name} must be a positive int, got {v!r}")
+    if isinstance(scales, (str, bytes)) or not hasattr(scales, "__iter__"):
+        raise ValueError(f"multiscale_sizes: scales must be a sequence of numbers, got {scales!r}")
+    scales = list(scales)
+    if not 1 <= len(scales) <= MAX_SCALES:
+        raise ValueError(f"multiscale_sizes: 1 to {MAX_SCALES} scales, got {len(scales)}")
+    sizes = []
+    for s in scales:
+        if isinstance(s, bool) or not isinstance(s, (int, float)) or not math.isfinite(s) or s <= 0:
+            raise ValueError(f"multiscale_sizes: a scale must be a finite positive number, got {s!r}")
+        size = tuple(32 * max(1, math.floor(v * s / 32 + 0.5)) for v in (height, width))
+        if size in sizes:
+            raise ValueError(f"multiscale_sizes: scales {scales[sizes.index(size)]!r} and {s!r} both give the canvas {size[0]} x {size[1]}")
+        sizes.append(size)
+    return sizes
+
+
 class LetterboxGeometry:
     """What letterbox_uint8 did to each frame: `table` is the device array of cnl_letterbox_frame records the kernels read,
     `frames` the host-side list of (h, w, new_h, new_w, pad_top, pad_left), `height` / `width` the canvas size; `yuv_table` is the

@@ -325,12 +325,49 @@ class CenterNet(nn.Module):
                                class_aware=class_aware, max_candidates=max_candidates)
         result = {"bboxes": m["bboxes"], "labels": m["labels"], "scores": m["scores"], "count": m["count"]}
         if "embeddings" in dets:
-            emb = dets["embeddings"]
-            k, E, N = emb.shape[1], emb.shape[2], m["source"].shape[0]
-            src = m["source"].long()
-            index = (src.clamp_min(0) + geom.first_view[:N].long()[:, None] * k).reshape(-1, 1).expand(-1, E)
-            picked = torch.gather(emb.reshape(-1, E), 0, index).view(N, -1, E)
-            result["embeddings"] = picked.masked_fill((src < 0).unsqueeze(-1), 0.0)          # (not a product: -x * 0 is -0)
+            result["embeddings"] = _tiles.pick_embeddings(dets["embeddings"], m["source"], geom.first_view)
+        return result
+
+    # ------------------------------------------------------------------ multi-scale test-time augmentation
+    def merge_soft(self, bboxes, scores, labels, geom, **kwargs):
+        """The detections of all views -> per frame, in its own pixels, merged by soft-NMS (cnl_merge_soft_f32); see tiles.merge_soft."""
+        return _tiles.merge_soft(bboxes, scores, labels, geom, **kwargs)
+
+    def detect_multiscale(self, frames, scales=(0.5, 0.75, 1.0, 1.25, 1.5), height: int = 512, width: int = 512, flip_test: bool = False,
+                          method: str = "gaussian", sigma: float = 0.5, iou_threshold: float = 0.5, score_threshold: float = 0.001,
+                          num_detections: int = 100, max_detections: int = 100, class_aware: bool = True, max_candidates: int = 4096,
+                          nms_kernel: int = 3, fill=(0, 0, 0), mean=IMAGENET_MEAN, std=IMAGENET_STD, pixel_format: str = "rgb",
+                          matrix: str = "bt601", full_range: bool = False):
+        """The multi-scale test of the original CenterNet -> {"bboxes" [N,max_detections,4] (each frame's own pixels), "labels", "scores",
+        "count" [N] int32[, "embeddings"]}; rows past a frame's count are zero.
+        For every scale, in the order given: the frames letterboxed to that scale's canvas (letterbox.multiscale_sizes(height, width,
+        scales): the canvas scaled and rounded to a multiple of 32) -> forward_uint8 -> the decode.  The S sets of detections are the S
+        full-frame views of each frame: one soft-NMS merge over all frames puts them into the frame's pixels (tiles.merge_soft: method,
+        sigma, iou_threshold, score_threshold, class_aware, max_candidates) -> for tracking models the embeddings of the picks.
+        Nothing between the frames and the result touches the host except the table uploads (one per scale and one for the merge).
+        Memory: each scale runs its own engine plan with its own arena; the default five scales take about 5.6 times the arena of scale
+        1 (0.25 + 0.5625 + 1 + 1.5625 + 2.25), flip_test doubles that.  At most 8 scales (the engine keeps 8 plans).
+        pixel_format, matrix, full_range, flip_test: as in detect_frames."""
+        sizes = _letterbox.multiscale_sizes(height, width, scales)
+        _tiles.check_soft_arguments("detect_multiscale", method, sigma, iou_threshold, score_threshold, max_detections, max_candidates)
+        parts, per_scale = [], []
+        for (h_s, w_s) in sizes:
+            canvas, geom = _letterbox.letterbox_frames(frames, h_s, w_s, fill, pixel_format, matrix, full_range)
+            if canvas.shape[-1] != 3:
+                raise ValueError(f"detect_multiscale expects 3-channel frames, got {canvas.shape[-1]} channels")
+            out = self.forward_uint8(canvas, mean=mean, std=std, flip_test=flip_test)
+            gather = self.gather_tracking2d if len(out) == 3 else self.gather_detection2d
+            parts.append(gather(out, num_detections=num_detections, nms_kernel=nms_kernel, normalize_bbox=False))
+            per_scale.append(geom.frames)
+        # [S][N, k, ...] -> [N * S, k, ...]: the views of a frame are its scales, in the order given
+        dets = {key: torch.stack([p[key] for p in parts], dim=1).flatten(0, 1) for key in parts[0]}
+        views = _tiles.scale_geometry(per_scale, dets["bboxes"].device)
+        m = _tiles.merge_soft(dets["bboxes"], dets["scores"], dets["labels"], views, method=method, sigma=sigma, iou_threshold=iou_threshold,
+                              score_threshold=score_threshold, max_detections=max_detections, class_aware=class_aware,
+                              max_candidates=max_candidates)
+        result = {"bboxes": m["bboxes"], "labels": m["labels"], "scores": m["scores"], "count": m["count"]}
+        if "embeddings" in dets:
+            result["embeddings"] = _tiles.pick_embeddings(dets["embeddings"], m["source"], views.first_view)
         return result
 
     # ------------------------------------------------------------------ decode (Gen-A names)

@@ -98,6 +98,13 @@ class TileGeometry:
         return cls(None, merge_table, first_view, views, ffv, [], 0, 0)
 
 
+def _full_frame_record(h: int, w: int, new_h: int, new_w: int, pad_top: int, pad_left: int):
+    """The merge record of a whole h x w frame letterboxed to new_h x new_w behind the pads: 8 int32 words, the last two the float bits."""
+    import numpy as np
+    sx, sy = np.float32(new_w) / np.float32(w), np.float32(new_h) / np.float32(h)         # as cnl_unletterbox_boxes_f32 forms them
+    return (w, h, 0, 0, pad_left, pad_top, sx.view(np.int32), sy.view(np.int32))
+
+
 def _view_records(sizes, tile_h: int, tile_w: int, overlap: float, full_frame: bool):
     """The views of frames of the given (h, w) sizes -> (windows [(frame, y0, x0, h, w, new_h, new_w, pad_top, pad_left)]: what the
     gather kernel needs per view, the merge records, TileGeometry.views, frame_first_view).  A tile is a 1:1 window at the canvas'
@@ -113,8 +120,7 @@ def _view_records(sizes, tile_h: int, tile_w: int, overlap: float, full_frame: b
         if full_frame:
             nh, nw, pt, pl = letterbox_geometry(h, w, tile_h, tile_w)
             windows.append((n, 0, 0, h, w, nh, nw, pt, pl))
-            sx, sy = np.float32(nw) / np.float32(w), np.float32(nh) / np.float32(h)       # as cnl_unletterbox_boxes_f32 forms them
-            mg.append((w, h, 0, 0, pl, pt, sx.view(np.int32), sy.view(np.int32)))
+            mg.append(_full_frame_record(h, w, nh, nw, pt, pl))
             views.append((n, 0, 0, h, w))
         ffv.append(len(views))
     return windows, mg, views, ffv
@@ -152,6 +158,31 @@ def tile_yuv420(frames, tile_h: int = 512, tile_w: int = 512, overlap: float = 0
     return tile_frames(frames, tile_h, tile_w, overlap, full_frame, fill, _frames.yuv_layout(layout), matrix, full_range)
 
 
+def _launch_merge(entry: str, bboxes, scores, labels, geom, max_detections: int, max_candidates: int, rule):
+    """The part merge_tiles and merge_soft share, after their checks: the workspace <entry>_workspace_bytes asks for, the five outputs and
+    the call of <entry>_f32, whose arguments differ only in `rule`, the values between max_candidates and the outputs."""
+    bboxes, scores, labels = bboxes.contiguous(), scores.contiguous(), labels.contiguous()
+    (V, k), N, dev = bboxes.shape[:2], geom.num_frames, bboxes.device
+    lib = _lib.load()
+    ws_bytes = int(getattr(lib, entry + "_workspace_bytes")(N, V, k, max_candidates))
+    if ws_bytes == 0:
+        _lib.check(_lib.CNL_E_BAD_ARG, entry + "_workspace_bytes")
+    with torch.cuda.device(dev):
+        ws = torch.empty((ws_bytes + 256,), device=dev, dtype=torch.uint8)
+        ws_ptr = (ws.data_ptr() + 255) & ~255
+        out_boxes = torch.empty((N, max_detections, 4), device=dev, dtype=torch.float32)
+        out_scores = torch.empty((N, max_detections), device=dev, dtype=torch.float32)
+        out_labels = torch.empty((N, max_detections), device=dev, dtype=torch.int64)
+        out_source = torch.empty((N, max_detections), device=dev, dtype=torch.int32)
+        out_count = torch.empty((N,), device=dev, dtype=torch.int32)
+        _lib.check(getattr(lib, entry + "_f32")(bboxes.data_ptr(), scores.data_ptr(), labels.data_ptr(), geom.merge_table.data_ptr(),
+                                                geom.first_view.data_ptr(), N, V, k, max_detections, max_candidates, *rule, out_boxes.data_ptr(),
+                                                out_scores.data_ptr(), out_labels.data_ptr(), out_source.data_ptr(), out_count.data_ptr(),
+                                                ws_ptr, ws_bytes, _lib.stream(dev)),
+                   entry + "_f32")
+    return {"bboxes": out_boxes, "scores": out_scores, "labels": out_labels, "source": out_source, "count": out_count}
+
+
 def merge_tiles(bboxes: torch.Tensor, scores: torch.Tensor, labels: torch.Tensor, geom: TileGeometry, max_detections: int = 300,
                 score_threshold: float = 0.1, match_threshold: float = 0.5, match_metric: str = "iou", class_aware: bool = True,
                 max_candidates: int = 4096):
@@ -175,24 +206,88 @@ def merge_tiles(bboxes: torch.Tensor, scores: torch.Tensor, labels: torch.Tensor
     for name, v in (("max_detections", max_detections), ("max_candidates", max_candidates)):
         if isinstance(v, bool) or not isinstance(v, int) or v < 1:
             raise ValueError(f"merge_tiles: {name} must be a positive int, got {v!r}")
-    bboxes, scores, labels = bboxes.contiguous(), scores.contiguous(), labels.contiguous()
-    N, dev = geom.num_frames, bboxes.device
-    lib = _lib.load()
-    ws_bytes = int(lib.cnl_merge_tiles_workspace_bytes(N, V, k, max_candidates))
-    if ws_bytes == 0:
-        _lib.check(_lib.CNL_E_BAD_ARG, "cnl_merge_tiles_workspace_bytes")
+    return _launch_merge("cnl_merge_tiles", bboxes, scores, labels, geom, max_detections, max_candidates,
+                         (float(score_threshold), float(match_threshold), METRICS[match_metric], int(bool(class_aware))))
+
+
+SOFT_METHODS = {"hard": 0, "linear": 1, "gaussian": 2}
+SOFT_MAX_CANDIDATES = 4096
+
+
+def _number(name: str, v, who: str) -> float:
+    if isinstance(v, bool) or not isinstance(v, (int, float)) or v != v:
+        raise ValueError(f"{who}: {name} must be a number that is not NaN, got {v!r}")
+    return float(v)
+
+
+def check_soft_arguments(who: str, method, sigma, iou_threshold, score_threshold, max_detections, max_candidates) -> None:
+    """The value checks merge_soft and detect_multiscale share (the latter makes them before its first launch)."""
+    if method not in SOFT_METHODS:
+        raise ValueError(f"{who}: method must be one of {sorted(SOFT_METHODS)}, got {method!r}")
+    sigma = _number("sigma", sigma, who)
+    if not 0.0 < sigma < float("inf"):
+        raise ValueError(f"{who}: sigma must be positive and finite, got {sigma!r}")
+    _number("iou_threshold", iou_threshold, who)
+    _number("score_threshold", score_threshold, who)
+    if isinstance(max_detections, bool) or not isinstance(max_detections, int) or max_detections < 1:
+        raise ValueError(f"{who}: max_detections must be a positive int, got {max_detections!r}")
+    if isinstance(max_candidates, bool) or not isinstance(max_candidates, int) or not 1 <= max_candidates <= SOFT_MAX_CANDIDATES:
+        raise ValueError(f"{who}: max_candidates must be an int in 1..{SOFT_MAX_CANDIDATES}, got {max_candidates!r}")
+
+
+def merge_soft(bboxes: torch.Tensor, scores: torch.Tensor, labels: torch.Tensor, geom: TileGeometry, method: str = "gaussian",
+               sigma: float = 0.5, iou_threshold: float = 0.5, score_threshold: float = 0.001, max_detections: int = 100,
+               class_aware: bool = True, max_candidates: int = 4096):
+    """merge_tiles with soft-NMS as the rule (cnl_merge_soft_f32; the rule: include/centernet_gfx950.h): a kept box multiplies the
+    working scores of its same-label neighbours by exp(-iou^2 / sigma) ("gaussian"), by 1 - iou where iou > iou_threshold ("linear"),
+    or by 0 where merge_tiles' IoU predicate holds ("hard": merge_tiles itself); the next pick is the best remaining score above
+    score_threshold.  Same inputs and the same dict as merge_tiles; "scores" are the decayed scores, in non-increasing order.
+    Works on any TileGeometry: one view per frame is the soft-NMS of a single pass, one view per (frame, scale) the multi-scale merge
+    of detect_multiscale.  max_candidates is at most 4096.  Two launches for the whole batch, no device sync.
+    Checks, all before any launch: the values and the tensors' dtypes and shapes (ValueError), then where the tensors live."""
+    check_soft_arguments("merge_soft", method, sigma, iou_threshold, score_threshold, max_detections, max_candidates)
+    for name, t in (("bboxes", bboxes), ("scores", scores), ("labels", labels)):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"merge_soft: {name} must be a tensor, got {type(t).__name__}")
+    if bboxes.dtype != torch.float32 or bboxes.dim() != 3 or bboxes.shape[-1] != 4 or scores.dtype != torch.float32 or labels.dtype != torch.int64:
+        raise ValueError(f"expected float32 [V,k,4] boxes, float32 [V,k] scores and int64 [V,k] labels, got {bboxes.dtype} {tuple(bboxes.shape)}, "
+                         f"{scores.dtype} {tuple(scores.shape)}, {labels.dtype} {tuple(labels.shape)}")
+    V, k = int(bboxes.shape[0]), int(bboxes.shape[1])
+    if tuple(scores.shape) != (V, k) or tuple(labels.shape) != (V, k):
+        raise ValueError(f"scores {tuple(scores.shape)} and labels {tuple(labels.shape)} must both be [{V}, {k}]")
+    if not (bboxes.is_cuda and scores.is_cuda and labels.is_cuda):
+        raise RuntimeError("merge_soft: bboxes, scores and labels must live on a HIP device (no CPU fallback)")
+    if not isinstance(geom, TileGeometry) or V != len(geom) or bboxes.device != geom.merge_table.device:
+        raise ValueError(f"detections of {V} views on {bboxes.device} against {geom!r}")
+    return _launch_merge("cnl_merge_soft", bboxes, scores, labels, geom, max_detections, max_candidates,
+                         (float(score_threshold), SOFT_METHODS[method], float(sigma), float(iou_threshold), int(bool(class_aware))))
+
+
+def scale_geometry(per_scale, dev) -> TileGeometry:
+    """The merge geometry of a multi-scale pass: per_scale[s] is the host list LetterboxGeometry.frames of scale s, [(h, w, new_h,
+    new_w, pad_top, pad_left)] for the same N frames -> one full-frame view per (frame, scale), frame-major (view n * S + s), each
+    record what _view_records writes for its full-frame view.  Host arithmetic on shapes and one pinned upload: no device sync."""
+    import numpy as np
+    S, N = len(per_scale), len(per_scale[0])
+    rec = np.zeros((N * S, 8), dtype=np.int32)
+    views, sizes = [], []
+    for n in range(N):
+        for s in range(S):
+            h, w = per_scale[s][n][:2]
+            rec[n * S + s] = _full_frame_record(*per_scale[s][n])
+            views.append((n, 0, 0, h, w))
+        sizes.append(per_scale[0][n][:2])
+    ffv = [n * S for n in range(N + 1)]
     with torch.cuda.device(dev):
-        ws = torch.empty((ws_bytes + 256,), device=dev, dtype=torch.uint8)
-        ws_ptr = (ws.data_ptr() + 255) & ~255
-        out_boxes = torch.empty((N, max_detections, 4), device=dev, dtype=torch.float32)
-        out_scores = torch.empty((N, max_detections), device=dev, dtype=torch.float32)
-        out_labels = torch.empty((N, max_detections), device=dev, dtype=torch.int64)
-        out_source = torch.empty((N, max_detections), device=dev, dtype=torch.int32)
-        out_count = torch.empty((N,), device=dev, dtype=torch.int32)
-        _lib.check(lib.cnl_merge_tiles_f32(bboxes.data_ptr(), scores.data_ptr(), labels.data_ptr(), geom.merge_table.data_ptr(),
-                                           geom.first_view.data_ptr(), N, V, k, max_detections, max_candidates, float(score_threshold),
-                                           float(match_threshold), METRICS[match_metric], int(bool(class_aware)), out_boxes.data_ptr(),
-                                           out_scores.data_ptr(), out_labels.data_ptr(), out_source.data_ptr(), out_count.data_ptr(),
-                                           ws_ptr, ws_bytes, _lib.stream(dev)),
-                   "cnl_merge_tiles_f32")
-    return {"bboxes": out_boxes, "scores": out_scores, "labels": out_labels, "source": out_source, "count": out_count}
+        merge_table, first_view = _gather.upload_parts([rec, np.array(ffv, dtype=np.int32)], dev)
+    return TileGeometry(None, merge_table, first_view, views, ffv, sizes, 0, 0)
+
+
+def pick_embeddings(embeddings: torch.Tensor, source: torch.Tensor, first_view: torch.Tensor) -> torch.Tensor:
+    """The embeddings [V, k, E] of all views, picked by a merge's `source` [N, K] (candidate numbers relative to the frame's first
+    view; -1 past the count gives a zero row) -> [N, K, E].  What detect_tiled and detect_multiscale return for tracking models."""
+    k, E, N = embeddings.shape[1], embeddings.shape[2], source.shape[0]
+    src = source.long()
+    index = (src.clamp_min(0) + first_view[:N].long()[:, None] * k).reshape(-1, 1).expand(-1, E)
+    picked = torch.gather(embeddings.reshape(-1, E), 0, index).view(N, -1, E)
+    return picked.masked_fill((src < 0).unsqueeze(-1), 0.0)          # (not a product: -x * 0 is -0)

@@ -15,6 +15,8 @@
 //   walk_kernel   one wave per frame walks the rows in order, 64 at a time: the diagonal words resolve the chunk inside the wave
 //                 (v_readlane, no memory), then the rows that survived are OR-ed into the `removed` words right of the chunk with
 //                 independent, coalesced loads.  It stops at K_out survivors and writes every output element.
+//   soft_kernel   the soft merge (cnl_merge_soft_f32: Gaussian / linear soft-NMS, the multi-scale test) behind the same sort_kernel: one
+//                 workgroup per frame runs the whole pick-and-decay loop with every candidate in registers; see the kernel below.
 // No float atomics anywhere; a frame's result depends on that frame's views only (its workgroups read nothing else).
 #include "cnl_common.h"
 
@@ -42,7 +44,8 @@ __host__ __device__ inline size_t align256(size_t v) { return (v + 255) & ~(size
 // workspace carve-up; T = V * k candidates in all
 struct Layout {
     size_t head, keys, box, label, source, score, matrix, total;
-    __host__ Layout(int N, int V, int k, int max_candidates) {
+    // with_matrix = false: the soft merge, which has no suppression bit matrix (`matrix` is then an empty tail)
+    __host__ Layout(int N, int V, int k, int max_candidates, bool with_matrix = true) {
         const size_t T = (size_t)V * k;
         const size_t rows = T < (size_t)N * max_candidates ? T : (size_t)N * max_candidates;      // sum over frames of min(C_n, max_candidates)
         size_t o = 0;
@@ -52,7 +55,7 @@ struct Layout {
         label = o;  o = align256(o + T * 4);
         source = o; o = align256(o + T * 4);
         score = o;  o = align256(o + T * 4);
-        matrix = o; o = align256(o + rows * (size_t)((max_candidates + 63) / 64) * 8);
+        matrix = o; o = align256(o + (with_matrix ? rows * (size_t)((max_candidates + 63) / 64) * 8 : 0));
         total = o;
     }
 };
@@ -255,6 +258,143 @@ __global__ __launch_bounds__(64) void walk_kernel(const FrameHead* __restrict__ 
     if (lane == 0) out_count[n] = kept;
 }
 
+// ---------------------------------------------------------------------------------------------------------------- the soft merge
+// soft_kernel: soft-NMS (Bodla et al.) behind the same sort stage, the rule of include/centernet_gfx950.h (cnl_merge_soft_f32).  A kept
+// box lowers its neighbours' scores, which changes who is picked next: nothing a bit matrix can hold, so the kernel IS the loop.
+// One workgroup of 256 threads per frame.  Position p (the index in the sorted order) belongs to thread p % 256, slot p / 256: a
+// thread keeps the box, label, source and float64 working score of its <= 16 candidates in registers (every index below is a constant
+// of an unrolled loop) and, beside them, its best live candidate.  A pick is: wave maximum of (score, position) by 6 xor-shuffles,
+// the owning lane of each wave publishes its candidate whole (48 bytes) in LDS, one barrier, every thread reads the 4 entries and knows
+// the winner and its box; then each thread decays its same-label candidates and finds its new best in the same pass.  The LDS entries
+// alternate between two buffers, so that one barrier per pick is enough.  The trip count is uniform: the winner is read by all
+// threads from the same LDS words.
+constexpr int SOFT_THREADS = 256;
+constexpr int SOFT_SLOTS = 16;
+constexpr int SOFT_MAX_CANDIDATES = SOFT_THREADS * SOFT_SLOTS;      // 4096: nine scales x 300 detections fit
+constexpr int SOFT_WAVES = SOFT_THREADS / 64;
+constexpr int NO_POSITION = 0x7fffffff;
+
+struct alignas(16) SoftBest {              // what a wave publishes per pick (48 bytes)
+    double score;
+    int position, label, source, reserved;
+    float4 box;
+};
+
+__device__ __forceinline__ double neg_inf() { return -__builtin_inf(); }
+
+// the weight the pick `a` puts on candidate `b` (rule 5 of cnl_merge_soft_f32); METHOD 0 is the fp32 predicate of the hard merge itself
+template <int METHOD>
+__device__ __forceinline__ double soft_weight(const float4 a, const float area_a, const float4 b, const float t, const double td, const double sigma) {
+    if (METHOD == 0) return match(a, area_a, b, t, 0) ? 0.0 : 1.0;
+    const double ax = a.x, ay = a.y, az = a.z, aw = a.w, bx = b.x, by = b.y, bz = b.z, bw = b.w;
+    const double iw = fmax(fmin(az, bz) - fmax(ax, bx), 0.0), ih = fmax(fmin(aw, bw) - fmax(ay, by), 0.0);
+    const double inter = iw * ih;
+    if (!(inter > 0.0)) return 1.0;        // ov = 0 (or ua is not positive): exp(-0) = 1 and 1 - 0 = 1 exactly, so nothing is skipped but work
+    const double ua = ((az - ax) * (aw - ay) + (bz - bx) * (bw - by)) - inter;
+    if (!(ua > 0.0)) return 1.0;
+    const double ov = inter / ua;
+    if (METHOD == 2) return exp(-(ov * ov) / sigma);
+    return ov > td ? 1.0 - ov : 1.0;
+}
+
+template <int METHOD>
+__global__ __launch_bounds__(SOFT_THREADS) void soft_kernel(const FrameHead* __restrict__ head, const int* __restrict__ first_view, int V, int k, int K_out,
+                                                            const float4* __restrict__ s_box, const int* __restrict__ s_label,
+                                                            const int* __restrict__ s_source, const float* __restrict__ s_score,
+                                                            float score_threshold, float sigma_f, float iou_threshold, int class_aware,
+                                                            float4* __restrict__ out_boxes, float* __restrict__ out_scores,
+                                                            long long* __restrict__ out_labels, int* __restrict__ out_source,
+                                                            int* __restrict__ out_count) {
+    __shared__ SoftBest published[2][SOFT_WAVES];
+    const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int M = min(max(head[n].M, 0), SOFT_MAX_CANDIDATES);          // (the entry point has bounded max_candidates: the clamp costs nothing)
+    const int S = (M + SOFT_THREADS - 1) / SOFT_THREADS;                // slots in use, uniform
+    const long base = (long)min(max(first_view[n], 0), V) * k;
+    const double thr = score_threshold, sigma = sigma_f, td = iou_threshold;
+
+    float4 box[SOFT_SLOTS];
+    int label[SOFT_SLOTS], source[SOFT_SLOTS];
+    double work[SOFT_SLOTS];               // the working score; -inf: picked, or no candidate in the slot
+    double best_s = neg_inf();             // this thread's best live candidate, carried whole
+    int best_p = NO_POSITION, best_label = 0, best_source = -1;
+    float4 best_box = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+    for (int s = 0; s < SOFT_SLOTS; ++s) {
+        const int p = s * SOFT_THREADS + tid;
+        const bool in = p < M;
+        box[s] = in ? s_box[base + p] : make_float4(0.f, 0.f, 0.f, 0.f);
+        label[s] = in ? s_label[base + p] : 0;
+        source[s] = in ? s_source[base + p] : -1;
+        work[s] = in ? (double)s_score[base + p] : neg_inf();
+        if (work[s] > thr && work[s] > best_s) {                        // (slots ascend: an equal score later loses to the lower position)
+            best_s = work[s]; best_p = p; best_label = label[s]; best_source = source[s]; best_box = box[s];
+        }
+    }
+
+    int r = 0;                                                          // uniform
+    for (; r < K_out; ++r) {
+        // the wave's maximum: larger score, then lower position
+        double ws = best_s;
+        int wp = best_p;
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            const double os = __shfl_xor(ws, off);
+            const int op = __shfl_xor(wp, off);
+            if (os > ws || (os == ws && op < wp)) { ws = os; wp = op; }
+        }
+        SoftBest* const slot = &published[r & 1][wave];
+        if (wp == NO_POSITION ? lane == 0 : wp == best_p) {             // positions are unique: exactly one lane of the wave
+            SoftBest e;
+            e.score = ws; e.position = wp; e.label = best_label; e.source = best_source; e.reserved = 0; e.box = best_box;
+            *slot = e;
+        }
+        __syncthreads();
+        int win = 0;
+        double pick_s = published[r & 1][0].score;
+        int pick_p = published[r & 1][0].position;
+#pragma unroll
+        for (int w = 1; w < SOFT_WAVES; ++w) {
+            const double os = published[r & 1][w].score;
+            const int op = published[r & 1][w].position;
+            if (os > pick_s || (os == pick_s && op < pick_p)) { pick_s = os; pick_p = op; win = w; }
+        }
+        if (pick_p == NO_POSITION) break;                               // no live candidate is left
+        const SoftBest pick = published[r & 1][win];
+        if (tid == 0) {
+            const long o = (long)n * K_out + r;
+            out_boxes[o] = pick.box;
+            out_scores[o] = (float)pick_s;
+            out_labels[o] = (long long)pick.label;
+            out_source[o] = pick.source;
+        }
+        if (r + 1 == K_out) { ++r; break; }
+        // decay, and the new local best, in one pass
+        const float area_pick = (pick.box.z - pick.box.x) * (pick.box.w - pick.box.y);
+        best_s = neg_inf();
+        best_p = NO_POSITION;
+#pragma unroll
+        for (int s = 0; s < SOFT_SLOTS; ++s) {
+            if (s < S) {
+                const int p = s * SOFT_THREADS + tid;
+                double v = work[s];
+                if (p == pick_p) v = neg_inf();
+                else if (v > neg_inf() && (!class_aware || label[s] == pick.label))
+                    v = v * soft_weight<METHOD>(pick.box, area_pick, box[s], iou_threshold, td, sigma);
+                work[s] = v;
+                if (v > thr && v > best_s) { best_s = v; best_p = p; best_label = label[s]; best_source = source[s]; best_box = box[s]; }
+            }
+        }
+    }
+    for (int q = r + tid; q < K_out; q += SOFT_THREADS) {
+        const long o = (long)n * K_out + q;
+        out_boxes[o] = make_float4(0.f, 0.f, 0.f, 0.f);
+        out_scores[o] = 0.f;
+        out_labels[o] = 0;
+        out_source[o] = -1;
+    }
+    if (tid == 0) out_count[n] = r;
+}
+
 }  // namespace cnl_tile_merge
 
 static int merge_check_sizes(const char* who, int32_t N, int32_t V, int32_t k, int32_t max_candidates) {
@@ -314,4 +454,55 @@ extern "C" int cnl_merge_tiles_f32(const float* boxes, const float* scores, cons
     hipLaunchKernelGGL(walk_kernel, dim3((unsigned)N), dim3(64), 0, s, head, frame_first_view, V, k, K_out, s_box, s_label, s_source, s_score, matrix,
                        reinterpret_cast<float4*>(out_boxes), out_scores, reinterpret_cast<long long*>(out_labels), out_source, out_count);
     return cnl::check_launch("tile_merge walk_kernel");
+}
+
+static int merge_soft_check_sizes(const char* who, int32_t N, int32_t V, int32_t k, int32_t max_candidates) {
+    CNL_REQUIRE(max_candidates >= 1 && max_candidates <= cnl_tile_merge::SOFT_MAX_CANDIDATES, CNL_E_BAD_ARG, "%s: max_candidates = %d outside 1..%d", who,
+                max_candidates, cnl_tile_merge::SOFT_MAX_CANDIDATES);
+    return merge_check_sizes(who, N, V, k, max_candidates);
+}
+
+extern "C" size_t cnl_merge_soft_workspace_bytes(int32_t N, int32_t V, int32_t k, int32_t max_candidates) {
+    if (merge_soft_check_sizes("cnl_merge_soft_workspace_bytes", N, V, k, max_candidates) != CNL_OK) return 0;
+    return cnl_tile_merge::Layout(N, V, k, max_candidates, false).total;
+}
+
+extern "C" int cnl_merge_soft_f32(const float* boxes, const float* scores, const int64_t* labels, const void* views,
+                                  const int32_t* frame_first_view, int32_t N, int32_t V, int32_t k, int32_t K_out, int32_t max_candidates,
+                                  float score_threshold, int32_t method, float sigma, float iou_threshold, int32_t class_aware, float* out_boxes,
+                                  float* out_scores, int64_t* out_labels, int32_t* out_source, int32_t* out_count, void* ws, size_t ws_bytes,
+                                  void* stream) {
+    using namespace cnl_tile_merge;
+    if (int rc = merge_soft_check_sizes("cnl_merge_soft_f32", N, V, k, max_candidates)) return rc;
+    CNL_REQUIRE(K_out >= 1, CNL_E_BAD_ARG, "cnl_merge_soft_f32: K_out = %d must be at least 1", K_out);
+    CNL_REQUIRE(method >= 0 && method <= 2, CNL_E_BAD_ARG, "cnl_merge_soft_f32: method = %d is none of 0 (hard), 1 (linear), 2 (gaussian)", method);
+    CNL_REQUIRE(score_threshold == score_threshold && iou_threshold == iou_threshold, CNL_E_BAD_ARG, "cnl_merge_soft_f32: a threshold is NaN");
+    CNL_REQUIRE(sigma > 0.f && sigma <= 3.402823466e38f, CNL_E_BAD_ARG, "cnl_merge_soft_f32: sigma = %g must be positive and finite", (double)sigma);
+    if (N == 0) return CNL_OK;
+    CNL_REQUIRE(frame_first_view && out_boxes && out_scores && out_labels && out_source && out_count, CNL_E_BAD_ARG,
+                "cnl_merge_soft_f32: null pointer");
+    CNL_REQUIRE(V == 0 || (boxes && scores && labels && views), CNL_E_BAD_ARG, "cnl_merge_soft_f32: null pointer");
+    CNL_REQUIRE(((uintptr_t)boxes & 15) == 0 && ((uintptr_t)out_boxes & 15) == 0 && ((uintptr_t)views & 3) == 0 && ((uintptr_t)labels & 7) == 0 &&
+                    ((uintptr_t)out_labels & 7) == 0, CNL_E_BAD_ARG,
+                "cnl_merge_soft_f32: boxes and out_boxes must be 16-byte, labels and out_labels 8-byte, views 4-byte aligned");
+    const Layout L(N, V, k, max_candidates, false);
+    CNL_REQUIRE(ws && ((uintptr_t)ws & 255) == 0, CNL_E_WORKSPACE, "cnl_merge_soft_f32: the workspace must be 256-byte aligned and not null");
+    CNL_REQUIRE(ws_bytes >= L.total, CNL_E_WORKSPACE, "cnl_merge_soft_f32: workspace of %zu bytes, %zu needed", ws_bytes, L.total);
+    char* const w = static_cast<char*>(ws);
+    FrameHead* const head = reinterpret_cast<FrameHead*>(w + L.head);
+    float4* const s_box = reinterpret_cast<float4*>(w + L.box);
+    int* const s_label = reinterpret_cast<int*>(w + L.label);
+    int* const s_source = reinterpret_cast<int*>(w + L.source);
+    float* const s_score = reinterpret_cast<float*>(w + L.score);
+    hipStream_t s = (hipStream_t)stream;
+    // the sort stage as the hard merge launches it; there is no bit matrix, so its "does the matrix fit" test is given no limit
+    hipLaunchKernelGGL(sort_kernel, dim3((unsigned)N), dim3(SORT_THREADS), 0, s, reinterpret_cast<const float4*>(boxes), scores,
+                       reinterpret_cast<const long long*>(labels), static_cast<const View*>(views), frame_first_view, V, k, max_candidates,
+                       score_threshold, ~0ull, head, reinterpret_cast<unsigned long long*>(w + L.keys), s_box, s_label, s_source, s_score);
+    if (int rc = cnl::check_launch("tile_merge sort_kernel")) return rc;
+    auto* const kernel = method == 0 ? soft_kernel<0> : method == 1 ? soft_kernel<1> : soft_kernel<2>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)N), dim3(SOFT_THREADS), 0, s, head, frame_first_view, V, k, K_out, s_box, s_label, s_source, s_score,
+                       score_threshold, sigma, iou_threshold, class_aware, reinterpret_cast<float4*>(out_boxes), out_scores,
+                       reinterpret_cast<long long*>(out_labels), out_source, out_count);
+    return cnl::check_launch("tile_merge soft_kernel");
 }

@@ -565,6 +565,56 @@ int cnl_merge_tiles_f32(const float* boxes, const float* scores, const int64_t* 
                         void* stream);
 
 /*
+ * The soft merge: Gaussian / linear soft-NMS (Bodla et al., "Soft-NMS", 2017) over the views of a frame, the merge rule of the
+ * original CenterNet's multi-scale test (every scale is one full-frame view).  A picked box does not delete its neighbours, it lowers
+ * their scores, so the second of two real objects that overlap by more than the hard threshold survives with a smaller score.  The
+ * reference has no soft-NMS to compare with: this comment is the specification and tests/soft_nms_ref.py restates it in numpy.
+ * Two launches for the whole batch (the sort stage of cnl_merge_tiles_f32, then one workgroup per frame), no device synchronisation,
+ * no float atomics.  Arguments, the `views` records, frame_first_view and the outputs are cnl_merge_tiles_f32's.
+ *
+ * The rule:
+ *   1. The candidates of a frame are those of cnl_merge_tiles_f32, rules 1-4: score > score_threshold (a NaN score never), boxes
+ *      mapped into the frame in fp32 and clamped, ordered by (score descending, candidate number ascending), the first max_candidates
+ *      of that order (max_candidates in 1..4096 HERE: nine scales of 300 detections fit).  A candidate's index in that order is its
+ *      POSITION.
+ *   2. Every candidate has a WORKING SCORE, a float64, at first its fp32 score.  All float64 arithmetic below is one IEEE rounding per
+ *      operation (no fused multiply-add); thresholds and sigma are the fp32 arguments widened.
+ *   3. For r = 0, 1, ... while r < K_out: among the candidates not yet picked whose working score is > score_threshold take the one
+ *      with the largest working score, among equal scores (-0 equals +0) the lowest position; if there is none, stop.
+ *   4. The pick is output row r: its box, label, source (the candidate number c, as in cnl_merge_tiles_f32) and its working score
+ *      rounded once to fp32.
+ *   5. Every candidate not yet picked with the pick's label (class_aware == 0: every candidate not yet picked) has its working score
+ *      multiplied by a weight w.  With the fp32 coordinates of the two boxes widened to float64:
+ *          iw = max(min(x2p, x2c) - max(x1p, x1c), 0), ih alike, inter = iw * ih,
+ *          ua = ((x2p - x1p) * (y2p - y1p) + (x2c - x1c) * (y2c - y1c)) - inter, ov = inter / ua;
+ *      if ua > 0 is false (degenerate boxes) w = 1; otherwise
+ *          method 2 (gaussian): w = exp(-(ov * ov) / sigma)   (exp is the platform's float64 exp: the one operation that is NOT
+ *                               reproducible to the bit; scores agree with another platform's to a few float64 ulp per decay)
+ *          method 1 (linear):   w = ov > iou_threshold ? 1 - ov : 1
+ *          method 0 (hard):     w = 0 if the fp32, division-free predicate of cnl_merge_tiles_f32's rule 5 with metric 0 holds for
+ *                               (pick, candidate) with match_threshold = iou_threshold, else 1.
+ *      (inter = 0 gives w = 1 exactly for methods 1 and 2, whatever the thresholds.)
+ *   6. Rows past the count hold score 0, label 0, box 0 and source -1; out_count[n] is the number of picks.  Every element is written.
+ * Properties (proved on the restatement by tests/test_multiscale_host.py):
+ *   - With scores >= 0 (what a sigmoid gives) working scores only decay, so the picks leave in non-increasing score order, and
+ *     stopping at K_out equals "soft-NMS of every class to exhaustion, then the K_out best over all classes", the two steps of the
+ *     original CenterNet.
+ *   - Method 0 with score_threshold >= 0 is cnl_merge_tiles_f32 with metric 0 and the same thresholds, bit for bit (a removed
+ *     candidate's working score is 0, which is not > score_threshold).
+ *   - A frame's output depends on that frame's views only, not on N or on the launch geometry.
+ *
+ * Limits (CNL_E_BAD_ARG otherwise): those of cnl_merge_tiles_f32 with max_candidates in 1..4096; method 0, 1 or 2; sigma positive and
+ * finite (whatever the method); thresholds not NaN.  ws: cnl_merge_soft_workspace_bytes(N, V, k, max_candidates) bytes, 256-byte
+ * aligned: the sort keys and the sorted candidates, no bit matrix (cnl_merge_tiles_workspace_bytes is unchanged and always enough).
+ */
+size_t cnl_merge_soft_workspace_bytes(int32_t N, int32_t V, int32_t k, int32_t max_candidates);
+int cnl_merge_soft_f32(const float* boxes, const float* scores, const int64_t* labels, const void* views,
+                       const int32_t* frame_first_view, int32_t N, int32_t V, int32_t k, int32_t K_out, int32_t max_candidates,
+                       float score_threshold, int32_t method, float sigma, float iou_threshold, int32_t class_aware, float* out_boxes,
+                       float* out_scores, int64_t* out_labels, int32_t* out_source, int32_t* out_count, void* ws, size_t ws_bytes,
+                       void* stream);
+
+/*
  * COCO box evaluation (eval/coco.py: CocoEvaluator -> pycocotools COCOeval, iouType "bbox") without pycocotools and without the
  * detections leaving the device.  Two entry points (pure additions: the ABI number stays); both are asynchronous on `stream`, allocate
  * nothing and do no device synchronisation.
