@@ -117,7 +117,14 @@ class WarpPlacement(Structure):
                 ("reserved", c_int32 * 2)]
 
 
+class PixelOp(Structure):
+    """cnl_pixel_op: the operation of one canvas of a pixel-level augmentation plan (400 bytes): its code, its parameter and the taps
+    (dx, dy, w) of a filter."""
+    _fields_ = [("op", c_int32), ("param", c_int32), ("n_taps", c_int32), ("reserved", c_int32), ("taps", (c_int32 * 3) * 32)]
+
+
 assert ctypes.sizeof(LetterboxFrame) == 40 and ctypes.sizeof(AugmentPlacement) == 96 and ctypes.sizeof(WarpPlacement) == 192
+assert ctypes.sizeof(PixelOp) == 400
 
 _REID_COMMON = [c_void_p, c_int64, c_int64, c_int64, c_int64, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int32,
                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, POINTER(ReidLossParams)]
@@ -209,6 +216,9 @@ _SIGNATURES = {
                                            c_uint32, c_void_p]),
     "cnl_augment_warp_boxes_f64": (ctypes.c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
                                                   c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_double, c_double, c_void_p]),
+    "cnl_augment_pixel_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32]),
+    "cnl_augment_pixel_u8": (ctypes.c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_uint32, c_void_p, c_void_p, c_size_t,
+                                            c_void_p]),
     "cnl_stem_conv7x7_u8": (ctypes.c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, POINTER(c_float), POINTER(c_float), c_void_p, c_void_p,
                                            c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "cnl_stem_packed_weight_floats": (c_size_t, []),

@@ -11,7 +11,9 @@ with 11-bit weights, all in integers).  The rules are stated in include/centerne
 pixel rule is deliberately neither cv2.warpAffine's nor the letterbox rule.
 
 Out of scope: rotate_method="ellipse", reflect or replicate borders (everything outside the clip window is one `border` colour),
-area-averaged minification (a strong reduction aliases, as bilinear sampling does), YUV sources, perspective, MotionBlur.
+area-averaged minification (a strong reduction aliases, as bilinear sampling does), YUV sources, perspective.  MotionBlur and the
+photometric members of TrivialAugmentWide (Sharpen, Posterize, Solarize, Equalize) are pixel.py's: a pass of its own over the finished
+canvas, and pixel.TrainTransform reads the lists that name them; TrainWarp.from_config still refuses them by name.
 """
 import dataclasses
 import math
@@ -276,7 +278,7 @@ class TrainWarp(_augment._Transform):
     from_config reads what TrainAugment.from_config reads (HorizontalFlip, RandomResizedCrop, Resize, ColorJitter, Cutout, Normalize), plus
     Affine.{scale, rotate, shear, translate_percent, translate_px, keep_ratio, p}; SmallestMaxSize.max_size -> smallest_max_size;
     RandomCrop.{height, width} -> crop="random" and the canvas size.  Any other name (MotionBlur, TrivialAugmentWide's photometric members,
-    ...) and any other Affine parameter is not supported."""
+    ...) and any other Affine parameter is not supported here; pixel.TrainTransform reads the pixel-level ones."""
     _sample, _run, _RESIZED = staticmethod(sample_warp), staticmethod(warp_batch), "resized"
     _SETTINGS = ("affine_scale", "rotate", "shear", "translate_percent", "translate_px", "keep_ratio", "affine_p", "crop", "smallest_max_size", "mosaic",
                  "scale", "ratio", "flip", "brightness", "contrast", "saturation", "hue", "contrast_center", "cutout")

@@ -1376,6 +1376,69 @@ int cnl_augment_warp_boxes_f64(const void* places, const int32_t* n_place, int32
                                const int64_t* labels, const int64_t* ids, const int32_t* count, int32_t Gmax, double* out_boxes, int64_t* out_labels,
                                int64_t* out_ids, int32_t* out_count, int32_t Gout, double min_area, double min_visibility, void* stream);
 
+/*
+ * Pixel-level training augmentation: the transforms of the reference's training lists that need a neighbourhood or a histogram — MotionBlur
+ * (configs/crowdhuman_tracking.yaml) and the photometric members of datasets/transforms.py::TrivialAugmentWide (Sharpen, Posterize, Solarize,
+ * Equalize).  A FINISHED canvas batch [N, height, width, 3] u8 (what cnl_augment_u8 / cnl_augment_warp_u8 wrote) goes through ONE operation
+ * per canvas, then that canvas's holes are punched (the reference's order: Cutout last, so a hole's edge is sharp and its colour does not
+ * bleed).  Everything is integer arithmetic; nothing is random, nothing goes to the host, no global atomics: the same bytes on every run, and
+ * a canvas's bytes do not depend on its batch.  New entry points and a new record only: the ABI version does not change.
+ *
+ *   ops      device array of N records, 400 bytes each, 4-byte aligned:
+ *     offset   0  int32 op             CNL_PIXEL_NONE / FILTER / POSTERIZE / SOLARIZE / EQUALIZE
+ *     offset   4  int32 param          POSTERIZE: bits, 0..8; SOLARIZE: the threshold t, 0..255; else 0
+ *     offset   8  int32 n_taps         FILTER: 1..32; else 0
+ *     offset  12  int32 reserved       0
+ *     offset  16  int32 taps[32][3]    FILTER: (dx, dy, w) with |dx|, |dy| <= 15, w signed; sum w = 65536 exactly, sum |w| <= 2^23
+ *   holes    cnl_augment_u8's: N * 16 slots (x0, y0, w, h), 16-byte aligned, or NULL; punched with hole_fill_rgba AFTER the operation
+ *   launches what the host-visible plan holds: 0, CNL_PIXEL_HAS_TABLE (some canvas has POSTERIZE, SOLARIZE or EQUALIZE: the table launch) or
+ *            CNL_PIXEL_HAS_TABLE | CNL_PIXEL_HAS_EQUALIZE (also the histogram launch).  Two or three launches, or one.
+ *
+ * The value of out pixel (y, x), channel c, from the canvas `in` of the same n (>> an arithmetic shift: floor):
+ *   NONE       in
+ *   FILTER     clamp((sum_i w_i * in[r(y + dy_i, height), r(x + dx_i, width), c] + 32768) >> 16, 0, 255), with r cv2's BORDER_REFLECT_101 made
+ *              total: r(i, 1) = 0; otherwise m = i mod 2(n - 1) (non-negative) and r = m if m < n, else 2(n - 1) - m — for a canvas smaller than
+ *              the radius too (numpy.pad(mode="reflect")).  A constant canvas is a fixed point of every such filter.
+ *   POSTERIZE  v & (0xFF << (8 - bits)) & 0xFF          SOLARIZE  v >= t ? 255 - v : v          (albumentations' tables)
+ *   EQUALIZE   albumentations' default (mode="cv", by_channels), per channel: h the channel's histogram over the whole canvas (before the
+ *              holes), i0 its first populated bin, d = height * width - h[i0]; d == 0 leaves the channel unchanged; otherwise lut[v] = 0 for
+ *              v <= i0 and lut[v] = (510 * cum(v) + d) / (2 d) (floor, 64-bit) with cum(v) = sum_{i0 < i <= v} h[i].  DEVIATION: cv2.equalizeHist
+ *              rounds cum * (255.f / d) in fp32, which differs from this exact rounding in a few table entries, by one level.
+ *   in a hole  hole_fill_rgba, overriding all of them.
+ * The MotionBlur and Sharpen taps are the host's (centernet_lightning_amd/pixel.py: the line rule and a = rint(alpha * 65536)).
+ *
+ * A BAD record is not a fault and can never index out of the kernel's LDS: a record whose op is none of the five, a FILTER with n_taps
+ * outside 1..32, any |dx| or |dy| > 15 or sum |w| > 2^23, and a POSTERIZE / SOLARIZE whose param is out of range all run as NONE (the canvas
+ * is copied and its holes punched: skipped, not clamped).  The sum of the weights is the host's to check; the device does not.  A table
+ * operation in a call whose `launches` lacks CNL_PIXEL_HAS_TABLE runs as NONE, and an EQUALIZE without CNL_PIXEL_HAS_EQUALIZE gets the identity
+ * table: a wrong `launches` never reads workspace bytes that were not written.
+ *
+ * workspace: exactly cnl_augment_pixel_workspace_bytes(N, height, width) bytes (a pure host function, monotone in each argument; 0 for
+ * arguments the entry refuses and for N == 0), 16-byte aligned: N * 768 table bytes, then N * min(ceil(height / 8), 32) partial histograms of
+ * 768 uint32.  It need not be cleared.  canvas is only read; out [N, height, width, 3] u8 must not overlap it (refused) and every byte of it is
+ * written exactly once.  canvas, out: 4-byte aligned; height in 1..32768, width in 4..32768 a multiple of 4; N in 0..65535, N == 0 a no-op.
+ * CNL_E_BAD_ARG (CNL_E_WORKSPACE for the size) with a message for everything the host can see, before anything is launched.
+ */
+#define CNL_PIXEL_NONE 0
+#define CNL_PIXEL_FILTER 1
+#define CNL_PIXEL_POSTERIZE 2
+#define CNL_PIXEL_SOLARIZE 3
+#define CNL_PIXEL_EQUALIZE 4
+#define CNL_PIXEL_MAX_TAPS 32
+#define CNL_PIXEL_MAX_RADIUS 15
+#define CNL_PIXEL_HAS_TABLE 1
+#define CNL_PIXEL_HAS_EQUALIZE 2
+typedef struct cnl_pixel_op {
+    int32_t op;
+    int32_t param;
+    int32_t n_taps;
+    int32_t reserved;
+    int32_t taps[CNL_PIXEL_MAX_TAPS][3];
+} cnl_pixel_op;
+size_t cnl_augment_pixel_workspace_bytes(int32_t N, int32_t height, int32_t width);
+int cnl_augment_pixel_u8(const uint8_t* canvas, int32_t N, int32_t height, int32_t width, const void* ops, int32_t launches, const int32_t* holes,
+                         uint32_t hole_fill_rgba, uint8_t* out, void* workspace, size_t workspace_bytes, void* stream);
+
 int cnl_version(void);
 /* sizeof(cnl_conv_params) / sizeof(cnl_decode_params) / sizeof(cnl_deconv_params) (which = 0 / 1 / 2), sizeof(cnl_loss_params) (which = 4) and sizeof(cnl_reid_loss_params) (which = 5; 3 is
  * unused; else 0) as the library was compiled — the structs grow at the end between ABI
