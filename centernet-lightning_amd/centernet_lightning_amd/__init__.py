@@ -21,6 +21,7 @@ from .loss import (DetectionLoss, LossMeter, ReIDLoss, TrackingLoss, detection_l
 from .augment import AugmentPlan, TrainAugment, augment_batch, sample_augment
 from .warp import TrainWarp, WarpPlan, affine_matrix, sample_warp, warp_batch, warp_inverse
 from .pixel import PixelPlan, TrainTransform, motion_blur_taps, pixel_batch, sample_pixel, sharpen_taps
+from .conv_grad import HeadTrainer, conv2d_nhwc
 from .export import TraceableCenterNet, export_onnx, export_torchscript
 
 __all__ = ["CenterNet", "build_centernet", "load_config", "DetectionOutput", "TrackingOutput", "decode",
@@ -33,4 +34,5 @@ __all__ = ["CenterNet", "build_centernet", "load_config", "DetectionOutput", "Tr
            "detection_loss_grad", "reid_loss", "reid_loss_grad", "ReIDLoss", "TrackingLoss",
            "augment_batch", "sample_augment", "AugmentPlan", "TrainAugment",
            "warp_batch", "sample_warp", "WarpPlan", "TrainWarp", "affine_matrix", "warp_inverse",
-           "pixel_batch", "sample_pixel", "PixelPlan", "TrainTransform", "motion_blur_taps", "sharpen_taps", "merge_soft", "multiscale_sizes"]
+           "pixel_batch", "sample_pixel", "PixelPlan", "TrainTransform", "motion_blur_taps", "sharpen_taps", "merge_soft", "multiscale_sizes",
+           "HeadTrainer", "conv2d_nhwc"]

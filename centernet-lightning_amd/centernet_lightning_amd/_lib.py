@@ -255,6 +255,16 @@ _SIGNATURES = {
     "cnl_track_streams_f32": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int32, c_int32, c_float,
                                              c_double, c_float, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p,
                                              ctypes.c_int64, c_void_p, ctypes.c_int64, c_void_p]),
+    "cnl_relu_grad_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32]),
+    "cnl_relu_grad_terms": (c_int64, [c_int32, c_int32, c_int32, c_int32]),
+    "cnl_relu_grad_f32": (ctypes.c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p,
+                                         c_int32, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "cnl_conv_wgrad_slices": (c_int64, [c_int32] * 7),
+    "cnl_conv_wgrad_workspace_bytes": (c_size_t, [c_int32] * 7),
+    "cnl_conv_wgrad_terms": (c_int64, [c_int32] * 7),
+    "cnl_conv_wgrad_nhwc_f32": (ctypes.c_int, [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                               c_int32, c_void_p, c_size_t, c_void_p]),
+    "cnl_conv1x1_dgrad_nhwc_f32": (ctypes.c_int, [c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "cnl_host_alloc": (ctypes.c_int, [ctypes.c_size_t, ctypes.POINTER(c_void_p)]),
     "cnl_host_free": (ctypes.c_int, [c_void_p]),
 }

@@ -1430,6 +1430,52 @@ class Engine:
         with torch.cuda.device(dev):
             return plan.run(x, norm)
 
+    def neck_features(self, x):
+        """The neck map the heads read for x [N,3,H,W] fp32: a fresh channels-last tensor, logical [N, C, H / stride, W / stride].  Runs the launches
+        of the forward's own plan up to the first head launch (Plan.neck_out) and copies the buffer out of the arena; where the plan folds a final
+        nearest-2x upsample into the first head blocks (neck_up) the copy is the upsampled map (cnl_upsample2x_nhwc_f32).  For conv_grad.HeadTrainer."""
+        if not (isinstance(x, torch.Tensor) and x.is_cuda):
+            raise RuntimeError("CenterNet (MI355X) runs on HIP devices only: move the input to 'cuda' (no CPU fallback)")
+        if x.dim() != 4 or x.shape[1] != 3 or x.dtype != torch.float32:
+            raise ValueError(f"expected float32 input of shape [N,3,H,W], got {x.dtype} {tuple(x.shape)}")
+        N, _, H, W = x.shape
+        dev = x.device
+        with self._lock, torch.no_grad():
+            if self.weights is None or self.weights_device != dev or self.weights.stale(self.model):
+                self.weights = PackedWeights(self.model, dev)
+                self.weights_device = dev
+                self.plans.clear()
+            chunk = self.sub_batch(N, H, W)
+            parts = [self._neck_run(x[i:i + chunk], H, W) for i in range(0, N, chunk)]
+            return parts[0] if len(parts) == 1 else torch.cat(parts, dim=0).contiguous(memory_format=torch.channels_last)
+
+    def _neck_run(self, x, H, W):
+        dev, N = x.device, x.shape[0]
+        key = (N, H, W, False, self.options, torch.cuda.current_stream(dev).cuda_stream)
+        plan = self.plans.get(key)
+        with torch.cuda.device(dev):
+            if plan is None:
+                plan = self.plans[key] = Plan(self.weights, N, H, W, dev, False, self.options)
+                while len(self.plans) > max(1, self.max_plans):
+                    self.plans.popitem(last=False)
+            else:
+                self.plans.move_to_end(key)
+            plan._norm = None
+            stream = _lib.stream(dev)
+            if plan.absmax is not None:
+                plan.absmax.zero_()
+            for L in plan.launches:
+                if L.what.startswith("heads."):
+                    break
+                _lib.check(plan.launch(L, x, stream), L.what)
+            buf, nh, nw, nc, up = plan.neck_out
+            src = plan.tensor(buf)
+            if not up:
+                return src.clone().permute(0, 3, 1, 2)
+            out = torch.empty((N, 2 * nh, 2 * nw, nc), device=dev, dtype=torch.float32)
+            _lib.check(plan.lib.cnl_upsample2x_nhwc_f32(src.data_ptr(), None, out.data_ptr(), N, nh, nw, nc, nc, 0, nc, 0, stream), "neck_features: upsample")
+            return out.permute(0, 3, 1, 2)
+
     def plan_for(self, x, sigmoid=True):
         """The (existing) plan a forward of x on the current stream uses — bench / tests introspection."""
         N, _, H, W = x.shape

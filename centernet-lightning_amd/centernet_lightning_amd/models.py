@@ -20,6 +20,7 @@ import torch
 from torch import nn
 
 from . import coco_eval as _coco_eval
+from . import conv_grad as _conv_grad
 from . import crops as _crops
 from . import decode as _decode
 from . import flip as _flip
@@ -136,8 +137,20 @@ class CenterNet(nn.Module):
     def train(self, mode: bool = True):
         if mode:
             raise RuntimeError("this CenterNet is the inference hot path only (eval-mode BatchNorm is folded into the HIP "
-                               "kernels); training stays with the reference's Lightning module")
+                               "kernels); training stays with the reference's Lightning module — except the heads over the frozen "
+                               "trunk: head_trainer()")
         return super().train(False)
+
+    # ------------------------------------------------------------------ fine-tuning the heads
+    def neck_features(self, x: torch.Tensor) -> torch.Tensor:
+        """The neck map the heads read, [N, C, H / stride, W / stride], as a fresh channels-last tensor: the plan run up to Plan.neck_out (where
+        the plan folds a nearest-2x upsample into the first head blocks, the upsampled map).  No grad flows into it: the trunk is frozen."""
+        return self._engine.neck_features(x)
+
+    def head_trainer(self):
+        """A conv_grad.HeadTrainer: an nn.Module whose parameters() are self.heads' own, and whose forward returns get_encoded_outputs' dict
+        with a grad_fn (conv backward on the GPU, frozen BatchNorm statistics) — criterion()(trainer(x), targets)["total"].backward()."""
+        return _conv_grad.HeadTrainer(self)
 
     # ------------------------------------------------------------------ forward
     def get_encoded_outputs(self, x: torch.Tensor, flip_test: bool = False) -> Dict[str, torch.Tensor]:

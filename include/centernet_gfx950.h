@@ -1439,6 +1439,58 @@ size_t cnl_augment_pixel_workspace_bytes(int32_t N, int32_t height, int32_t widt
 int cnl_augment_pixel_u8(const uint8_t* canvas, int32_t N, int32_t height, int32_t width, const void* ops, int32_t launches, const int32_t* holes,
                          uint32_t hole_fill_rgba, uint8_t* out, void* workspace, size_t workspace_bytes, void* stream);
 
+/*
+ * ---- Convolution gradients: fine-tuning the heads (csrc/conv_grad.hip; no ABI bump: new entry points only) ----
+ * The backward pass of  z = conv(x, w) + bias, y = relu(z)  for the stride-1 3x3 / pad 1 and 1x1 / pad 0 convolutions of a head
+ * (reference models/meta.py:21-30), given the loss gradient dy.  LAYOUT: every tensor is NHWC fp32 with a pixel stride in elements
+ * (ldx >= Cin, lddz >= Cout, lddx >= Cin; each % 4 == 0 and each of x, dz, dx, dw, w and the wgrad workspace 16-byte aligned, else
+ * CNL_E_BAD_ARG), so a tensor may be a channel slice of a wider buffer; a tensor spans at most the engine's 4 GiB addressing
+ * (N * H * W * ld * 4 <= 0xEF000000, else CNL_E_UNSUPPORTED: split the batch).  OUTPUT CONTRACT, as for the conv family: an entry point
+ * writes its declared channels of its declared pixels (dw: all Cout * KH * KW * Cin floats) and nothing else.  DETERMINISM: no atomics and
+ * no memset; partial results go to a workspace that need not be cleared and are added in a fixed order — the same bytes on every run.
+ * ARITHMETIC: fp32 only.  The weight gradient runs on the fp32 matrix cores (v_mfma_f32_32x32x2_f32: exact fp32 products, bit for bit an
+ * fmaf chain in pixel order); the 1x1 input gradient is an fmaf chain over co = 0, 1, ... on the vector ALU.  The scaled two-way fp16
+ * split of the forward kernels is NOT used: it promises fp32-level results for inputs within 1e4 of the image maximum, and a loss
+ * gradient map (the focal loss at a box centre beside far negatives) spans many more decades.  The 3x3 INPUT gradient needs no entry
+ * point of its own: dx = conv3x3(dz, w rotated by 180 degrees with O and I swapped) is cnl_conv2d_nhwc_f32 without x_absmax / w_absmax
+ * (Cin of that call = Cout of the layer, so Cout % 32 == 0).  Every refusal happens before anything is launched, with cnl_last_error text.
+ *
+ * cnl_relu_grad_f32: dz[p][c] = y[p][c] > 0 ? dy[n][c][h][w] : 0 (torch's ReLU backward: exactly 0 where y == 0; a NaN y gives 0), for
+ *   p = (n * H + h) * W + w; y == NULL: a plain copy into the dz layout (a conv without activation).  dy: element strides of the logical
+ *   axes (n, c, h, w), any non-negative values, 4-byte aligned; y: [N * H * W][ldy], ldy >= C.  dbias (NULL: not wanted; then no workspace):
+ *   dbias[c] = sum_p dz[p][c] — a workgroup owns 256 consecutive pixels and adds them in fp32 (cpt = min(256, C rounded up to a power of
+ *   two) threads per pixel, 256 / cpt pixel lanes with stride 256 / cpt, each in pixel order, then the lanes in lane order), the
+ *   workgroups' sums are added in workgroup order in float64 and rounded once.  cnl_relu_grad_terms: an upper bound on the roundings on
+ *   the path to a dbias element (257).  workspace: cnl_relu_grad_workspace_bytes = ceil(N * H * W / 256) * C * 4 bytes, 4-byte aligned.
+ *
+ * cnl_conv_wgrad_nhwc_f32: dw[co][ky][kx][ci] = sum over n, oy, ox of dz[n, oy, ox, co] * x[n, oy + ky - pad, ox + kx - pad, ci], zero outside
+ *   the image; dw is OHWI and dense, the layout of cnl_conv_params.w.  (KH, KW, pad) = (3, 3, 1) or (1, 1, 0), Cin % 32 == 0 (else
+ *   CNL_E_UNSUPPORTED), any Cout >= 1.  A GEMM with M = Cout, N = KH * KW * Cin, K = N * H * W: a workgroup owns 128 couts x all taps x 32
+ *   input channels for ONE slice of the image rows (row r = n * H + oy), stages dz and the x rows with their one-pixel halo through LDS
+ *   (each x element staged serves all taps), accumulates in pixel order and writes its partial tile to workspace[slice][co][tap][ci]; a
+ *   second launch adds the slices in slice order.  THE SLICE FUNCTION (of the layer shape and N, H, W alone — so the result is a function
+ *   of the inputs alone): tiles = ceil(Cout / 128) * (Cin / 32); rows = N * H; rows_per_slice = min(rows, max(ceil(rows / ceil(1024 /
+ *   tiles)), ceil(512 / W))); slices = ceil(rows / rows_per_slice) = cnl_conv_wgrad_slices (0 for a shape the entry refuses).
+ *   cnl_conv_wgrad_workspace_bytes = slices * Cout * KH * KW * Cin * 4.  cnl_conv_wgrad_terms = rows_per_slice * W + slices: an upper
+ *   bound on the fp32 additions on the path to any dw element (the chain inside a slice plus the reduce).  All three are pure host
+ *   functions.  CNL_E_WORKSPACE for a null or short workspace.
+ *
+ * cnl_conv1x1_dgrad_nhwc_f32: dx[p][ci] = sum_co dz[p][co] * w[co][ci] (w: [Cout][Cin] dense), the input gradient of a 1x1 conv whose
+ *   Cout is the head's channel count (any value >= 1: the case the forward kernels refuse as Cin of the transposed problem); Cin % 32 == 0.
+ *   Exactly Cout fmaf per element, co ascending.
+ */
+size_t cnl_relu_grad_workspace_bytes(int32_t N, int32_t C, int32_t H, int32_t W);
+int64_t cnl_relu_grad_terms(int32_t N, int32_t C, int32_t H, int32_t W);
+int cnl_relu_grad_f32(const float* dy, int64_t dy_sn, int64_t dy_sc, int64_t dy_sh, int64_t dy_sw, const float* y, int32_t ldy, int32_t N, int32_t C,
+                      int32_t H, int32_t W, float* dz, int32_t lddz, float* dbias, void* workspace, size_t workspace_bytes, void* stream);
+int64_t cnl_conv_wgrad_slices(int32_t N, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t KH, int32_t KW);
+size_t cnl_conv_wgrad_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t KH, int32_t KW);
+int64_t cnl_conv_wgrad_terms(int32_t N, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t KH, int32_t KW);
+int cnl_conv_wgrad_nhwc_f32(const float* x, int32_t ldx, const float* dz, int32_t lddz, float* dw, int32_t N, int32_t H, int32_t W, int32_t Cin,
+                            int32_t Cout, int32_t KH, int32_t KW, int32_t pad, void* workspace, size_t workspace_bytes, void* stream);
+int cnl_conv1x1_dgrad_nhwc_f32(const float* dz, int32_t lddz, const float* w, float* dx, int32_t lddx, int32_t N, int32_t H, int32_t W, int32_t Cin,
+                               int32_t Cout, void* stream);
+
 int cnl_version(void);
 /* sizeof(cnl_conv_params) / sizeof(cnl_decode_params) / sizeof(cnl_deconv_params) (which = 0 / 1 / 2), sizeof(cnl_loss_params) (which = 4) and sizeof(cnl_reid_loss_params) (which = 5; 3 is
  * unused; else 0) as the library was compiled — the structs grow at the end between ABI
