@@ -19,6 +19,7 @@ from typing import Any, Dict, Union
 import torch
 from torch import nn
 
+from . import _lib
 from . import coco_eval as _coco_eval
 from . import conv_grad as _conv_grad
 from . import crops as _crops
@@ -37,6 +38,21 @@ DetectionOutput = namedtuple("DetectionOutput", ["heatmap", "box_2d"])
 TrackingOutput = namedtuple("TrackingOutput", ["heatmap", "box_2d", "reid"])
 
 _HEAD_CHANNELS = {"box_2d": lambda cfg: 4}
+
+
+def _as_output(out):
+    """The engine's output dict -> the namedtuple forward() and forward_uint8() return."""
+    if "reid" in out:
+        return TrackingOutput(out["heatmap"], out["box_2d"], out["reid"])
+    return DetectionOutput(out["heatmap"], out["box_2d"])
+
+
+def _merged_result(merged, dets, first_view):
+    """What detect_tiled and detect_multiscale return: the merge's dict without "source", and for tracking models the embeddings it picks."""
+    result = {key: merged[key] for key in ("bboxes", "labels", "scores", "count")}
+    if "embeddings" in dets:
+        result["embeddings"] = _tiles.pick_embeddings(dets["embeddings"], merged["source"], first_view)
+    return result
 
 
 class _Head(GenericHead):
@@ -170,10 +186,7 @@ class CenterNet(nn.Module):
         right and is averaged as the raw head output, which with box_log is a geometric mean of the sizes)."""
         if flip_test:
             return _flip.flip_merge(self.forward(_flip.mirror_append(x)), x.shape[0])
-        out = self._engine.forward(x, sigmoid=True)
-        if "reid" in out:
-            return TrackingOutput(out["heatmap"], out["box_2d"], out["reid"])
-        return DetectionOutput(out["heatmap"], out["box_2d"])
+        return _as_output(self._engine.forward(x, sigmoid=True))
 
     # ------------------------------------------------------------------ step before the path (SURVEY §8f next #2)
     IMAGENET_MEAN = (0.485, 0.456, 0.406)      # datasets/utils.py:9-10 of the reference
@@ -182,24 +195,16 @@ class CenterNet(nn.Module):
     def preprocess_uint8(self, images: torch.Tensor, mean=IMAGENET_MEAN, std=IMAGENET_STD) -> torch.Tensor:
         """uint8 RGB frames [N,H,W,3] on the GPU -> normalised fp32 batch, logical [N,3,H,W] (channels_last storage, read
         zero-copy by forward()).  Same arithmetic as albumentations A.Normalize + ToTensorV2 (README.md:79-87)."""
-        import ctypes
-        import numpy as np
-        from . import _lib
         if not (isinstance(images, torch.Tensor) and images.is_cuda):
             raise RuntimeError("preprocess_uint8 runs on HIP devices only (no CPU fallback)")
         if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[-1] != 3:
             raise ValueError(f"expected uint8 [N,H,W,3], got {images.dtype} {tuple(images.shape)}")
         images = images.contiguous()
         N, H, W, _ = images.shape
-        m = np.array(mean, dtype=np.float32) * np.float32(255.0)
-        r = np.reciprocal(np.array(std, dtype=np.float32) * np.float32(255.0), dtype=np.float32)
-        lib = _lib.load()
+        m, r = self._norm_constants(mean, std)
         with torch.cuda.device(images.device):
             out = torch.empty((N, H, W, 3), device=images.device, dtype=torch.float32)
-            _lib.check(lib.cnl_normalize_u8_nhwc_f32(images.data_ptr(), out.data_ptr(), N, H, W,
-                                                     m.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
-                                                     r.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
-                                                     _lib.stream(images.device)),
+            _lib.check(_lib.load().cnl_normalize_u8_nhwc_f32(images.data_ptr(), out.data_ptr(), N, H, W, m, r, _lib.stream(images.device)),
                        "cnl_normalize_u8_nhwc_f32")
         return out.permute(0, 3, 1, 2)
 
@@ -213,7 +218,6 @@ class CenterNet(nn.Module):
     def resize_uint8(self, images: torch.Tensor, height: int, width: int) -> torch.Tensor:
         """albumentations A.Resize(height, width) (README.md:84) = cv2.resize(..., INTER_LINEAR) on uint8 frames [N,H,W,C] -> [N,height,width,C]
         (cnl_resize_bilinear_u8: OpenCV's 8-bit fixed-point rule, bit-exact against oracle/decode_ref.resize_bilinear_u8)."""
-        from . import _lib
         if not (isinstance(images, torch.Tensor) and images.is_cuda):
             raise RuntimeError("resize_uint8 runs on HIP devices only (no CPU fallback)")
         if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[-1] > 4:
@@ -238,10 +242,7 @@ class CenterNet(nn.Module):
         if flip_test:
             return _flip.flip_merge(self.forward_uint8(_flip.mirror_append_uint8(images), mean=mean, std=std), images.shape[0])
         m, r = self._norm_constants(mean, std)
-        out = self._engine.forward_u8(images.contiguous(), m, r, sigmoid=True)
-        if "reid" in out:
-            return TrackingOutput(out["heatmap"], out["box_2d"], out["reid"])
-        return DetectionOutput(out["heatmap"], out["box_2d"])
+        return _as_output(self._engine.forward_u8(images.contiguous(), m, r, sigmoid=True))
 
     # ------------------------------------------------------------------ frames of different sizes
     def letterbox_uint8(self, frames, height: int, width: int, fill=(0, 0, 0)):
@@ -271,13 +272,18 @@ class CenterNet(nn.Module):
         `full_range` choose the conversion); "rgb" ignores both.
         flip_test: forward_uint8's; the CANVAS is mirrored, after the letterbox, so the geometry table and unletterbox are untouched."""
         canvas, geom = _letterbox.letterbox_frames(frames, height, width, fill, pixel_format, matrix, full_range)
-        if canvas.shape[-1] != 3:
-            raise ValueError(f"detect_frames expects 3-channel frames, got {canvas.shape[-1]} channels")
-        out = self.forward_uint8(canvas, mean=mean, std=std, flip_test=flip_test)
-        gather = self.gather_tracking2d if len(out) == 3 else self.gather_detection2d
-        dets = gather(out, num_detections=num_detections, nms_kernel=nms_kernel, normalize_bbox=False)
+        dets = self._detect_views(canvas, "detect_frames", mean, std, flip_test, num_detections, nms_kernel)
         _letterbox.unletterbox_(dets["bboxes"], geom, True)
         return dets
+
+    def _detect_views(self, views_u8, who, mean, std, flip_test, num_detections, nms_kernel):
+        """The step detect_frames, detect_tiled (per chunk) and detect_multiscale (per scale) share: uint8 views [V, h, w, 3] -> forward_uint8
+        -> the decode of the model's kind, boxes in view pixels."""
+        if views_u8.shape[-1] != 3:
+            raise ValueError(f"{who} expects 3-channel frames, got {views_u8.shape[-1]} channels")
+        out = self.forward_uint8(views_u8, mean=mean, std=std, flip_test=flip_test)
+        gather = self.gather_tracking2d if len(out) == 3 else self.gather_detection2d
+        return gather(out, num_detections=num_detections, nms_kernel=nms_kernel, normalize_bbox=False)
 
     def crop_detections(self, frames, bboxes, size=(128, 64), scores=None, score_threshold=None, count=None, pad: float = 0.0,
                         keep_aspect: bool = False, fill=(0, 0, 0), pixel_format: str = "rgb", matrix: str = "bt601", full_range: bool = False):
@@ -322,24 +328,15 @@ class CenterNet(nn.Module):
         pixel_format "nv12" / "i420": the frames are YUV 4:2:0 surfaces (tile_yuv420 in place of tile_uint8), as in detect_frames.
         flip_test: forward_uint8's, on the gathered VIEWS (the tile table and merge_tiles are untouched): a chunk is still at most
         `batch` views, and its forward sees twice that many inputs."""
-        if isinstance(batch, bool) or not isinstance(batch, int) or batch < 1:
-            raise ValueError(f"detect_tiled: batch must be a positive int, got {batch!r}")
+        _tiles.positive_int("detect_tiled", "batch", batch)
         views, geom = _tiles.tile_frames(frames, int(tile[0]), int(tile[1]), overlap, full_frame, fill, pixel_format, matrix, full_range)
-        if views.shape[-1] != 3:
-            raise ValueError(f"detect_tiled expects 3-channel frames, got {views.shape[-1]} channels")
-        parts = []
-        for i in range(0, views.shape[0], batch):
-            out = self.forward_uint8(views[i:i + batch], mean=mean, std=std, flip_test=flip_test)
-            gather = self.gather_tracking2d if len(out) == 3 else self.gather_detection2d
-            parts.append(gather(out, num_detections=num_detections, nms_kernel=nms_kernel, normalize_bbox=False))
+        parts = [self._detect_views(views[i:i + batch], "detect_tiled", mean, std, flip_test, num_detections, nms_kernel)
+                 for i in range(0, views.shape[0], batch)]
         dets = {key: (torch.cat([p[key] for p in parts]) if len(parts) > 1 else parts[0][key]) for key in parts[0]}
         m = _tiles.merge_tiles(dets["bboxes"], dets["scores"], dets["labels"], geom, max_detections=max_detections,
                                score_threshold=score_threshold, match_threshold=match_threshold, match_metric=match_metric,
                                class_aware=class_aware, max_candidates=max_candidates)
-        result = {"bboxes": m["bboxes"], "labels": m["labels"], "scores": m["scores"], "count": m["count"]}
-        if "embeddings" in dets:
-            result["embeddings"] = _tiles.pick_embeddings(dets["embeddings"], m["source"], geom.first_view)
-        return result
+        return _merged_result(m, dets, geom.first_view)
 
     # ------------------------------------------------------------------ multi-scale test-time augmentation
     def merge_soft(self, bboxes, scores, labels, geom, **kwargs):
@@ -363,25 +360,23 @@ class CenterNet(nn.Module):
         pixel_format, matrix, full_range, flip_test: as in detect_frames."""
         sizes = _letterbox.multiscale_sizes(height, width, scales)
         _tiles.check_soft_arguments("detect_multiscale", method, sigma, iou_threshold, score_threshold, max_detections, max_candidates)
-        parts, per_scale = [], []
-        for (h_s, w_s) in sizes:
-            canvas, geom = _letterbox.letterbox_frames(frames, h_s, w_s, fill, pixel_format, matrix, full_range)
-            if canvas.shape[-1] != 3:
-                raise ValueError(f"detect_multiscale expects 3-channel frames, got {canvas.shape[-1]} channels")
-            out = self.forward_uint8(canvas, mean=mean, std=std, flip_test=flip_test)
-            gather = self.gather_tracking2d if len(out) == 3 else self.gather_detection2d
-            parts.append(gather(out, num_detections=num_detections, nms_kernel=nms_kernel, normalize_bbox=False))
-            per_scale.append(geom.frames)
-        # [S][N, k, ...] -> [N * S, k, ...]: the views of a frame are its scales, in the order given
-        dets = {key: torch.stack([p[key] for p in parts], dim=1).flatten(0, 1) for key in parts[0]}
-        views = _tiles.scale_geometry(per_scale, dets["bboxes"].device)
+        dets, views = self._detect_scales(frames, sizes, fill, mean, std, num_detections, nms_kernel, pixel_format, matrix, full_range, flip_test)
         m = _tiles.merge_soft(dets["bboxes"], dets["scores"], dets["labels"], views, method=method, sigma=sigma, iou_threshold=iou_threshold,
                               score_threshold=score_threshold, max_detections=max_detections, class_aware=class_aware,
                               max_candidates=max_candidates)
-        result = {"bboxes": m["bboxes"], "labels": m["labels"], "scores": m["scores"], "count": m["count"]}
-        if "embeddings" in dets:
-            result["embeddings"] = _tiles.pick_embeddings(dets["embeddings"], m["source"], views.first_view)
-        return result
+        return _merged_result(m, dets, views.first_view)
+
+    def _detect_scales(self, frames, sizes, fill=(0, 0, 0), mean=IMAGENET_MEAN, std=IMAGENET_STD, num_detections: int = 100, nms_kernel: int = 3,
+                       pixel_format: str = "rgb", matrix: str = "bt601", full_range: bool = False, flip_test: bool = False):
+        """What detect_multiscale merges (tools/multiscale_bench.py times the merge on it): per canvas size the frames letterboxed and
+        _detect_views -> (the detections [N * S, k, ...], the views of a frame being its scales in the order given; their scale_geometry)."""
+        parts, per_scale = [], []
+        for (h_s, w_s) in sizes:
+            canvas, geom = _letterbox.letterbox_frames(frames, h_s, w_s, fill, pixel_format, matrix, full_range)
+            parts.append(self._detect_views(canvas, "detect_multiscale", mean, std, flip_test, num_detections, nms_kernel))
+            per_scale.append(geom.frames)
+        dets = {key: torch.stack([p[key] for p in parts], dim=1).flatten(0, 1) for key in parts[0]}           # [S][N, k, ...] -> [N * S, k, ...]
+        return dets, _tiles.scale_geometry(per_scale, dets["bboxes"].device)
 
     # ------------------------------------------------------------------ decode (Gen-A names)
     def gather_detection2d(self, heatmap, box_2d=None, num_detections=100, nms_kernel=3, normalize_bbox=False):

@@ -7,6 +7,7 @@ view is the plain letterbox record.  The merge is cnl_merge_tiles_f32 (csrc/tile
 """
 from typing import List, Tuple
 
+import numpy as np
 import torch
 
 from . import _frames, _gather, _lib
@@ -79,7 +80,6 @@ class TileGeometry:
         """Advanced / testing constructor: a geometry for merge_tiles ALONE, from merge records [(frame_w, frame_h, x0, y0, pad_left,
         pad_top, sx, sy)] and the list frame_first_view (N + 1 entries), for detections that did not come from tile_uint8.  There are no
         pixels behind it: `table` is None, `sizes` is empty and the `views` entries carry th = tw = 0.  One blocking upload."""
-        import numpy as np
         V = len(records)
         ffv = [int(v) for v in frame_first_view]
         if len(ffv) < 1 or ffv[0] != 0 or ffv[-1] != V or any(b < a for a, b in zip(ffv, ffv[1:])):
@@ -91,16 +91,20 @@ class TileGeometry:
         device = torch.device(device)
         if device.type != "cuda":
             raise RuntimeError("the tile merge runs on HIP devices only (no CPU fallback)")
-        with torch.cuda.device(device):
-            merge_table = torch.from_numpy(rec).to(device)
-            first_view = torch.tensor(ffv, dtype=torch.int32).to(device)
         views = [(n, int(r[3]), int(r[2]), 0, 0) for n in range(len(ffv) - 1) for r in records[ffv[n]:ffv[n + 1]]]
-        return cls(None, merge_table, first_view, views, ffv, [], 0, 0)
+        return cls._merge_only(rec, ffv, views, [], device, lambda parts, dev: [torch.from_numpy(p).to(dev) for p in parts])
+
+    @classmethod
+    def _merge_only(cls, rec, ffv, views, sizes, device, upload):
+        """A geometry without pixels (`table` is None, tile_h = tile_w = 0) from the [V, 8] int32 merge records and the host lists; `upload`
+        takes the two numpy tables to the device: blocking copies for from_records, _gather.upload_parts for scale_geometry."""
+        with torch.cuda.device(device):
+            merge_table, first_view = upload([rec, np.array(ffv, dtype=np.int32)], device)
+        return cls(None, merge_table, first_view, views, ffv, sizes, 0, 0)
 
 
 def _full_frame_record(h: int, w: int, new_h: int, new_w: int, pad_top: int, pad_left: int):
     """The merge record of a whole h x w frame letterboxed to new_h x new_w behind the pads: 8 int32 words, the last two the float bits."""
-    import numpy as np
     sx, sy = np.float32(new_w) / np.float32(w), np.float32(new_h) / np.float32(h)         # as cnl_unletterbox_boxes_f32 forms them
     return (w, h, 0, 0, pad_left, pad_top, sx.view(np.int32), sy.view(np.int32))
 
@@ -109,7 +113,6 @@ def _view_records(sizes, tile_h: int, tile_w: int, overlap: float, full_frame: b
     """The views of frames of the given (h, w) sizes -> (windows [(frame, y0, x0, h, w, new_h, new_w, pad_top, pad_left)]: what the
     gather kernel needs per view, the merge records, TileGeometry.views, frame_first_view).  A tile is a 1:1 window at the canvas'
     top left; the full-frame view is the whole frame letterboxed."""
-    import numpy as np
     windows, mg, views, ffv = [], [], [], [0]
     one = np.float32(1.0).view(np.int32)
     for n, (h, w) in enumerate(sizes):
@@ -183,6 +186,27 @@ def _launch_merge(entry: str, bboxes, scores, labels, geom, max_detections: int,
     return {"bboxes": out_boxes, "scores": out_scores, "labels": out_labels, "source": out_source, "count": out_count}
 
 
+def positive_int(who: str, name: str, v, most=None) -> None:
+    """v must be an int (not a bool) of at least 1, and of at most `most` where there is a limit; otherwise ValueError."""
+    if isinstance(v, bool) or not isinstance(v, int) or v < 1 or (most is not None and v > most):
+        raise ValueError(f"{who}: {name} must be " + ("a positive int" if most is None else f"an int in 1..{most}") + f", got {v!r}")
+
+
+def _check_detections(who: str, bboxes, scores, labels) -> Tuple[int, int]:
+    """What the detections are, not where they live (that half is _gather.require_hip): float32 [V, k, 4] boxes, float32 [V, k] scores
+    and int64 [V, k] labels, all tensors -> (V, k); otherwise ValueError."""
+    for name, t in (("bboxes", bboxes), ("scores", scores), ("labels", labels)):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{who}: {name} must be a tensor, got {type(t).__name__}")
+    if bboxes.dtype != torch.float32 or bboxes.dim() != 3 or bboxes.shape[-1] != 4 or scores.dtype != torch.float32 or labels.dtype != torch.int64:
+        raise ValueError(f"{who}: expected float32 [V,k,4] boxes, float32 [V,k] scores and int64 [V,k] labels, got {bboxes.dtype} "
+                         f"{tuple(bboxes.shape)}, {scores.dtype} {tuple(scores.shape)}, {labels.dtype} {tuple(labels.shape)}")
+    V, k = int(bboxes.shape[0]), int(bboxes.shape[1])
+    if tuple(scores.shape) != (V, k) or tuple(labels.shape) != (V, k):
+        raise ValueError(f"{who}: scores {tuple(scores.shape)} and labels {tuple(labels.shape)} must both be [{V}, {k}]")
+    return V, k
+
+
 def merge_tiles(bboxes: torch.Tensor, scores: torch.Tensor, labels: torch.Tensor, geom: TileGeometry, max_detections: int = 300,
                 score_threshold: float = 0.1, match_threshold: float = 0.5, match_metric: str = "iou", class_aware: bool = True,
                 max_candidates: int = 4096):
@@ -190,22 +214,14 @@ def merge_tiles(bboxes: torch.Tensor, scores: torch.Tensor, labels: torch.Tensor
     normalize_bbox=False) -> per frame, in the frame's own pixels and with the duplicates removed:
     {"bboxes" [N, max_detections, 4], "scores", "labels" (int64), "source" (int32: the candidate number v * k + r relative to the frame's
     first view, -1 past the count), "count" [N] int32}.  Three launches for the whole batch, no device sync."""
-    for name, t in (("bboxes", bboxes), ("scores", scores), ("labels", labels)):
-        if not (isinstance(t, torch.Tensor) and t.is_cuda):
-            raise RuntimeError(f"merge_tiles: {name} must live on a HIP device (no CPU fallback)")
+    _gather.require_hip((bboxes, scores, labels), "merge_tiles")
     if match_metric not in METRICS:
-        raise ValueError(f"match_metric must be one of {sorted(METRICS)}, got {match_metric!r}")
-    if bboxes.dtype != torch.float32 or bboxes.dim() != 3 or bboxes.shape[-1] != 4 or scores.dtype != torch.float32 or labels.dtype != torch.int64:
-        raise ValueError(f"expected float32 [V,k,4] boxes, float32 [V,k] scores and int64 [V,k] labels, got {bboxes.dtype} {tuple(bboxes.shape)}, "
-                         f"{scores.dtype} {tuple(scores.shape)}, {labels.dtype} {tuple(labels.shape)}")
-    V, k = int(bboxes.shape[0]), int(bboxes.shape[1])
-    if tuple(scores.shape) != (V, k) or tuple(labels.shape) != (V, k):
-        raise ValueError(f"scores {tuple(scores.shape)} and labels {tuple(labels.shape)} must both be [{V}, {k}]")
+        raise ValueError(f"merge_tiles: match_metric must be one of {sorted(METRICS)}, got {match_metric!r}")
+    V, _ = _check_detections("merge_tiles", bboxes, scores, labels)
     if V != len(geom) or bboxes.device != geom.merge_table.device:
-        raise ValueError(f"detections of {V} views on {bboxes.device} against a geometry of {len(geom)} views on {geom.merge_table.device}")
-    for name, v in (("max_detections", max_detections), ("max_candidates", max_candidates)):
-        if isinstance(v, bool) or not isinstance(v, int) or v < 1:
-            raise ValueError(f"merge_tiles: {name} must be a positive int, got {v!r}")
+        raise ValueError(f"merge_tiles: detections of {V} views on {bboxes.device} against a geometry of {len(geom)} views on {geom.merge_table.device}")
+    positive_int("merge_tiles", "max_detections", max_detections)
+    positive_int("merge_tiles", "max_candidates", max_candidates)
     return _launch_merge("cnl_merge_tiles", bboxes, scores, labels, geom, max_detections, max_candidates,
                          (float(score_threshold), float(match_threshold), METRICS[match_metric], int(bool(class_aware))))
 
@@ -229,10 +245,8 @@ def check_soft_arguments(who: str, method, sigma, iou_threshold, score_threshold
         raise ValueError(f"{who}: sigma must be positive and finite, got {sigma!r}")
     _number("iou_threshold", iou_threshold, who)
     _number("score_threshold", score_threshold, who)
-    if isinstance(max_detections, bool) or not isinstance(max_detections, int) or max_detections < 1:
-        raise ValueError(f"{who}: max_detections must be a positive int, got {max_detections!r}")
-    if isinstance(max_candidates, bool) or not isinstance(max_candidates, int) or not 1 <= max_candidates <= SOFT_MAX_CANDIDATES:
-        raise ValueError(f"{who}: max_candidates must be an int in 1..{SOFT_MAX_CANDIDATES}, got {max_candidates!r}")
+    positive_int(who, "max_detections", max_detections)
+    positive_int(who, "max_candidates", max_candidates, SOFT_MAX_CANDIDATES)
 
 
 def merge_soft(bboxes: torch.Tensor, scores: torch.Tensor, labels: torch.Tensor, geom: TileGeometry, method: str = "gaussian",
@@ -246,19 +260,10 @@ def merge_soft(bboxes: torch.Tensor, scores: torch.Tensor, labels: torch.Tensor,
     of detect_multiscale.  max_candidates is at most 4096.  Two launches for the whole batch, no device sync.
     Checks, all before any launch: the values and the tensors' dtypes and shapes (ValueError), then where the tensors live."""
     check_soft_arguments("merge_soft", method, sigma, iou_threshold, score_threshold, max_detections, max_candidates)
-    for name, t in (("bboxes", bboxes), ("scores", scores), ("labels", labels)):
-        if not isinstance(t, torch.Tensor):
-            raise ValueError(f"merge_soft: {name} must be a tensor, got {type(t).__name__}")
-    if bboxes.dtype != torch.float32 or bboxes.dim() != 3 or bboxes.shape[-1] != 4 or scores.dtype != torch.float32 or labels.dtype != torch.int64:
-        raise ValueError(f"expected float32 [V,k,4] boxes, float32 [V,k] scores and int64 [V,k] labels, got {bboxes.dtype} {tuple(bboxes.shape)}, "
-                         f"{scores.dtype} {tuple(scores.shape)}, {labels.dtype} {tuple(labels.shape)}")
-    V, k = int(bboxes.shape[0]), int(bboxes.shape[1])
-    if tuple(scores.shape) != (V, k) or tuple(labels.shape) != (V, k):
-        raise ValueError(f"scores {tuple(scores.shape)} and labels {tuple(labels.shape)} must both be [{V}, {k}]")
-    if not (bboxes.is_cuda and scores.is_cuda and labels.is_cuda):
-        raise RuntimeError("merge_soft: bboxes, scores and labels must live on a HIP device (no CPU fallback)")
+    V, _ = _check_detections("merge_soft", bboxes, scores, labels)
+    _gather.require_hip((bboxes, scores, labels), "merge_soft")
     if not isinstance(geom, TileGeometry) or V != len(geom) or bboxes.device != geom.merge_table.device:
-        raise ValueError(f"detections of {V} views on {bboxes.device} against {geom!r}")
+        raise ValueError(f"merge_soft: detections of {V} views on {bboxes.device} against {geom!r}")
     return _launch_merge("cnl_merge_soft", bboxes, scores, labels, geom, max_detections, max_candidates,
                          (float(score_threshold), SOFT_METHODS[method], float(sigma), float(iou_threshold), int(bool(class_aware))))
 
@@ -267,20 +272,11 @@ def scale_geometry(per_scale, dev) -> TileGeometry:
     """The merge geometry of a multi-scale pass: per_scale[s] is the host list LetterboxGeometry.frames of scale s, [(h, w, new_h,
     new_w, pad_top, pad_left)] for the same N frames -> one full-frame view per (frame, scale), frame-major (view n * S + s), each
     record what _view_records writes for its full-frame view.  Host arithmetic on shapes and one pinned upload: no device sync."""
-    import numpy as np
     S, N = len(per_scale), len(per_scale[0])
-    rec = np.zeros((N * S, 8), dtype=np.int32)
-    views, sizes = [], []
-    for n in range(N):
-        for s in range(S):
-            h, w = per_scale[s][n][:2]
-            rec[n * S + s] = _full_frame_record(*per_scale[s][n])
-            views.append((n, 0, 0, h, w))
-        sizes.append(per_scale[0][n][:2])
-    ffv = [n * S for n in range(N + 1)]
-    with torch.cuda.device(dev):
-        merge_table, first_view = _gather.upload_parts([rec, np.array(ffv, dtype=np.int32)], dev)
-    return TileGeometry(None, merge_table, first_view, views, ffv, sizes, 0, 0)
+    frames = [per_scale[s][n] for n in range(N) for s in range(S)]
+    rec = np.array([_full_frame_record(*f) for f in frames], dtype=np.int32).reshape(N * S, 8)
+    views = [(i // S, 0, 0, f[0], f[1]) for i, f in enumerate(frames)]
+    return TileGeometry._merge_only(rec, [n * S for n in range(N + 1)], views, [per_scale[0][n][:2] for n in range(N)], dev, _gather.upload_parts)
 
 
 def pick_embeddings(embeddings: torch.Tensor, source: torch.Tensor, first_view: torch.Tensor) -> torch.Tensor:

@@ -395,19 +395,58 @@ __global__ __launch_bounds__(SOFT_THREADS) void soft_kernel(const FrameHead* __r
     if (tid == 0) out_count[n] = r;
 }
 
-}  // namespace cnl_tile_merge
-
-static int merge_check_sizes(const char* who, int32_t N, int32_t V, int32_t k, int32_t max_candidates) {
+// What the two merges share on the host.  `limit` is the entry point's own bound on max_candidates: where it is tighter than the common
+// one (the soft merge's) it is reported first; the workspace queries have no K_out.
+static int merge_check_sizes(const char* who, int32_t N, int32_t V, int32_t k, int32_t max_candidates, int limit = MAX_CANDIDATES, int32_t K_out = 1) {
+    const bool within = max_candidates >= 1 && max_candidates <= limit;
+    if (limit < MAX_CANDIDATES) CNL_REQUIRE(within, CNL_E_BAD_ARG, "%s: max_candidates = %d outside 1..%d", who, max_candidates, limit);
     CNL_REQUIRE(N >= 0 && N <= 65535, CNL_E_BAD_ARG, "%s: N = %d outside 0..65535", who, N);
     CNL_REQUIRE(V >= 0 && k >= 1, CNL_E_BAD_ARG, "%s: V = %d must be >= 0 and k = %d >= 1", who, V, k);
     CNL_REQUIRE((long)V * k <= (1L << 30), CNL_E_BAD_ARG, "%s: V * k = %ld candidates exceed 2^30", who, (long)V * k);
-    CNL_REQUIRE(max_candidates >= 1 && max_candidates <= cnl_tile_merge::MAX_CANDIDATES, CNL_E_BAD_ARG, "%s: max_candidates = %d outside 1..%d",
-                who, max_candidates, cnl_tile_merge::MAX_CANDIDATES);
+    CNL_REQUIRE(within, CNL_E_BAD_ARG, "%s: max_candidates = %d outside 1..%d", who, max_candidates, limit);
+    CNL_REQUIRE(K_out >= 1, CNL_E_BAD_ARG, "%s: K_out = %d must be at least 1", who, K_out);
     return CNL_OK;
 }
 
+struct MergeCall {                         // the workspace carved up (Layout) and the stream: what an entry point's own kernels are launched with
+    FrameHead* head;
+    float4* s_box;
+    int* s_label;
+    int* s_source;
+    float* s_score;
+    unsigned long long* matrix;            // (an empty tail without with_matrix)
+    hipStream_t stream;
+};
+
+// after an entry point's own checks, for N >= 1: the pointer and workspace checks, the carve-up, and the sort stage both merges start with
+static int merge_begin(const char* who, bool with_matrix, const float* boxes, const float* scores, const int64_t* labels, const void* views,
+                       const int32_t* frame_first_view, int32_t N, int32_t V, int32_t k, int32_t max_candidates, float score_threshold,
+                       const float* out_boxes, const float* out_scores, const int64_t* out_labels, const int32_t* out_source, const int32_t* out_count,
+                       void* ws, size_t ws_bytes, void* stream, MergeCall& c) {
+    CNL_REQUIRE(frame_first_view && out_boxes && out_scores && out_labels && out_source && out_count, CNL_E_BAD_ARG, "%s: null pointer", who);
+    CNL_REQUIRE(V == 0 || (boxes && scores && labels && views), CNL_E_BAD_ARG, "%s: null pointer", who);
+    CNL_REQUIRE(((uintptr_t)boxes & 15) == 0 && ((uintptr_t)out_boxes & 15) == 0 && ((uintptr_t)views & 3) == 0 && ((uintptr_t)labels & 7) == 0 &&
+                    ((uintptr_t)out_labels & 7) == 0, CNL_E_BAD_ARG,
+                "%s: boxes and out_boxes must be 16-byte, labels and out_labels 8-byte, views 4-byte aligned", who);
+    const Layout L(N, V, k, max_candidates, with_matrix);
+    CNL_REQUIRE(ws && ((uintptr_t)ws & 255) == 0, CNL_E_WORKSPACE, "%s: the workspace must be 256-byte aligned and not null", who);
+    CNL_REQUIRE(ws_bytes >= L.total, CNL_E_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who, ws_bytes, L.total);
+    char* const w = static_cast<char*>(ws);
+    c = MergeCall{reinterpret_cast<FrameHead*>(w + L.head), reinterpret_cast<float4*>(w + L.box), reinterpret_cast<int*>(w + L.label),
+                  reinterpret_cast<int*>(w + L.source), reinterpret_cast<float*>(w + L.score), reinterpret_cast<unsigned long long*>(w + L.matrix),
+                  (hipStream_t)stream};
+    // the sort stage's "does the matrix fit" test: the words the workspace has for it, or no limit where there is no bit matrix
+    const unsigned long long matrix_words = with_matrix ? (unsigned long long)((L.total - L.matrix) / 8) : ~0ull;
+    hipLaunchKernelGGL(sort_kernel, dim3((unsigned)N), dim3(SORT_THREADS), 0, c.stream, reinterpret_cast<const float4*>(boxes), scores,
+                       reinterpret_cast<const long long*>(labels), static_cast<const View*>(views), frame_first_view, V, k, max_candidates,
+                       score_threshold, matrix_words, c.head, reinterpret_cast<unsigned long long*>(w + L.keys), c.s_box, c.s_label, c.s_source, c.s_score);
+    return cnl::check_launch("tile_merge sort_kernel");
+}
+
+}  // namespace cnl_tile_merge
+
 extern "C" size_t cnl_merge_tiles_workspace_bytes(int32_t N, int32_t V, int32_t k, int32_t max_candidates) {
-    if (merge_check_sizes("cnl_merge_tiles_workspace_bytes", N, V, k, max_candidates) != CNL_OK) return 0;
+    if (cnl_tile_merge::merge_check_sizes("cnl_merge_tiles_workspace_bytes", N, V, k, max_candidates) != CNL_OK) return 0;
     return cnl_tile_merge::Layout(N, V, k, max_candidates).total;
 }
 
@@ -417,54 +456,30 @@ extern "C" int cnl_merge_tiles_f32(const float* boxes, const float* scores, cons
                                    float* out_scores, int64_t* out_labels, int32_t* out_source, int32_t* out_count, void* ws, size_t ws_bytes,
                                    void* stream) {
     using namespace cnl_tile_merge;
-    if (int rc = merge_check_sizes("cnl_merge_tiles_f32", N, V, k, max_candidates)) return rc;
-    CNL_REQUIRE(K_out >= 1, CNL_E_BAD_ARG, "cnl_merge_tiles_f32: K_out = %d must be at least 1", K_out);
+    if (int rc = merge_check_sizes("cnl_merge_tiles_f32", N, V, k, max_candidates, MAX_CANDIDATES, K_out)) return rc;
     CNL_REQUIRE(metric == 0 || metric == 1, CNL_E_BAD_ARG, "cnl_merge_tiles_f32: metric = %d is neither 0 (IoU) nor 1 (IoS)", metric);
     CNL_REQUIRE(score_threshold == score_threshold && match_threshold == match_threshold, CNL_E_BAD_ARG, "cnl_merge_tiles_f32: a threshold is NaN");
     if (N == 0) return CNL_OK;
-    CNL_REQUIRE(frame_first_view && out_boxes && out_scores && out_labels && out_source && out_count, CNL_E_BAD_ARG,
-                "cnl_merge_tiles_f32: null pointer");
-    CNL_REQUIRE(V == 0 || (boxes && scores && labels && views), CNL_E_BAD_ARG, "cnl_merge_tiles_f32: null pointer");
-    CNL_REQUIRE(((uintptr_t)boxes & 15) == 0 && ((uintptr_t)out_boxes & 15) == 0 && ((uintptr_t)views & 3) == 0 && ((uintptr_t)labels & 7) == 0 &&
-                    ((uintptr_t)out_labels & 7) == 0, CNL_E_BAD_ARG,
-                "cnl_merge_tiles_f32: boxes and out_boxes must be 16-byte, labels and out_labels 8-byte, views 4-byte aligned");
-    const Layout L(N, V, k, max_candidates);
-    CNL_REQUIRE(ws && ((uintptr_t)ws & 255) == 0, CNL_E_WORKSPACE, "cnl_merge_tiles_f32: the workspace must be 256-byte aligned and not null");
-    CNL_REQUIRE(ws_bytes >= L.total, CNL_E_WORKSPACE, "cnl_merge_tiles_f32: workspace of %zu bytes, %zu needed", ws_bytes, L.total);
-    char* const w = static_cast<char*>(ws);
-    FrameHead* const head = reinterpret_cast<FrameHead*>(w + L.head);
-    float4* const s_box = reinterpret_cast<float4*>(w + L.box);
-    int* const s_label = reinterpret_cast<int*>(w + L.label);
-    int* const s_source = reinterpret_cast<int*>(w + L.source);
-    float* const s_score = reinterpret_cast<float*>(w + L.score);
-    unsigned long long* const matrix = reinterpret_cast<unsigned long long*>(w + L.matrix);
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(sort_kernel, dim3((unsigned)N), dim3(SORT_THREADS), 0, s, reinterpret_cast<const float4*>(boxes), scores,
-                       reinterpret_cast<const long long*>(labels), static_cast<const View*>(views), frame_first_view, V, k, max_candidates,
-                       score_threshold, (unsigned long long)((L.total - L.matrix) / 8), head, reinterpret_cast<unsigned long long*>(w + L.keys), s_box, s_label, s_source, s_score);
-    if (int rc = cnl::check_launch("tile_merge sort_kernel")) return rc;
+    MergeCall c;
+    if (int rc = merge_begin("cnl_merge_tiles_f32", true, boxes, scores, labels, views, frame_first_view, N, V, k, max_candidates, score_threshold,
+                             out_boxes, out_scores, out_labels, out_source, out_count, ws, ws_bytes, stream, c)) return rc;
     // no frame has more candidates than all of them: the grid covers min(V * k, max_candidates) rows, workgroups past a frame's own M leave at once
     const long rows_max = (long)V * k < max_candidates ? (long)V * k : max_candidates;
     if (rows_max > 0) {
         const unsigned row_blocks = (unsigned)((rows_max + 63) / 64);
-        hipLaunchKernelGGL(match_kernel, dim3((row_blocks + MATCH_WORDS - 1) / MATCH_WORDS, row_blocks, (unsigned)N), dim3(64 * MATCH_WORDS), 0, s,
-                           head, frame_first_view, V, k, s_box, s_label, match_threshold, metric, class_aware, matrix);
+        hipLaunchKernelGGL(match_kernel, dim3((row_blocks + MATCH_WORDS - 1) / MATCH_WORDS, row_blocks, (unsigned)N), dim3(64 * MATCH_WORDS), 0, c.stream,
+                           c.head, frame_first_view, V, k, c.s_box, c.s_label, match_threshold, metric, class_aware, c.matrix);
         if (int rc = cnl::check_launch("tile_merge match_kernel")) return rc;
     }
-    hipLaunchKernelGGL(walk_kernel, dim3((unsigned)N), dim3(64), 0, s, head, frame_first_view, V, k, K_out, s_box, s_label, s_source, s_score, matrix,
-                       reinterpret_cast<float4*>(out_boxes), out_scores, reinterpret_cast<long long*>(out_labels), out_source, out_count);
+    hipLaunchKernelGGL(walk_kernel, dim3((unsigned)N), dim3(64), 0, c.stream, c.head, frame_first_view, V, k, K_out, c.s_box, c.s_label, c.s_source,
+                       c.s_score, c.matrix, reinterpret_cast<float4*>(out_boxes), out_scores, reinterpret_cast<long long*>(out_labels), out_source, out_count);
     return cnl::check_launch("tile_merge walk_kernel");
 }
 
-static int merge_soft_check_sizes(const char* who, int32_t N, int32_t V, int32_t k, int32_t max_candidates) {
-    CNL_REQUIRE(max_candidates >= 1 && max_candidates <= cnl_tile_merge::SOFT_MAX_CANDIDATES, CNL_E_BAD_ARG, "%s: max_candidates = %d outside 1..%d", who,
-                max_candidates, cnl_tile_merge::SOFT_MAX_CANDIDATES);
-    return merge_check_sizes(who, N, V, k, max_candidates);
-}
-
 extern "C" size_t cnl_merge_soft_workspace_bytes(int32_t N, int32_t V, int32_t k, int32_t max_candidates) {
-    if (merge_soft_check_sizes("cnl_merge_soft_workspace_bytes", N, V, k, max_candidates) != CNL_OK) return 0;
-    return cnl_tile_merge::Layout(N, V, k, max_candidates, false).total;
+    using namespace cnl_tile_merge;
+    if (merge_check_sizes("cnl_merge_soft_workspace_bytes", N, V, k, max_candidates, SOFT_MAX_CANDIDATES) != CNL_OK) return 0;
+    return Layout(N, V, k, max_candidates, false).total;
 }
 
 extern "C" int cnl_merge_soft_f32(const float* boxes, const float* scores, const int64_t* labels, const void* views,
@@ -473,36 +488,17 @@ extern "C" int cnl_merge_soft_f32(const float* boxes, const float* scores, const
                                   float* out_scores, int64_t* out_labels, int32_t* out_source, int32_t* out_count, void* ws, size_t ws_bytes,
                                   void* stream) {
     using namespace cnl_tile_merge;
-    if (int rc = merge_soft_check_sizes("cnl_merge_soft_f32", N, V, k, max_candidates)) return rc;
-    CNL_REQUIRE(K_out >= 1, CNL_E_BAD_ARG, "cnl_merge_soft_f32: K_out = %d must be at least 1", K_out);
+    if (int rc = merge_check_sizes("cnl_merge_soft_f32", N, V, k, max_candidates, SOFT_MAX_CANDIDATES, K_out)) return rc;
     CNL_REQUIRE(method >= 0 && method <= 2, CNL_E_BAD_ARG, "cnl_merge_soft_f32: method = %d is none of 0 (hard), 1 (linear), 2 (gaussian)", method);
     CNL_REQUIRE(score_threshold == score_threshold && iou_threshold == iou_threshold, CNL_E_BAD_ARG, "cnl_merge_soft_f32: a threshold is NaN");
     CNL_REQUIRE(sigma > 0.f && sigma <= 3.402823466e38f, CNL_E_BAD_ARG, "cnl_merge_soft_f32: sigma = %g must be positive and finite", (double)sigma);
     if (N == 0) return CNL_OK;
-    CNL_REQUIRE(frame_first_view && out_boxes && out_scores && out_labels && out_source && out_count, CNL_E_BAD_ARG,
-                "cnl_merge_soft_f32: null pointer");
-    CNL_REQUIRE(V == 0 || (boxes && scores && labels && views), CNL_E_BAD_ARG, "cnl_merge_soft_f32: null pointer");
-    CNL_REQUIRE(((uintptr_t)boxes & 15) == 0 && ((uintptr_t)out_boxes & 15) == 0 && ((uintptr_t)views & 3) == 0 && ((uintptr_t)labels & 7) == 0 &&
-                    ((uintptr_t)out_labels & 7) == 0, CNL_E_BAD_ARG,
-                "cnl_merge_soft_f32: boxes and out_boxes must be 16-byte, labels and out_labels 8-byte, views 4-byte aligned");
-    const Layout L(N, V, k, max_candidates, false);
-    CNL_REQUIRE(ws && ((uintptr_t)ws & 255) == 0, CNL_E_WORKSPACE, "cnl_merge_soft_f32: the workspace must be 256-byte aligned and not null");
-    CNL_REQUIRE(ws_bytes >= L.total, CNL_E_WORKSPACE, "cnl_merge_soft_f32: workspace of %zu bytes, %zu needed", ws_bytes, L.total);
-    char* const w = static_cast<char*>(ws);
-    FrameHead* const head = reinterpret_cast<FrameHead*>(w + L.head);
-    float4* const s_box = reinterpret_cast<float4*>(w + L.box);
-    int* const s_label = reinterpret_cast<int*>(w + L.label);
-    int* const s_source = reinterpret_cast<int*>(w + L.source);
-    float* const s_score = reinterpret_cast<float*>(w + L.score);
-    hipStream_t s = (hipStream_t)stream;
-    // the sort stage as the hard merge launches it; there is no bit matrix, so its "does the matrix fit" test is given no limit
-    hipLaunchKernelGGL(sort_kernel, dim3((unsigned)N), dim3(SORT_THREADS), 0, s, reinterpret_cast<const float4*>(boxes), scores,
-                       reinterpret_cast<const long long*>(labels), static_cast<const View*>(views), frame_first_view, V, k, max_candidates,
-                       score_threshold, ~0ull, head, reinterpret_cast<unsigned long long*>(w + L.keys), s_box, s_label, s_source, s_score);
-    if (int rc = cnl::check_launch("tile_merge sort_kernel")) return rc;
+    MergeCall c;
+    if (int rc = merge_begin("cnl_merge_soft_f32", false, boxes, scores, labels, views, frame_first_view, N, V, k, max_candidates, score_threshold,
+                             out_boxes, out_scores, out_labels, out_source, out_count, ws, ws_bytes, stream, c)) return rc;
     auto* const kernel = method == 0 ? soft_kernel<0> : method == 1 ? soft_kernel<1> : soft_kernel<2>;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)N), dim3(SOFT_THREADS), 0, s, head, frame_first_view, V, k, K_out, s_box, s_label, s_source, s_score,
-                       score_threshold, sigma, iou_threshold, class_aware, reinterpret_cast<float4*>(out_boxes), out_scores,
+    hipLaunchKernelGGL(kernel, dim3((unsigned)N), dim3(SOFT_THREADS), 0, c.stream, c.head, frame_first_view, V, k, K_out, c.s_box, c.s_label, c.s_source,
+                       c.s_score, score_threshold, sigma, iou_threshold, class_aware, reinterpret_cast<float4*>(out_boxes), out_scores,
                        reinterpret_cast<long long*>(out_labels), out_source, out_count);
     return cnl::check_launch("tile_merge soft_kernel");
 }

@@ -143,6 +143,38 @@ def test_python_surface_rejects_cpu_and_malformed_input():
         model.detect_tiled([frame], batch=0)
 
 
+def _malformed_detections():
+    """(what is wrong, bboxes, scores, labels): one argument of a well-formed CPU triple replaced per row; the last row is the triple itself."""
+    good = (torch.zeros((2, 4, 4)), torch.zeros((2, 4)), torch.zeros((2, 4), dtype=torch.int64))
+
+    def swap(i, value):
+        return tuple(value if j == i else t for j, t in enumerate(good))
+    return [("numpy array instead of tensor", *swap(0, np.zeros((2, 4, 4), dtype=F))),
+            ("None", *swap(1, None)),
+            ("float64 boxes", *swap(0, good[0].double())),
+            ("fp16 scores", *swap(1, good[1].half())),
+            ("int32 labels", *swap(2, good[2].int())),
+            ("rank-2 boxes", *swap(0, torch.zeros((2, 4)))),
+            ("last dimension of 5", *swap(0, torch.zeros((2, 4, 5)))),
+            ("scores of another shape", *swap(1, torch.zeros((2, 3)))),
+            ("labels of another shape", *swap(2, torch.zeros((4, 2), dtype=torch.int64))),
+            ("a well-formed CPU triple", *good)]
+
+
+def test_merges_keep_their_exception_types_for_malformed_detections():
+    """merge_tiles looks at where the tensors live first, so without a device every row is a RuntimeError; merge_soft looks at what they
+    are first (ValueError) and only then at where they live, so only the well-formed CPU triple gets that far."""
+    _lib.load()
+    model = cl.build_centernet(os.path.join(ROOT, "centernet-lightning_amd", "configs", "resnet34_simple.yaml"))
+    for what, bboxes, scores, labels in _malformed_detections():
+        soft_raises = RuntimeError if what == "a well-formed CPU triple" else ValueError
+        for merge, raises in ((cl.merge_tiles, RuntimeError), (model.merge_tiles, RuntimeError), (cl.merge_soft, soft_raises),
+                              (model.merge_soft, soft_raises)):
+            with pytest.raises((RuntimeError, ValueError)) as caught:
+                merge(bboxes, scores, labels, None)
+            assert type(caught.value) is raises, f"{merge.__qualname__} on {what}: {caught.value!r}"
+
+
 # ----------------------------------------------------------------------------- the restated rule on hand-made cases
 TILE = (1000, 1000, 0, 0, 0, 0, F(1), F(1))          # one view that is the frame: boxes map to themselves
 

@@ -26,7 +26,6 @@ for p in (os.path.join(ROOT, "centernet-lightning_amd"), os.path.join(ROOT, "ora
 import bench  # noqa: E402
 import soft_nms_ref as ref  # noqa: E402
 import centernet_lightning_amd as cl  # noqa: E402
-from centernet_lightning_amd import letterbox as _letterbox, tiles as _tiles  # noqa: E402
 
 
 def p50_ms(fn, reps, warmup=3):
@@ -98,13 +97,7 @@ def main():
     t_multi = p50_ms(lambda: model.detect_multiscale(frames), args.reps)
     t_frames = [p50_ms(lambda: model.detect_frames(frames, h, w), args.reps) for (h, w) in sizes]
     # merge_soft on the detections detect_multiscale itself merges
-    parts, per_scale = [], []
-    for (h, w) in sizes:
-        canvas, lg = _letterbox.letterbox_frames(frames, h, w)
-        parts.append(model.gather_detection2d(model.forward_uint8(canvas), num_detections=100, nms_kernel=3, normalize_bbox=False))
-        per_scale.append(lg.frames)
-    dets = {key: torch.stack([p[key] for p in parts], dim=1).flatten(0, 1) for key in parts[0]}
-    views = _tiles.scale_geometry(per_scale, dets["bboxes"].device)
+    dets, views = model._detect_scales(frames, sizes)
     own = cl.merge_soft(dets["bboxes"], dets["scores"], dets["labels"], views)
     assert torch.equal(own["scores"], multi["scores"]) and torch.equal(own["bboxes"], multi["bboxes"])
     t_own = p50_ms(lambda: cl.merge_soft(dets["bboxes"], dets["scores"], dets["labels"], views), args.reps)

@@ -108,7 +108,7 @@ def main():
     V = views.shape[0]
 
     def forward_and_decode():
-        parts = [model.gather_detection2d(model.forward_uint8(views[i:i + 32]), num_detections=100) for i in range(0, V, 32)]
+        parts = [model._detect_views(views[i:i + 32], "tiled_bench", model.IMAGENET_MEAN, model.IMAGENET_STD, False, 100, 3) for i in range(0, V, 32)]
         return {key: torch.cat([p[key] for p in parts]) for key in parts[0]}
 
     dets = forward_and_decode()
