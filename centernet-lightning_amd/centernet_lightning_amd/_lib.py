@@ -244,6 +244,9 @@ _SIGNATURES = {
                                                   c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "cnl_track_apply_f32": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_double,
                                            c_void_p, c_void_p, c_void_p]),
+    "cnl_track_kalman_out_bytes": (ctypes.c_int64, [c_int32]),
+    "cnl_track_kalman_f64": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p,
+                                            c_void_p, c_void_p, c_void_p]),
     "cnl_conv_split_weight_floats": (ctypes.c_size_t, [c_int32, c_int32, c_int32, c_int32]),
     "cnl_conv_split_weights_f32": (ctypes.c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "cnl_track_frame_bytes": (ctypes.c_int64, [c_int32, c_int32, c_int32]),

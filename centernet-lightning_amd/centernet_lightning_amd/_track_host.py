@@ -204,13 +204,36 @@ class BoxKalman:
         return self.x[:4].copy()
 
 
+_KALMAN_MODES = ("host", "device")
+
+
+class DeviceKalman:
+    """`Track.kf` with kalman="device": a view of the track's row of the device state tables (cnl_track_kalman_f64), fetched on access
+    as `Track.embedding` is.  `x` float64 [8] (corners, velocities), `P` float64 [8, 8]; there is nothing to call: the filter runs in the
+    launch behind the table update."""
+    __slots__ = ("_track",)
+
+    def __init__(self, track):
+        self._track = track
+
+    @property
+    def x(self):
+        return self._track._tracker._table.kx[self._track._row].cpu().numpy()
+
+    @property
+    def P(self):
+        return self._track._tracker._table.kP[self._track._row].cpu().numpy().reshape(8, 8)
+
+
 class Track:
     """Host record of one track (tracker.py:217-347).  bbox / label live here (they are reported every frame); the embedding
-    lives in the tracker's device table and is fetched on access."""
+    lives in the tracker's device table and is fetched on access.  `use_kalman`: False, True / "host" (a BoxKalman beside the record) or
+    "device" (the state lives in the device table; `kf` is a DeviceKalman view and `bbox` is set from the launch's record)."""
 
     def __init__(self, tracker, track_id, bbox, label, min_birth_age=2, max_inactive_age=30, smoothing_factor=0.9, use_kalman=False):
         self._tracker = tracker
-        self.kf = BoxKalman(bbox) if use_kalman else None
+        self._device_kalman = use_kalman == "device"
+        self.kf = DeviceKalman(self) if self._device_kalman else BoxKalman(bbox) if use_kalman else None
         self._row = -1
         self.track_id = track_id
         self.state = TrackState.UNCONFIRMED
@@ -246,13 +269,14 @@ class Track:
         elif self.state == TrackState.INACTIVE:
             self.state = TrackState.ACTIVE
             self.inactive_age = 0
-        # tracker.py:311-323: the detection's box, or the filtered state when the track carries a Kalman filter
-        self.bbox = bbox if self.kf is None else self.kf.update(bbox)
+        # tracker.py:311-323: the detection's box, or the filtered state when the track carries a Kalman filter (a device filter: the
+        # detection's box until TrackTable.apply_kalman's caller replaces it with the filtered one of the launch's record)
+        self.bbox = bbox if self.kf is None or self._device_kalman else self.kf.update(bbox)
 
     def kalman_predict(self):
         """tracker.py:281-290 (called at the end of every Tracker.update; `bbox` keeps the last UPDATED state, as in the reference,
-        where it is a view of the array that filterpy's predict replaces)."""
-        if self.kf is not None:
+        where it is a view of the array that filterpy's predict replaces).  A device filter predicts in its launch, not here."""
+        if self.kf is not None and not self._device_kalman:
             self.kf.predict()
 
     def update_unmatched(self):
@@ -273,9 +297,11 @@ class Track:
 def life_cycle(tracks, matches, unmatched_dets, unmatched_tracks, det_index, boxes, labels, next_id, settings):
     """One frame of the track life cycle (tracker.py:164-196) from an assignment; pure host code (no torch, no library call).  `boxes` /
     `labels`: the frame's UNfiltered [k, ...] arrays; `settings`: the tracker or bank (its min_birth_age, max_inactive_age, smoothing_factor
-    and use_kalman go to the tracks born now, whose `embedding` reads its device table).
+    and use_kalman / kalman go to the tracks born now, whose `embedding` reads its device table; with kalman="device" no BoxKalman is built
+    or called here: the tracks' filtered boxes come from TrackTable.apply_kalman afterwards).
     Returns (tracks, next_id, old_rows, det_rows): per surviving track its row in `tracks` as given (-1: born now) and the detection row
     that feeds its table row (-1: carried over) — the two index lists of cnl_track_apply_f32."""
+    use_kalman = settings.use_kalman and getattr(settings, "kalman", "host")     # False | "host" | "device" (Track.__init__)
     old_rows = list(range(len(tracks)))
     det_rows = [-1] * len(tracks)
     for det_idx, track_idx in matches:
@@ -290,7 +316,7 @@ def life_cycle(tracks, matches, unmatched_dets, unmatched_tracks, det_index, box
         src = int(det_index[det_idx])
         tracks.append(Track(settings, next_id, boxes[src], labels[src], min_birth_age=settings.min_birth_age,
                             max_inactive_age=settings.max_inactive_age, smoothing_factor=settings.smoothing_factor,
-                            use_kalman=settings.use_kalman))
+                            use_kalman=use_kalman))
         next_id += 1
         old_rows.append(-1)
         det_rows.append(src)
@@ -300,11 +326,16 @@ def life_cycle(tracks, matches, unmatched_dets, unmatched_tracks, det_index, box
 
 class TrackTable:
     """The device track table: `emb` [capacity, E] / `box` [capacity, 4] float32 (first rows live), the spare pair the next update writes
-    (ping-pong), the mapped host memory holding the two index lists cnl_track_apply_f32 reads, the stream of the last update."""
-    __slots__ = ("emb", "box", "stream", "_spare", "_src", "_lists")
+    (ping-pong), the mapped host memory holding the two index lists cnl_track_apply_f32 reads, the stream of the last update.
+    With `kalman` (use_kalman=True, kalman="device") also the filter state `kx` [capacity, 8] / `kP` [capacity, 64] float64 and its spare
+    pair, at the capacities of emb / box; the mapped index block then holds a third list, the flags of cnl_track_kalman_f64, and a second
+    mapped block receives that launch's record (filtered boxes, status words)."""
+    __slots__ = ("emb", "box", "stream", "_spare", "_src", "_lists", "kalman", "kx", "kP", "_kspare", "_kout")
 
-    def __init__(self):
+    def __init__(self, kalman=False):
         self.emb = self.box = self.stream = self._spare = self._src = self._lists = None
+        self.kalman = bool(kalman)
+        self.kx = self.kP = self._kspare = self._kout = None
 
     def wait_for_other_stream(self, cur=None):
         """The caller changed streams between frames: the previous table update (which reads the mapped index lists and writes the tables
@@ -316,6 +347,7 @@ class TrackTable:
         """Forget the rows, behind the last update (the mapped index lists stay)."""
         self.wait_for_other_stream()
         self.emb = self.box = self.stream = self._spare = None
+        self.kx = self.kP = self._kspare = None
 
     def apply(self, src_trk, src_det, d_emb, d_box, E, smoothing_factor, cur):
         """One cnl_track_apply_f32 launch on `cur` builds the new table: row r is old row src_trk[r] (-1: a birth), updated from detection
@@ -326,9 +358,10 @@ class TrackTable:
         # the two index lists sit in mapped host memory that the kernel reads directly (2 x rows int32 over PCIe): no host -> device
         # copy.  The kernel still reads them after the host has moved on: they are overwritten only behind the synchronisation of the
         # next frame's association, which follows this launch in stream order (another stream: wait_for_other_stream)
-        if self._src is None or self._src.nbytes < 8 * rows:
-            self._src = _Mapped(8 * max(1024, 1 << (rows - 1).bit_length()))
-            self._lists = self._src.np.view(np.int32).reshape(2, -1)
+        nl = 3 if self.kalman else 2            # the third list: the flags of cnl_track_kalman_f64 (apply_kalman)
+        if self._src is None or self._src.nbytes < 4 * nl * rows:
+            self._src = _Mapped(4 * nl * max(1024, 1 << (rows - 1).bit_length()))
+            self._lists = self._src.np.view(np.int32).reshape(nl, -1)
         lists = self._lists
         lists[0, :rows] = src_trk
         lists[1, :rows] = src_det
@@ -345,6 +378,37 @@ class TrackTable:
         self.stream = cur
         self._spare, self.emb, self.box = ((self.emb, self.box) if old else None), new_emb, new_box
 
+    def apply_kalman(self, src_trk, src_det, flags, d_emb, d_box, E, smoothing_factor, cur):
+        """kalman="device": `apply`, then ONE cnl_track_kalman_f64 launch behind it on `cur`, driven by the same two lists plus `flags` (bit 0:
+        predict the row at the end; a sequence, or one int for every row), then the step's SECOND stream synchronisation, which makes the
+        launch's record readable -> (the born / matched rows int64 [m], their filtered boxes float64 [m, 4] — one copy the tracks' `bbox` may
+        keep views of —, out_status int32 [rows] view).  Births are initialised from their detection, matched rows updated with it (their
+        rows of `box` become the filtered boxes), carried rows copied through.  The caller holds the device guard."""
+        rows = len(src_trk)
+        if rows == 0:
+            return np.zeros(0, np.int64), np.zeros((0, 4)), np.zeros(0, np.int32)
+        old_x, old_P = self.kx, self.kP
+        self.apply(src_trk, src_det, d_emb, d_box, E, smoothing_factor, cur)
+        lists = self._lists
+        lists[2, :rows] = flags
+        cap = self.emb.shape[0]                 # the state tables grow with the emb / box pair, at the same capacities
+        if self._kspare is None or self._kspare[0].shape[0] != cap:
+            self._kspare = (torch.empty((cap, 8), device=self.emb.device, dtype=torch.float64),
+                            torch.empty((cap, 64), device=self.emb.device, dtype=torch.float64))
+        new_x, new_P = self._kspare
+        if self._kout is None or self._kout.nbytes < 36 * rows:
+            self._kout = _Mapped(36 * max(1024, 1 << (rows - 1).bit_length()))
+        out, n = self._kout, lists.shape[1]
+        old = old_x is not None
+        _lib.check(_lib.load().cnl_track_kalman_f64(old_x.data_ptr() if old else None, old_P.data_ptr() if old else None, d_box.data_ptr(),
+                                                    self._src.ptr, self._src.ptr + 4 * n, self._src.ptr + 8 * n, rows, new_x.data_ptr(),
+                                                    new_P.data_ptr(), self.box.data_ptr(), out.ptr, out.ptr + 32 * rows,
+                                                    ctypes.c_void_p(cur.cuda_stream)), "cnl_track_kalman_f64")
+        self._kspare, self.kx, self.kP = ((old_x, old_P) if old else None), new_x, new_P
+        cur.synchronize()
+        hit = np.flatnonzero(lists[1, :rows] >= 0)
+        return hit, out.np[:32 * rows].view(np.float64).reshape(rows, 4)[hit], out.np[32 * rows:36 * rows].view(np.int32)
+
     def upload_boxes(self, tracks):
         """use_kalman: the table's boxes are the detections' (cnl_track_apply_f32); a Kalman track's box is its filtered state, computed on
         the host with the life cycle (8x8 float64 algebra per track): the boxes of `tracks` (rows 0..len - 1) go up in ONE copy."""
@@ -360,8 +424,15 @@ class TrackerSettings:
 
     def __init__(self, model=None, nms_kernel=3, num_detections=300, detection_threshold=0.3, reid_cost="cosine",
                  reid_threshold=0.2, box_cost="iou", box_threshold=0.5, smoothing_factor=0.5, use_kalman=False,
-                 max_inactive_age=30, min_birth_age=2, device=None, allow_host_cost=False):
-        """reid_cost: "cosine" (default), "euclidean", "sqeuclidean", "cityblock", "chebyshev", "canberra", "braycurtis", "correlation" run on the device.  The reference accepts ANY scipy cdist metric name or
+                 max_inactive_age=30, min_birth_age=2, device=None, allow_host_cost=False, kalman="host"):
+        """kalman (with use_kalman=True; without it, accepted and without effect): "host" (default) keeps a float64 numpy filter per track
+        beside the life cycle (`Track.kf` is a BoxKalman) and uploads the filtered boxes; "device" keeps the filter state in the device
+        table and runs the filter in ONE launch behind the table update (cnl_track_kalman_f64; `Track.kf` is a DeviceKalman view) — no
+        per-track arithmetic and no box upload on the host, at the price of a SECOND stream synchronisation at the end of every step, which
+        makes the filtered boxes readable when the step returns.  A track whose innovation covariance has no positive finite pivots (a
+        zero-area box, a non-finite state) skips its update there (`kalman_skipped` counts them per step) where the host filter raises
+        numpy's LinAlgError.
+        reid_cost: "cosine" (default), "euclidean", "sqeuclidean", "cityblock", "chebyshev", "canberra", "braycurtis", "correlation" run on the device.  The reference accepts ANY scipy cdist metric name or
         a callable (tracker.py:51, 62-64), and a callable box_cost: those are computed on the HOST from copies of the frame's kept embeddings /
         boxes and the track table (two more device -> host copies per frame) — only with allow_host_cost=True, otherwise they raise: a silent
         CPU detour is not what a caller of a gfx950 tracker expects."""
@@ -385,10 +456,14 @@ class TrackerSettings:
         self.box_threshold = box_threshold
         self.smoothing_factor = smoothing_factor
         self.use_kalman = bool(use_kalman)
+        if kalman not in _KALMAN_MODES:
+            raise ValueError(f"kalman={kalman!r}: expected 'host' or 'device'")
+        self.kalman = kalman
+        self.kalman_skipped = 0     # kalman="device": rows of the last step whose update was skipped (status bit 0 of cnl_track_kalman_f64)
         self.max_inactive_age = max_inactive_age
         self.min_birth_age = min_birth_age
         self._device = torch.device(device) if device is not None else None
-        self._table = TrackTable()
+        self._table = TrackTable(kalman=self._device_kalman)
         self._rec = None            # mapped host memory the association kernel writes its record(s) into
         self.reset()
 
@@ -405,6 +480,15 @@ class TrackerSettings:
 
     _emb = property(lambda self: self._table.emb)       # device track table [capacity, E] / [capacity, 4] (Track.embedding, tests, tools)
     _box = property(lambda self: self._table.box)
+    _device_kalman = property(lambda self: self.use_kalman and self.kalman == "device")
+
+    def _apply_with_kalman(self, tracks, src_trk, src_det, flags, d_emb, d_box, E, cur):
+        """kalman="device": the table update and the filter launch for `tracks` (row order of the new table), then the filtered box of every
+        born / matched track from the launch's record (a carried track keeps its `bbox`).  The caller holds the device guard."""
+        hit, boxes, status = self._table.apply_kalman(src_trk, src_det, flags, d_emb, d_box, E, self.smoothing_factor, cur)
+        for r, b in zip(hit.tolist(), boxes):
+            tracks[r].bbox = b
+        self.kalman_skipped = int(np.count_nonzero(status))
 
     def _thresholds(self, kwargs):
         """(detection, re-ID, box) thresholds of one call: the settings unless the call overrides them."""

@@ -11,6 +11,14 @@ match list goes back.  The reference instead copies every frame's k x (6+E) dete
 
 `use_kalman=True` (tracker.py:243-262, 281-323): the per-track 8-state filter is a float64 numpy restatement of filterpy's
 KalmanFilter (third-party, absent) on the host, beside the life cycle; the filtered boxes are uploaded to the device table.
+`kalman="device"` (opt-in; the default "host" is the path above, bit for bit) moves that last per-track state to the device: the table gains
+x [T, 8] / P [T, 64] float64, and ONE launch (cnl_track_kalman_f64, csrc/track_kalman.hip) behind the table update initialises the born rows,
+updates the matched ones with their detection, carries the others, predicts the rows of the streams that took part and writes the filtered
+boxes into the box table and into a mapped record; a SECOND stream synchronisation at the end of the step makes that record readable, so
+`Track.bbox` holds the filtered box when update / update_batch / step_batch return.  No BoxKalman exists in that mode, no box upload, no
+per-track arithmetic in Python; `Track.kf` is a view (`.x`, `.P`) that fetches the track's row on access.  The rule is the header's
+(filterpy's equations, S^-1 through LDL', every sum in index order; tests/kalman_ref.py restates it bit for bit); its one deviation from the
+host path: a row whose S has no positive finite pivots (zero-area box, non-finite state) skips its update where np.linalg.inv raises.
 Per frame: ONE kernel launch (cnl_track_frame_f32) writes the frame record — kept-detection indices, boxes / scores / labels, cost
 matrices — straight into mapped host memory, ONE stream synchronisation makes it readable; no copy operation in either direction.
 `reid_cost`: "cosine" / "euclidean" / "sqeuclidean" / "cityblock" / "chebyshev" / "canberra" / "braycurtis" / "correlation" have kernels; any other scipy
@@ -54,7 +62,8 @@ class Tracker(TrackerSettings):
     @torch.no_grad()
     def step_batch(self, images: torch.Tensor, **kwargs):
         """Run the model on a batch of consecutive frames and update the tracks frame by frame (tracker.py:84-121).
-        Returns {"bboxes": [...], "track_ids": [...]} with one list per frame (active tracks only)."""
+        Returns {"bboxes": [...], "track_ids": [...]} with one list per frame (active tracks only).
+        (kalman="device": two stream synchronisations per frame instead of one, see `update`.)"""
         det = self._detect(images, kwargs)
         out = {"bboxes": [], "track_ids": []}
         for i in range(images.shape[0]):
@@ -71,7 +80,9 @@ class Tracker(TrackerSettings):
     # ------------------------------------------------------------------ one frame
     def update(self, bboxes, labels, scores, embeddings, **kwargs):
         """Update current tracks with one frame's detections (tracker.py:123-201).  Accepts numpy arrays (as the reference) or
-        torch tensors; the arrays are moved to the HIP device, where the association costs are computed."""
+        torch tensors; the arrays are moved to the HIP device, where the association costs are computed.
+        With use_kalman=True, kalman="device" the filter runs in one launch behind the table update, and the call ends with a SECOND stream
+        synchronisation (the first makes the frame record readable), so that the filtered boxes are in `Track.bbox` when it returns."""
         dev = self.device
         d_box, d_score, d_emb, d_label, host, label_kind = normalise_detections(dev, bboxes, labels, scores, embeddings)
         detection_threshold, reid_threshold, box_threshold = self._thresholds(kwargs)
@@ -102,6 +113,13 @@ class Tracker(TrackerSettings):
             self.last_costs = (reid.copy(), None if box is None or callable(box) else box.copy(), det_index)
         self.tracks, self.next_track_id, old_rows, det_rows = life_cycle(self.tracks, matches, unmatched_dets, unmatched_tracks, det_index,
                                                                          h_box, h_label, self.next_track_id, self)
+        if self._device_kalman:             # every track predicts at the end of the step, as on the host path below
+            with _on(dev):
+                self._apply_with_kalman(self.tracks, old_rows, det_rows, 1, d_emb, d_box, E, cur)
+            self.d2h_bytes += 36 * len(self.tracks)
+            for r, t in enumerate(self.tracks):
+                t._row = r
+            return
         with _on(dev):
             table.apply(old_rows, det_rows, d_emb, d_box, E, self.smoothing_factor, cur)
         for r, t in enumerate(self.tracks):
@@ -157,7 +175,7 @@ class TrackerBank(TrackerSettings):
 
     def __init__(self, num_streams, model=None, nms_kernel=3, num_detections=300, detection_threshold=0.3, reid_cost="cosine",
                  reid_threshold=0.2, box_cost="iou", box_threshold=0.5, smoothing_factor=0.5, use_kalman=False,
-                 max_inactive_age=30, min_birth_age=2, device=None, allow_host_cost=False):
+                 max_inactive_age=30, min_birth_age=2, device=None, allow_host_cost=False, kalman="host"):
         if isinstance(num_streams, bool) or not isinstance(num_streams, (int, np.integer)) or num_streams < 1:
             raise ValueError(f"num_streams={num_streams!r}: expected an integer >= 1")
         if callable(reid_cost) or callable(box_cost) or reid_cost not in _REID_METRICS:
@@ -170,7 +188,7 @@ class TrackerBank(TrackerSettings):
         self._off = np.zeros(self.num_streams + 1, np.int64)        # pooled device table: stream s owns rows _off[s] .. _off[s + 1]
         self._ctl = self._ws = self._redo_rec = None    # mapped live list + trk_off; device workspace; mapped record of a redone stream
         super().__init__(model, nms_kernel, num_detections, detection_threshold, reid_cost, reid_threshold, box_cost, box_threshold,
-                         smoothing_factor, use_kalman, max_inactive_age, min_birth_age, device)
+                         smoothing_factor, use_kalman, max_inactive_age, min_birth_age, device, kalman=kalman)
 
     def __len__(self):
         return self.num_streams
@@ -202,8 +220,12 @@ class TrackerBank(TrackerSettings):
         dev = self.device
         with _on(dev):
             table.wait_for_other_stream()             # its reads of the index lists come before this overwrite
-            table.apply(rows.astype(np.int32), np.full(len(rows), -1, np.int32), table.emb, table.box, table.emb.shape[1],
-                        self.smoothing_factor, torch.cuda.current_stream(dev))
+            # (kalman="device": the filter state moves with the rows — no row is updated or predicted)
+            args = (table.emb, table.box, table.emb.shape[1], self.smoothing_factor, torch.cuda.current_stream(dev))
+            if self._device_kalman:
+                table.apply_kalman(rows.astype(np.int32), np.full(len(rows), -1, np.int32), 0, *args)
+            else:
+                table.apply(rows.astype(np.int32), np.full(len(rows), -1, np.int32), *args)
         self._set_offsets()
 
     def _set_offsets(self):
@@ -226,7 +248,8 @@ class TrackerBank(TrackerSettings):
     @torch.no_grad()
     def step_batch(self, images: torch.Tensor, streams=None, **kwargs):
         """Run the model on one frame from each participating stream (images[i] is the next frame of stream streams[i]; default: stream i)
-        and advance those streams.  Returns {"bboxes": [...], "track_ids": [...]} with one list per image (active tracks only)."""
+        and advance those streams.  Returns {"bboxes": [...], "track_ids": [...]} with one list per image (active tracks only).
+        (kalman="device": two stream synchronisations per step instead of one, see `update_batch`.)"""
         live = self._check_streams(streams)
         if images.dim() != 4 or images.shape[0] != len(live):
             raise ValueError(f"images {tuple(images.shape)}: expected [{len(live)}, 3, H, W], one frame per participating stream")
@@ -256,7 +279,9 @@ class TrackerBank(TrackerSettings):
 
     def update_batch(self, bboxes, labels, scores, embeddings, streams=None, **kwargs):
         """One frame's detections for each participating stream: [L, k, 4], [L, k], [L, k], [L, k, E] (numpy arrays or torch tensors; L =
-        len(streams), default every stream).  As `Tracker.update`, it does not advance `frame`."""
+        len(streams), default every stream).  As `Tracker.update`, it does not advance `frame`.  With use_kalman=True, kalman="device" the
+        step ends with a SECOND stream synchronisation, behind the filter launch (see `Tracker.update`); a stream that takes no part keeps
+        its filter state unpredicted, as on the host path."""
         self._step(bboxes, labels, scores, embeddings, self._check_streams(streams), kwargs)
 
     def _step(self, bboxes, labels, scores, embeddings, live, kwargs):
@@ -308,18 +333,27 @@ class TrackerBank(TrackerSettings):
         self.d2h_bytes = d2h
 
         # ---- track life cycle per stream (host) + the rows of the new pooled table ----
-        src_trk, src_det = [], []
+        src_trk, src_det, predict = [], [], []      # predict: (flag, rows) per stream for cnl_track_kalman_f64 — only the streams of this step predict
         for s, st in enumerate(self._streams):
             base = int(off[s])
             if s not in assoc:              # took no part in this step: its rows are copied through
                 src_trk.extend(range(base, base + len(st.tracks)))
                 src_det.extend([-1] * len(st.tracks))
+                predict.append((0, len(st.tracks)))
                 continue
             det_base, matches, *rest = assoc[s]
             self.last_matches[s] = matches
             st.tracks, st.next_track_id, old_rows, det_rows = life_cycle(st.tracks, matches, *rest, st.next_track_id, self)
             src_trk.extend(base + r if r >= 0 else -1 for r in old_rows)
             src_det.extend(det_base + d if d >= 0 else -1 for d in det_rows)
+            predict.append((1, len(old_rows)))
+        if self._device_kalman:
+            flags = np.repeat(np.array([p for p, _ in predict], np.int32), [n for _, n in predict])
+            with _on(dev):
+                self._apply_with_kalman([t for st in self._streams for t in st.tracks], src_trk, src_det, flags, d_emb, d_box, E, cur)
+            self.d2h_bytes += 36 * len(src_trk)
+            self._set_offsets()
+            return
         with _on(dev):
             table.apply(src_trk, src_det, d_emb, d_box, E, self.smoothing_factor, cur)
         self._set_offsets()

@@ -1068,6 +1068,49 @@ int cnl_track_streams_f32(const float* det_emb, const float* det_box, const floa
                           int64_t workspace_bytes, void* record, int64_t record_stride, void* stream);
 
 /*
+ * The per-track Kalman filter on the device (csrc/track_kalman.hip): Track.__init__ / predict / update of models/tracker.py:243-262,
+ * 281-290, 317-323 with use_kalman=True, for the rows of the device track table.  ONE launch behind cnl_track_apply_f32, driven by the same
+ * two index lists, builds the new state tables (ping-pong, not in place):
+ *   x [T_old,8] f64, P [T_old,64] f64 (row-major 8x8): the old tables; both null when there is no old table (then every row is a birth);
+ *   det_box [*,4] f32, src_trk / src_det [T_new] int32: the operands cnl_track_apply_f32 was given (the lists may be cnl_host_alloc memory);
+ *   flags [T_new] int32 (may be cnl_host_alloc memory): bit 0 = predict this row at the end;
+ *   new_x [T_new,8], new_P [T_new,64] f64 <- the new tables; new_box [T_new,4] f32: the box table cnl_track_apply_f32 has just written;
+ *   out_box [T_new,4] f64, out_status [T_new] int32: device memory or cnl_host_alloc memory (cnl_track_kalman_out_bytes(T_new) = 36 T_new
+ *   holds both, out_box first).
+ * Per new row r, with t = src_trk[r], d = src_det[r]:
+ *   birth   (t <  0, d >= 0): b = det_box[d] converted to f64; x = (b, 0, 0, 0, 0); w = b2 - b0, h = b3 - b1; P = diag(s_i * s_i) with
+ *                             s_i = (i odd ? h : w) / 10 for i < 4 and / 16 for i >= 4.  new_box[r] = float32(x[:4]), out_box[r] = x[:4].
+ *   matched (t >= 0, d >= 0): old row t, the measurement update below with z = det_box[d]; new_box[r] = float32(x[:4]), out_box[r] = x[:4].
+ *   carried (t >= 0, d <  0): old row t; new_box[r] is NOT written (it keeps the last updated box, not the predicted one: the reference's
+ *                             behaviour); out_box[r] = x[:4].
+ *   then, if bit 0 of flags[r] is set, the prediction step below; then new_x[r] / new_P[r] are stored; out_status[r] is always written.
+ * Arithmetic: float64 throughout, one rounding per operation, no fused multiply-add, every sum starts with its first term and adds the others in
+ * ascending index order; P is read and kept as its upper triangle and stored mirrored, so the stored matrix is exactly symmetric.  With
+ * P = [[A, B], [B', C]] (4x4 blocks), F = [[I, I], [0, I]], H = [I 0]:
+ *   update:  w = x2 - x0, h = x3 - x1, r_i = t_i * t_i with t_i = (i odd ? h : w) / 20 (i < 4);  y_i = z_i - x_i;
+ *            S = A + diag(r) (only the diagonal is added to) = L D L' without square roots, column j = 0..3:
+ *              c_ij = S_ij - sum_{k<j} c_ik * L_jk  (i = j..3; no subtraction for j = 0),  d_j = c_jj,  L_ij = c_ij / d_j  (i > j);
+ *            K = P[:, :4] S^-1 row by row (m = 0..7):  u_i = P_mi - sum_{k<i} L_ik * u_k  (i = 0..3),  v_i = u_i / d_i,
+ *              K_mi = v_i - sum_{k>i} L_ki * K_mk  (i = 3..0);
+ *            x_m <- x_m + sum_{k<4} K_mk * y_k;
+ *            P <- (I - KH) P (I - KH)' + K R K':  W_ij = P_ij - sum_{k<4} K_ik * P_kj,
+ *              P_ij <- (W_ij - sum_{k<4} W_ik * K_jk) + sum_{k<4} (K_ik * r_k) * K_jk   for i <= j, mirrored.
+ *   predict: w, h from x before the step; x_i <- x_i + x_{i+4} (i < 4);  A_ij <- (A_ij + B_ji) + (B_ij + C_ij) for i <= j, mirrored;
+ *            B_ij <- B_ij + C_ij;  then P_ii <- P_ii + q_i * q_i with q_i = (i odd ? h : w) / 20 for i < 4 and / 160 for i >= 4.
+ * The ONE deviation from the host path (BoxKalman, whose np.linalg.inv raises LinAlgError on a singular S): if a pivot d_j is not finite
+ * and strictly positive — a zero-area box, or a non-finite state — the row skips the update: x and P stay as loaded and bit 0 of
+ * out_status[r] is set.  Bit 1 marks a row without a source (t >= 0 without old tables, or t < 0 and d < 0: a caller's error): it is stored
+ * as zeros.  Rows are independent: a non-finite row never changes another row's bits.  No atomics, no memset; the same bytes on every run.
+ * CNL_E_BAD_ARG before any HIP call: T_new < 0; a null pointer other than x / P (which are null together); a new table that aliases the old
+ * one; x, P, new_x, new_P or out_box not 8-byte aligned; det_box not 16-byte aligned (a box is read as one 16-byte word).  T_new == 0 returns
+ * CNL_OK without a launch.
+ */
+int64_t cnl_track_kalman_out_bytes(int32_t T_new);
+int cnl_track_kalman_f64(const double* x, const double* P, const float* det_box, const int32_t* src_trk, const int32_t* src_det,
+                         const int32_t* flags, int32_t T_new, double* new_x, double* new_P, float* new_box, double* out_box,
+                         int32_t* out_status, void* stream);
+
+/*
  * Wire formats: COCO boxes are xywh — torchvision box_convert(boxes, "xyxy", "xywh") of
  * CenterNet.validation_step (models/centernet.py:207): out[i] = (x1, y1, x2 - x1, y2 - y1); n boxes of 4 floats, may be in place.
  * boxes and out are 16-byte aligned (a box is moved as one 16-byte word; CNL_E_BAD_ARG otherwise).
