@@ -258,6 +258,16 @@ _SIGNATURES = {
     "cnl_track_streams_f32": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int32, c_int32, c_float,
                                              c_double, c_float, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p,
                                              ctypes.c_int64, c_void_p, ctypes.c_int64, c_void_p]),
+    "cnl_track_frame_low_bytes": (ctypes.c_int64, [c_int32, c_int32, c_int32]),
+    "cnl_track_frame_low_f32": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_float, c_float, c_void_p, c_void_p,
+                                               c_int32, c_int32, c_int32, c_int32, c_void_p, ctypes.c_int64, c_void_p]),
+    "cnl_track_streams_low_workspace_bytes": (ctypes.c_int64, [c_int32, c_int32, c_int32]),
+    "cnl_track_streams_low_record_bytes": (ctypes.c_int64, [c_int32, c_int32, c_int32]),
+    "cnl_track_streams_low_f32": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int32, c_int32, c_float,
+                                                 c_double, c_float, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32,
+                                                 c_int32, c_int32, c_void_p, ctypes.c_int64, c_void_p, ctypes.c_int64, c_void_p]),
+    "cnl_track_apply_keep_f32": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_double,
+                                                c_void_p, c_void_p, c_void_p, c_void_p]),
     "cnl_relu_grad_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32]),
     "cnl_relu_grad_terms": (c_int64, [c_int32, c_int32, c_int32, c_int32]),
     "cnl_relu_grad_f32": (ctypes.c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p,

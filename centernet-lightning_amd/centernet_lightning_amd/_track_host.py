@@ -58,7 +58,13 @@ F_N, F_K, F_T, F_WITH_DETS, F_OFF_INDEX, F_OFF_DETS, F_OFF_REID, F_OFF_BOX = ran
 # ... and of one stream's record (csrc/track_streams.hip: streams_costs_kernel, streams_assign_kernel); M1 = matches of stage 1 alone
 (S_N, S_K, S_T, S_STATUS, S_OFF_INDEX, S_OFF_DETS, S_OFF_MATCH, S_OFF_UDET, S_OFF_UTRK, S_M, S_M1, S_NUDET, S_NUTRK, S_WITH_DETS, S_SLOT,
  S_STREAM) = range(16)
-_STATUS_TOO_LARGE = (3, 4, 19)          # status words of a stream whose k / T lie beyond the supported sizes
+_STATUS_TOO_LARGE = (3, 4, 19, 35)      # status words of a stream whose k / T lie beyond the supported sizes
+# The BYTE stage's additions (low_threshold set): the frame record's header grows to int32[12], a stream's to int32[24]
+FrameLowLayout = FrameLayout
+StreamsLowLayout = namedtuple("StreamsLowLayout", "off_index off_dets off_match off_udet off_utrk off_low_index off_low_match bytes")
+F_NLOW, F_OFF_LOW_INDEX, F_OFF_LOW_BOX = 8, 9, 10
+S_NLOW, S_NLOW_MATCH, S_OFF_LOW_INDEX, S_OFF_LOW_MATCH = 16, 17, 18, 19
+_LOW_MATCH = ("active", "all")
 
 
 def frame_layout(k, T, with_dets):
@@ -81,6 +87,29 @@ def streams_layout(k, T_max, with_dets):
 def streams_workspace_bytes(S, k, R):
     """Device workspace of one step over S streams whose pooled table has R rows: 20 B per (detection, row) pair + the index lists."""
     return 20 * k * R + 4 * (S + 2 * S * k + 2 * R)
+
+
+def frame_low_layout(k, T, with_dets):
+    """cnl_track_frame_low_bytes: [header 48 B | det_index[k] | (boxes scores labels) | reid f64 n*T | box f32 n*T | low_index[k] | low_box f32
+    n_low*T]; the kept and the low detections are disjoint (n + n_low <= k), so 12 k T bounds the three matrices."""
+    off_dets = (48 + 4 * k + 7) & ~7
+    off_reid = (off_dets + (24 * k if with_dets else 0) + 7) & ~7
+    return FrameLowLayout(48, off_dets, off_reid, off_reid + 12 * k * T + 4 * k)
+
+
+def streams_low_layout(k, T_max, with_dets):
+    """cnl_track_streams_low_record_bytes: streams_layout behind a 96-byte header, then low_index[k] | low_matches[k][2]."""
+    off_dets = (96 + 4 * k + 7) & ~7
+    off_match = off_dets + (24 * k if with_dets else 0)
+    off_utrk = off_match + 12 * k
+    off_low_index = off_utrk + 4 * T_max
+    return StreamsLowLayout(96, off_dets, off_match, off_match + 8 * k, off_utrk, off_low_index, off_low_index + 4 * k,
+                            (off_low_index + 12 * k + 7) & ~7)
+
+
+def streams_low_workspace_bytes(S, k, R):
+    """streams_workspace_bytes + the low detections' box costs (4 B per pair) and their count per stream."""
+    return streams_workspace_bytes(S, k, R) + 4 * k * R + 4 * S
 
 
 def _read_dets(r, off, k):
@@ -112,6 +141,34 @@ def read_stream_record(r):
     matches = [tuple(p) for p in r[off_match:off_match + 8 * m].view(np.int32).reshape(m, 2).tolist()]
     return (n, hdr[S_T], hdr[S_STATUS], r[off_index:off_index + 4 * n].view(np.int32).copy(), *dets, matches,
             r[off_udet:off_udet + 4 * hdr[S_NUDET]].view(np.int32).tolist(), r[off_utrk:off_utrk + 4 * hdr[S_NUTRK]].view(np.int32).tolist())
+
+
+def read_frame_low_record(h):
+    """uint8 view of a cnl_track_frame_low_f32 record -> read_frame_record's tuple + (low_index int32 [n_low] copy, low_box f32 [n_low, T] view)."""
+    hdr = h[:48].view(np.int32).tolist()
+    n_low, T, off_li, off_lb = hdr[F_NLOW], hdr[F_T], hdr[F_OFF_LOW_INDEX], hdr[F_OFF_LOW_BOX]
+    return (*read_frame_record(h, True), h[off_li:off_li + 4 * n_low].view(np.int32).copy(),
+            h[off_lb:off_lb + 4 * n_low * T].view(np.float32).reshape(n_low, T))
+
+
+def read_stream_low_record(r):
+    """uint8 view of one stream's cnl_track_streams_low_f32 record -> read_stream_record's tuple (its unmatched tracks: after all three
+    stages) + (n_low, low_matches as (ORIGINAL detection index, track), in low-row order)."""
+    hdr = r[64:96].view(np.int32).tolist()
+    n_low, m, off_li, off_lm = hdr[S_NLOW - 16], hdr[S_NLOW_MATCH - 16], hdr[S_OFF_LOW_INDEX - 16], hdr[S_OFF_LOW_MATCH - 16]
+    low_index = r[off_li:off_li + 4 * n_low].view(np.int32)
+    pairs = r[off_lm:off_lm + 8 * m].view(np.int32).reshape(m, 2).tolist()
+    return (*read_stream_record(r), n_low, [(int(low_index[x]), t) for x, t in pairs])
+
+
+def launch_frame_low(lib, rec, d_emb, d_box, d_score, d_label, label_kind, k, E, detection_threshold, low_threshold, t_emb, t_box, T, box_mode,
+                     reid_metric, with_dets, cur):
+    """launch_frame with the BYTE stage's sections (cnl_track_frame_low_f32) -> read_frame_low_record's tuple."""
+    _lib.check(lib.cnl_track_frame_low_f32(d_emb, d_box, d_score, d_label, label_kind, k, E, float(detection_threshold), float(low_threshold), t_emb,
+                                           t_box, T, box_mode, reid_metric, int(with_dets), rec.ptr, rec.nbytes, ctypes.c_void_p(cur.cuda_stream)),
+               "cnl_track_frame_low_f32")
+    cur.synchronize()
+    return read_frame_low_record(rec.np)
 
 
 def launch_frame(lib, rec, d_emb, d_box, d_score, d_label, label_kind, k, E, detection_threshold, t_emb, t_box, T, box_mode, reid_metric,
@@ -156,6 +213,18 @@ def two_stage_assignment(reid, reid_threshold, box_threshold, box=None):
         matches.extend((unmatched_dets[x], unmatched_tracks[y]) for x, y in new_matches)
         unmatched_dets, unmatched_tracks = [unmatched_dets[x] for x in ud], [unmatched_tracks[y] for y in ut]
     return matches, unmatched_dets, unmatched_tracks
+
+
+def low_stage(low_box, low_index, unmatched_tracks, eligible, low_box_threshold):
+    """The BYTE stage (include/centernet_gfx950.h): the tracks still unmatched after two_stage_assignment, restricted to those with
+    eligible[t] (None: all), against the low-score detections by box cost alone.  `low_box` float32 [n_low, T] (rows: low_index).
+    -> (low matches as (ORIGINAL detection index, track) in low-row order, the tracks unmatched after all three stages)."""
+    U = [t for t in unmatched_tracks if eligible is None or eligible[t]]
+    if not U or low_box.shape[0] == 0:
+        return [], unmatched_tracks
+    pairs, _, _ = match_with_threshold(low_box[:, U], low_box_threshold)
+    hit = {U[y] for _, y in pairs}
+    return [(int(low_index[x]), U[y]) for x, y in pairs], [t for t in unmatched_tracks if t not in hit]
 
 
 class TrackState(Enum):
@@ -294,13 +363,16 @@ class Track:
         return f"track id: {self.track_id}, bbox: {self.bbox}, label: {self.label}, state: {self.state.name}"
 
 
-def life_cycle(tracks, matches, unmatched_dets, unmatched_tracks, det_index, boxes, labels, next_id, settings):
+def life_cycle(tracks, matches, unmatched_dets, unmatched_tracks, det_index, boxes, labels, next_id, settings, low_matches=None):
     """One frame of the track life cycle (tracker.py:164-196) from an assignment; pure host code (no torch, no library call).  `boxes` /
     `labels`: the frame's UNfiltered [k, ...] arrays; `settings`: the tracker or bank (its min_birth_age, max_inactive_age, smoothing_factor
     and use_kalman / kalman go to the tracks born now, whose `embedding` reads its device table; with kalman="device" no BoxKalman is built
     or called here: the tracks' filtered boxes come from TrackTable.apply_kalman afterwards).
     Returns (tracks, next_id, old_rows, det_rows): per surviving track its row in `tracks` as given (-1: born now) and the detection row
-    that feeds its table row (-1: carried over) — the two index lists of cnl_track_apply_f32."""
+    that feeds its table row (-1: carried over) — the two index lists of cnl_track_apply_f32.
+    `low_matches` (None: no low-score stage, the four values above): the BYTE stage's (ORIGINAL detection index, track) pairs, possibly none
+    — no quirk: the track takes that detection's box and keeps its embedding.  When given, a fifth value is returned: per surviving track 1
+    if its table row keeps the old embedding (cnl_track_apply_keep_f32)."""
     use_kalman = settings.use_kalman and getattr(settings, "kalman", "host")     # False | "host" | "device" (Track.__init__)
     old_rows = list(range(len(tracks)))
     det_rows = [-1] * len(tracks)
@@ -309,6 +381,11 @@ def life_cycle(tracks, matches, unmatched_dets, unmatched_tracks, det_index, box
         # unfiltered ones at the same position; identical when scores are sorted descending (gather_tracking2d output)
         tracks[track_idx].update_matched(boxes[det_idx])
         det_rows[track_idx] = det_idx
+    keep_emb = [0] * len(tracks)
+    for det_idx, track_idx in low_matches or ():
+        tracks[track_idx].update_matched(boxes[det_idx])
+        det_rows[track_idx] = det_idx
+        keep_emb[track_idx] = 1
     for track_idx in unmatched_tracks:
         tracks[track_idx].update_unmatched()
     tracks = list(tracks)
@@ -321,7 +398,8 @@ def life_cycle(tracks, matches, unmatched_dets, unmatched_tracks, det_index, box
         old_rows.append(-1)
         det_rows.append(src)
     keep = [i for i, t in enumerate(tracks) if t.state is not TrackState.TO_DELETE]
-    return [tracks[i] for i in keep], next_id, [old_rows[i] for i in keep], [det_rows[i] for i in keep]
+    out = [tracks[i] for i in keep], next_id, [old_rows[i] for i in keep], [det_rows[i] for i in keep]
+    return out if low_matches is None else (*out, [keep_emb[i] if i < len(keep_emb) else 0 for i in keep])
 
 
 class TrackTable:
@@ -349,17 +427,19 @@ class TrackTable:
         self.emb = self.box = self.stream = self._spare = None
         self.kx = self.kP = self._kspare = None
 
-    def apply(self, src_trk, src_det, d_emb, d_box, E, smoothing_factor, cur):
+    def apply(self, src_trk, src_det, d_emb, d_box, E, smoothing_factor, cur, keep_emb=None):
         """One cnl_track_apply_f32 launch on `cur` builds the new table: row r is old row src_trk[r] (-1: a birth), updated from detection
-        row src_det[r] of d_emb / d_box (-1: copied through).  The caller holds the device guard."""
+        row src_det[r] of d_emb / d_box (-1: copied through).  The caller holds the device guard.
+        `keep_emb` (the BYTE stage; None: the launch above, unchanged): one flag per row, a matched row with its flag set takes the detection's
+        box and keeps the old embedding (cnl_track_apply_keep_f32); the flags are one more row of the mapped index block, one byte each."""
         rows = len(src_trk)
         if rows == 0:
             return
         # the two index lists sit in mapped host memory that the kernel reads directly (2 x rows int32 over PCIe): no host -> device
         # copy.  The kernel still reads them after the host has moved on: they are overwritten only behind the synchronisation of the
         # next frame's association, which follows this launch in stream order (another stream: wait_for_other_stream)
-        nl = 3 if self.kalman else 2            # the third list: the flags of cnl_track_kalman_f64 (apply_kalman)
-        if self._src is None or self._src.nbytes < 4 * nl * rows:
+        nl = (3 if self.kalman else 2) + (keep_emb is not None)     # the third list: the flags of cnl_track_kalman_f64 (apply_kalman); last: keep_emb
+        if self._src is None or self._lists.shape[0] < nl or self._lists.shape[1] < rows:
             self._src = _Mapped(4 * nl * max(1024, 1 << (rows - 1).bit_length()))
             self._lists = self._src.np.view(np.int32).reshape(nl, -1)
         lists = self._lists
@@ -371,14 +451,19 @@ class TrackTable:
                            torch.empty((cap, 4), device=d_emb.device, dtype=torch.float32))
         new_emb, new_box = self._spare
         old = self.emb is not None
-        _lib.check(_lib.load().cnl_track_apply_f32(self.emb.data_ptr() if old else None, self.box.data_ptr() if old else None, d_emb.data_ptr(),
-                                                   d_box.data_ptr(), self._src.ptr, self._src.ptr + 4 * lists.shape[1], rows, E,
-                                                   float(smoothing_factor), new_emb.data_ptr(), new_box.data_ptr(),
-                                                   ctypes.c_void_p(cur.cuda_stream)), "cnl_track_apply_f32")
+        n = lists.shape[1]
+        args = (self.emb.data_ptr() if old else None, self.box.data_ptr() if old else None, d_emb.data_ptr(), d_box.data_ptr(), self._src.ptr,
+                self._src.ptr + 4 * n, rows, E, float(smoothing_factor), new_emb.data_ptr(), new_box.data_ptr())
+        if keep_emb is None:
+            _lib.check(_lib.load().cnl_track_apply_f32(*args, ctypes.c_void_p(cur.cuda_stream)), "cnl_track_apply_f32")
+        else:
+            lists[nl - 1].view(np.uint8)[:rows] = keep_emb
+            _lib.check(_lib.load().cnl_track_apply_keep_f32(*args, self._src.ptr + 4 * n * (nl - 1), ctypes.c_void_p(cur.cuda_stream)),
+                       "cnl_track_apply_keep_f32")
         self.stream = cur
         self._spare, self.emb, self.box = ((self.emb, self.box) if old else None), new_emb, new_box
 
-    def apply_kalman(self, src_trk, src_det, flags, d_emb, d_box, E, smoothing_factor, cur):
+    def apply_kalman(self, src_trk, src_det, flags, d_emb, d_box, E, smoothing_factor, cur, keep_emb=None):
         """kalman="device": `apply`, then ONE cnl_track_kalman_f64 launch behind it on `cur`, driven by the same two lists plus `flags` (bit 0:
         predict the row at the end; a sequence, or one int for every row), then the step's SECOND stream synchronisation, which makes the
         launch's record readable -> (the born / matched rows int64 [m], their filtered boxes float64 [m, 4] — one copy the tracks' `bbox` may
@@ -388,7 +473,7 @@ class TrackTable:
         if rows == 0:
             return np.zeros(0, np.int64), np.zeros((0, 4)), np.zeros(0, np.int32)
         old_x, old_P = self.kx, self.kP
-        self.apply(src_trk, src_det, d_emb, d_box, E, smoothing_factor, cur)
+        self.apply(src_trk, src_det, d_emb, d_box, E, smoothing_factor, cur, keep_emb)
         lists = self._lists
         lists[2, :rows] = flags
         cap = self.emb.shape[0]                 # the state tables grow with the emb / box pair, at the same capacities
@@ -424,8 +509,14 @@ class TrackerSettings:
 
     def __init__(self, model=None, nms_kernel=3, num_detections=300, detection_threshold=0.3, reid_cost="cosine",
                  reid_threshold=0.2, box_cost="iou", box_threshold=0.5, smoothing_factor=0.5, use_kalman=False,
-                 max_inactive_age=30, min_birth_age=2, device=None, allow_host_cost=False, kalman="host"):
-        """kalman (with use_kalman=True; without it, accepted and without effect): "host" (default) keeps a float64 numpy filter per track
+                 max_inactive_age=30, min_birth_age=2, device=None, allow_host_cost=False, low_threshold=None,
+                 low_box_threshold=None, low_match="active", kalman="host"):
+        """low_threshold (None: off, the path and results without it): BYTE's second association (Zhang et al., ByteTrack) — the tracks still
+        unmatched after the re-ID and box stages are matched by box cost alone (cost < low_box_threshold, default box_threshold) against the
+        detections with low_threshold <= score < detection_threshold; such a match gives the track the detection's box (a measurement for
+        its Kalman filter) and leaves its embedding as it was, and a low detection never starts a track.  low_match: "active" (only tracks
+        that are ACTIVE at the start of the step take part) or "all".  Needs box_cost "iou" / "giou"; the rule is the header's.
+        kalman (with use_kalman=True; without it, accepted and without effect): "host" (default) keeps a float64 numpy filter per track
         beside the life cycle (`Track.kf` is a BoxKalman) and uploads the filtered boxes; "device" keeps the filter state in the device
         table and runs the filter in ONE launch behind the table update (cnl_track_kalman_f64; `Track.kf` is a DeviceKalman view) — no
         per-track arithmetic and no box upload on the host, at the price of a SECOND stream synchronisation at the end of every step, which
@@ -462,6 +553,12 @@ class TrackerSettings:
         self.kalman_skipped = 0     # kalman="device": rows of the last step whose update was skipped (status bit 0 of cnl_track_kalman_f64)
         self.max_inactive_age = max_inactive_age
         self.min_birth_age = min_birth_age
+        if low_match not in _LOW_MATCH:
+            raise ValueError(f"low_match={low_match!r}: expected 'active' or 'all'")
+        if low_threshold is not None and (self._host_box is not None or box_cost is None):
+            raise ValueError(f"low_threshold={low_threshold!r} with box_cost={box_cost!r}: the low-score stage matches by the 'iou' / 'giou' box cost")
+        self.low_threshold, self.low_box_threshold, self.low_match = low_threshold, low_box_threshold, low_match
+        self._check_low(low_threshold, detection_threshold)
         self._device = torch.device(device) if device is not None else None
         self._table = TrackTable(kalman=self._device_kalman)
         self._rec = None            # mapped host memory the association kernel writes its record(s) into
@@ -482,20 +579,35 @@ class TrackerSettings:
     _box = property(lambda self: self._table.box)
     _device_kalman = property(lambda self: self.use_kalman and self.kalman == "device")
 
-    def _apply_with_kalman(self, tracks, src_trk, src_det, flags, d_emb, d_box, E, cur):
+    def _apply_with_kalman(self, tracks, src_trk, src_det, flags, d_emb, d_box, E, cur, keep_emb=None):
         """kalman="device": the table update and the filter launch for `tracks` (row order of the new table), then the filtered box of every
         born / matched track from the launch's record (a carried track keeps its `bbox`).  The caller holds the device guard."""
-        hit, boxes, status = self._table.apply_kalman(src_trk, src_det, flags, d_emb, d_box, E, self.smoothing_factor, cur)
+        hit, boxes, status = self._table.apply_kalman(src_trk, src_det, flags, d_emb, d_box, E, self.smoothing_factor, cur, keep_emb)
         for r, b in zip(hit.tolist(), boxes):
             tracks[r].bbox = b
         self.kalman_skipped = int(np.count_nonzero(status))
 
+    @staticmethod
+    def _check_low(low_threshold, detection_threshold):
+        if low_threshold is not None and not 0 <= low_threshold <= detection_threshold:
+            raise ValueError(f"low_threshold={low_threshold!r}: expected a value in [0, detection_threshold = {detection_threshold!r}]")
+
     def _thresholds(self, kwargs):
-        """(detection, re-ID, box) thresholds of one call: the settings unless the call overrides them."""
+        """(detection, re-ID, box, low, low box) thresholds of one call: the settings unless the call overrides them (low: None = no low-score
+        stage; low box: the call's box threshold unless set)."""
         if not kwargs:
-            return self.detection_threshold, self.reid_threshold, self.box_threshold
-        return (kwargs.get("detection_threshold", self.detection_threshold), kwargs.get("reid_threshold", self.reid_threshold),
-                kwargs.get("box_threshold", self.box_threshold))
+            low_box = self.box_threshold if self.low_box_threshold is None else self.low_box_threshold
+            return self.detection_threshold, self.reid_threshold, self.box_threshold, self.low_threshold, low_box
+        det, box = kwargs.get("detection_threshold", self.detection_threshold), kwargs.get("box_threshold", self.box_threshold)
+        low, low_box = kwargs.get("low_threshold", self.low_threshold), kwargs.get("low_box_threshold", self.low_box_threshold)
+        self._check_low(low, det)
+        if low is not None and (self._host_box is not None or self.box_cost is None):
+            raise ValueError(f"low_threshold={low!r} with box_cost={self.box_cost!r}: the low-score stage matches by the 'iou' / 'giou' box cost")
+        return det, kwargs.get("reid_threshold", self.reid_threshold), box, low, box if low_box is None else low_box
+
+    def _eligible(self, tracks):
+        """low_match: which of `tracks` may be matched in the low-score stage, by their state at the start of the step (None: all)."""
+        return None if self.low_match == "all" else [t.state is TrackState.ACTIVE for t in tracks]
 
     def _detect(self, images, kwargs):
         """The model's detections for a batch of frames (tracker.py:98-104); the kernel that computes a frame's costs also writes its

@@ -25,6 +25,12 @@ matrices — straight into mapped host memory, ONE stream synchronisation makes 
 cdist name or a callable, and a callable `box_cost`
 (tracker.py:51, 62-64), are computed on the host from copies only with `allow_host_cost=True` (otherwise the constructor raises).
 There is no CPU fallback for the device path: without the HIP library or a GPU, `update` raises.
+`low_threshold` (opt-in; None is the path above, entry points and bytes included): BYTE's low-score association — after the two stages the
+tracks still unmatched (`low_match`: the ACTIVE ones, or all) are matched by box cost alone against the detections with low_threshold <=
+score < detection_threshold; a match gives the track the detection's box and leaves its embedding row untouched, and a low detection never
+starts a track.  `Tracker` reads the low detections' box costs from a larger frame record (cnl_track_frame_low_f32) and assigns on the host
+as it does stages 1 and 2; `TrackerBank` runs the stage on the device behind stage 2 (cnl_track_streams_low_f32).  `last_low_matches` lists
+the stage's (original detection index, track row) pairs.
 
 `Tracker` (one video) and `TrackerBank` (S videos, one frame each per step) are thin callers of the shared host side in _track_host.py:
 normalise the inputs, launch, read the record, assign (or take the device's lists), life cycle, table update, Kalman.
@@ -37,8 +43,9 @@ import torch
 
 from . import _lib
 from ._track_host import (_BOX_MODES, _REID_METRICS, _STATUS_TOO_LARGE, BoxKalman, Track, TrackerSettings, TrackState, _grown,  # noqa: F401
-                          _Mapped, _on, check_kept_count, frame_layout, launch_frame, life_cycle, match_with_threshold, normalise_detections,
-                          read_stream_record, streams_layout, streams_workspace_bytes, two_stage_assignment)
+                          _Mapped, _on, check_kept_count, frame_layout, frame_low_layout, launch_frame, launch_frame_low, life_cycle, low_stage,
+                          match_with_threshold, normalise_detections, read_stream_low_record, read_stream_record, streams_layout,
+                          streams_low_layout, streams_low_workspace_bytes, streams_workspace_bytes, two_stage_assignment)
 from .config import load_config
 
 
@@ -56,6 +63,8 @@ class Tracker(TrackerSettings):
         self.next_track_id = 0
         self.tracks: List[Track] = []
         self.last_costs = None      # (reid [n,T] f64, box [n,T] f32 | None, det_index [n]) of the last update (host numpy)
+        self.last_matches = None    # (kept-detection row, track row) pairs of stages 1 and 2 of the last update
+        self.last_low_matches = None        # low_threshold set: (original detection index, track row) pairs of the low-score stage
         self._table.clear()
 
     # ------------------------------------------------------------------ inference
@@ -85,24 +94,33 @@ class Tracker(TrackerSettings):
         synchronisation (the first makes the frame record readable), so that the filtered boxes are in `Track.bbox` when it returns."""
         dev = self.device
         d_box, d_score, d_emb, d_label, host, label_kind = normalise_detections(dev, bboxes, labels, scores, embeddings)
-        detection_threshold, reid_threshold, box_threshold = self._thresholds(kwargs)
+        detection_threshold, reid_threshold, box_threshold, low_threshold, low_box_threshold = self._thresholds(kwargs)
         k, E = d_emb.shape
         T = len(self.tracks)
         table = self._table
         box_mode = 0 if self._host_box is not None else _BOX_MODES[self.box_cost]
         with_dets = host is None
+        low = low_threshold is not None
         with _on(dev):
             cur = torch.cuda.current_stream(dev)
             table.wait_for_other_stream(cur)
-            rec = self._rec = _grown(self._rec, frame_layout(k, T, with_dets).bytes, 1 << 18)
-            n, det_index, h_box, h_score, h_label, reid, box = launch_frame(
-                _lib.load(), rec, d_emb.data_ptr(), d_box.data_ptr(), d_score.data_ptr(), d_label.data_ptr() if label_kind else None, label_kind,
-                k, E, detection_threshold, table.emb.data_ptr() if T else None, table.box.data_ptr() if T else None, T, box_mode,
-                _REID_METRICS.get(self.reid_cost, 0), with_dets, cur)
+            rec = self._rec = _grown(self._rec, (frame_low_layout if low else frame_layout)(k, T, with_dets).bytes, 1 << 18)
+            if low:
+                n, det_index, h_box, h_score, h_label, reid, box, low_index, low_box = launch_frame_low(
+                    _lib.load(), rec, d_emb.data_ptr(), d_box.data_ptr(), d_score.data_ptr(), d_label.data_ptr() if label_kind else None, label_kind,
+                    k, E, detection_threshold, low_threshold, table.emb.data_ptr() if T else None, table.box.data_ptr() if T else None, T, box_mode,
+                    _REID_METRICS.get(self.reid_cost, 0), with_dets, cur)
+            else:
+                n, det_index, h_box, h_score, h_label, reid, box = launch_frame(
+                    _lib.load(), rec, d_emb.data_ptr(), d_box.data_ptr(), d_score.data_ptr(), d_label.data_ptr() if label_kind else None, label_kind,
+                    k, E, detection_threshold, table.emb.data_ptr() if T else None, table.box.data_ptr() if T else None, T, box_mode,
+                    _REID_METRICS.get(self.reid_cost, 0), with_dets, cur)
         if not with_dets:
             h_box, h_label, h_score = host
             check_kept_count(h_score, detection_threshold, n)
         self.d2h_bytes = 32 + 4 * n + (24 * k if with_dets else 0) + (12 if box_mode else 8) * n * T      # bytes the kernel stored over PCIe
+        if low:
+            self.d2h_bytes += 16 + 4 * len(low_index) * (1 + T)
         self.last_costs = None
 
         # ---- assignment on the host (tracker.py:139-176), track life cycle, the rows of the new device table ----
@@ -111,17 +129,26 @@ class Tracker(TrackerSettings):
         matches, unmatched_dets, unmatched_tracks = two_stage_assignment(reid, reid_threshold, box_threshold, box)
         if T:
             self.last_costs = (reid.copy(), None if box is None or callable(box) else box.copy(), det_index)
-        self.tracks, self.next_track_id, old_rows, det_rows = life_cycle(self.tracks, matches, unmatched_dets, unmatched_tracks, det_index,
-                                                                         h_box, h_label, self.next_track_id, self)
+        self.last_matches = matches
+        keep_emb = None
+        if low:
+            low_matches, unmatched_tracks = low_stage(low_box, low_index, unmatched_tracks, self._eligible(self.tracks), low_box_threshold)
+            self.last_low_matches = low_matches
+            self.tracks, self.next_track_id, old_rows, det_rows, keep_emb = life_cycle(
+                self.tracks, matches, unmatched_dets, unmatched_tracks, det_index, h_box, h_label, self.next_track_id, self, low_matches)
+        else:
+            self.last_low_matches = None
+            self.tracks, self.next_track_id, old_rows, det_rows = life_cycle(self.tracks, matches, unmatched_dets, unmatched_tracks, det_index,
+                                                                             h_box, h_label, self.next_track_id, self)
         if self._device_kalman:             # every track predicts at the end of the step, as on the host path below
             with _on(dev):
-                self._apply_with_kalman(self.tracks, old_rows, det_rows, 1, d_emb, d_box, E, cur)
+                self._apply_with_kalman(self.tracks, old_rows, det_rows, 1, d_emb, d_box, E, cur, keep_emb)
             self.d2h_bytes += 36 * len(self.tracks)
             for r, t in enumerate(self.tracks):
                 t._row = r
             return
         with _on(dev):
-            table.apply(old_rows, det_rows, d_emb, d_box, E, self.smoothing_factor, cur)
+            table.apply(old_rows, det_rows, d_emb, d_box, E, self.smoothing_factor, cur, keep_emb)
         for r, t in enumerate(self.tracks):
             t._row = r
         if self.use_kalman and self.tracks:
@@ -175,7 +202,8 @@ class TrackerBank(TrackerSettings):
 
     def __init__(self, num_streams, model=None, nms_kernel=3, num_detections=300, detection_threshold=0.3, reid_cost="cosine",
                  reid_threshold=0.2, box_cost="iou", box_threshold=0.5, smoothing_factor=0.5, use_kalman=False,
-                 max_inactive_age=30, min_birth_age=2, device=None, allow_host_cost=False, kalman="host"):
+                 max_inactive_age=30, min_birth_age=2, device=None, allow_host_cost=False, low_threshold=None,
+                 low_box_threshold=None, low_match="active", kalman="host"):
         if isinstance(num_streams, bool) or not isinstance(num_streams, (int, np.integer)) or num_streams < 1:
             raise ValueError(f"num_streams={num_streams!r}: expected an integer >= 1")
         if callable(reid_cost) or callable(box_cost) or reid_cost not in _REID_METRICS:
@@ -187,8 +215,10 @@ class TrackerBank(TrackerSettings):
         self.num_streams = int(num_streams)
         self._off = np.zeros(self.num_streams + 1, np.int64)        # pooled device table: stream s owns rows _off[s] .. _off[s + 1]
         self._ctl = self._ws = self._redo_rec = None    # mapped live list + trk_off; device workspace; mapped record of a redone stream
+        self._elig = None           # low_match="active": mapped eligibility bytes of the pooled table's rows (cnl_track_streams_low_f32)
         super().__init__(model, nms_kernel, num_detections, detection_threshold, reid_cost, reid_threshold, box_cost, box_threshold,
-                         smoothing_factor, use_kalman, max_inactive_age, min_birth_age, device, kalman=kalman)
+                         smoothing_factor, use_kalman, max_inactive_age, min_birth_age, device, kalman=kalman, low_threshold=low_threshold,
+                         low_box_threshold=low_box_threshold, low_match=low_match)
 
     def __len__(self):
         return self.num_streams
@@ -208,10 +238,11 @@ class TrackerBank(TrackerSettings):
             self._table.clear()
             self._off[:] = 0
             self.last_matches = [None] * self.num_streams
+            self.last_low_matches = [None] * self.num_streams      # low_threshold set: (original detection index, track row) pairs per stream
             return
         s = self._check_streams([stream])[0]
         self._streams[s] = _StreamState()
-        self.last_matches[s] = None
+        self.last_matches[s] = self.last_low_matches[s] = None
         if self._off[s + 1] == self._off[s]:
             return
         # repack the pooled table without stream s's rows: the pooled apply launch with every kept row copied through (src_det = -1)
@@ -262,20 +293,31 @@ class TrackerBank(TrackerSettings):
         return out
 
     # ------------------------------------------------------------------ one step
-    def _host_association(self, i, s, d_box, d_score, d_emb, detection_threshold, reid_threshold, box_threshold):
+    def _host_association(self, i, s, d_box, d_score, d_emb, detection_threshold, reid_threshold, box_threshold, low_threshold=None,
+                          low_box_threshold=None):
         """Stream s's association through the single-stream path (cnl_track_frame_f32 + scipy on the host) on its slice of the operands:
-        what a stream with non-finite costs is redone with, so that the caller sees what Tracker raises (scipy: ValueError)."""
+        what a stream with non-finite costs is redone with, so that the caller sees what Tracker raises (scipy: ValueError).  With
+        low_threshold the low-score stage too (cnl_track_frame_low_f32): the three lists, then its matches."""
         dev = self.device
         k, E = d_emb.shape[1], d_emb.shape[2]
         t0, T = int(self._off[s]), int(self._off[s + 1] - self._off[s])
         table = self._table
-        rec = self._redo_rec = _grown(self._redo_rec, frame_layout(k, T, 0).bytes, 0)
+        low = low_threshold is not None
+        rec = self._redo_rec = _grown(self._redo_rec, (frame_low_layout if low else frame_layout)(k, T, 0).bytes, 0)
+        operands = (d_emb[i].data_ptr(), d_box[i].data_ptr(), d_score[i].data_ptr(), None, 0, k, E)
+        table_args = (table.emb[t0:].data_ptr() if T else None, table.box[t0:].data_ptr() if T else None, T, _BOX_MODES[self.box_cost],
+                      _REID_METRICS[self.reid_cost], 0)
         with _on(dev):
-            _, _, _, _, _, reid, box = launch_frame(
-                _lib.load(), rec, d_emb[i].data_ptr(), d_box[i].data_ptr(), d_score[i].data_ptr(), None, 0, k, E, detection_threshold,
-                table.emb[t0:].data_ptr() if T else None, table.box[t0:].data_ptr() if T else None, T, _BOX_MODES[self.box_cost],
-                _REID_METRICS[self.reid_cost], 0, torch.cuda.current_stream(dev))
-        return two_stage_assignment(reid, reid_threshold, box_threshold, box)
+            if low:
+                *_, reid, box, low_index, low_box = launch_frame_low(_lib.load(), rec, *operands, detection_threshold, low_threshold, *table_args,
+                                                                     torch.cuda.current_stream(dev))
+            else:
+                _, _, _, _, _, reid, box = launch_frame(_lib.load(), rec, *operands, detection_threshold, *table_args, torch.cuda.current_stream(dev))
+        matches, unmatched_dets, unmatched_tracks = two_stage_assignment(reid, reid_threshold, box_threshold, box)
+        if not low:
+            return matches, unmatched_dets, unmatched_tracks
+        low_matches, unmatched_tracks = low_stage(low_box, low_index, unmatched_tracks, self._eligible(self._streams[s].tracks), low_box_threshold)
+        return matches, unmatched_dets, unmatched_tracks, low_matches
 
     def update_batch(self, bboxes, labels, scores, embeddings, streams=None, **kwargs):
         """One frame's detections for each participating stream: [L, k, 4], [L, k], [L, k], [L, k, E] (numpy arrays or torch tensors; L =
@@ -288,15 +330,16 @@ class TrackerBank(TrackerSettings):
         dev = self.device
         S, L = self.num_streams, len(live)
         d_box, d_score, d_emb, d_label, host, label_kind = normalise_detections(dev, bboxes, labels, scores, embeddings, (L,))
-        detection_threshold, reid_threshold, box_threshold = self._thresholds(kwargs)
+        detection_threshold, reid_threshold, box_threshold, low_threshold, low_box_threshold = self._thresholds(kwargs)
+        low = low_threshold is not None
         lib = _lib.load()
         k, E = int(d_emb.shape[1]), int(d_emb.shape[2])
         with_dets = host is None
         table, off = self._table, self._off
         R = int(off[S])
         T_max = max(int(off[s + 1] - off[s]) for s in live)
-        stride = streams_layout(k, T_max, with_dets).bytes
-        ws_need = streams_workspace_bytes(S, k, R)
+        stride = (streams_low_layout if low else streams_layout)(k, T_max, with_dets).bytes
+        ws_need = (streams_low_workspace_bytes if low else streams_workspace_bytes)(S, k, R)
         with _on(dev):
             cur = torch.cuda.current_stream(dev)
             table.wait_for_other_stream(cur)
@@ -310,29 +353,47 @@ class TrackerBank(TrackerSettings):
             ctl = self._ctl.np.view(np.int32)
             ctl[:L] = live
             ctl[S:2 * S + 1] = off
-            _lib.check(lib.cnl_track_streams_f32(d_emb.data_ptr(), d_box.data_ptr(), d_score.data_ptr(), d_label.data_ptr() if label_kind else None,
-                                                 label_kind, S, L, self._ctl.ptr, k, E, float(detection_threshold), float(reid_threshold),
-                                                 float(box_threshold), table.emb.data_ptr() if R else None, table.box.data_ptr() if R else None,
-                                                 self._ctl.ptr + 4 * S, R, T_max, _BOX_MODES[self.box_cost], _REID_METRICS[self.reid_cost],
-                                                 int(with_dets), self._ws.data_ptr(), self._ws.numel(), rec.ptr, stride,
-                                                 ctypes.c_void_p(cur.cuda_stream)), "cnl_track_streams_f32")
+            operands = (d_emb.data_ptr(), d_box.data_ptr(), d_score.data_ptr(), d_label.data_ptr() if label_kind else None, label_kind, S, L,
+                        self._ctl.ptr, k, E, float(detection_threshold), float(reid_threshold), float(box_threshold))
+            tables = (table.emb.data_ptr() if R else None, table.box.data_ptr() if R else None, self._ctl.ptr + 4 * S)
+            rest = (R, T_max, _BOX_MODES[self.box_cost], _REID_METRICS[self.reid_cost], int(with_dets), self._ws.data_ptr(), self._ws.numel(), rec.ptr,
+                    stride, ctypes.c_void_p(cur.cuda_stream))
+            if low:
+                eligible = None
+                if self.low_match != "all" and R:
+                    # the rows' eligibility sits in mapped memory the assign kernel reads (the rows of this step's streams only): finished
+                    # with at this step's synchronisation
+                    self._elig = _grown(self._elig, R, 1 << 12)
+                    for s in live:
+                        flags = bytes([t.state is TrackState.ACTIVE for t in self._streams[s].tracks])
+                        self._elig.np[off[s]:off[s] + len(flags)] = np.frombuffer(flags, np.uint8)
+                    eligible = self._elig.ptr
+                _lib.check(lib.cnl_track_streams_low_f32(*operands, float(low_threshold), float(low_box_threshold), *tables, eligible, *rest),
+                           "cnl_track_streams_low_f32")
+            else:
+                _lib.check(lib.cnl_track_streams_f32(*operands, *tables, *rest), "cnl_track_streams_f32")
             cur.synchronize()
         # ---- read every stream's lists first: an exception leaves all streams untouched ----
         assoc, d2h = {}, 0
         for i, s in enumerate(live):
-            n, T, status, det_index, h_box, _, h_label, *lists = read_stream_record(rec.np[s * stride:(s + 1) * stride])
+            n, T, status, det_index, h_box, _, h_label, *lists = (read_stream_low_record if low else read_stream_record)(rec.np[s * stride:(s + 1) * stride])
             if status in _STATUS_TOO_LARGE:
                 raise ValueError(f"stream {s}: association status {status} (k = {k}, T = {T}: beyond the supported sizes)")
             d2h += 64 + 4 * n + (24 * k if with_dets else 0) + 8 * len(lists[0]) + 4 * len(lists[1]) + 4 * len(lists[2])
+            if low:
+                n_low = lists.pop(3)
+                d2h += 32 + 4 * n_low + 8 * len(lists[3])
             if status:
-                lists = self._host_association(i, s, d_box, d_score, d_emb, detection_threshold, reid_threshold, box_threshold)
+                lists = self._host_association(i, s, d_box, d_score, d_emb, detection_threshold, reid_threshold, box_threshold, low_threshold,
+                                               low_box_threshold)
             if not with_dets:
                 h_box, h_label = host[0][i], host[1][i]
                 check_kept_count(host[2][i], detection_threshold, n, f"stream {s}: ")
-            assoc[s] = (i * k, *lists, det_index, h_box, h_label)
+            assoc[s] = (i * k, *lists[:3], det_index, h_box, h_label, *lists[3:])
         self.d2h_bytes = d2h
 
         # ---- track life cycle per stream (host) + the rows of the new pooled table ----
+        keep_emb = [] if low else None              # low: per row of the new pooled table, 1 = a low-score match (the embedding is carried over)
         src_trk, src_det, predict = [], [], []      # predict: (flag, rows) per stream for cnl_track_kalman_f64 — only the streams of this step predict
         for s, st in enumerate(self._streams):
             base = int(off[s])
@@ -340,22 +401,30 @@ class TrackerBank(TrackerSettings):
                 src_trk.extend(range(base, base + len(st.tracks)))
                 src_det.extend([-1] * len(st.tracks))
                 predict.append((0, len(st.tracks)))
+                if low:
+                    keep_emb.extend([0] * len(st.tracks))
                 continue
             det_base, matches, *rest = assoc[s]
             self.last_matches[s] = matches
-            st.tracks, st.next_track_id, old_rows, det_rows = life_cycle(st.tracks, matches, *rest, st.next_track_id, self)
+            if low:
+                self.last_low_matches[s] = rest[5]
+                st.tracks, st.next_track_id, old_rows, det_rows, kept = life_cycle(st.tracks, matches, *rest[:5], st.next_track_id, self, rest[5])
+                keep_emb.extend(kept)
+            else:
+                self.last_low_matches[s] = None
+                st.tracks, st.next_track_id, old_rows, det_rows = life_cycle(st.tracks, matches, *rest, st.next_track_id, self)
             src_trk.extend(base + r if r >= 0 else -1 for r in old_rows)
             src_det.extend(det_base + d if d >= 0 else -1 for d in det_rows)
             predict.append((1, len(old_rows)))
         if self._device_kalman:
             flags = np.repeat(np.array([p for p, _ in predict], np.int32), [n for _, n in predict])
             with _on(dev):
-                self._apply_with_kalman([t for st in self._streams for t in st.tracks], src_trk, src_det, flags, d_emb, d_box, E, cur)
+                self._apply_with_kalman([t for st in self._streams for t in st.tracks], src_trk, src_det, flags, d_emb, d_box, E, cur, keep_emb)
             self.d2h_bytes += 36 * len(src_trk)
             self._set_offsets()
             return
         with _on(dev):
-            table.apply(src_trk, src_det, d_emb, d_box, E, self.smoothing_factor, cur)
+            table.apply(src_trk, src_det, d_emb, d_box, E, self.smoothing_factor, cur, keep_emb)
         self._set_offsets()
         if self.use_kalman and off[S]:
             # the boxes of all streams go up in ONE copy; only the streams of this step predict

@@ -46,15 +46,18 @@ __device__ __forceinline__ void seq_dots(const float* __restrict__ u, const floa
     }
 }
 
-// The (tiny) stable compaction {i : score[i] >= thr} into LDS, rebuilt by every workgroup — cheaper than a second launch.  Returns n.
-__device__ __forceinline__ int compact_scores(const float* __restrict__ det_score, const int k, const float thr, int* sel, int* wave_sum) {
+// The (tiny) stable compaction {i : score[i] >= thr} — WINDOW: {i : thr <= score[i] < below} — into LDS, rebuilt by every workgroup: cheaper
+// than a second launch.  Returns n.  (May be called again with the same wave_sum: every read of it lies before the closing barrier.)
+template <bool WINDOW>
+__device__ __forceinline__ int compact_scores_in(const float* __restrict__ det_score, const int k, const float thr, const float below, int* sel,
+                                                 int* wave_sum) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     // thread t owns scores 4t..4t+3 (k <= 1024)
     int flag[4], cnt = 0;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int idx = tid * 4 + i;
-        flag[i] = idx < k && det_score[idx] >= thr;         // NaN compares false, as in numpy
+        flag[i] = idx < k && det_score[idx] >= thr && (!WINDOW || det_score[idx] < below);         // NaN compares false, as in numpy
         cnt += flag[i];
     }
     int incl = cnt;                                          // inclusive scan of cnt over the wave
@@ -77,6 +80,9 @@ __device__ __forceinline__ int compact_scores(const float* __restrict__ det_scor
         if (flag[i]) sel[pos++] = tid * 4 + i;
     __syncthreads();
     return n;
+}
+__device__ __forceinline__ int compact_scores(const float* __restrict__ det_score, const int k, const float thr, int* sel, int* wave_sum) {
+    return compact_scores_in<false>(det_score, k, thr, 0.f, sel, wave_sum);
 }
 
 // Row mean in float64 in numpy's order (np.add.reduce over a contiguous last axis = pairwise summation: eight strided partial sums per block of <= 128 elements,
@@ -103,6 +109,33 @@ __device__ double np_pairwise_sum(const float* a, int n) {
     int n2 = n / 2;
     n2 -= n2 % 8;
     return np_pairwise_sum(a, n2) + np_pairwise_sum(a + n2, n - n2);
+}
+
+// Box distance of one (detection box, track box) pair: utils/box.py:49-92 in float32, numpy's operation order; box_mode 1 "iou", 2 "giou".
+__device__ __forceinline__ float box_pair_cost(const float4 a, const float4 b, const int box_mode) {
+    const float area1 = ((a.z - a.x) * (a.w - a.y));
+    const float area2 = ((b.z - b.x) * (b.w - b.y));
+    const float w = np_max((np_min(a.z, b.z) - np_max(a.x, b.x)), 0.f);
+    const float h = np_max((np_min(a.w, b.w) - np_max(a.y, b.y)), 0.f);
+    const float inter = (w * h);
+    const float uni = ((area1 + area2) - inter);
+    const float iou = (inter / uni);
+    float score = iou;
+    if (box_mode == 2) {
+        const float wi = np_max((np_max(a.z, b.z) - np_min(a.x, b.x)), 0.f);
+        const float hi = np_max((np_max(a.w, b.w) - np_min(a.y, b.y)), 0.f);
+        const float hull = (wi * hi);
+        score = (iou - ((hull - uni) / hull));
+    }
+    return (1.f - score);
+}
+
+// Box costs alone of pair p = r * T + t of an n x T problem (the low-score stage: no re-ID matrix), written at box_cost[p].
+__device__ __forceinline__ void pair_box_cost_at(const long p, const int* sel, const int n, const float* __restrict__ det_box,
+                                                 const float* __restrict__ trk_box, const int T, const int box_mode, float* __restrict__ box_cost) {
+    if (T <= 0 || p >= (long)n * T) return;
+    const int r = (int)(p / T), t = (int)(p - (long)r * T);
+    box_cost[p] = box_pair_cost(*reinterpret_cast<const float4*>(det_box + (long)sel[r] * 4), *reinterpret_cast<const float4*>(trk_box + (long)t * 4), box_mode);
 }
 
 // Costs of pair p = r * T + t (kept detection r, track t) of an n x T problem, written at reid_cost[p] / box_cost[p].
@@ -160,25 +193,8 @@ __device__ __forceinline__ void pair_costs_at(const long p, const int* sel, cons
         }
         reid_cost[p] = reid_metric == 6 ? acc / den : acc;
     }
-    if (box_mode) {   // utils/box.py:49-92 in float32, numpy's operation order
-        const float4 a = *reinterpret_cast<const float4*>(det_box + (long)d * 4);
-        const float4 b = *reinterpret_cast<const float4*>(trk_box + (long)t * 4);
-        const float area1 = ((a.z - a.x) * (a.w - a.y));
-        const float area2 = ((b.z - b.x) * (b.w - b.y));
-        const float w = np_max((np_min(a.z, b.z) - np_max(a.x, b.x)), 0.f);
-        const float h = np_max((np_min(a.w, b.w) - np_max(a.y, b.y)), 0.f);
-        const float inter = (w * h);
-        const float uni = ((area1 + area2) - inter);
-        const float iou = (inter / uni);
-        float score = iou;
-        if (box_mode == 2) {
-            const float wi = np_max((np_max(a.z, b.z) - np_min(a.x, b.x)), 0.f);
-            const float hi = np_max((np_max(a.w, b.w) - np_min(a.y, b.y)), 0.f);
-            const float hull = (wi * hi);
-            score = (iou - ((hull - uni) / hull));
-        }
-        box_cost[p] = (1.f - score);
-    }
+    if (box_mode)
+        box_cost[p] = box_pair_cost(*reinterpret_cast<const float4*>(det_box + (long)d * 4), *reinterpret_cast<const float4*>(trk_box + (long)t * 4), box_mode);
 }
 
 // Workgroup blockIdx.x of a 1-D grid of 256-thread workgroups handles pairs 256 * blockIdx.x ... + 255.

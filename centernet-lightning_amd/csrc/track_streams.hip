@@ -9,6 +9,8 @@
 //   streams_assign_kernel   per stream: stage 1 (re-ID matrix, cost < reid_threshold), stage 2 (box-cost sub-matrix of what is still
 //                           unmatched, cost < box_threshold), match / unmatched lists into the stream's record (mapped host memory)
 //   lsap_batch_kernel       the solver alone on B caller-supplied matrices (cnl_lsap_batch_f64)
+// cnl_track_streams_low_f32 instantiates both stream kernels with LOW: the cost launch also compacts the low-score detections and writes their
+// box costs, the assign kernel runs a third stage (BYTE) on them behind stage 2 — same bodies, same solver, same LDS bound.
 //
 // The solver is scipy.optimize.linear_sum_assignment's algorithm (rectangular shortest augmenting path, Crouse 2016) in scipy's
 // order and in float64, because the RESULT must be scipy's, ties included: box-cost matrices are full of ties (every non-overlapping
@@ -43,8 +45,11 @@ struct StreamWs {
     double *reid, *sub;
     float* box;
     int *n, *col, *ud, *ut, *tflag;
+    float* low_box;     // LOW only: behind everything above, f32 low_box[P] | int32 n_low[S]
+    int* n_low;
 };
 __host__ __device__ inline size_t streams_ws_bytes(long S, long k, long R) { return 20ul * k * R + 4ul * (S + 2 * S * k + 2 * R); }
+__host__ __device__ inline size_t streams_low_ws_bytes(long S, long k, long R) { return streams_ws_bytes(S, k, R) + 4ul * k * R + 4ul * S; }
 __device__ __forceinline__ StreamWs streams_ws(char* ws, int S, int k, int R, int s, int t0) {
     const long P = (long)k * R;
     StreamWs w;
@@ -57,32 +62,41 @@ __device__ __forceinline__ StreamWs streams_ws(char* ws, int S, int k, int R, in
     w.ud = ints + S + (long)S * k + (long)s * k;
     w.ut = ints + S + 2l * S * k + t0;
     w.tflag = w.ut + R;
+    char* low = ws + streams_ws_bytes(S, k, R);
+    w.low_box = reinterpret_cast<float*>(low) + (long)k * t0;
+    w.n_low = reinterpret_cast<int*>(low + 4 * P) + s;
     return w;
 }
 // Record of one stream: int32 header[16] | det_index[k] | (boxes[k][4] scores[k] labels[k]) | matches[k][2] | unmatched dets[k] | unmatched tracks[T]
+// LOW: int32 header[24], and behind the unmatched tracks: low_index[k] | low_matches[k][2]
 struct StreamRec {
-    int off_index, off_dets, off_match, off_udet, off_utrk;
+    int off_index, off_dets, off_match, off_udet, off_utrk, off_low_index, off_low_match;
     long bytes;
 };
-__host__ __device__ inline StreamRec stream_rec(int k, int T, int with_dets) {
+__host__ __device__ inline StreamRec stream_rec(int k, int T, int with_dets, bool low = false) {
     StreamRec r;
-    r.off_index = 64;
-    r.off_dets = (64 + 4 * k + 7) & ~7;
+    r.off_index = low ? 96 : 64;
+    r.off_dets = (r.off_index + 4 * k + 7) & ~7;
     r.off_match = r.off_dets + (with_dets ? 24 * k : 0);
     r.off_udet = r.off_match + 8 * k;
     r.off_utrk = r.off_udet + 4 * k;
-    r.bytes = ((long)r.off_utrk + 4l * T + 7) & ~7l;
+    r.off_low_index = r.off_utrk + 4 * T;
+    r.off_low_match = r.off_low_index + 4 * k;
+    r.bytes = ((low ? (long)r.off_low_match + 8l * k : (long)r.off_utrk + 4l * T) + 7) & ~7l;
     return r;
 }
 
 // grid (pair blocks of the largest stream, S_live): blockIdx.y = slot i of this step's detections, stream live[i].
+template <bool LOW>
 __global__ __launch_bounds__(256) void streams_costs_kernel(const float* __restrict__ det_emb, const float* __restrict__ det_box,
                                                             const float* __restrict__ det_score, const void* __restrict__ det_label, int label_kind,
                                                             const int* __restrict__ live, const int* __restrict__ trk_off, int S, int k, int E, float thr,
+                                                            float low_thr,
                                                             const float* __restrict__ trk_emb, const float* __restrict__ trk_box, int R, int T_max,
                                                             int box_mode, int reid_metric, int with_dets, char* __restrict__ ws,
                                                             char* __restrict__ record, long record_stride) {
     __shared__ int sel[MAXK];
+    __shared__ int low_sel[LOW ? MAXK : 1];
     __shared__ int wave_sum[4];
     const int i = blockIdx.y, s = live[i];
     if (s < 0 || s >= S) return;                                   // (refused on the host; never index with it)
@@ -92,15 +106,24 @@ __global__ __launch_bounds__(256) void streams_costs_kernel(const float* __restr
     const float* db = det_box + (long)i * k * 4;
     const float* dsc = det_score + (long)i * k;
     const int n = compact_scores(dsc, k, thr, sel, wave_sum);
+    const int n_low = LOW ? compact_scores_in<true>(dsc, k, low_thr, thr, low_sel, wave_sum) : 0;
     if (blockIdx.x == 0) {
         const int tid = threadIdx.x;
         char* rec = record + (long)s * record_stride;
-        const StreamRec ro = stream_rec(k, T_max, with_dets);
+        const StreamRec ro = stream_rec(k, T_max, with_dets, LOW);
         int* hdr = reinterpret_cast<int*>(rec);
         if (tid == 0) {
             hdr[0] = n; hdr[1] = k; hdr[2] = T; hdr[4] = ro.off_index; hdr[5] = ro.off_dets; hdr[6] = ro.off_match; hdr[7] = ro.off_udet;
             hdr[8] = ro.off_utrk; hdr[13] = with_dets; hdr[14] = i; hdr[15] = s;
             if (table_ok) *streams_ws(ws, S, k, R, s, t0).n = n;
+            if (LOW) {
+                hdr[16] = n_low; hdr[18] = ro.off_low_index; hdr[19] = ro.off_low_match; hdr[20] = hdr[21] = hdr[22] = hdr[23] = 0;
+                if (table_ok) *streams_ws(ws, S, k, R, s, t0).n_low = n_low;
+            }
+        }
+        if (LOW) {
+            int* low_index = reinterpret_cast<int*>(rec + ro.off_low_index);
+            for (int q = tid; q < n_low; q += 256) low_index[q] = low_sel[q];
         }
         int* det_index = reinterpret_cast<int*>(rec + ro.off_index);
         for (int q = tid; q < n; q += 256) det_index[q] = sel[q];
@@ -119,6 +142,8 @@ __global__ __launch_bounds__(256) void streams_costs_kernel(const float* __restr
     const StreamWs w = streams_ws(ws, S, k, R, s, t0);
     pair_costs_at((long)blockIdx.x * 256 + threadIdx.x, sel, n, de, db, E, trk_emb + (long)t0 * E, trk_box + (long)t0 * 4, T, box_mode, reid_metric,
                   w.reid, w.box);
+    if (LOW)      // n_low <= k: the grid that covers k * T_max pairs covers these
+        pair_box_cost_at((long)blockIdx.x * 256 + threadIdx.x, low_sel, n_low, db, trk_box + (long)t0 * 4, T, box_mode, w.low_box);
 }
 
 // lanes with `flag` take consecutive positions from `count` on, in lane order (count: uniform, advanced)
@@ -129,9 +154,13 @@ __device__ __forceinline__ int wave_pos(const bool flag, int& count) {
     return pos;
 }
 
-// One single-wave workgroup per live stream: both assignment stages and the lists of the stream's record.
+// One single-wave workgroup per live stream: both assignment stages and the lists of the stream's record.  LOW: then stage 3 — the tracks still
+// unmatched that trk_eligible admits (null: all) against the low-score detections, by box cost < low_box_thr; the unmatched-track list is what
+// remains after it.
+template <bool LOW>
 __global__ __launch_bounds__(64) void streams_assign_kernel(const int* __restrict__ live, const int* __restrict__ trk_off, int S, int k, int R, int T_max,
-                                                            double reid_thr, float box_thr, int box_mode, int with_dets, char* __restrict__ ws,
+                                                            double reid_thr, float box_thr, float low_box_thr,
+                                                            const uint8_t* __restrict__ trk_eligible, int box_mode, int with_dets, char* __restrict__ ws,
                                                             char* __restrict__ record, long record_stride, int nr_cap, int nc_cap) {
     extern __shared__ double lsap_lds[];
     const int lane = threadIdx.x, s = live[blockIdx.x];
@@ -140,11 +169,11 @@ __global__ __launch_bounds__(64) void streams_assign_kernel(const int* __restric
     int* hdr = reinterpret_cast<int*>(rec);
     const int t0 = trk_off[s], T = trk_off[s + 1] - t0;
     int status = (t0 >= 0 && T >= 0 && t0 + T <= R) ? (T <= T_max ? LSAP_OK : LSAP_TOO_LARGE) : STREAM_BAD_TABLE;
-    const StreamRec ro = stream_rec(k, T_max, with_dets);
+    const StreamRec ro = stream_rec(k, T_max, with_dets, LOW);
     int* omatch = reinterpret_cast<int*>(rec + ro.off_match);
     int* oud = reinterpret_cast<int*>(rec + ro.off_udet);
     int* out = reinterpret_cast<int*>(rec + ro.off_utrk);
-    int m = 0, m1 = 0, nu = 0, tu = 0;
+    int m = 0, m1 = 0, nu = 0, tu = 0, m3 = 0;
     if (status == LSAP_OK) {
         const StreamWs w = streams_ws(ws, S, k, R, s, t0);
         const LsapLds L = lsap_carve(lsap_lds, nr_cap, nc_cap);
@@ -211,6 +240,43 @@ __global__ __launch_bounds__(64) void streams_assign_kernel(const int* __restric
                 for (int x = lane; x < nu; x += 64) oud[x] = w.ud[x];
             }
             __syncthreads();
+            if (LOW && status == LSAP_OK) {
+                // stage 3: low_box[:, U] for U = the eligible tracks still unmatched (ascending), converted to float64 as scipy does
+                const int n_low = *w.n_low;
+                int n3 = 0;
+                for (int q0 = 0; q0 < T; q0 += 64) {
+                    const int t = q0 + lane;
+                    const bool fr = t < T && !w.tflag[t] && (trk_eligible == nullptr || trk_eligible[t0 + t] != 0);
+                    const int pos = wave_pos(fr, n3);
+                    if (fr) w.ut[pos] = t;
+                }
+                __syncthreads();
+                if (n_low > 0 && n3 > 0) {
+                    for (long p = lane; p < (long)n_low * n3; p += 64) {
+                        const int x = (int)(p / n3), y = (int)(p - (long)x * n3);
+                        w.sub[p] = (double)w.low_box[(long)x * T + w.ut[y]];
+                    }
+                    __syncthreads();
+                    const int st3 = lsap_problem(w.sub, n3, n_low, n3, nr_cap, nc_cap, L, w.col);
+                    __syncthreads();
+                    if (st3 != LSAP_OK) status = 32 + st3;
+                    else {
+                        int* olow = reinterpret_cast<int*>(rec + ro.off_low_match);
+                        for (int x0 = 0; x0 < n_low; x0 += 64) {      // float32 cost against the threshold as float32, as in stage 2
+                            const int x = x0 + lane;
+                            int t = -1;
+                            bool keep = false;
+                            if (x < n_low) {
+                                const int c = w.col[x];
+                                if (c >= 0) { t = w.ut[c]; keep = w.low_box[(long)x * T + t] < low_box_thr; }
+                            }
+                            const int pos = wave_pos(keep, m3);
+                            if (keep) { olow[2 * pos] = x; olow[2 * pos + 1] = t; w.tflag[t] = 1; }
+                        }
+                    }
+                    __syncthreads();
+                }
+            }
             tu = 0;
             if (status == LSAP_OK)
                 for (int q0 = 0; q0 < T; q0 += 64) {
@@ -224,10 +290,11 @@ __global__ __launch_bounds__(64) void streams_assign_kernel(const int* __restric
     if (lane == 0) {
         const bool ok = status == LSAP_OK;
         hdr[3] = status; hdr[9] = ok ? m : 0; hdr[10] = ok ? m1 : 0; hdr[11] = ok ? nu : 0; hdr[12] = ok ? tu : 0;
+        if (LOW) hdr[17] = ok ? m3 : 0;
     }
 }
 
-static cnl::DeviceOnce lsap_once, assign_once;
+static cnl::DeviceOnce lsap_once, assign_once, assign_low_once;
 constexpr int LSAP_LDS_MAX = 12 * LSAP_MAX_SHORT + 28 * LSAP_MAX_LONG;      // 126976 of the CU's 160 KiB
 
 }  // namespace cnl_track
@@ -261,43 +328,81 @@ extern "C" int64_t cnl_track_streams_record_bytes(int32_t k, int32_t T_max, int3
     return stream_rec(k, T_max, with_detections ? 1 : 0).bytes;
 }
 
+extern "C" int64_t cnl_track_streams_low_workspace_bytes(int32_t S, int32_t k, int32_t T_max) {
+    if (S <= 0 || k <= 0 || T_max < 0) return 0;
+    return (int64_t)streams_low_ws_bytes(S, k, (long)S * T_max);
+}
+
+extern "C" int64_t cnl_track_streams_low_record_bytes(int32_t k, int32_t T_max, int32_t with_detections) {
+    if (k <= 0 || T_max < 0) return 0;
+    return stream_rec(k, T_max, with_detections ? 1 : 0, true).bytes;
+}
+
+// cnl_track_streams_f32 (low = false; the three low arguments unused) and cnl_track_streams_low_f32: one set of checks, the same two launches.
+static int streams_launch(const char* name, bool low, const float* det_emb, const float* det_box, const float* det_score, const void* det_label,
+                          int32_t label_kind, int32_t S, int32_t S_live, const int32_t* live, int32_t k, int32_t E, float detection_threshold,
+                          double reid_threshold, float box_threshold, float low_threshold, float low_box_threshold, const float* trk_emb,
+                          const float* trk_box, const int32_t* trk_off, const uint8_t* trk_eligible, int32_t R, int32_t T_max, int32_t box_cost,
+                          int32_t reid_metric, int32_t with_detections, void* workspace, int64_t workspace_bytes, void* record, int64_t record_stride,
+                          void* stream) {
+    CNL_REQUIRE(det_emb && det_box && det_score && live && trk_off && workspace && record, CNL_E_BAD_ARG, "%s: null pointer", name);
+    CNL_REQUIRE(S > 0 && S_live > 0 && S_live <= S && k > 0 && E > 0 && R >= 0 && T_max >= 0, CNL_E_BAD_ARG,
+                "%s: bad S / S_live / k / E / R / T_max (%d / %d / %d / %d / %d / %d)", name, S, S_live, k, E, R, T_max);
+    CNL_REQUIRE(k <= MAXK, CNL_E_UNSUPPORTED, "%s: k = %d > %d detections per frame", name, k, MAXK);
+    CNL_REQUIRE(T_max <= LSAP_MAX_LONG, CNL_E_UNSUPPORTED, "%s: T_max = %d > %d tracks per stream", name, T_max, LSAP_MAX_LONG);
+    CNL_REQUIRE(S_live <= 65535, CNL_E_UNSUPPORTED, "%s: S_live = %d > 65535 streams per step", name, S_live);
+    CNL_REQUIRE(box_cost >= (low ? 1 : 0) && box_cost <= 2, CNL_E_BAD_ARG, "%s: box_cost must be %s1 (iou), 2 (giou)", name, low ? "" : "0 (none), ");
+    CNL_REQUIRE(!low || (low_threshold >= 0.f && low_threshold <= detection_threshold), CNL_E_BAD_ARG,
+                "%s: low_threshold %g must lie in [0, detection_threshold = %g]", name, (double)low_threshold, (double)detection_threshold);
+    CNL_REQUIRE(reid_metric >= 0 && reid_metric <= 7, CNL_E_BAD_ARG, "%s: reid_metric must be 0 (cosine) .. 7 (correlation)", name);
+    CNL_REQUIRE(label_kind >= 0 && label_kind <= 3 && (label_kind == 0 || det_label), CNL_E_BAD_ARG,
+                "%s: label_kind must be 0 (none), 1 (int64), 2 (int32), 3 (float32) with det_label set", name);
+    CNL_REQUIRE(R == 0 || trk_emb, CNL_E_BAD_ARG, "%s: R > 0 without track table", name);
+    CNL_REQUIRE(R == 0 || box_cost == 0 || trk_box, CNL_E_BAD_ARG, "%s: box cost requested without track boxes", name);
+    CNL_REQUIRE(((uintptr_t)record & 7) == 0 && ((uintptr_t)workspace & 7) == 0 && (record_stride & 7) == 0, CNL_E_BAD_ARG,
+                "%s: record, record_stride and workspace must be 8-byte aligned", name);
+    CNL_REQUIRE(inputs_aligned(det_emb, det_box, trk_emb, trk_box, E, R, box_cost), CNL_E_BAD_ARG, "%s: %s", name, INPUTS_ALIGNED);
+    const int wd = with_detections ? 1 : 0;
+    const int64_t rec_need = stream_rec(k, T_max, wd, low).bytes, ws_need = (int64_t)(low ? streams_low_ws_bytes(S, k, R) : streams_ws_bytes(S, k, R));
+    CNL_REQUIRE(record_stride >= rec_need, CNL_E_BAD_ARG, "%s: record_stride %ld, k = %d, T_max = %d needs %ld (cnl_track_streams%s_record_bytes)", name,
+                (long)record_stride, k, T_max, (long)rec_need, low ? "_low" : "");
+    CNL_REQUIRE(workspace_bytes >= ws_need, CNL_E_BAD_ARG, "%s: workspace holds %ld bytes, S = %d, k = %d, R = %d needs %ld", name, (long)workspace_bytes, S,
+                k, R, (long)ws_need);
+    const int lo = k < T_max ? k : T_max, hi = k < T_max ? T_max : k;
+    const int nr_cap = lo > 0 ? lo : 1, nc_cap = hi;
+    if (int rc = low ? cnl::kernel_setup(assign_low_once, (const void*)streams_assign_kernel<true>, LSAP_LDS_MAX)
+                     : cnl::kernel_setup(assign_once, (const void*)streams_assign_kernel<false>, LSAP_LDS_MAX))
+        return rc;
+    const long pairs = (long)k * T_max;
+    const unsigned gx = (unsigned)(pairs > 0 ? (pairs + 255) / 256 : 1);
+    hipLaunchKernelGGL(low ? streams_costs_kernel<true> : streams_costs_kernel<false>, dim3(gx, (unsigned)S_live), dim3(256), 0, (hipStream_t)stream, det_emb,
+                       det_box, det_score, det_label, label_kind, live, trk_off, S, k, E, detection_threshold, low_threshold, trk_emb, trk_box, R, T_max,
+                       box_cost, reid_metric, wd, (char*)workspace, (char*)record, (long)record_stride);
+    if (int rc = cnl::check_launch("track streams_costs_kernel")) return rc;
+    hipLaunchKernelGGL(low ? streams_assign_kernel<true> : streams_assign_kernel<false>, dim3((unsigned)S_live), dim3(64), lsap_lds_bytes(nr_cap, nc_cap),
+                       (hipStream_t)stream, live, trk_off, S, k, R, T_max, reid_threshold, box_threshold, low_box_threshold, trk_eligible, box_cost, wd,
+                       (char*)workspace, (char*)record, (long)record_stride, nr_cap, nc_cap);
+    return cnl::check_launch("track streams_assign_kernel");
+}
+
 extern "C" int cnl_track_streams_f32(const float* det_emb, const float* det_box, const float* det_score, const void* det_label, int32_t label_kind,
                                      int32_t S, int32_t S_live, const int32_t* live, int32_t k, int32_t E, float detection_threshold,
                                      double reid_threshold, float box_threshold, const float* trk_emb, const float* trk_box,
                                      const int32_t* trk_off, int32_t R, int32_t T_max, int32_t box_cost, int32_t reid_metric,
                                      int32_t with_detections, void* workspace, int64_t workspace_bytes, void* record, int64_t record_stride,
                                      void* stream) {
-    CNL_REQUIRE(det_emb && det_box && det_score && live && trk_off && workspace && record, CNL_E_BAD_ARG, "cnl_track_streams_f32: null pointer");
-    CNL_REQUIRE(S > 0 && S_live > 0 && S_live <= S && k > 0 && E > 0 && R >= 0 && T_max >= 0, CNL_E_BAD_ARG,
-                "cnl_track_streams_f32: bad S / S_live / k / E / R / T_max (%d / %d / %d / %d / %d / %d)", S, S_live, k, E, R, T_max);
-    CNL_REQUIRE(k <= MAXK, CNL_E_UNSUPPORTED, "cnl_track_streams_f32: k = %d > %d detections per frame", k, MAXK);
-    CNL_REQUIRE(T_max <= LSAP_MAX_LONG, CNL_E_UNSUPPORTED, "cnl_track_streams_f32: T_max = %d > %d tracks per stream", T_max, LSAP_MAX_LONG);
-    CNL_REQUIRE(S_live <= 65535, CNL_E_UNSUPPORTED, "cnl_track_streams_f32: S_live = %d > 65535 streams per step", S_live);
-    CNL_REQUIRE(box_cost >= 0 && box_cost <= 2, CNL_E_BAD_ARG, "cnl_track_streams_f32: box_cost must be 0 (none), 1 (iou), 2 (giou)");
-    CNL_REQUIRE(reid_metric >= 0 && reid_metric <= 7, CNL_E_BAD_ARG, "cnl_track_streams_f32: reid_metric must be 0 (cosine) .. 7 (correlation)");
-    CNL_REQUIRE(label_kind >= 0 && label_kind <= 3 && (label_kind == 0 || det_label), CNL_E_BAD_ARG,
-                "cnl_track_streams_f32: label_kind must be 0 (none), 1 (int64), 2 (int32), 3 (float32) with det_label set");
-    CNL_REQUIRE(R == 0 || trk_emb, CNL_E_BAD_ARG, "cnl_track_streams_f32: R > 0 without track table");
-    CNL_REQUIRE(R == 0 || box_cost == 0 || trk_box, CNL_E_BAD_ARG, "cnl_track_streams_f32: box cost requested without track boxes");
-    CNL_REQUIRE(((uintptr_t)record & 7) == 0 && ((uintptr_t)workspace & 7) == 0 && (record_stride & 7) == 0, CNL_E_BAD_ARG,
-                "cnl_track_streams_f32: record, record_stride and workspace must be 8-byte aligned");
-    CNL_REQUIRE(inputs_aligned(det_emb, det_box, trk_emb, trk_box, E, R, box_cost), CNL_E_BAD_ARG, "cnl_track_streams_f32: %s", INPUTS_ALIGNED);
-    const int wd = with_detections ? 1 : 0;
-    const int64_t rec_need = stream_rec(k, T_max, wd).bytes, ws_need = (int64_t)streams_ws_bytes(S, k, R);
-    CNL_REQUIRE(record_stride >= rec_need, CNL_E_BAD_ARG, "cnl_track_streams_f32: record_stride %ld, k = %d, T_max = %d needs %ld (cnl_track_streams_record_bytes)",
-                (long)record_stride, k, T_max, (long)rec_need);
-    CNL_REQUIRE(workspace_bytes >= ws_need, CNL_E_BAD_ARG, "cnl_track_streams_f32: workspace holds %ld bytes, S = %d, k = %d, R = %d needs %ld",
-                (long)workspace_bytes, S, k, R, (long)ws_need);
-    const int lo = k < T_max ? k : T_max, hi = k < T_max ? T_max : k;
-    const int nr_cap = lo > 0 ? lo : 1, nc_cap = hi;
-    if (int rc = cnl::kernel_setup(assign_once, (const void*)streams_assign_kernel, LSAP_LDS_MAX)) return rc;
-    const long pairs = (long)k * T_max;
-    const unsigned gx = (unsigned)(pairs > 0 ? (pairs + 255) / 256 : 1);
-    hipLaunchKernelGGL(streams_costs_kernel, dim3(gx, (unsigned)S_live), dim3(256), 0, (hipStream_t)stream, det_emb, det_box, det_score, det_label,
-                       label_kind, live, trk_off, S, k, E, detection_threshold, trk_emb, trk_box, R, T_max, box_cost, reid_metric, wd, (char*)workspace,
-                       (char*)record, (long)record_stride);
-    if (int rc = cnl::check_launch("track streams_costs_kernel")) return rc;
-    hipLaunchKernelGGL(streams_assign_kernel, dim3((unsigned)S_live), dim3(64), lsap_lds_bytes(nr_cap, nc_cap), (hipStream_t)stream, live, trk_off, S, k, R,
-                       T_max, reid_threshold, box_threshold, box_cost, wd, (char*)workspace, (char*)record, (long)record_stride, nr_cap, nc_cap);
-    return cnl::check_launch("track streams_assign_kernel");
+    return streams_launch("cnl_track_streams_f32", false, det_emb, det_box, det_score, det_label, label_kind, S, S_live, live, k, E, detection_threshold,
+                          reid_threshold, box_threshold, 0.f, 0.f, trk_emb, trk_box, trk_off, nullptr, R, T_max, box_cost, reid_metric, with_detections,
+                          workspace, workspace_bytes, record, record_stride, stream);
+}
+
+extern "C" int cnl_track_streams_low_f32(const float* det_emb, const float* det_box, const float* det_score, const void* det_label, int32_t label_kind,
+                                         int32_t S, int32_t S_live, const int32_t* live, int32_t k, int32_t E, float detection_threshold,
+                                         double reid_threshold, float box_threshold, float low_threshold, float low_box_threshold,
+                                         const float* trk_emb, const float* trk_box, const int32_t* trk_off, const uint8_t* trk_eligible, int32_t R,
+                                         int32_t T_max, int32_t box_cost, int32_t reid_metric, int32_t with_detections, void* workspace,
+                                         int64_t workspace_bytes, void* record, int64_t record_stride, void* stream) {
+    return streams_launch("cnl_track_streams_low_f32", true, det_emb, det_box, det_score, det_label, label_kind, S, S_live, live, k, E,
+                          detection_threshold, reid_threshold, box_threshold, low_threshold, low_box_threshold, trk_emb, trk_box, trk_off, trk_eligible, R,
+                          T_max, box_cost, reid_metric, with_detections, workspace, workspace_bytes, record, record_stride, stream);
 }

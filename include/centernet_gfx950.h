@@ -1068,6 +1068,69 @@ int cnl_track_streams_f32(const float* det_emb, const float* det_box, const floa
                           int64_t workspace_bytes, void* record, int64_t record_stride, void* stream);
 
 /*
+ * BYTE low-score association (Zhang et al., ByteTrack), opt-in: one more association stage that keeps a track alive through an occlusion.
+ * The entries below are the ones above with the stage added; without it (the entries above) nothing changes.
+ * The rule, for scores s[0..k) compared in float32 as the compaction above does (a NaN score belongs to neither set):
+ *   H = { d : s[d] >= detection_threshold } ascending (unchanged);  L = { d : low_threshold <= s[d] < detection_threshold } ascending.
+ *   Stages 1 (re-ID) and 2 (box cost) run on H exactly as above: same matrices bit for bit, same matches in the same order.
+ *   Stage 3: U = the tracks still unmatched after stage 2, ascending, restricted to the eligible ones (the caller's choice: e.g. the tracks
+ *   that are ACTIVE at the start of the step, or all).  The cost is the configured box cost (box_cost 1 / 2, float32, the device function of
+ *   stage 2) between the boxes of L and the table's track boxes; the |L| x |U| sub-matrix, converted to float64 as scipy does, is assigned
+ *   as scipy.optimize.linear_sum_assignment does, and the pairs with cost < low_box_threshold are kept (float32 compare, as in stage 2).
+ *   If L or U is empty the stage does nothing.
+ *   A stage-3 pair (low detection d, track t): the track takes the box of detection d (d is the ORIGINAL index) — an ordinary measurement for
+ *   its Kalman filter (cnl_track_kalman_f64 unchanged, src_det = d) — and its embedding row is carried over UNCHANGED: an occluded
+ *   detection's appearance is not trusted.  Only tracks unmatched after all three stages count as unmatched; new tracks come from the
+ *   unmatched members of H only, unmatched members of L are dropped.
+ * Deviations from ByteTrack: unconfirmed tracks take part in stages 1 and 2 as in the reference (no separate unconfirmed pass); no score
+ * fusion; the cost is this tracker's box cost on the table's boxes (the filtered ones with a Kalman filter), not a predicted box's.
+ *
+ * cnl_track_frame_low_f32: cnl_track_frame_f32 plus low_threshold.  The record is that entry's behind a larger header, with two sections
+ * more (every section the old record holds carries the same values):
+ *   int32 header[12] = { n, k, T, with_detections, off_index, off_dets, off_reid, off_box, n_low, off_low_index, off_low_box, 0 }
+ *   int32 low_index[k]      at off_low_index = off_box + 4 n T   (first n_low valid: the original indices of L)
+ *   f32 low_box[n_low][T]   at off_low_box = off_low_index + 4 k: row x is detection low_index[x] against every track
+ * cnl_track_frame_low_bytes(k, T, with_detections) bounds the record (n + n_low <= k).  box_cost == 0, or a low_threshold outside
+ * [0, detection_threshold] (a NaN included), is CNL_E_BAD_ARG; the other checks are cnl_track_frame_f32's.  Stage 3 itself is the host's.
+ */
+int64_t cnl_track_frame_low_bytes(int32_t k, int32_t T, int32_t with_detections);
+int cnl_track_frame_low_f32(const float* det_emb, const float* det_box, const float* det_score, const void* det_label, int32_t label_kind,
+                            int32_t k, int32_t E, float detection_threshold, float low_threshold, const float* trk_emb, const float* trk_box,
+                            int32_t T, int32_t box_cost, int32_t reid_metric, int32_t with_detections, void* record, int64_t record_bytes,
+                            void* stream);
+/*
+ * cnl_track_streams_low_f32: cnl_track_streams_f32 plus low_threshold, low_box_threshold and trk_eligible — one byte per row of the pooled
+ * table (R bytes, device or cnl_host_alloc memory; non-zero = the row may be matched in stage 3; null = every row).  The cost launch
+ * compacts L beside H and writes the |L| x T box costs into a further workspace section; the assign kernel runs stage 3 behind stage 2 with
+ * the same solver and the same LDS bound (n_low <= k, |U| <= T_max).  The stream's record:
+ *   int32 header[24]: fields 0..15 as cnl_track_streams_f32's, except that off_utrk / n_utrk list the tracks unmatched after ALL THREE
+ *                     stages; 16 n_low, 17 n_low_match, 18 off_low_index, 19 off_low_match, 20..23 zero
+ *   the sections of cnl_track_streams_f32's record (behind the 96-byte header), then
+ *   int32 low_index[k]                     at off_low_index  (first n_low valid: the original indices of L)
+ *   int32 low_matches[n_low_match][2] = (low row, track)   at off_low_match, in low-row order; low rows index low_index
+ * status: as cnl_track_streams_f32, and 33 / 34 / 35 for stage 3 (1 / 2 / 3 of cnl_lsap_batch_f64: e.g. a NaN coordinate in a low detection).
+ * cnl_track_streams_low_record_bytes / cnl_track_streams_low_workspace_bytes are the sizes (each at least the plain entry's); alignment,
+ * the bytes left untouched (between records, past workspace_bytes, in the records of streams not in `live`) and the argument checks are
+ * cnl_track_streams_f32's; box_cost == 0 or a low_threshold outside [0, detection_threshold] is CNL_E_BAD_ARG.
+ */
+int64_t cnl_track_streams_low_workspace_bytes(int32_t S, int32_t k, int32_t T_max);
+int64_t cnl_track_streams_low_record_bytes(int32_t k, int32_t T_max, int32_t with_detections);
+int cnl_track_streams_low_f32(const float* det_emb, const float* det_box, const float* det_score, const void* det_label, int32_t label_kind,
+                              int32_t S, int32_t S_live, const int32_t* live, int32_t k, int32_t E, float detection_threshold,
+                              double reid_threshold, float box_threshold, float low_threshold, float low_box_threshold, const float* trk_emb,
+                              const float* trk_box, const int32_t* trk_off, const uint8_t* trk_eligible, int32_t R, int32_t T_max,
+                              int32_t box_cost, int32_t reid_metric, int32_t with_detections, void* workspace, int64_t workspace_bytes,
+                              void* record, int64_t record_stride, void* stream);
+/*
+ * cnl_track_apply_keep_f32: cnl_track_apply_f32 plus keep_emb [T_new] (one byte per new row; device or cnl_host_alloc memory): a row with
+ * src_trk[r] >= 0, src_det[r] >= 0 and keep_emb[r] != 0 takes the OLD row's embedding bytes and the detection's box (a stage-3 match).  A null
+ * keep_emb, or all zeros, gives exactly cnl_track_apply_f32's output.
+ */
+int cnl_track_apply_keep_f32(const float* trk_emb, const float* trk_box, const float* det_emb, const float* det_box, const int32_t* src_trk,
+                             const int32_t* src_det, int32_t T_new, int32_t E, double smoothing, float* new_emb, float* new_box,
+                             const uint8_t* keep_emb, void* stream);
+
+/*
  * The per-track Kalman filter on the device (csrc/track_kalman.hip): Track.__init__ / predict / update of models/tracker.py:243-262,
  * 281-290, 317-323 with use_kalman=True, for the rows of the device track table.  ONE launch behind cnl_track_apply_f32, driven by the same
  * two index lists, builds the new state tables (ping-pong, not in place):
