@@ -287,11 +287,11 @@ class DeviceKalman:
 
     @property
     def x(self):
-        return self._track._tracker._table.kx[self._track._row].cpu().numpy()
+        return self._track._tracker._table.read_row("kx", self._track._row)
 
     @property
     def P(self):
-        return self._track._tracker._table.kP[self._track._row].cpu().numpy().reshape(8, 8)
+        return self._track._tracker._table.read_row("kP", self._track._row).reshape(8, 8)
 
 
 class Track:
@@ -328,7 +328,7 @@ class Track:
 
     @property
     def embedding(self):
-        return self._tracker._emb[self._row].cpu().numpy()
+        return self._tracker._table.read_row("emb", self._row)
 
     def update_matched(self, bbox):
         if self.state == TrackState.UNCONFIRMED:
@@ -407,7 +407,12 @@ class TrackTable:
     (ping-pong), the mapped host memory holding the two index lists cnl_track_apply_f32 reads, the stream of the last update.
     With `kalman` (use_kalman=True, kalman="device") also the filter state `kx` [capacity, 8] / `kP` [capacity, 64] float64 and its spare
     pair, at the capacities of emb / box; the mapped index block then holds a third list, the flags of cnl_track_kalman_f64, and a second
-    mapped block receives that launch's record (filtered boxes, status words)."""
+    mapped block receives that launch's record (filtered boxes, status words).
+    The stream rule: every launch that writes the tables goes to the caller's current stream, remembered in `stream`, and may still be queued
+    when the caller gets control back.  Whoever touches the tables or the mapped index lists from the host side under ANOTHER stream finishes
+    `stream` first, with a host-blocking synchronize: the next update (wait_for_other_stream) and the host reads of a row (read_row, behind
+    Track.embedding and DeviceKalman).  Under the same stream, stream order does it and nothing blocks.  The device views (`emb`, `box`,
+    `kx`, `kP`, track_embeddings()) are ordered on `stream` alone: a caller that reads them on another stream orders that stream itself."""
     __slots__ = ("emb", "box", "stream", "_spare", "_src", "_lists", "kalman", "kx", "kP", "_kspare", "_kout")
 
     def __init__(self, kalman=False):
@@ -420,6 +425,16 @@ class TrackTable:
         this frame reads) ran on another stream — finish it first (same stream: stream order does it; None: finish it anyway)."""
         if self.stream is not None and (cur is None or self.stream != cur):
             self.stream.synchronize()
+
+    def read_row(self, name, row, cur=None):
+        """Host copy of row `row` of the table `name` ("emb", "box", "kx", "kP"), read under the stream `cur` (default: the current stream of
+        the table's device): the bytes of the finished last update, which may have run on another stream (wait_for_other_stream's rule)."""
+        table = getattr(self, name)
+        if cur is None:
+            cur = torch.cuda.current_stream(table.device)
+        self.wait_for_other_stream(cur)
+        with torch.cuda.stream(cur) if table.is_cuda else _NO_GUARD:
+            return table[row].cpu().numpy()
 
     def clear(self):
         """Forget the rows, behind the last update (the mapped index lists stay)."""

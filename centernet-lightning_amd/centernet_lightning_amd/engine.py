@@ -163,6 +163,7 @@ def _layer_up2(self):
             stream = _lib.stream(self.w.device)
             _lib.check(lib.cnl_up2_pack_weights_f32(self.w.data_ptr(), self._up2.data_ptr(), self.cin, self.cout, stream), "cnl_up2_pack_weights_f32")
             self.up2_wmax = self._up2.abs().max().reshape(1).contiguous()
+            torch.cuda.current_stream(self.w.device).synchronize()      # (as up_rows / split_w: one pack and one maximum for the plans of every stream)
     return self._up2
 
 
