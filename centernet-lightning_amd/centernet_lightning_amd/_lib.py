@@ -89,6 +89,11 @@ class MotTables(Structure):
     _fields_ = [(n, c_void_p) for n in POINTERS] + [(n, c_int64) for n in SCALARS]
 
 
+class TrackGate(Structure):
+    """cnl_track_gate: the gate operands of cnl_track_frame_gated_f32 / cnl_track_streams_gated_f32 (40 bytes); null members: that gate is off."""
+    _fields_ = [("trk_label", c_void_p), ("kx", c_void_p), ("kP", c_void_p), ("motion_gate", c_double), ("motion_weight", c_double)]
+
+
 class LossParams(Structure):
     """cnl_loss_params: the rule of one cnl_detection_loss_f64 call (72 bytes; cnl_sizeof_params(4))."""
     _fields_ = [("stride", c_double), ("target_param", c_double), ("hm_alpha", c_double), ("hm_beta", c_double),
@@ -268,6 +273,12 @@ _SIGNATURES = {
                                                  c_int32, c_int32, c_void_p, ctypes.c_int64, c_void_p, ctypes.c_int64, c_void_p]),
     "cnl_track_apply_keep_f32": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_double,
                                                 c_void_p, c_void_p, c_void_p, c_void_p]),
+    "cnl_track_frame_gated_f32": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_float, c_float, c_void_p, c_void_p,
+                                                 c_int32, c_int32, c_int32, c_int32, c_void_p, ctypes.c_int64, ctypes.POINTER(TrackGate), c_void_p]),
+    "cnl_track_streams_gated_f32": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int32, c_int32, c_float,
+                                                   c_double, c_float, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32,
+                                                   c_int32, c_int32, c_void_p, ctypes.c_int64, c_void_p, ctypes.c_int64, ctypes.POINTER(TrackGate),
+                                                   c_void_p]),
     "cnl_relu_grad_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32]),
     "cnl_relu_grad_terms": (c_int64, [c_int32, c_int32, c_int32, c_int32]),
     "cnl_relu_grad_f32": (ctypes.c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p,

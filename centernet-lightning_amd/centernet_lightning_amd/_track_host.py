@@ -65,6 +65,10 @@ StreamsLowLayout = namedtuple("StreamsLowLayout", "off_index off_dets off_match 
 F_NLOW, F_OFF_LOW_INDEX, F_OFF_LOW_BOX = 8, 9, 10
 S_NLOW, S_NLOW_MATCH, S_OFF_LOW_INDEX, S_OFF_LOW_MATCH = 16, 17, 18, 19
 _LOW_MATCH = ("active", "all")
+# The gates (class_aware / motion_gate): a gated pair's cost, CNL_TRACK_GATE_COST of the header, and motion_gate=True's threshold (the 0.95
+# quantile of chi-square with 4 degrees of freedom, DeepSORT's chi2inv95[4])
+GATE_COST = 1e5
+CHI2INV95_4 = 9.4877
 
 
 def frame_layout(k, T, with_dets):
@@ -169,6 +173,93 @@ def launch_frame_low(lib, rec, d_emb, d_box, d_score, d_label, label_kind, k, E,
                "cnl_track_frame_low_f32")
     cur.synchronize()
     return read_frame_low_record(rec.np)
+
+
+def launch_frame_gated(lib, rec, d_emb, d_box, d_score, d_label, label_kind, k, E, detection_threshold, low_threshold, t_emb, t_box, T, box_mode,
+                       reid_metric, with_dets, gate, cur):
+    """launch_frame_low through cnl_track_frame_gated_f32 (`gate`: a _lib.TrackGate; low_threshold == detection_threshold: no low-score stage,
+    and then box_mode may be 0) -> read_frame_low_record's tuple, the box matrix None without a box cost."""
+    _lib.check(lib.cnl_track_frame_gated_f32(d_emb, d_box, d_score, d_label, label_kind, k, E, float(detection_threshold), float(low_threshold), t_emb,
+                                             t_box, T, box_mode, reid_metric, int(with_dets), rec.ptr, rec.nbytes, ctypes.byref(gate),
+                                             ctypes.c_void_p(cur.cuda_stream)), "cnl_track_frame_gated_f32")
+    cur.synchronize()
+    out = read_frame_low_record(rec.np)
+    return out if box_mode else (*out[:6], None, *out[7:])
+
+
+def _seq_sum(terms):
+    acc = terms[0]
+    for t in terms[1:]:
+        acc = acc + t
+    return acc
+
+
+def mahalanobis_sq(det_boxes, kx, kP):
+    """The motion gate's squared Mahalanobis distance (include/centernet_gfx950.h: cnl_track_gate) of every (detection box, track) pair in the
+    header's operation order, float64, one numpy operation = one IEEE operation per pair: det_boxes float32 [n, 4], kx [T, 8], kP [T, 64]
+    -> (m float64 [n, T], ok bool [T]: every pivot of the track's S = P[:4, :4] + diag(r) = L D L' finite and strictly positive)."""
+    z = np.asarray(det_boxes, np.float32).reshape(-1, 4).astype(np.float64)
+    x = np.asarray(kx, np.float64).reshape(-1, 8)
+    P = np.asarray(kP, np.float64).reshape(-1, 8, 8)
+    with np.errstate(all="ignore"):
+        wh = (x[:, 2] - x[:, 0], x[:, 3] - x[:, 1])
+        r = []
+        for i in range(4):
+            q = wh[i & 1] / 20.0
+            r.append(q * q)
+        c = [[None] * 4 for _ in range(4)]
+        L = [[None] * 4 for _ in range(4)]
+        d = [None] * 4
+        ok = np.ones(x.shape[0], bool)
+        for j in range(4):
+            for i in range(j, 4):
+                v = P[:, i, i] + r[i] if i == j else P[:, j, i]      # the upper triangle, as the filter reads P
+                if j > 0:
+                    v = v - _seq_sum([c[i][k] * L[j][k] for k in range(j)])
+                c[i][j] = v
+            d[j] = c[j][j]
+            ok &= np.isfinite(d[j]) & (d[j] > 0.0)
+            for i in range(j + 1, 4):
+                L[i][j] = c[i][j] / d[j]
+        u = [None] * 4
+        for i in range(4):
+            v = z[:, i, None] - x[None, :, i]
+            if i > 0:
+                v = v - _seq_sum([L[i][k][None, :] * u[k] for k in range(i)])
+            u[i] = v
+        m = _seq_sum([(u[i] / d[i][None, :]) * u[i] for i in range(4)])
+    return m, ok
+
+
+def gate_costs(reid, box, low_box, det_labels, trk_labels, det_boxes, kx, kP, motion_gate, motion_weight, det_index=None, low_index=None):
+    """The gates of cnl_track_frame_gated_f32 / cnl_track_streams_gated_f32 applied on the host to ungated matrices (what a redone stream of a
+    TrackerBank goes through): reid float64 [n, T], box float32 [n, T] | None, low_box float32 [n_low, T] | None; det_labels / det_boxes: the
+    frame's [k] / [k, 4] arrays, det_index / low_index the rows' original detections (None: rows 0, 1, ...).  trk_labels None: no class gate;
+    kx / kP None or motion_gate None: no motion gate.  -> gated copies (reid, box, low_box)."""
+    reid = np.array(reid, np.float64)
+    n, T = reid.shape
+    box = None if box is None else np.array(box, np.float32)
+    low_box = None if low_box is None else np.array(low_box, np.float32)
+    det_index = np.arange(n) if det_index is None else np.asarray(det_index, np.int64)
+    cross = np.zeros((n, T), bool)
+    if trk_labels is not None:
+        lab = np.asarray(det_labels).astype(np.int64).astype(np.int32)
+        trk = np.asarray(trk_labels).astype(np.int64).astype(np.int32)
+        cross = lab[det_index][:, None] != trk[None, :T]
+        if low_box is not None:
+            low_index = np.arange(low_box.shape[0]) if low_index is None else np.asarray(low_index, np.int64)
+            low_box[lab[low_index][:, None] != trk[None, :T]] = np.float32(GATE_COST)
+    if motion_gate is not None and kx is not None and n and T:
+        m, ok = mahalanobis_sq(np.asarray(det_boxes, np.float32).reshape(-1, 4)[det_index], np.asarray(kx)[:T], np.asarray(kP)[:T])
+        with np.errstate(all="ignore"):
+            inside = ok[None, :] & (m <= motion_gate)
+            if motion_weight != 1.0:
+                reid = motion_weight * reid + (1.0 - motion_weight) * m
+        reid[~inside] = GATE_COST
+    reid[cross] = GATE_COST
+    if box is not None:
+        box[cross] = np.float32(GATE_COST)
+    return reid, box, low_box
 
 
 def launch_frame(lib, rec, d_emb, d_box, d_score, d_label, label_kind, k, E, detection_threshold, t_emb, t_box, T, box_mode, reid_metric,
@@ -525,8 +616,15 @@ class TrackerSettings:
     def __init__(self, model=None, nms_kernel=3, num_detections=300, detection_threshold=0.3, reid_cost="cosine",
                  reid_threshold=0.2, box_cost="iou", box_threshold=0.5, smoothing_factor=0.5, use_kalman=False,
                  max_inactive_age=30, min_birth_age=2, device=None, allow_host_cost=False, low_threshold=None,
-                 low_box_threshold=None, low_match="active", kalman="host"):
-        """low_threshold (None: off, the path and results without it): BYTE's second association (Zhang et al., ByteTrack) — the tracks still
+                 low_box_threshold=None, low_match="active", class_aware=False, motion_gate=None, motion_weight=1.0, kalman="host"):
+        """class_aware / motion_gate / motion_weight (off by default: the entry points and bytes without them): gates inside the cost kernels
+        (cnl_track_frame_gated_f32 / cnl_track_streams_gated_f32; the rule is the header's).  class_aware: a detection and a track may only be
+        matched, in any of the three stages, if the detection's label equals the track's `label` (the label at birth).  motion_gate (True: 9.4877,
+        DeepSORT's chi2inv95[4]; or a threshold; needs use_kalman=True, kalman="device"): a re-ID pair whose squared Mahalanobis distance m from
+        the track's predicted filter state fails m <= motion_gate cannot be matched in stage 1 (the box stages are not motion-gated, as in
+        DeepSORT); motion_weight (FairMOT's lambda): inside the gate the stage-1 cost is motion_weight * reid + (1 - motion_weight) * m, the re-ID
+        cost itself at 1.  A gated pair costs 1e5 in the matrices (`last_costs` shows them), so every threshold must stay below that.
+        low_threshold (None: off, the path and results without it): BYTE's second association (Zhang et al., ByteTrack) — the tracks still
         unmatched after the re-ID and box stages are matched by box cost alone (cost < low_box_threshold, default box_threshold) against the
         detections with low_threshold <= score < detection_threshold; such a match gives the track the detection's box (a measurement for
         its Kalman filter) and leaves its embedding as it was, and a low detection never starts a track.  low_match: "active" (only tracks
@@ -574,6 +672,32 @@ class TrackerSettings:
             raise ValueError(f"low_threshold={low_threshold!r} with box_cost={box_cost!r}: the low-score stage matches by the 'iou' / 'giou' box cost")
         self.low_threshold, self.low_box_threshold, self.low_match = low_threshold, low_box_threshold, low_match
         self._check_low(low_threshold, detection_threshold)
+        if not isinstance(class_aware, (bool, int, np.bool_, np.integer)):
+            # the three gate keywords stand in front of `kalman`, which stays the last parameter: a caller written against the earlier signature
+            # who passed kalman by position lands here — refused by name, never taken for a truth value
+            raise ValueError(f"class_aware={class_aware!r}: expected a bool (pass kalman, class_aware, motion_gate and motion_weight by keyword)")
+        self.class_aware = bool(class_aware)
+        if motion_gate is True:
+            motion_gate = CHI2INV95_4
+        elif motion_gate is False:
+            motion_gate = None
+        if motion_gate is not None:
+            if not (self.use_kalman and kalman == "device"):
+                raise ValueError(f"motion_gate={motion_gate!r} needs use_kalman=True, kalman='device': the gate reads the filter state of the device table")
+            if not 0 <= motion_gate < GATE_COST:
+                raise ValueError(f"motion_gate={motion_gate!r}: expected True, None or a threshold in [0, {GATE_COST:g})")
+            motion_gate = float(motion_gate)
+        if not 0 <= motion_weight <= 1:
+            raise ValueError(f"motion_weight={motion_weight!r}: expected a value in [0, 1]")
+        if motion_weight != 1 and motion_gate is None:
+            raise ValueError(f"motion_weight={motion_weight!r} without motion_gate: the weight applies inside the motion gate")
+        self.motion_gate, self.motion_weight = motion_gate, float(motion_weight)
+        for name, on in (("class_aware", self.class_aware), ("motion_gate", motion_gate is not None)):
+            if on and (self._host_reid is not None or self._host_box is not None):
+                raise ValueError(f"{name} with reid_cost={reid_cost!r} / box_cost={box_cost!r}: the gates sit inside the gfx950 cost kernels; host-side "
+                                 "costs (allow_host_cost) are not gated")
+        self._check_gate_thresholds(reid_threshold, box_threshold, low_box_threshold)
+        self._lab = None            # gates: mapped int32 labels of the table's rows (cnl_track_gate.trk_label)
         self._device = torch.device(device) if device is not None else None
         self._table = TrackTable(kalman=self._device_kalman)
         self._rec = None            # mapped host memory the association kernel writes its record(s) into
@@ -602,6 +726,30 @@ class TrackerSettings:
             tracks[r].bbox = b
         self.kalman_skipped = int(np.count_nonzero(status))
 
+    _gated = property(lambda self: self.class_aware or self.motion_gate is not None)
+
+    def _check_gate_thresholds(self, *thresholds):
+        """With a gate on, a threshold at or above the gated pairs' cost would accept them."""
+        if self._gated:
+            for t in thresholds:
+                if t is not None and not t < GATE_COST:
+                    raise ValueError(f"threshold {t!r} with class_aware / motion_gate: gated pairs cost {GATE_COST:g}, every threshold must be below it")
+
+    def _gate(self, spans, rows, kx, kP):
+        """The cnl_track_gate of one launch over a table of `rows` rows.  spans: (first row, tracks in row order) of every stream that takes
+        part — their labels go into mapped memory that the cost kernel reads, as it reads the eligibility bytes (finished with at the step's
+        synchronisation).  kx / kP: the table's state tensors (None: no rows yet)."""
+        gate = _lib.TrackGate(None, None, None, 0.0, 1.0)
+        if self.class_aware and rows:
+            self._lab = _grown(self._lab, 4 * rows, 1 << 12)
+            lab = self._lab.np.view(np.int32)
+            for row0, tracks in spans:
+                lab[row0:row0 + len(tracks)] = [int(t.label) for t in tracks]
+            gate.trk_label = self._lab.ptr
+        if self.motion_gate is not None and rows and kx is not None:
+            gate.kx, gate.kP, gate.motion_gate, gate.motion_weight = kx.data_ptr(), kP.data_ptr(), self.motion_gate, self.motion_weight
+        return gate
+
     @staticmethod
     def _check_low(low_threshold, detection_threshold):
         if low_threshold is not None and not 0 <= low_threshold <= detection_threshold:
@@ -616,6 +764,7 @@ class TrackerSettings:
         det, box = kwargs.get("detection_threshold", self.detection_threshold), kwargs.get("box_threshold", self.box_threshold)
         low, low_box = kwargs.get("low_threshold", self.low_threshold), kwargs.get("low_box_threshold", self.low_box_threshold)
         self._check_low(low, det)
+        self._check_gate_thresholds(kwargs.get("reid_threshold"), box, low_box)
         if low is not None and (self._host_box is not None or self.box_cost is None):
             raise ValueError(f"low_threshold={low!r} with box_cost={self.box_cost!r}: the low-score stage matches by the 'iou' / 'giou' box cost")
         return det, kwargs.get("reid_threshold", self.reid_threshold), box, low, box if low_box is None else low_box

@@ -31,6 +31,11 @@ score < detection_threshold; a match gives the track the detection's box and lea
 starts a track.  `Tracker` reads the low detections' box costs from a larger frame record (cnl_track_frame_low_f32) and assigns on the host
 as it does stages 1 and 2; `TrackerBank` runs the stage on the device behind stage 2 (cnl_track_streams_low_f32).  `last_low_matches` lists
 the stage's (original detection index, track row) pairs.
+`class_aware` / `motion_gate` / `motion_weight` (opt-in; off is the paths above, entry points and bytes included): gates inside the per-pair cost
+functions.  A detection may only take a track of its own label (all three stages), and a re-ID pair must lie within the chi-square gate of the
+track's predicted filter state (stage 1; needs kalman="device").  A gated pair costs 1e5 — finite, so that scipy never sees an infeasible matrix —
+and the assignment code is the one above: it solves the gated matrices and its thresholds reject the gated pairs.  Both paths launch one gated
+entry (cnl_track_frame_gated_f32 / cnl_track_streams_gated_f32) that covers the step with and without the low-score stage on the `_low` layouts.
 
 `Tracker` (one video) and `TrackerBank` (S videos, one frame each per step) are thin callers of the shared host side in _track_host.py:
 normalise the inputs, launch, read the record, assign (or take the device's lists), life cycle, table update, Kalman.
@@ -43,7 +48,8 @@ import torch
 
 from . import _lib
 from ._track_host import (_BOX_MODES, _REID_METRICS, _STATUS_TOO_LARGE, BoxKalman, Track, TrackerSettings, TrackState, _grown,  # noqa: F401
-                          _Mapped, _on, check_kept_count, frame_layout, frame_low_layout, launch_frame, launch_frame_low, life_cycle, low_stage,
+                          _Mapped, _on, check_kept_count, frame_layout, frame_low_layout, gate_costs, launch_frame, launch_frame_gated, launch_frame_low,
+                          life_cycle, low_stage,
                           match_with_threshold, normalise_detections, read_stream_low_record, read_stream_record, streams_layout,
                           streams_low_layout, streams_low_workspace_bytes, streams_workspace_bytes, two_stage_assignment)
 from .config import load_config
@@ -101,11 +107,21 @@ class Tracker(TrackerSettings):
         box_mode = 0 if self._host_box is not None else _BOX_MODES[self.box_cost]
         with_dets = host is None
         low = low_threshold is not None
+        gated = self._gated
         with _on(dev):
             cur = torch.cuda.current_stream(dev)
             table.wait_for_other_stream(cur)
-            rec = self._rec = _grown(self._rec, (frame_low_layout if low else frame_layout)(k, T, with_dets).bytes, 1 << 18)
-            if low:
+            rec = self._rec = _grown(self._rec, (frame_low_layout if low or gated else frame_layout)(k, T, with_dets).bytes, 1 << 18)
+            if gated:
+                if self.class_aware and not label_kind:         # host arrays: the class gate reads the labels on the device
+                    d_label, label_kind = torch.from_numpy(np.ascontiguousarray(host[1]).astype(np.int64)).to(dev), 1
+                # one entry with and without the low-score stage: none = an empty score window
+                n, det_index, h_box, h_score, h_label, reid, box, low_index, low_box = launch_frame_gated(
+                    _lib.load(), rec, d_emb.data_ptr(), d_box.data_ptr(), d_score.data_ptr(), d_label.data_ptr() if label_kind else None, label_kind,
+                    k, E, detection_threshold, low_threshold if low else detection_threshold, table.emb.data_ptr() if T else None,
+                    table.box.data_ptr() if T else None, T, box_mode, _REID_METRICS.get(self.reid_cost, 0), with_dets,
+                    self._gate([(0, self.tracks)], T, table.kx, table.kP), cur)
+            elif low:
                 n, det_index, h_box, h_score, h_label, reid, box, low_index, low_box = launch_frame_low(
                     _lib.load(), rec, d_emb.data_ptr(), d_box.data_ptr(), d_score.data_ptr(), d_label.data_ptr() if label_kind else None, label_kind,
                     k, E, detection_threshold, low_threshold, table.emb.data_ptr() if T else None, table.box.data_ptr() if T else None, T, box_mode,
@@ -119,7 +135,7 @@ class Tracker(TrackerSettings):
             h_box, h_label, h_score = host
             check_kept_count(h_score, detection_threshold, n)
         self.d2h_bytes = 32 + 4 * n + (24 * k if with_dets else 0) + (12 if box_mode else 8) * n * T      # bytes the kernel stored over PCIe
-        if low:
+        if low or gated:
             self.d2h_bytes += 16 + 4 * len(low_index) * (1 + T)
         self.last_costs = None
 
@@ -203,7 +219,7 @@ class TrackerBank(TrackerSettings):
     def __init__(self, num_streams, model=None, nms_kernel=3, num_detections=300, detection_threshold=0.3, reid_cost="cosine",
                  reid_threshold=0.2, box_cost="iou", box_threshold=0.5, smoothing_factor=0.5, use_kalman=False,
                  max_inactive_age=30, min_birth_age=2, device=None, allow_host_cost=False, low_threshold=None,
-                 low_box_threshold=None, low_match="active", kalman="host"):
+                 low_box_threshold=None, low_match="active", class_aware=False, motion_gate=None, motion_weight=1.0, kalman="host"):
         if isinstance(num_streams, bool) or not isinstance(num_streams, (int, np.integer)) or num_streams < 1:
             raise ValueError(f"num_streams={num_streams!r}: expected an integer >= 1")
         if callable(reid_cost) or callable(box_cost) or reid_cost not in _REID_METRICS:
@@ -218,7 +234,8 @@ class TrackerBank(TrackerSettings):
         self._elig = None           # low_match="active": mapped eligibility bytes of the pooled table's rows (cnl_track_streams_low_f32)
         super().__init__(model, nms_kernel, num_detections, detection_threshold, reid_cost, reid_threshold, box_cost, box_threshold,
                          smoothing_factor, use_kalman, max_inactive_age, min_birth_age, device, kalman=kalman, low_threshold=low_threshold,
-                         low_box_threshold=low_box_threshold, low_match=low_match)
+                         low_box_threshold=low_box_threshold, low_match=low_match, class_aware=class_aware, motion_gate=motion_gate,
+                         motion_weight=motion_weight)
 
     def __len__(self):
         return self.num_streams
@@ -294,10 +311,11 @@ class TrackerBank(TrackerSettings):
 
     # ------------------------------------------------------------------ one step
     def _host_association(self, i, s, d_box, d_score, d_emb, detection_threshold, reid_threshold, box_threshold, low_threshold=None,
-                          low_box_threshold=None):
+                          low_box_threshold=None, gate_dets=None):
         """Stream s's association through the single-stream path (cnl_track_frame_f32 + scipy on the host) on its slice of the operands:
         what a stream with non-finite costs is redone with, so that the caller sees what Tracker raises (scipy: ValueError).  With
-        low_threshold the low-score stage too (cnl_track_frame_low_f32): the three lists, then its matches."""
+        low_threshold the low-score stage too (cnl_track_frame_low_f32): the three lists, then its matches.  With a gate on (gate_dets: the
+        slot's (det_index, boxes, labels) as the life cycle reads them) the matrices go through the host's gate_costs before the assignment."""
         dev = self.device
         k, E = d_emb.shape[1], d_emb.shape[2]
         t0, T = int(self._off[s]), int(self._off[s + 1] - self._off[s])
@@ -307,12 +325,19 @@ class TrackerBank(TrackerSettings):
         operands = (d_emb[i].data_ptr(), d_box[i].data_ptr(), d_score[i].data_ptr(), None, 0, k, E)
         table_args = (table.emb[t0:].data_ptr() if T else None, table.box[t0:].data_ptr() if T else None, T, _BOX_MODES[self.box_cost],
                       _REID_METRICS[self.reid_cost], 0)
+        low_index = low_box = None
         with _on(dev):
             if low:
                 *_, reid, box, low_index, low_box = launch_frame_low(_lib.load(), rec, *operands, detection_threshold, low_threshold, *table_args,
                                                                      torch.cuda.current_stream(dev))
             else:
                 _, _, _, _, _, reid, box = launch_frame(_lib.load(), rec, *operands, detection_threshold, *table_args, torch.cuda.current_stream(dev))
+            if self._gated and T:
+                det_index, h_box, h_label = gate_dets
+                motion = self.motion_gate is not None
+                kx, kP = (table.kx[t0:t0 + T].cpu().numpy(), table.kP[t0:t0 + T].cpu().numpy()) if motion else (None, None)
+                reid, box, low_box = gate_costs(reid, box, low_box, h_label, [t.label for t in self._streams[s].tracks] if self.class_aware else None,
+                                                h_box, kx, kP, self.motion_gate, self.motion_weight, det_index, low_index)
         matches, unmatched_dets, unmatched_tracks = two_stage_assignment(reid, reid_threshold, box_threshold, box)
         if not low:
             return matches, unmatched_dets, unmatched_tracks
@@ -332,14 +357,16 @@ class TrackerBank(TrackerSettings):
         d_box, d_score, d_emb, d_label, host, label_kind = normalise_detections(dev, bboxes, labels, scores, embeddings, (L,))
         detection_threshold, reid_threshold, box_threshold, low_threshold, low_box_threshold = self._thresholds(kwargs)
         low = low_threshold is not None
+        gated = self._gated
+        low_rec = low or gated          # the gated entry writes the `_low` record whether the stage runs or not
         lib = _lib.load()
         k, E = int(d_emb.shape[1]), int(d_emb.shape[2])
         with_dets = host is None
         table, off = self._table, self._off
         R = int(off[S])
         T_max = max(int(off[s + 1] - off[s]) for s in live)
-        stride = (streams_low_layout if low else streams_layout)(k, T_max, with_dets).bytes
-        ws_need = (streams_low_workspace_bytes if low else streams_workspace_bytes)(S, k, R)
+        stride = (streams_low_layout if low_rec else streams_layout)(k, T_max, with_dets).bytes
+        ws_need = (streams_low_workspace_bytes if low_rec else streams_workspace_bytes)(S, k, R)
         with _on(dev):
             cur = torch.cuda.current_stream(dev)
             table.wait_for_other_stream(cur)
@@ -353,14 +380,16 @@ class TrackerBank(TrackerSettings):
             ctl = self._ctl.np.view(np.int32)
             ctl[:L] = live
             ctl[S:2 * S + 1] = off
+            if self.class_aware and not label_kind:             # host arrays: the class gate reads the labels on the device
+                d_label, label_kind = torch.from_numpy(np.ascontiguousarray(host[1]).astype(np.int64)).to(dev), 1
             operands = (d_emb.data_ptr(), d_box.data_ptr(), d_score.data_ptr(), d_label.data_ptr() if label_kind else None, label_kind, S, L,
                         self._ctl.ptr, k, E, float(detection_threshold), float(reid_threshold), float(box_threshold))
             tables = (table.emb.data_ptr() if R else None, table.box.data_ptr() if R else None, self._ctl.ptr + 4 * S)
             rest = (R, T_max, _BOX_MODES[self.box_cost], _REID_METRICS[self.reid_cost], int(with_dets), self._ws.data_ptr(), self._ws.numel(), rec.ptr,
                     stride, ctypes.c_void_p(cur.cuda_stream))
-            if low:
+            if low_rec:
                 eligible = None
-                if self.low_match != "all" and R:
+                if low and self.low_match != "all" and R:
                     # the rows' eligibility sits in mapped memory the assign kernel reads (the rows of this step's streams only): finished
                     # with at this step's synchronisation
                     self._elig = _grown(self._elig, R, 1 << 12)
@@ -368,27 +397,35 @@ class TrackerBank(TrackerSettings):
                         flags = bytes([t.state is TrackState.ACTIVE for t in self._streams[s].tracks])
                         self._elig.np[off[s]:off[s] + len(flags)] = np.frombuffer(flags, np.uint8)
                     eligible = self._elig.ptr
-                _lib.check(lib.cnl_track_streams_low_f32(*operands, float(low_threshold), float(low_box_threshold), *tables, eligible, *rest),
-                           "cnl_track_streams_low_f32")
+                if gated:       # one entry with and without the low-score stage: none = an empty score window
+                    gate = self._gate([(int(off[s]), self._streams[s].tracks) for s in live], R, table.kx, table.kP)
+                    _lib.check(lib.cnl_track_streams_gated_f32(*operands, float(low_threshold if low else detection_threshold), float(low_box_threshold),
+                                                               *tables, eligible, *rest[:-1], ctypes.byref(gate), rest[-1]),
+                               "cnl_track_streams_gated_f32")
+                else:
+                    _lib.check(lib.cnl_track_streams_low_f32(*operands, float(low_threshold), float(low_box_threshold), *tables, eligible, *rest),
+                               "cnl_track_streams_low_f32")
             else:
                 _lib.check(lib.cnl_track_streams_f32(*operands, *tables, *rest), "cnl_track_streams_f32")
             cur.synchronize()
         # ---- read every stream's lists first: an exception leaves all streams untouched ----
         assoc, d2h = {}, 0
         for i, s in enumerate(live):
-            n, T, status, det_index, h_box, _, h_label, *lists = (read_stream_low_record if low else read_stream_record)(rec.np[s * stride:(s + 1) * stride])
+            n, T, status, det_index, h_box, _, h_label, *lists = (read_stream_low_record if low_rec else read_stream_record)(rec.np[s * stride:(s + 1) * stride])
             if status in _STATUS_TOO_LARGE:
                 raise ValueError(f"stream {s}: association status {status} (k = {k}, T = {T}: beyond the supported sizes)")
             d2h += 64 + 4 * n + (24 * k if with_dets else 0) + 8 * len(lists[0]) + 4 * len(lists[1]) + 4 * len(lists[2])
-            if low:
+            if low_rec:
                 n_low = lists.pop(3)
                 d2h += 32 + 4 * n_low + 8 * len(lists[3])
-            if status:
-                lists = self._host_association(i, s, d_box, d_score, d_emb, detection_threshold, reid_threshold, box_threshold, low_threshold,
-                                               low_box_threshold)
+                if not low:
+                    lists = lists[:3]
             if not with_dets:
                 h_box, h_label = host[0][i], host[1][i]
                 check_kept_count(host[2][i], detection_threshold, n, f"stream {s}: ")
+            if status:
+                lists = self._host_association(i, s, d_box, d_score, d_emb, detection_threshold, reid_threshold, box_threshold, low_threshold,
+                                               low_box_threshold, (det_index, h_box, h_label))
             assoc[s] = (i * k, *lists[:3], det_index, h_box, h_label, *lists[3:])
         self.d2h_bytes = d2h
 

@@ -11,6 +11,8 @@
 // Arithmetic mirrors the CPU libraries operation by operation (no fma contraction) so that the integer decisions taken
 // from the costs (thresholds, Hungarian assignment) are the reference's: the cosine distance is evaluated in float64 with the
 // sequential dot product, the |cos| <= 1 clamp and 1 - cos of scipy's cdist; the box distances in float32 in numpy's order.
+// cnl_track_frame_gated_f32 (frame_gated_kernel) writes the same record with the class / motion gates of cnl_track_gate applied inside the
+// per-pair cost functions (track_costs.h): no counterpart in the reference, whose tracker.py:145-147 leaves class filtering as a TODO.
 #include "track_costs.h"      // compact_scores / pair_costs (shared with track_streams.hip)
 
 #pragma clang fp contract(off)   // one rounding per operation, like numpy / scipy: the costs feed thresholds and the Hungarian step
@@ -38,12 +40,13 @@ __global__ __launch_bounds__(256) void costs_kernel(const float* __restrict__ de
 // memory mapped into the device's address space: the frame's only device -> host traffic is these stores, no copy engine involved.
 // LOW (cnl_track_frame_low_f32): a 48-byte header, and behind the box matrix the low-score detections {i : low_thr <= score[i] < thr} and their
 // box costs, for the host's third association stage.
-template <bool LOW>
-__global__ __launch_bounds__(256) void frame_kernel(const float* __restrict__ det_emb, const float* __restrict__ det_box,
-                                                    const float* __restrict__ det_score, const void* __restrict__ det_label, int label_kind,
-                                                    int k, int E, float thr, float low_thr, const float* __restrict__ trk_emb,
-                                                    const float* __restrict__ trk_box, int T, int box_mode, int reid_metric, int with_dets,
-                                                    char* __restrict__ record) {
+// GATED (cnl_track_frame_gated_f32): the class / motion gates inside the per-pair cost functions; every other byte as LOW writes it.
+template <bool LOW, bool GATED>
+__device__ __forceinline__ void frame_body(const float* __restrict__ det_emb, const float* __restrict__ det_box,
+                                           const float* __restrict__ det_score, const void* __restrict__ det_label, int label_kind,
+                                           int k, int E, float thr, float low_thr, const float* __restrict__ trk_emb,
+                                           const float* __restrict__ trk_box, int T, int box_mode, int reid_metric, int with_dets,
+                                           char* __restrict__ record, const GateOps& g) {
     __shared__ int sel[MAXK];
     __shared__ int low_sel[LOW ? MAXK : 1];
     __shared__ int wave_sum[4];
@@ -73,10 +76,30 @@ __global__ __launch_bounds__(256) void frame_kernel(const float* __restrict__ de
                       : label_kind == 3 ? (int)reinterpret_cast<const float*>(det_label)[i] : 0;
         }
     }
-    pair_costs(sel, n, det_emb, det_box, E, trk_emb, trk_box, T, box_mode, reid_metric, reinterpret_cast<double*>(record + off_reid),
-               reinterpret_cast<float*>(record + off_box));
+    pair_costs_at<GATED>((long)blockIdx.x * 256 + threadIdx.x, sel, n, det_emb, det_box, E, trk_emb, trk_box, T, box_mode, reid_metric,
+                         reinterpret_cast<double*>(record + off_reid), reinterpret_cast<float*>(record + off_box), g);
     if (LOW)      // n_low <= k: the grid that covers k * T pairs covers these
-        pair_box_cost_at((long)blockIdx.x * 256 + threadIdx.x, low_sel, n_low, det_box, trk_box, T, box_mode, reinterpret_cast<float*>(record + off_low_box));
+        pair_box_cost_at<GATED>((long)blockIdx.x * 256 + threadIdx.x, low_sel, n_low, det_box, trk_box, T, box_mode,
+                                reinterpret_cast<float*>(record + off_low_box), g);
+}
+
+template <bool LOW>
+__global__ __launch_bounds__(256) void frame_kernel(const float* __restrict__ det_emb, const float* __restrict__ det_box,
+                                                    const float* __restrict__ det_score, const void* __restrict__ det_label, int label_kind,
+                                                    int k, int E, float thr, float low_thr, const float* __restrict__ trk_emb,
+                                                    const float* __restrict__ trk_box, int T, int box_mode, int reid_metric, int with_dets,
+                                                    char* __restrict__ record) {
+    frame_body<LOW, false>(det_emb, det_box, det_score, det_label, label_kind, k, E, thr, low_thr, trk_emb, trk_box, T, box_mode, reid_metric, with_dets,
+                           record, GateOps{});
+}
+
+__global__ __launch_bounds__(256) void frame_gated_kernel(const float* __restrict__ det_emb, const float* __restrict__ det_box,
+                                                          const float* __restrict__ det_score, const void* __restrict__ det_label, int label_kind,
+                                                          int k, int E, float thr, float low_thr, const float* __restrict__ trk_emb,
+                                                          const float* __restrict__ trk_box, int T, int box_mode, int reid_metric, int with_dets,
+                                                          char* __restrict__ record, GateOps g) {
+    frame_body<true, true>(det_emb, det_box, det_score, det_label, label_kind, k, E, thr, low_thr, trk_emb, trk_box, T, box_mode, reid_metric, with_dets, record,
+                           g);
 }
 
 // One wave per row of the new track table.  KEEP (cnl_track_apply_keep_f32): a matched row whose keep_emb byte is set takes the detection's
@@ -146,20 +169,23 @@ static int64_t frame_bytes(int32_t k, int32_t T, int32_t with_detections, bool l
 extern "C" int64_t cnl_track_frame_bytes(int32_t k, int32_t T, int32_t with_detections) { return frame_bytes(k, T, with_detections, false); }
 extern "C" int64_t cnl_track_frame_low_bytes(int32_t k, int32_t T, int32_t with_detections) { return frame_bytes(k, T, with_detections, true); }
 
-// cnl_track_frame_f32 (low = false; low_threshold unused) and cnl_track_frame_low_f32: one set of checks, one kernel body.
-static int frame_launch(const char* name, bool low, const float* det_emb, const float* det_box, const float* det_score, const void* det_label,
+// cnl_track_frame_f32 (low = false; low_threshold unused), cnl_track_frame_low_f32 and cnl_track_frame_gated_f32 (low, gate set; without a low-score
+// stage — low_threshold == detection_threshold, n_low = 0 — it also takes box_cost 0): one set of checks, one kernel body.
+static int frame_launch(const char* name, bool low, const cnl_track_gate* gate, const float* det_emb, const float* det_box, const float* det_score, const void* det_label,
                         int32_t label_kind, int32_t k, int32_t E, float detection_threshold, float low_threshold, const float* trk_emb,
                         const float* trk_box, int32_t T, int32_t box_cost, int32_t reid_metric, int32_t with_detections, void* record,
                         int64_t record_bytes, void* stream) {
     CNL_REQUIRE(det_emb && det_box && det_score && record, CNL_E_BAD_ARG, "%s: null pointer", name);
     CNL_REQUIRE(k > 0 && E > 0 && T >= 0, CNL_E_BAD_ARG, "%s: bad k/E/T", name);
     CNL_REQUIRE(k <= MAXK, CNL_E_UNSUPPORTED, "%s: k = %d > %d detections per frame", name, k, MAXK);
-    CNL_REQUIRE(box_cost >= (low ? 1 : 0) && box_cost <= 2, CNL_E_BAD_ARG, "%s: box_cost must be %s1 (iou), 2 (giou)", name, low ? "" : "0 (none), ");
+    const bool low_stage = low && !(gate != nullptr && low_threshold == detection_threshold);
+    CNL_REQUIRE(box_cost >= (low_stage ? 1 : 0) && box_cost <= 2, CNL_E_BAD_ARG, "%s: box_cost must be %s1 (iou), 2 (giou)", name, low_stage ? "" : "0 (none), ");
     CNL_REQUIRE(!low || (low_threshold >= 0.f && low_threshold <= detection_threshold), CNL_E_BAD_ARG,
                 "%s: low_threshold %g must lie in [0, detection_threshold = %g]", name, (double)low_threshold, (double)detection_threshold);
     CNL_REQUIRE(reid_metric >= 0 && reid_metric <= 7, CNL_E_BAD_ARG, "%s: reid_metric must be 0 (cosine) .. 7 (correlation)", name);
     CNL_REQUIRE(label_kind >= 0 && label_kind <= 3 && (label_kind == 0 || det_label), CNL_E_BAD_ARG,
                 "%s: label_kind must be 0 (none), 1 (int64), 2 (int32), 3 (float32) with det_label set", name);
+    if (int rc = check_gate(name, gate, det_box, {})) return rc;
     CNL_REQUIRE(T == 0 || trk_emb, CNL_E_BAD_ARG, "%s: T > 0 without track table", name);
     CNL_REQUIRE(T == 0 || box_cost == 0 || trk_box, CNL_E_BAD_ARG, "%s: box cost requested without track boxes", name);
     CNL_REQUIRE(((uintptr_t)record & 7) == 0, CNL_E_BAD_ARG, "%s: record must be 8-byte aligned", name);
@@ -170,6 +196,12 @@ static int frame_launch(const char* name, bool low, const float* det_emb, const 
                 low ? "_low" : "");
     const long pairs = (long)k * T;
     const unsigned grid = (unsigned)(pairs > 0 ? (pairs + 255) / 256 : 1);
+    if (gate != nullptr) {
+        const GateOps g{gate->trk_label, gate->kx, gate->kP, gate->motion_gate, gate->motion_weight, det_label, label_kind, 0};
+        hipLaunchKernelGGL(frame_gated_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, det_emb, det_box, det_score, det_label, label_kind, k, E,
+                           detection_threshold, low_threshold, trk_emb, trk_box, T, box_cost, reid_metric, with_detections ? 1 : 0, (char*)record, g);
+        return cnl::check_launch("track frame_gated_kernel");
+    }
     hipLaunchKernelGGL(low ? frame_kernel<true> : frame_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, det_emb, det_box, det_score, det_label,
                        label_kind, k, E, detection_threshold, low_threshold, trk_emb, trk_box, T, box_cost, reid_metric, with_detections ? 1 : 0,
                        (char*)record);
@@ -180,7 +212,7 @@ extern "C" int cnl_track_frame_f32(const float* det_emb, const float* det_box, c
                                    int32_t k, int32_t E, float detection_threshold, const float* trk_emb, const float* trk_box, int32_t T,
                                    int32_t box_cost, int32_t reid_metric, int32_t with_detections, void* record, int64_t record_bytes,
                                    void* stream) {
-    return frame_launch("cnl_track_frame_f32", false, det_emb, det_box, det_score, det_label, label_kind, k, E, detection_threshold, 0.f, trk_emb, trk_box,
+    return frame_launch("cnl_track_frame_f32", false, nullptr, det_emb, det_box, det_score, det_label, label_kind, k, E, detection_threshold, 0.f, trk_emb, trk_box,
                         T, box_cost, reid_metric, with_detections, record, record_bytes, stream);
 }
 
@@ -188,8 +220,17 @@ extern "C" int cnl_track_frame_low_f32(const float* det_emb, const float* det_bo
                                        int32_t k, int32_t E, float detection_threshold, float low_threshold, const float* trk_emb,
                                        const float* trk_box, int32_t T, int32_t box_cost, int32_t reid_metric, int32_t with_detections, void* record,
                                        int64_t record_bytes, void* stream) {
-    return frame_launch("cnl_track_frame_low_f32", true, det_emb, det_box, det_score, det_label, label_kind, k, E, detection_threshold, low_threshold,
+    return frame_launch("cnl_track_frame_low_f32", true, nullptr, det_emb, det_box, det_score, det_label, label_kind, k, E, detection_threshold, low_threshold,
                         trk_emb, trk_box, T, box_cost, reid_metric, with_detections, record, record_bytes, stream);
+}
+
+extern "C" int cnl_track_frame_gated_f32(const float* det_emb, const float* det_box, const float* det_score, const void* det_label, int32_t label_kind,
+                                         int32_t k, int32_t E, float detection_threshold, float low_threshold, const float* trk_emb,
+                                         const float* trk_box, int32_t T, int32_t box_cost, int32_t reid_metric, int32_t with_detections, void* record,
+                                         int64_t record_bytes, const cnl_track_gate* gate, void* stream) {
+    static const cnl_track_gate off = {nullptr, nullptr, nullptr, 0.0, 1.0};
+    return frame_launch("cnl_track_frame_gated_f32", true, gate ? gate : &off, det_emb, det_box, det_score, det_label, label_kind, k, E, detection_threshold,
+                        low_threshold, trk_emb, trk_box, T, box_cost, reid_metric, with_detections, record, record_bytes, stream);
 }
 
 extern "C" int cnl_track_costs_f32(const float* det_emb, const float* det_box, const float* det_score, int32_t k, int32_t E,

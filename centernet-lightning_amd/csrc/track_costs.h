@@ -2,8 +2,12 @@
 // per-pair re-ID (float64) / box (float32) costs.  Shared by track.hip (one stream per launch) and track_streams.hip (S streams per
 // launch) so that both write bit-identical matrices: the integer decisions taken from them (thresholds, assignment) must not depend on
 // which entry point computed them.
+// GATED instantiations of the per-pair functions (cnl_track_frame_gated_f32 / cnl_track_streams_gated_f32) apply the class and motion gates of
+// the header's cnl_track_gate before the one store of each cost; the ungated instantiations carry none of that code.
 #pragma once
 #include "cnl_common.h"
+#include <initializer_list>
+#include "kalman_ldl.h"     // ldl4: the motion gate factors the filter's S as the filter does
 
 #pragma clang fp contract(off)   // one rounding per operation, like numpy / scipy: the costs feed thresholds and the Hungarian step
 
@@ -18,6 +22,25 @@ inline bool inputs_aligned(const float* det_emb, const float* det_box, const flo
     if (T == 0) return true;
     const uintptr_t boxes = box_cost ? (uintptr_t)det_box | (uintptr_t)trk_box : 0, embs = (E & 3) == 0 ? (uintptr_t)det_emb | (uintptr_t)trk_emb : 0;
     return ((boxes | embs) & 15) == 0;
+}
+
+// The checks of a cnl_track_gate that both gated entries share (a null gate: every gate off); `thresholds`: the entry's own.
+inline int check_gate(const char* name, const cnl_track_gate* gate, const float* det_box, std::initializer_list<double> thresholds) {
+    if (gate == nullptr || (gate->trk_label == nullptr && gate->kx == nullptr && gate->kP == nullptr)) return CNL_OK;
+    CNL_REQUIRE((gate->kx == nullptr) == (gate->kP == nullptr), CNL_E_BAD_ARG, "%s: gate kx and kP come together (both null: no motion gate)", name);
+    CNL_REQUIRE((((uintptr_t)gate->kx | (uintptr_t)gate->kP) & 7) == 0 && ((uintptr_t)gate->trk_label & 3) == 0, CNL_E_BAD_ARG,
+                "%s: gate kx / kP must be 8-byte aligned, trk_label 4-byte aligned", name);
+    if (gate->kx != nullptr) {
+        CNL_REQUIRE(((uintptr_t)det_box & 15) == 0, CNL_E_BAD_ARG, "%s: with the motion gate det_box must be 16-byte aligned", name);
+        CNL_REQUIRE(gate->motion_gate >= 0.0 && gate->motion_gate < CNL_TRACK_GATE_COST, CNL_E_BAD_ARG,
+                    "%s: motion_gate %g must lie in [0, %g)", name, gate->motion_gate, CNL_TRACK_GATE_COST);
+        CNL_REQUIRE(gate->motion_weight >= 0.0 && gate->motion_weight <= 1.0, CNL_E_BAD_ARG, "%s: motion_weight %g must lie in [0, 1]", name,
+                    gate->motion_weight);
+    }
+    for (const double t : thresholds)
+        CNL_REQUIRE(!(t >= CNL_TRACK_GATE_COST), CNL_E_BAD_ARG, "%s: a threshold of %g would accept gated pairs (their cost is %g)", name, t,
+                    CNL_TRACK_GATE_COST);
+    return CNL_OK;
 }
 
 // numpy maximum/minimum propagate NaN (fmaxf/fminf do not)
@@ -130,21 +153,98 @@ __device__ __forceinline__ float box_pair_cost(const float4 a, const float4 b, c
     return (1.f - score);
 }
 
-// Box costs alone of pair p = r * T + t of an n x T problem (the low-score stage: no re-ID matrix), written at box_cost[p].
+// The gates of cnl_track_frame_gated_f32 / cnl_track_streams_gated_f32 (include/centernet_gfx950.h: cnl_track_gate) as the cost functions read them:
+// the table pointers start at the stream's first row, det_label at the launch's first detection and det0 is the first detection of the stream's slot.
+constexpr double GATE_COST = CNL_TRACK_GATE_COST;
+struct GateOps {
+    const int* trk_label;      // null: no class gate
+    const double *kx, *kP;     // null (together): no motion gate
+    double motion_gate, motion_weight;
+    const void* det_label;
+    int label_kind;
+    long det0;
+};
+
+// A detection's label as the records carry it (label_kind 1 int64, 2 int32, 3 float32 cast to int, 0: none = 0).
+__device__ __forceinline__ int det_label_at(const void* __restrict__ det_label, const int label_kind, const long i) {
+    return label_kind == 1 ? (int)reinterpret_cast<const long long*>(det_label)[i]
+         : label_kind == 2 ? reinterpret_cast<const int*>(det_label)[i]
+         : label_kind == 3 ? (int)reinterpret_cast<const float*>(det_label)[i] : 0;
+}
+__device__ __forceinline__ bool cross_class(const GateOps& g, const int d, const int t) {
+    return g.trk_label != nullptr && det_label_at(g.det_label, g.label_kind, g.det0 + d) != g.trk_label[t];
+}
+
+// The motion gate of one pair (the header's rule): the squared Mahalanobis distance m of the detection's box z from track t's predicted state in
+// the filter's own innovation metric S = P[:4, :4] + diag(r) = L D L' (kalman_ldl.h).  -> the stage-1 cost: GATE_COST outside the gate (a bad
+// pivot and a NaN included), inside it reid (untouched bits) when motion_weight == 1, else motion_weight * reid + (1 - motion_weight) * m.
+__device__ inline double motion_gated_cost(const double reid, const float4 zf, const double* __restrict__ x, const double* __restrict__ P,
+                                                    const double motion_gate, const double motion_weight) {
+    const double z[4] = {(double)zf.x, (double)zf.y, (double)zf.z, (double)zf.w};
+    const double xs[4] = {x[0], x[1], x[2], x[3]};
+    const double w = xs[2] - xs[0], h = xs[3] - xs[1];
+    double r[4], y[4], L[4][4], dd[4], u[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const double q = ((i & 1) ? h : w) / 20.0;
+        r[i] = q * q;
+        y[i] = z[i] - xs[i];
+    }
+    const bool ok = cnl_kalman::ldl4([P](int i, int j) { return P[j * 8 + i]; }, r, L, dd);      // i >= j: the upper triangle, as the filter reads P
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        double v = y[i];
+        if (i > 0) {
+            double acc = L[i][0] * u[0];
+#pragma unroll
+            for (int k = 1; k < i; ++k) acc = acc + L[i][k] * u[k];
+            v = v - acc;
+        }
+        u[i] = v;
+    }
+    const double m = (((u[0] / dd[0]) * u[0] + (u[1] / dd[1]) * u[1]) + (u[2] / dd[2]) * u[2]) + (u[3] / dd[3]) * u[3];
+    if (!ok || !(m <= motion_gate)) return GATE_COST;
+    return motion_weight == 1.0 ? reid : motion_weight * reid + (1.0 - motion_weight) * m;
+}
+
+// Box costs alone of pair p = r * T + t of an n x T problem (the low-score stage: no re-ID matrix), written at box_cost[p].  GATED: a cross-class
+// pair costs GATE_COST.
+template <bool GATED = false>
 __device__ __forceinline__ void pair_box_cost_at(const long p, const int* sel, const int n, const float* __restrict__ det_box,
-                                                 const float* __restrict__ trk_box, const int T, const int box_mode, float* __restrict__ box_cost) {
+                                                 const float* __restrict__ trk_box, const int T, const int box_mode, float* __restrict__ box_cost,
+                                                 const GateOps& g = GateOps{}) {
     if (T <= 0 || p >= (long)n * T) return;
     const int r = (int)(p / T), t = (int)(p - (long)r * T);
+    if (GATED && cross_class(g, sel[r], t)) {
+        box_cost[p] = (float)GATE_COST;
+        return;
+    }
     box_cost[p] = box_pair_cost(*reinterpret_cast<const float4*>(det_box + (long)sel[r] * 4), *reinterpret_cast<const float4*>(trk_box + (long)t * 4), box_mode);
 }
 
-// Costs of pair p = r * T + t (kept detection r, track t) of an n x T problem, written at reid_cost[p] / box_cost[p].
+// The one store of a pair's re-ID cost (the matrix may sit in mapped host memory and is never read back); GATED: through the motion gate.
+template <bool GATED>
+__device__ __forceinline__ void put_reid(double* __restrict__ reid_cost, const long p, const double c, const float4 zf, const int t, const GateOps& g) {
+    if (GATED && g.kx != nullptr) reid_cost[p] = motion_gated_cost(c, zf, g.kx + (long)t * 8, g.kP + (long)t * 64, g.motion_gate, g.motion_weight);
+    else reid_cost[p] = c;
+}
+
+// Costs of pair p = r * T + t (kept detection r, track t) of an n x T problem, written at reid_cost[p] / box_cost[p].  GATED: a cross-class pair
+// costs GATE_COST in both matrices, and the re-ID cost of the others goes through the motion gate.
+template <bool GATED = false>
 __device__ __forceinline__ void pair_costs_at(const long p, const int* sel, const int n, const float* __restrict__ det_emb, const float* __restrict__ det_box,
                                               const int E, const float* __restrict__ trk_emb, const float* __restrict__ trk_box, const int T, const int box_mode,
-                                              const int reid_metric, double* __restrict__ reid_cost, float* __restrict__ box_cost) {
+                                              const int reid_metric, double* __restrict__ reid_cost, float* __restrict__ box_cost,
+                                              const GateOps& g = GateOps{}) {
     if (T <= 0 || p >= (long)n * T) return;
     const int r = (int)(p / T), t = (int)(p - (long)r * T);
     const int d = sel[r];
+    if (GATED && cross_class(g, d, t)) {
+        reid_cost[p] = GATE_COST;
+        if (box_mode) box_cost[p] = (float)GATE_COST;
+        return;
+    }
+    const float4 zf = GATED && g.kx != nullptr ? *reinterpret_cast<const float4*>(det_box + (long)d * 4) : float4{0.f, 0.f, 0.f, 0.f};
     if (reid_metric == 0) {   // scipy cdist "cosine": 1 - clamp(u.v / (|u| |v|))
         const float* u = det_emb + (long)d * E;
         const float* v = trk_emb + (long)t * E;
@@ -152,7 +252,7 @@ __device__ __forceinline__ void pair_costs_at(const long p, const int* sel, cons
         seq_dots(u, v, E, uu, vv, uv);
         double c = uv / (sqrt(uu) * sqrt(vv));
         if (fabs(c) > 1.0) c = copysign(1.0, c);
-        reid_cost[p] = (1.0 - c);
+        put_reid<GATED>(reid_cost, p, (1.0 - c), zf, t, g);
     } else if (reid_metric == 7) {   // scipy cdist "correlation": both rows centred by their float64 mean (numpy's pairwise order), then the cosine kernel
         const float* u = det_emb + (long)d * E;
         const float* v = trk_emb + (long)t * E;
@@ -164,7 +264,7 @@ __device__ __forceinline__ void pair_costs_at(const long p, const int* sel, cons
         }
         double c = uv / (sqrt(uu) * sqrt(vv));
         if (fabs(c) > 1.0) c = copysign(1.0, c);
-        reid_cost[p] = (1.0 - c);
+        put_reid<GATED>(reid_cost, p, (1.0 - c), zf, t, g);
     } else if (reid_metric <= 2) {   // scipy cdist "euclidean" (1) / "sqeuclidean" (2): s += (u - v)^2 sequentially in float64, then sqrt
         const float* u = det_emb + (long)d * E;
         const float* v = trk_emb + (long)t * E;
@@ -173,7 +273,7 @@ __device__ __forceinline__ void pair_costs_at(const long p, const int* sel, cons
             const double df = (double)u[e] - (double)v[e];
             acc = acc + df * df;
         }
-        reid_cost[p] = reid_metric == 1 ? sqrt(acc) : acc;
+        put_reid<GATED>(reid_cost, p, reid_metric == 1 ? sqrt(acc) : acc, zf, t, g);
     } else {                  // "cityblock" (3), "chebyshev" (4), "canberra" (5), "braycurtis" (6): scipy's element order, float64
         const float* u = det_emb + (long)d * E;
         const float* v = trk_emb + (long)t * E;
@@ -191,7 +291,7 @@ __device__ __forceinline__ void pair_costs_at(const long p, const int* sel, cons
                 den = den + fabs(x + y);
             }
         }
-        reid_cost[p] = reid_metric == 6 ? acc / den : acc;
+        put_reid<GATED>(reid_cost, p, reid_metric == 6 ? acc / den : acc, zf, t, g);
     }
     if (box_mode)
         box_cost[p] = box_pair_cost(*reinterpret_cast<const float4*>(det_box + (long)d * 4), *reinterpret_cast<const float4*>(trk_box + (long)t * 4), box_mode);

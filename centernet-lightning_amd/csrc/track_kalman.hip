@@ -15,6 +15,7 @@
 // operations per row, at most a few thousand rows), rows are independent, and this mapping needs no LDS, no shuffles and no scratch
 // (DESIGN.md records the compiled resource usage).
 #include "cnl_common.h"
+#include "kalman_ldl.h"       // ldl4 (shared with track_costs.h)
 
 #pragma clang fp contract(off)   // one rounding per operation: tests/kalman_ref.py restates every operation in numpy
 
@@ -53,27 +54,9 @@ __device__ __forceinline__ bool update(State& s, const float4 zf) {
         r[i] = t * t;
         y[i] = z[i] - s.x[i];
     }
-    // S = P[:4, :4] + diag(r) = L D L': column by column, c[i][j] = L[i][j] * d[j]
-    double c[4][4], L[4][4], d[4];
-    bool ok = true;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-#pragma unroll
-        for (int i = j; i < 4; ++i) {
-            double v = i == j ? s.p[tri(i, i)] + r[i] : s.p[tri(i, j)];
-            if (j > 0) {
-                double acc = c[i][0] * L[j][0];
-#pragma unroll
-                for (int k = 1; k < j; ++k) acc = acc + c[i][k] * L[j][k];
-                v = v - acc;
-            }
-            c[i][j] = v;
-        }
-        d[j] = c[j][j];
-        ok = ok && d[j] > 0.0 && d[j] < __builtin_inf();
-#pragma unroll
-        for (int i = j + 1; i < 4; ++i) L[i][j] = c[i][j] / d[j];
-    }
+    // S = P[:4, :4] + diag(r) = L D L' (kalman_ldl.h: the motion gate of the association entries factors the same S the same way)
+    double L[4][4], d[4];
+    const bool ok = ldl4([&s](int i, int j) { return s.p[tri(i, j)]; }, r, L, d);
     // K = P[:, :4] S^-1, row by row: forward solve with L, divide by D, backward solve with L'
     double K[8][4];
 #pragma unroll

@@ -11,6 +11,8 @@
 //   lsap_batch_kernel       the solver alone on B caller-supplied matrices (cnl_lsap_batch_f64)
 // cnl_track_streams_low_f32 instantiates both stream kernels with LOW: the cost launch also compacts the low-score detections and writes their
 // box costs, the assign kernel runs a third stage (BYTE) on them behind stage 2 — same bodies, same solver, same LDS bound.
+// cnl_track_streams_gated_f32 is that entry with a gated cost launch (streams_costs_gated_kernel: class / motion gates inside the per-pair cost
+// functions, a gated pair costs CNL_TRACK_GATE_COST); the assign kernel is the same one and never learns of the gates.
 //
 // The solver is scipy.optimize.linear_sum_assignment's algorithm (rectangular shortest augmenting path, Crouse 2016) in scipy's
 // order and in float64, because the RESULT must be scipy's, ties included: box-cost matrices are full of ties (every non-overlapping
@@ -87,14 +89,15 @@ __host__ __device__ inline StreamRec stream_rec(int k, int T, int with_dets, boo
 }
 
 // grid (pair blocks of the largest stream, S_live): blockIdx.y = slot i of this step's detections, stream live[i].
-template <bool LOW>
-__global__ __launch_bounds__(256) void streams_costs_kernel(const float* __restrict__ det_emb, const float* __restrict__ det_box,
-                                                            const float* __restrict__ det_score, const void* __restrict__ det_label, int label_kind,
-                                                            const int* __restrict__ live, const int* __restrict__ trk_off, int S, int k, int E, float thr,
-                                                            float low_thr,
-                                                            const float* __restrict__ trk_emb, const float* __restrict__ trk_box, int R, int T_max,
-                                                            int box_mode, int reid_metric, int with_dets, char* __restrict__ ws,
-                                                            char* __restrict__ record, long record_stride) {
+// GATED (cnl_track_streams_gated_f32): the class / motion gates inside the per-pair cost functions (`g`: the pooled tables); every other byte as LOW.
+template <bool LOW, bool GATED>
+__device__ __forceinline__ void streams_costs_body(const float* __restrict__ det_emb, const float* __restrict__ det_box,
+                                                   const float* __restrict__ det_score, const void* __restrict__ det_label, int label_kind,
+                                                   const int* __restrict__ live, const int* __restrict__ trk_off, int S, int k, int E, float thr,
+                                                   float low_thr,
+                                                   const float* __restrict__ trk_emb, const float* __restrict__ trk_box, int R, int T_max,
+                                                   int box_mode, int reid_metric, int with_dets, char* __restrict__ ws,
+                                                   char* __restrict__ record, long record_stride, const GateOps& pooled) {
     __shared__ int sel[MAXK];
     __shared__ int low_sel[LOW ? MAXK : 1];
     __shared__ int wave_sum[4];
@@ -140,10 +143,39 @@ __global__ __launch_bounds__(256) void streams_costs_kernel(const float* __restr
     }
     if (!table_ok) return;
     const StreamWs w = streams_ws(ws, S, k, R, s, t0);
-    pair_costs_at((long)blockIdx.x * 256 + threadIdx.x, sel, n, de, db, E, trk_emb + (long)t0 * E, trk_box + (long)t0 * 4, T, box_mode, reid_metric,
-                  w.reid, w.box);
+    GateOps g = pooled;       // the stream's rows of the pooled tables, the slot's labels
+    if (GATED) {
+        if (g.trk_label) g.trk_label += t0;
+        if (g.kx) { g.kx += (long)t0 * 8; g.kP += (long)t0 * 64; }
+        g.det0 = (long)i * k;
+    }
+    pair_costs_at<GATED>((long)blockIdx.x * 256 + threadIdx.x, sel, n, de, db, E, trk_emb + (long)t0 * E, trk_box + (long)t0 * 4, T, box_mode, reid_metric,
+                         w.reid, w.box, g);
     if (LOW)      // n_low <= k: the grid that covers k * T_max pairs covers these
-        pair_box_cost_at((long)blockIdx.x * 256 + threadIdx.x, low_sel, n_low, db, trk_box + (long)t0 * 4, T, box_mode, w.low_box);
+        pair_box_cost_at<GATED>((long)blockIdx.x * 256 + threadIdx.x, low_sel, n_low, db, trk_box + (long)t0 * 4, T, box_mode, w.low_box, g);
+}
+
+template <bool LOW>
+__global__ __launch_bounds__(256) void streams_costs_kernel(const float* __restrict__ det_emb, const float* __restrict__ det_box,
+                                                            const float* __restrict__ det_score, const void* __restrict__ det_label, int label_kind,
+                                                            const int* __restrict__ live, const int* __restrict__ trk_off, int S, int k, int E, float thr,
+                                                            float low_thr,
+                                                            const float* __restrict__ trk_emb, const float* __restrict__ trk_box, int R, int T_max,
+                                                            int box_mode, int reid_metric, int with_dets, char* __restrict__ ws,
+                                                            char* __restrict__ record, long record_stride) {
+    streams_costs_body<LOW, false>(det_emb, det_box, det_score, det_label, label_kind, live, trk_off, S, k, E, thr, low_thr, trk_emb, trk_box, R, T_max, box_mode,
+                                   reid_metric, with_dets, ws, record, record_stride, GateOps{});
+}
+
+__global__ __launch_bounds__(256) void streams_costs_gated_kernel(const float* __restrict__ det_emb, const float* __restrict__ det_box,
+                                                                  const float* __restrict__ det_score, const void* __restrict__ det_label, int label_kind,
+                                                                  const int* __restrict__ live, const int* __restrict__ trk_off, int S, int k, int E,
+                                                                  float thr, float low_thr, const float* __restrict__ trk_emb,
+                                                                  const float* __restrict__ trk_box, int R, int T_max, int box_mode, int reid_metric,
+                                                                  int with_dets, char* __restrict__ ws, char* __restrict__ record, long record_stride,
+                                                                  GateOps pooled) {
+    streams_costs_body<true, true>(det_emb, det_box, det_score, det_label, label_kind, live, trk_off, S, k, E, thr, low_thr, trk_emb, trk_box, R, T_max, box_mode,
+                                   reid_metric, with_dets, ws, record, record_stride, pooled);
 }
 
 // lanes with `flag` take consecutive positions from `count` on, in lane order (count: uniform, advanced)
@@ -338,8 +370,10 @@ extern "C" int64_t cnl_track_streams_low_record_bytes(int32_t k, int32_t T_max, 
     return stream_rec(k, T_max, with_detections ? 1 : 0, true).bytes;
 }
 
-// cnl_track_streams_f32 (low = false; the three low arguments unused) and cnl_track_streams_low_f32: one set of checks, the same two launches.
-static int streams_launch(const char* name, bool low, const float* det_emb, const float* det_box, const float* det_score, const void* det_label,
+// cnl_track_streams_f32 (low = false; the three low arguments unused), cnl_track_streams_low_f32 and cnl_track_streams_gated_f32 (low, gate set: its
+// cost launch is the gated one, and without a low-score stage — low_threshold == detection_threshold — it also takes box_cost 0): one set of checks,
+// the same assign launch.
+static int streams_launch(const char* name, bool low, const cnl_track_gate* gate, const float* det_emb, const float* det_box, const float* det_score, const void* det_label,
                           int32_t label_kind, int32_t S, int32_t S_live, const int32_t* live, int32_t k, int32_t E, float detection_threshold,
                           double reid_threshold, float box_threshold, float low_threshold, float low_box_threshold, const float* trk_emb,
                           const float* trk_box, const int32_t* trk_off, const uint8_t* trk_eligible, int32_t R, int32_t T_max, int32_t box_cost,
@@ -351,12 +385,14 @@ static int streams_launch(const char* name, bool low, const float* det_emb, cons
     CNL_REQUIRE(k <= MAXK, CNL_E_UNSUPPORTED, "%s: k = %d > %d detections per frame", name, k, MAXK);
     CNL_REQUIRE(T_max <= LSAP_MAX_LONG, CNL_E_UNSUPPORTED, "%s: T_max = %d > %d tracks per stream", name, T_max, LSAP_MAX_LONG);
     CNL_REQUIRE(S_live <= 65535, CNL_E_UNSUPPORTED, "%s: S_live = %d > 65535 streams per step", name, S_live);
-    CNL_REQUIRE(box_cost >= (low ? 1 : 0) && box_cost <= 2, CNL_E_BAD_ARG, "%s: box_cost must be %s1 (iou), 2 (giou)", name, low ? "" : "0 (none), ");
+    const bool low_stage = low && !(gate != nullptr && low_threshold == detection_threshold);
+    CNL_REQUIRE(box_cost >= (low_stage ? 1 : 0) && box_cost <= 2, CNL_E_BAD_ARG, "%s: box_cost must be %s1 (iou), 2 (giou)", name, low_stage ? "" : "0 (none), ");
     CNL_REQUIRE(!low || (low_threshold >= 0.f && low_threshold <= detection_threshold), CNL_E_BAD_ARG,
                 "%s: low_threshold %g must lie in [0, detection_threshold = %g]", name, (double)low_threshold, (double)detection_threshold);
     CNL_REQUIRE(reid_metric >= 0 && reid_metric <= 7, CNL_E_BAD_ARG, "%s: reid_metric must be 0 (cosine) .. 7 (correlation)", name);
     CNL_REQUIRE(label_kind >= 0 && label_kind <= 3 && (label_kind == 0 || det_label), CNL_E_BAD_ARG,
                 "%s: label_kind must be 0 (none), 1 (int64), 2 (int32), 3 (float32) with det_label set", name);
+    if (int rc = check_gate(name, gate, det_box, {reid_threshold, (double)box_threshold, (double)low_box_threshold})) return rc;
     CNL_REQUIRE(R == 0 || trk_emb, CNL_E_BAD_ARG, "%s: R > 0 without track table", name);
     CNL_REQUIRE(R == 0 || box_cost == 0 || trk_box, CNL_E_BAD_ARG, "%s: box cost requested without track boxes", name);
     CNL_REQUIRE(((uintptr_t)record & 7) == 0 && ((uintptr_t)workspace & 7) == 0 && (record_stride & 7) == 0, CNL_E_BAD_ARG,
@@ -375,9 +411,15 @@ static int streams_launch(const char* name, bool low, const float* det_emb, cons
         return rc;
     const long pairs = (long)k * T_max;
     const unsigned gx = (unsigned)(pairs > 0 ? (pairs + 255) / 256 : 1);
-    hipLaunchKernelGGL(low ? streams_costs_kernel<true> : streams_costs_kernel<false>, dim3(gx, (unsigned)S_live), dim3(256), 0, (hipStream_t)stream, det_emb,
-                       det_box, det_score, det_label, label_kind, live, trk_off, S, k, E, detection_threshold, low_threshold, trk_emb, trk_box, R, T_max,
-                       box_cost, reid_metric, wd, (char*)workspace, (char*)record, (long)record_stride);
+    if (gate != nullptr) {
+        const GateOps g{gate->trk_label, gate->kx, gate->kP, gate->motion_gate, gate->motion_weight, det_label, label_kind, 0};
+        hipLaunchKernelGGL(streams_costs_gated_kernel, dim3(gx, (unsigned)S_live), dim3(256), 0, (hipStream_t)stream, det_emb, det_box, det_score, det_label,
+                           label_kind, live, trk_off, S, k, E, detection_threshold, low_threshold, trk_emb, trk_box, R, T_max, box_cost, reid_metric, wd,
+                           (char*)workspace, (char*)record, (long)record_stride, g);
+    } else
+        hipLaunchKernelGGL(low ? streams_costs_kernel<true> : streams_costs_kernel<false>, dim3(gx, (unsigned)S_live), dim3(256), 0, (hipStream_t)stream,
+                           det_emb, det_box, det_score, det_label, label_kind, live, trk_off, S, k, E, detection_threshold, low_threshold, trk_emb, trk_box, R,
+                           T_max, box_cost, reid_metric, wd, (char*)workspace, (char*)record, (long)record_stride);
     if (int rc = cnl::check_launch("track streams_costs_kernel")) return rc;
     hipLaunchKernelGGL(low ? streams_assign_kernel<true> : streams_assign_kernel<false>, dim3((unsigned)S_live), dim3(64), lsap_lds_bytes(nr_cap, nc_cap),
                        (hipStream_t)stream, live, trk_off, S, k, R, T_max, reid_threshold, box_threshold, low_box_threshold, trk_eligible, box_cost, wd,
@@ -391,7 +433,7 @@ extern "C" int cnl_track_streams_f32(const float* det_emb, const float* det_box,
                                      const int32_t* trk_off, int32_t R, int32_t T_max, int32_t box_cost, int32_t reid_metric,
                                      int32_t with_detections, void* workspace, int64_t workspace_bytes, void* record, int64_t record_stride,
                                      void* stream) {
-    return streams_launch("cnl_track_streams_f32", false, det_emb, det_box, det_score, det_label, label_kind, S, S_live, live, k, E, detection_threshold,
+    return streams_launch("cnl_track_streams_f32", false, nullptr, det_emb, det_box, det_score, det_label, label_kind, S, S_live, live, k, E, detection_threshold,
                           reid_threshold, box_threshold, 0.f, 0.f, trk_emb, trk_box, trk_off, nullptr, R, T_max, box_cost, reid_metric, with_detections,
                           workspace, workspace_bytes, record, record_stride, stream);
 }
@@ -402,7 +444,19 @@ extern "C" int cnl_track_streams_low_f32(const float* det_emb, const float* det_
                                          const float* trk_emb, const float* trk_box, const int32_t* trk_off, const uint8_t* trk_eligible, int32_t R,
                                          int32_t T_max, int32_t box_cost, int32_t reid_metric, int32_t with_detections, void* workspace,
                                          int64_t workspace_bytes, void* record, int64_t record_stride, void* stream) {
-    return streams_launch("cnl_track_streams_low_f32", true, det_emb, det_box, det_score, det_label, label_kind, S, S_live, live, k, E,
+    return streams_launch("cnl_track_streams_low_f32", true, nullptr, det_emb, det_box, det_score, det_label, label_kind, S, S_live, live, k, E,
+                          detection_threshold, reid_threshold, box_threshold, low_threshold, low_box_threshold, trk_emb, trk_box, trk_off, trk_eligible, R,
+                          T_max, box_cost, reid_metric, with_detections, workspace, workspace_bytes, record, record_stride, stream);
+}
+
+extern "C" int cnl_track_streams_gated_f32(const float* det_emb, const float* det_box, const float* det_score, const void* det_label, int32_t label_kind,
+                                           int32_t S, int32_t S_live, const int32_t* live, int32_t k, int32_t E, float detection_threshold,
+                                           double reid_threshold, float box_threshold, float low_threshold, float low_box_threshold,
+                                           const float* trk_emb, const float* trk_box, const int32_t* trk_off, const uint8_t* trk_eligible, int32_t R,
+                                           int32_t T_max, int32_t box_cost, int32_t reid_metric, int32_t with_detections, void* workspace,
+                                           int64_t workspace_bytes, void* record, int64_t record_stride, const cnl_track_gate* gate, void* stream) {
+    static const cnl_track_gate off = {nullptr, nullptr, nullptr, 0.0, 1.0};
+    return streams_launch("cnl_track_streams_gated_f32", true, gate ? gate : &off, det_emb, det_box, det_score, det_label, label_kind, S, S_live, live, k, E,
                           detection_threshold, reid_threshold, box_threshold, low_threshold, low_box_threshold, trk_emb, trk_box, trk_off, trk_eligible, R,
                           T_max, box_cost, reid_metric, with_detections, workspace, workspace_bytes, record, record_stride, stream);
 }

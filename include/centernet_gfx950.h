@@ -1174,6 +1174,62 @@ int cnl_track_kalman_f64(const double* x, const double* P, const float* det_box,
                          int32_t* out_status, void* stream);
 
 /*
+ * Class-aware and Kalman-gated association, opt-in: the cost stage of the two association paths with gates inside the per-pair cost functions.
+ * The entries above are unchanged; the assignment code is unchanged too — it solves the gated matrices, and the thresholds reject gated pairs.
+ *
+ * A gated pair's cost is the constant CNL_TRACK_GATE_COST = 1e5 (exact in float32 and float64; DeepSORT's INFTY_COST).  It is finite on purpose:
+ * with +inf, scipy.optimize.linear_sum_assignment raises "cost matrix is infeasible" as soon as one class has more detections than tracks.  An
+ * optimal assignment of the gated matrix restricted to the ungated pairs is the assignment of each class on its own, and every threshold below
+ * 1e5 drops the gated pairs it had to use; so every threshold (re-ID, box, low box, motion_gate) >= 1e5 is CNL_E_BAD_ARG while a gate is on.
+ *
+ * Class gate (trk_label set): detection d and track row t may be matched only if label(d) == trk_label[t], label(d) being det_label[d] read by
+ * label_kind and cast to int32 exactly as the record's label section is (label_kind 0: every label is 0).  A cross-class pair costs
+ * CNL_TRACK_GATE_COST in the re-ID matrix, in the box matrix and in the low-score stage's box matrix.
+ *
+ * Motion gate (kx / kP set: the state tables cnl_track_kalman_f64 wrote, i.e. the PREDICTED state the previous step left), stage 1 only — the
+ * box matrices are not motion-gated, as in DeepSORT.  For kept detection d with box z (float32 converted to float64) and track row t, in
+ * float64, one rounding per operation, no fused multiply-add, every sum starting with its first term and adding the others in ascending order:
+ *   1. x = kx[t][0:4], A = the upper-left 4 x 4 block of kP[t], read as its upper triangle;
+ *   2. w = x2 - x0, h = x3 - x1, r_i = q_i * q_i with q_i = (i odd ? h : w) / 20;
+ *   3. S = A + diag(r) = L D L' exactly as the update step of cnl_track_kalman_f64 factors it (one device function, shared);
+ *   4. y_i = z_i - x_i;  u_i = y_i - sum_{k<i} L_ik * u_k  (i = 0..3; no subtraction for i = 0);  v_i = u_i / d_i;
+ *      m = ((v0 * u0 + v1 * u1) + v2 * u2) + v3 * u3   — the squared Mahalanobis distance y' S^-1 y;
+ *   5. a pivot d_j that is not finite and strictly positive, or an m for which m <= motion_gate is false (a NaN included), gates the pair:
+ *      its re-ID cost is CNL_TRACK_GATE_COST.  Otherwise the re-ID cost is reid (its bits untouched) when motion_weight == 1, else
+ *      (motion_weight * reid) + ((1 - motion_weight) * m)  (FairMOT's lambda; 1 - motion_weight is one float64 subtraction).
+ * A cross-class pair is gated whatever its motion.  Pairs are independent: a NaN coordinate gates its own pairs and changes no other pair's bits.
+ *
+ * cnl_track_gate carries the operands (40 bytes); a null `gate`, or null members, switch that gate off.  trk_label [T] (pooled [R] for the
+ * streams entry), kx [T,8] / kP [T,64] f64 (pooled likewise) are device or cnl_host_alloc memory.
+ *
+ * cnl_track_frame_gated_f32 / cnl_track_streams_gated_f32: cnl_track_frame_low_f32 / cnl_track_streams_low_f32 plus `gate`.  Records,
+ * workspace, sizes (the _low_ helpers), status words and checks are those entries'; "no low-score stage" is low_threshold ==
+ * detection_threshold (n_low = 0), and then box_cost may be 0.  With every gate off they write byte for byte what the _low_ entries write.
+ * CNL_E_BAD_ARG in addition: kx and kP not null together or not 8-byte aligned; trk_label not 4-byte aligned; with the motion gate, det_box
+ * not 16-byte aligned (a box is read as one 16-byte word), motion_gate not in [0, 1e5) or motion_weight not in [0, 1] (a NaN included); with
+ * any gate on, a threshold >= 1e5.  The class gate is on exactly when trk_label is set, so a caller whose table is empty (T == 0, R == 0: no
+ * pairs) may pass null; with label_kind 0 every detection is of class 0.
+ */
+#define CNL_TRACK_GATE_COST 1e5
+typedef struct cnl_track_gate {
+    const int32_t* trk_label;   /* the tracks' labels (the label at birth); null: the class gate is off */
+    const double* kx;           /* filter state table; null together with kP: the motion gate is off */
+    const double* kP;
+    double motion_gate;         /* threshold on m; DeepSORT's chi2inv95[4] is 9.4877 */
+    double motion_weight;       /* 1: the re-ID cost as it is inside the gate */
+} cnl_track_gate;
+int cnl_track_frame_gated_f32(const float* det_emb, const float* det_box, const float* det_score, const void* det_label, int32_t label_kind,
+                              int32_t k, int32_t E, float detection_threshold, float low_threshold, const float* trk_emb, const float* trk_box,
+                              int32_t T, int32_t box_cost, int32_t reid_metric, int32_t with_detections, void* record, int64_t record_bytes,
+                              const cnl_track_gate* gate, void* stream);
+int cnl_track_streams_gated_f32(const float* det_emb, const float* det_box, const float* det_score, const void* det_label, int32_t label_kind,
+                                int32_t S, int32_t S_live, const int32_t* live, int32_t k, int32_t E, float detection_threshold,
+                                double reid_threshold, float box_threshold, float low_threshold, float low_box_threshold, const float* trk_emb,
+                                const float* trk_box, const int32_t* trk_off, const uint8_t* trk_eligible, int32_t R, int32_t T_max,
+                                int32_t box_cost, int32_t reid_metric, int32_t with_detections, void* workspace, int64_t workspace_bytes,
+                                void* record, int64_t record_stride, const cnl_track_gate* gate, void* stream);
+
+/*
  * Wire formats: COCO boxes are xywh — torchvision box_convert(boxes, "xyxy", "xywh") of
  * CenterNet.validation_step (models/centernet.py:207): out[i] = (x1, y1, x2 - x1, y2 - y1); n boxes of 4 floats, may be in place.
  * boxes and out are 16-byte aligned (a box is moved as one 16-byte word; CNL_E_BAD_ARG otherwise).
