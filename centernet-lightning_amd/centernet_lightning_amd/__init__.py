@@ -7,7 +7,7 @@ is in libcenternet_gfx950.so (hand-written HIP kernels, C ABI in include/centern
 from .config import load_config
 from .models import CenterNet, DetectionOutput, TrackingOutput, build_centernet
 from .collate import (Collator, all_gather_records, collate_detections, pack_detections, shard_range, unpack_detections)
-from .tracker import Tracker, TrackerBank, Track, TrackState, build_tracker, match_with_threshold
+from .tracker import Tracker, TrackerBank, Track, TrackState, ResidentTrack, build_tracker, match_with_threshold
 from . import decode, formats
 from .letterbox import LetterboxGeometry, letterbox_geometry, letterbox_yuv420, multiscale_sizes
 from .tiles import TileGeometry, merge_soft, merge_tiles, tile_grid, tile_uint8, tile_yuv420
@@ -26,7 +26,7 @@ from .export import TraceableCenterNet, export_onnx, export_torchscript
 
 __all__ = ["CenterNet", "build_centernet", "load_config", "DetectionOutput", "TrackingOutput", "decode",
            "collate_detections", "Collator", "all_gather_records", "pack_detections", "unpack_detections", "shard_range",
-           "Tracker", "TrackerBank", "Track", "TrackState", "build_tracker", "match_with_threshold", "formats", "TraceableCenterNet", "export_torchscript", "export_onnx",
+           "Tracker", "TrackerBank", "Track", "TrackState", "ResidentTrack", "build_tracker", "match_with_threshold", "formats", "TraceableCenterNet", "export_torchscript", "export_onnx",
            "letterbox_geometry", "LetterboxGeometry", "TileGeometry", "tile_grid", "tile_uint8", "merge_tiles",
            "letterbox_yuv420", "tile_yuv420", "yuv_coefficients", "split_planes", "crop_detections",
            "draw_detections", "DEFAULT_PALETTE", "rgb_to_yuv", "flip_merge", "mirror_append_uint8", "CocoEvaluator",

@@ -94,6 +94,21 @@ class TrackGate(Structure):
     _fields_ = [("trk_label", c_void_p), ("kx", c_void_p), ("kP", c_void_p), ("motion_gate", c_double), ("motion_weight", c_double)]
 
 
+class TrackRows(Structure):
+    """cnl_track_rows: the per-row state arrays of the device life cycle (56 bytes), all device memory."""
+    _fields_ = [(n, c_void_p) for n in ("track_id", "state", "birth_age", "inactive_age", "label", "box", "trk_off")]
+
+
+class TrackLifecycle(Structure):
+    """cnl_track_lifecycle: the operands of cnl_track_lifecycle_i32 / cnl_track_lifecycle_emit_f64 (320 bytes)."""
+    _fields_ = [("old_rows", TrackRows), ("new_rows", TrackRows), ("record", c_void_p), ("record_stride", ctypes.c_int64)] + \
+               [(n, c_void_p) for n in ("live", "slot_of", "det_label", "det_box", "next_track_id", "status", "src_trk", "src_det", "flags", "keep_emb",
+                                        "trk_eligible", "kalman_box", "out_box", "out_track_id", "out_label", "out_count", "workspace")] + \
+               [("workspace_bytes", ctypes.c_int64)] + \
+               [(n, c_int32) for n in ("S", "S_live", "k", "max_tracks", "label_kind", "low_record", "min_birth_age", "max_inactive_age", "step",
+                                       "out_box_f64", "reset_stream", "reserved")]
+
+
 class LossParams(Structure):
     """cnl_loss_params: the rule of one cnl_detection_loss_f64 call (72 bytes; cnl_sizeof_params(4))."""
     _fields_ = [("stride", c_double), ("target_param", c_double), ("hm_alpha", c_double), ("hm_beta", c_double),
@@ -279,6 +294,9 @@ _SIGNATURES = {
                                                    c_double, c_float, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32,
                                                    c_int32, c_int32, c_void_p, ctypes.c_int64, c_void_p, ctypes.c_int64, ctypes.POINTER(TrackGate),
                                                    c_void_p]),
+    "cnl_track_lifecycle_workspace_bytes": (ctypes.c_int64, [c_int32, c_int32]),
+    "cnl_track_lifecycle_i32": (ctypes.c_int, [ctypes.POINTER(TrackLifecycle), c_void_p]),
+    "cnl_track_lifecycle_emit_f64": (ctypes.c_int, [ctypes.POINTER(TrackLifecycle), c_void_p]),
     "cnl_relu_grad_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32]),
     "cnl_relu_grad_terms": (c_int64, [c_int32, c_int32, c_int32, c_int32]),
     "cnl_relu_grad_f32": (ctypes.c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p,

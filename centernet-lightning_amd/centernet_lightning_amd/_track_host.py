@@ -608,6 +608,141 @@ class TrackTable:
             self.box[:len(tracks)].copy_(torch.from_numpy(boxes), non_blocking=False)
 
 
+_LIFECYCLE_MODES = ("host", "device")
+_STATES = (None, TrackState.UNCONFIRMED, TrackState.ACTIVE, TrackState.INACTIVE, TrackState.TO_DELETE)      # the device's state words
+STATUS_OVERFLOW = 1 << 16       # bit of a stream's sticky status word: births were dropped at max_tracks (cnl_track_lifecycle_i32)
+
+
+class ResidentKalman:
+    """`kf` of a ResidentTrack: the filter state of its row at the download, `x` float64 [8], `P` float64 [8, 8]."""
+    __slots__ = ("x", "P")
+
+    def __init__(self, x, P):
+        self.x, self.P = x, P
+
+
+class ResidentTrack:
+    """A track of a TrackerBank with lifecycle="device" as one download found it: Track's fields as plain values (`embedding` and `kf` are
+    copies of the row, not views of the device table; nothing here changes the device state)."""
+    __slots__ = ("track_id", "bbox", "label", "state", "birth_age", "inactive_age", "embedding", "kf")
+
+    def __init__(self, track_id, bbox, label, state, birth_age, inactive_age, embedding, kf):
+        self.track_id, self.bbox, self.label, self.state = track_id, bbox, label, state
+        self.birth_age, self.inactive_age, self.embedding, self.kf = birth_age, inactive_age, embedding, kf
+
+    active = property(lambda self: self.state == TrackState.ACTIVE)
+    confirmed = property(lambda self: self.state != TrackState.UNCONFIRMED)
+    to_delete = property(lambda self: self.state == TrackState.TO_DELETE)
+
+    def __repr__(self):
+        return f"track id: {self.track_id}, bbox: {self.bbox}, label: {self.label}, state: {self.state.name}"
+
+
+class ResidentState:
+    """Device memory of a TrackerBank with lifecycle="device" (cnl_track_lifecycle_i32): everything a step reads or writes, allocated ONCE at
+    the capacity C = S * max_tracks rows and zeroed.
+    One control block (uint8) holds the two banks of per-row state (track_id int64, reported box float64 [C, 4], state / birth_age /
+    inactive_age / label int32, trk_off int32 [S + 1]; one is current, the next step writes the other), next_track_id int64 [S], the sticky
+    status words int32 [S, 2], the S association records; and, behind what a download copies, the index lists of the table update (src_trk,
+    src_det, flags, keep_emb), the eligibility bytes, the filter launch's record and the life cycle's staging.  Beside it the ping-pong
+    pairs of the pooled tables (emb / box float32, kx / kP float64 with the device filter) and the association workspace:
+    streams(_low)_workspace_bytes(S, k, C), 20 (24) bytes per (detection, row) pair — about 49 MB at S = 32, k = 300, max_tracks = 256.
+    `args[b]` is the cnl_track_lifecycle of a step whose current bank is b; `live_lists` keeps one device copy per distinct `live` tuple
+    (never rewritten, so a queued launch can never see another step's list)."""
+
+    def __init__(self, S, M, k, E, dev, kalman, low_rec):
+        lib = _lib.load()
+        self.S, self.M, self.k, self.E, self.dev, self.kalman, self.low_rec = S, M, k, E, dev, kalman, low_rec
+        C = self.C = S * M
+        self.stride = (streams_low_layout if low_rec else streams_layout)(k, M, 0).bytes
+        self.cur = 0
+        off, at = {}, 0
+
+        def carve(name, nbytes):
+            nonlocal at
+            off[name] = at
+            at = (at + nbytes + 7) & ~7
+
+        for b in (0, 1):
+            for name, nbytes in (("track_id", 8 * C), ("box", 32 * C), ("state", 4 * C), ("birth_age", 4 * C), ("inactive_age", 4 * C),
+                                 ("label", 4 * C), ("trk_off", 4 * (S + 1))):
+                carve((name, b), nbytes)
+        carve("next_track_id", 8 * S)
+        carve("status", 8 * S)
+        carve("record", S * self.stride)
+        self.down_bytes = at            # a download copies the block up to here
+        for name, nbytes in (("src_trk", 4 * C), ("src_det", 4 * C), ("flags", 4 * C), ("keep_emb", C), ("trk_eligible", C),
+                             ("kalman_box", 32 * C if kalman else 0), ("kalman_status", 4 * C if kalman else 0)):
+            carve(name, nbytes)
+        lc_bytes = int(lib.cnl_track_lifecycle_workspace_bytes(S, M))
+        carve("workspace", lc_bytes)
+        self.off = off
+        self.ctl = torch.zeros(at, device=dev, dtype=torch.uint8)
+        ws_bytes = (streams_low_workspace_bytes if low_rec else streams_workspace_bytes)(S, k, C)
+        self.ws = torch.empty(ws_bytes, device=dev, dtype=torch.uint8)
+        self.emb = [torch.zeros((C, E), device=dev, dtype=torch.float32) for _ in (0, 1)]
+        self.box = [torch.zeros((C, 4), device=dev, dtype=torch.float32) for _ in (0, 1)]
+        self.kx = [torch.zeros((C, 8), device=dev, dtype=torch.float64) for _ in (0, 1)] if kalman else None
+        self.kP = [torch.zeros((C, 64), device=dev, dtype=torch.float64) for _ in (0, 1)] if kalman else None
+        self.live_lists = {}
+        self.live_list(())
+        base = self.ctl.data_ptr()
+        self.args = []
+        for b in (0, 1):
+            a = _lib.TrackLifecycle()
+            for rows, bank in ((a.old_rows, b), (a.new_rows, 1 - b)):
+                for name in ("track_id", "state", "birth_age", "inactive_age", "label", "box", "trk_off"):
+                    setattr(rows, name, base + off[(name, bank)])
+            a.record, a.record_stride = base + off["record"], self.stride
+            for name in ("next_track_id", "status", "src_trk", "src_det", "flags", "keep_emb", "trk_eligible", "workspace"):
+                setattr(a, name, base + off[name])
+            a.kalman_box = base + off["kalman_box"] if kalman else None
+            a.workspace_bytes = lc_bytes
+            a.S, a.k, a.max_tracks, a.low_record, a.out_box_f64 = S, k, M, int(low_rec), int(kalman)
+            self.args.append(a)
+
+    def ptr(self, name, bank=None):
+        return self.ctl.data_ptr() + self.off[name if bank is None else (name, bank)]
+
+    def live_list(self, live):
+        """Device int32 [L + S]: the `live` list of a step, then slot_of (stream -> slot, -1: no part); () — nobody, what reset(stream) runs
+        with — is uploaded with the allocation."""
+        t = self.live_lists.get(live)
+        if t is None:
+            slot_of = [-1] * self.S
+            for i, s in enumerate(live):
+                slot_of[s] = i
+            t = self.live_lists[live] = torch.tensor(list(live) + slot_of, dtype=torch.int32).to(self.dev)
+        return t
+
+    def download(self):
+        """ONE device -> host copy: the control block's state part and the current tables -> dict of numpy arrays over all C rows
+        (`trk_off` says which are live) + `records`, the uint8 records of the S streams."""
+        b, C, S = self.cur, self.C, self.S
+        parts = [self.ctl[:self.down_bytes], self.emb[b].view(-1).view(torch.uint8), self.box[b].view(-1).view(torch.uint8)]
+        if self.kalman:
+            parts += [self.kx[b].view(-1).view(torch.uint8), self.kP[b].view(-1).view(torch.uint8)]
+        h = torch.cat(parts).cpu().numpy()
+        off = self.off
+
+        def take(name, dtype, count, bank=None):
+            o = off[name if bank is None else (name, bank)]
+            return h[o:o + count * np.dtype(dtype).itemsize].view(dtype)
+
+        out = {"track_id": take("track_id", np.int64, C, b), "bbox": take("box", np.float64, 4 * C, b).reshape(C, 4),
+               "trk_off": take("trk_off", np.int32, S + 1, b), "next_track_id": take("next_track_id", np.int64, S),
+               "status": take("status", np.int32, 2 * S).reshape(S, 2),
+               "records": h[off["record"]:off["record"] + S * self.stride].reshape(S, self.stride)}
+        for name in ("state", "birth_age", "inactive_age", "label"):
+            out[name] = take(name, np.int32, C, b)
+        at = self.down_bytes
+        for name, dtype, width in (("emb", np.float32, self.E), ("box", np.float32, 4)) + ((("kx", np.float64, 8), ("kP", np.float64, 64)) if self.kalman else ()):
+            n = C * width * np.dtype(dtype).itemsize
+            out[name] = h[at:at + n].view(dtype).reshape(C, width)
+            at += n
+        return out
+
+
 class TrackerSettings:
     """What `Tracker` and `TrackerBank` share: the reference's constructor arguments (tracker.py:50), the device, the model run."""
     _update_name = "update"

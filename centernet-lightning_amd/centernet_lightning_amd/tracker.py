@@ -36,18 +36,23 @@ functions.  A detection may only take a track of its own label (all three stages
 track's predicted filter state (stage 1; needs kalman="device").  A gated pair costs 1e5 — finite, so that scipy never sees an infeasible matrix —
 and the assignment code is the one above: it solves the gated matrices and its thresholds reject the gated pairs.  Both paths launch one gated
 entry (cnl_track_frame_gated_f32 / cnl_track_streams_gated_f32) that covers the step with and without the low-score stage on the `_low` layouts.
+`TrackerBank(lifecycle="device")` (opt-in; "host" is everything above) also runs the track life cycle on the device (cnl_track_lifecycle_i32,
+csrc/track_lifecycle.hip): a step is 6 or 7 launches without a synchronisation and returns device tensors; the host reads tracks, counters and
+match lists from one download on demand (`snapshot()`, `bank[s].tracks`) and the status words through `check()`.  See its constructor.
 
 `Tracker` (one video) and `TrackerBank` (S videos, one frame each per step) are thin callers of the shared host side in _track_host.py:
 normalise the inputs, launch, read the record, assign (or take the device's lists), life cycle, table update, Kalman.
 """
 import ctypes
+import functools
 from typing import List
 
 import numpy as np
 import torch
 
 from . import _lib
-from ._track_host import (_BOX_MODES, _REID_METRICS, _STATUS_TOO_LARGE, BoxKalman, Track, TrackerSettings, TrackState, _grown,  # noqa: F401
+from ._track_host import (_BOX_MODES, _LIFECYCLE_MODES, _REID_METRICS, _STATES, _STATUS_TOO_LARGE, STATUS_OVERFLOW, BoxKalman,  # noqa: F401
+                          ResidentKalman, ResidentState, ResidentTrack, Track, TrackerSettings, TrackState, _grown,
                           _Mapped, _on, check_kept_count, frame_layout, frame_low_layout, gate_costs, launch_frame, launch_frame_gated, launch_frame_low,
                           life_cycle, low_stage,
                           match_with_threshold, normalise_detections, read_stream_low_record, read_stream_record, streams_layout,
@@ -203,6 +208,55 @@ class _StreamState:
         self.next_track_id = 0
 
 
+class _ResidentStream:
+    """What `TrackerBank[s]` returns with lifecycle="device": the same names, read from the bank's last download (made on first use after a
+    step; ONE device -> host copy for all streams)."""
+    __slots__ = ("_bank", "_s")
+
+    def __init__(self, bank, s):
+        self._bank, self._s = bank, s
+
+    tracks = property(lambda self: self._bank._resident_tracks(self._s))
+    next_track_id = property(lambda self: int(self._bank._download()["next_track_id"][self._s]))
+    frame = property(lambda self: self._bank._frames[self._s])
+
+
+class _ResidentLists:
+    """`last_matches` / `last_low_matches` with lifecycle="device": a sequence over the streams, read from the records of the last download."""
+    __slots__ = ("_bank", "_low")
+
+    def __init__(self, bank, low):
+        self._bank, self._low = bank, low
+
+    def __len__(self):
+        return self._bank.num_streams
+
+    def __getitem__(self, s):
+        return self._bank._resident_matches(range(self._bank.num_streams)[s], self._low)
+
+    def __iter__(self):
+        return (self[s] for s in range(len(self)))
+
+
+def _lifecycle_options(init):
+    """TrackerBank.__init__ with the keyword-only options `lifecycle` and `max_tracks`.  They are taken here, in front of the constructor, so
+    that its own parameter list stays the one callers and introspection know: it still ends with `kalman`."""
+    @functools.wraps(init)
+    def with_options(self, *args, lifecycle="host", max_tracks=256, **kwargs):
+        if lifecycle not in _LIFECYCLE_MODES:
+            raise ValueError(f"lifecycle={lifecycle!r}: expected 'host' or 'device'")
+        if isinstance(max_tracks, bool) or not isinstance(max_tracks, (int, np.integer)) or max_tracks < 1:
+            raise ValueError(f"max_tracks={max_tracks!r}: expected an integer >= 1")
+        if lifecycle == "device" and max_tracks > 4096:
+            raise ValueError(f"max_tracks={max_tracks!r} with lifecycle='device': the device assignment takes at most 4096 tracks per stream")
+        self.lifecycle, self.max_tracks = lifecycle, int(max_tracks)
+        self._resident = lifecycle == "device"
+        self._res = self._snap = None       # lifecycle="device": the ResidentState (allocated by the first step); the last download
+        self._step_no = 0
+        init(self, *args, **kwargs)
+    return with_options
+
+
 class TrackerBank(TrackerSettings):
     """S independent trackers whose unit of work is ONE FRAME FROM EACH STREAM (csrc/track_streams.hip): `step_batch(images)` takes frame i
     as the next frame of stream i — what a live deployment with S cameras has in hand — where `Tracker.step_batch` takes the batch as
@@ -216,10 +270,30 @@ class TrackerBank(TrackerSettings):
     caller sees what `Tracker` raises there (scipy's ValueError); the exception leaves EVERY stream of the bank as it was before the step."""
     _update_name = "update_batch"
 
+    @_lifecycle_options
     def __init__(self, num_streams, model=None, nms_kernel=3, num_detections=300, detection_threshold=0.3, reid_cost="cosine",
                  reid_threshold=0.2, box_cost="iou", box_threshold=0.5, smoothing_factor=0.5, use_kalman=False,
                  max_inactive_age=30, min_birth_age=2, device=None, allow_host_cost=False, low_threshold=None,
                  low_box_threshold=None, low_match="active", class_aware=False, motion_gate=None, motion_weight=1.0, kalman="host"):
+        """lifecycle, max_tracks (keyword-only, taken by _lifecycle_options around this constructor): "host" (default) is the bank described
+        above — same launches, same bytes; max_tracks is accepted and has no effect.  "device" moves the track life cycle to the device (cnl_track_lifecycle_i32, csrc/track_lifecycle.hip): a
+        step is a fixed sequence of launches on the caller's current stream — association (2), life cycle + pack (2), table update (1), the
+        filter with kalman="device" (1), emit (1): 6 or 7 — with NO synchronisation and no per-track Python.  `step_batch` / `update_batch`
+        then return device tensors ordered on that stream, for L = len(streams): "bboxes" [L, max_tracks, 4] (float32; float64 with the
+        filter), "track_ids" / "labels" [L, max_tracks] int64, "count" [L] int32 — the ACTIVE tracks of each participating stream compacted in
+        row order, zeros from `count` on; `draw_detections(..., numbers=, count=)` and `crop_detections` take them as they are.
+        `bank[s].tracks` / `.next_track_id`, `last_matches[s]`, `last_low_matches[s]` and `snapshot()` are read from ONE download made on
+        first use after a step (it finishes the table's stream first); `check()` downloads the sticky status words.
+        Every stream owns at most max_tracks (<= 4096) rows; the state is allocated once at S * max_tracks rows, the association workspace
+        at 20 (24 with low_threshold / gates) bytes per (detection, row) pair: about 49 MB at S = 32, k = 300, max_tracks = 256.  Births
+        beyond max_tracks are dropped (the first unmatched detections are born first, a dropped one takes no id) and `check()` reports it.
+        Detections are tensors on the bank's device (host arrays are refused), k and E are fixed by the first step.
+        The mode's one deviation: a stream whose costs are not finite cannot be redone on the host without reading; it is SKIPPED for that
+        step — rows carried, nothing aged, no prediction, as if it had not been in `streams` — and `check()` raises for it later.
+        Refused: use_kalman=True with kalman="host" (per-track host arithmetic is what the mode removes)."""
+        if self._resident and use_kalman and kalman == "host":
+            raise ValueError("lifecycle='device' with use_kalman=True, kalman='host': the host filter is per-track arithmetic on the host; "
+                             "pass kalman='device'")
         if isinstance(num_streams, bool) or not isinstance(num_streams, (int, np.integer)) or num_streams < 1:
             raise ValueError(f"num_streams={num_streams!r}: expected an integer >= 1")
         if callable(reid_cost) or callable(box_cost) or reid_cost not in _REID_METRICS:
@@ -241,15 +315,22 @@ class TrackerBank(TrackerSettings):
         return self.num_streams
 
     def __getitem__(self, s):
-        return self._streams[s]
+        return _ResidentStream(self, range(self.num_streams)[s]) if self._resident else self._streams[s]
 
     def track_embeddings(self, s):
         """Device view [T_s, E] of stream s's rows of the pooled table (row order = self[s].tracks)."""
+        if self._resident:
+            off = self._download()["trk_off"] if self._res is not None else None
+            return self._emb[int(off[s]):int(off[s + 1])] if off is not None else None
         return self._emb[int(self._off[s]):int(self._off[s + 1])] if self._emb is not None else None
 
     # ------------------------------------------------------------------ state
     def reset(self, stream=None):
-        """Forget every stream (None) or one stream; the other streams keep tracks, counters and table rows."""
+        """Forget every stream (None) or one stream; the other streams keep tracks, counters and table rows.
+        lifecycle="device": stream-ordered, no synchronisation (a zeroing of the state; for one stream, the step's launches with that stream
+        marked)."""
+        if self._resident:
+            return self._reset_device(stream)
         if stream is None:
             self._streams = [_StreamState() for _ in range(self.num_streams)]
             self._table.clear()
@@ -302,6 +383,11 @@ class TrackerBank(TrackerSettings):
         if images.dim() != 4 or images.shape[0] != len(live):
             raise ValueError(f"images {tuple(images.shape)}: expected [{len(live)}, 3, H, W], one frame per participating stream")
         det = self._detect(images, kwargs)
+        if self._resident:
+            out = self._step_device(det["bboxes"], det["labels"], det["scores"], det["embeddings"], live, kwargs)
+            for s in live:
+                self._frames[s] += 1
+            return out
         self._step(det["bboxes"], det["labels"], det["scores"], det["embeddings"], live, kwargs)
         out = {"bboxes": [], "track_ids": []}
         for s in live:
@@ -348,7 +434,10 @@ class TrackerBank(TrackerSettings):
         """One frame's detections for each participating stream: [L, k, 4], [L, k], [L, k], [L, k, E] (numpy arrays or torch tensors; L =
         len(streams), default every stream).  As `Tracker.update`, it does not advance `frame`.  With use_kalman=True, kalman="device" the
         step ends with a SECOND stream synchronisation, behind the filter launch (see `Tracker.update`); a stream that takes no part keeps
-        its filter state unpredicted, as on the host path."""
+        its filter state unpredicted, as on the host path.
+        lifecycle="device": returns the step's device tensors (see the constructor); None on the host path."""
+        if self._resident:
+            return self._step_device(bboxes, labels, scores, embeddings, self._check_streams(streams), kwargs)
         self._step(bboxes, labels, scores, embeddings, self._check_streams(streams), kwargs)
 
     def _step(self, bboxes, labels, scores, embeddings, live, kwargs):
@@ -471,10 +560,213 @@ class TrackerBank(TrackerSettings):
                     t.kalman_predict()
 
 
+    # ------------------------------------------------------------------ lifecycle="device"
+    def _reset_device(self, stream):
+        S = self.num_streams
+        res = self._res
+        self._snap = None
+        if stream is None:
+            self._frames = [0] * S
+            self._has_rec = [False] * S
+            self.last_matches, self.last_low_matches = _ResidentLists(self, False), _ResidentLists(self, True)
+            if res is not None:
+                with _on(res.dev):
+                    cur = torch.cuda.current_stream(res.dev)
+                    self._table.wait_for_other_stream(cur)
+                    res.ctl[:res.down_bytes].zero_()        # offsets, counters, states, status words, records: behind the last step, in stream order
+                    self._table.stream = cur
+            return
+        s = self._check_streams([stream])[0]
+        self._frames[s] = 0
+        self._has_rec[s] = False
+        if res is None:
+            return
+        with _on(res.dev):
+            cur = torch.cuda.current_stream(res.dev)
+            self._table.wait_for_other_stream(cur)
+            # the step's launches without a slot: stream s loses its rows and its counter, every other row is carried (no update, no prediction)
+            self._lifecycle_launches(res, res.live_list(()), 0, res.emb[res.cur], res.box[res.cur], None, 0, None, cur, reset_stream=s)
+
+    def _lifecycle_launches(self, res, lv, L, d_emb, d_box, d_label, label_kind, outs, cur, reset_stream=-1):
+        """Life cycle + pack, table update, filter, emit on `cur`, then the banks and tables change places.  lv: ResidentState.live_list;
+        outs: the step's four output tensors (None with L == 0).  The caller holds the device guard."""
+        lib = _lib.load()
+        b, C = res.cur, res.C
+        stream = ctypes.c_void_p(cur.cuda_stream)
+        a = res.args[b]
+        a.live, a.slot_of, a.S_live = lv.data_ptr(), lv.data_ptr() + 4 * L, L
+        a.det_label, a.label_kind, a.det_box = (d_label.data_ptr() if label_kind else None), label_kind, d_box.data_ptr()
+        a.min_birth_age, a.max_inactive_age, a.step = int(self.min_birth_age), int(self.max_inactive_age), self._step_no & 0x7fffffff
+        a.reset_stream = reset_stream
+        a.out_box, a.out_track_id, a.out_label, a.out_count = (t.data_ptr() for t in outs) if outs is not None else (None,) * 4
+        _lib.check(lib.cnl_track_lifecycle_i32(ctypes.byref(a), stream), "cnl_track_lifecycle_i32")
+        new_emb, new_box = res.emb[1 - b], res.box[1 - b]
+        _lib.check(lib.cnl_track_apply_keep_f32(res.emb[b].data_ptr(), res.box[b].data_ptr(), d_emb.data_ptr(), d_box.data_ptr(), res.ptr("src_trk"),
+                                                res.ptr("src_det"), C, res.E, float(self.smoothing_factor), new_emb.data_ptr(), new_box.data_ptr(),
+                                                res.ptr("keep_emb"), stream), "cnl_track_apply_keep_f32")
+        if res.kalman:
+            _lib.check(lib.cnl_track_kalman_f64(res.kx[b].data_ptr(), res.kP[b].data_ptr(), d_box.data_ptr(), res.ptr("src_trk"), res.ptr("src_det"),
+                                                res.ptr("flags"), C, res.kx[1 - b].data_ptr(), res.kP[1 - b].data_ptr(), new_box.data_ptr(),
+                                                res.ptr("kalman_box"), res.ptr("kalman_status"), stream), "cnl_track_kalman_f64")
+        _lib.check(lib.cnl_track_lifecycle_emit_f64(ctypes.byref(a), stream), "cnl_track_lifecycle_emit_f64")
+        res.cur = 1 - b
+        table = self._table
+        table.emb, table.box, table.stream = new_emb, new_box, cur
+        if res.kalman:
+            table.kx, table.kP = res.kx[1 - b], res.kP[1 - b]
+        self._snap = None
+        self._step_no += 1
+
+    def _step_device(self, bboxes, labels, scores, embeddings, live, kwargs):
+        S, L, M = self.num_streams, len(live), self.max_tracks
+        for name, t in (("bboxes", bboxes), ("labels", labels), ("scores", scores), ("embeddings", embeddings)):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device == self.device):
+                raise ValueError(f"lifecycle='device': {name} must be a tensor on the bank's device, got {type(t).__name__}"
+                                 f"{' on ' + str(t.device) if isinstance(t, torch.Tensor) else ''} (host arrays are refused: the mode exists to "
+                                 "stay on the device)")
+        dev = self.device
+        d_box, d_score, d_emb, d_label, _, label_kind = normalise_detections(dev, bboxes, labels, scores, embeddings, (L,))
+        detection_threshold, reid_threshold, box_threshold, low_threshold, low_box_threshold = self._thresholds(kwargs)
+        low = low_threshold is not None
+        gated = self._gated
+        low_rec = low or gated
+        k, E = int(d_emb.shape[1]), int(d_emb.shape[2])
+        lib = _lib.load()
+        table = self._table
+        with _on(dev):
+            cur = torch.cuda.current_stream(dev)
+            table.wait_for_other_stream(cur)
+            res = self._res
+            if res is None:
+                res = self._res = ResidentState(S, M, k, E, dev, self._device_kalman, low_rec)
+            if (k, E) != (res.k, res.E):
+                raise ValueError(f"lifecycle='device': detections [{L}, {k}, {E}] after [.., {res.k}, {res.E}]: the buffers are sized by the first "
+                                 "step (keep num_detections and the embedding size fixed)")
+            if low_rec != res.low_rec:
+                raise ValueError("lifecycle='device': low_threshold cannot be switched on or off per call (the records are laid out by the first step)")
+            lv = res.live_list(tuple(live))
+            b, C = res.cur, res.C
+            operands = (d_emb.data_ptr(), d_box.data_ptr(), d_score.data_ptr(), d_label.data_ptr() if label_kind else None, label_kind, S, L,
+                        lv.data_ptr(), k, E, float(detection_threshold), float(reid_threshold), float(box_threshold))
+            tables = (res.emb[b].data_ptr(), res.box[b].data_ptr(), res.ptr("trk_off", b))
+            rest = (C, M, _BOX_MODES[self.box_cost], _REID_METRICS[self.reid_cost], 0, res.ws.data_ptr(), res.ws.numel(), res.ptr("record"), res.stride,
+                    ctypes.c_void_p(cur.cuda_stream))
+            if low_rec:
+                eligible = res.ptr("trk_eligible") if low and self.low_match != "all" else None
+                if gated:
+                    gate = _lib.TrackGate(res.ptr("label", b) if self.class_aware else None, None, None, 0.0, 1.0)
+                    if self.motion_gate is not None:
+                        gate.kx, gate.kP, gate.motion_gate, gate.motion_weight = res.kx[b].data_ptr(), res.kP[b].data_ptr(), self.motion_gate, self.motion_weight
+                    _lib.check(lib.cnl_track_streams_gated_f32(*operands, float(low_threshold if low else detection_threshold), float(low_box_threshold),
+                                                               *tables, eligible, *rest[:-1], ctypes.byref(gate), rest[-1]),
+                               "cnl_track_streams_gated_f32")
+                else:
+                    _lib.check(lib.cnl_track_streams_low_f32(*operands, float(low_threshold), float(low_box_threshold), *tables, eligible, *rest),
+                               "cnl_track_streams_low_f32")
+            else:
+                _lib.check(lib.cnl_track_streams_f32(*operands, *tables, *rest), "cnl_track_streams_f32")
+            outs = (torch.empty((L, M, 4), device=dev, dtype=torch.float64 if res.kalman else torch.float32),
+                    torch.empty((L, M), device=dev, dtype=torch.int64), torch.empty((L, M), device=dev, dtype=torch.int64),
+                    torch.empty((L,), device=dev, dtype=torch.int32))
+            self._lifecycle_launches(res, lv, L, d_emb, d_box, d_label, label_kind, outs, cur)
+        for s in live:
+            self._has_rec[s] = True
+        self.d2h_bytes = 0
+        return {"bboxes": outs[0], "track_ids": outs[1], "labels": outs[2], "count": outs[3]}
+
+    def _download(self):
+        """The last download (ResidentState.download), made now if a step or reset came after it: finishes the table's stream first when the
+        caller is on another one (TrackTable's stream rule)."""
+        if self._snap is None:
+            res = self._res
+            if res is None:
+                S = self.num_streams
+                return {"trk_off": np.zeros(S + 1, np.int32), "next_track_id": np.zeros(S, np.int64), "status": np.zeros((S, 2), np.int32)}
+            with _on(res.dev):
+                self._table.wait_for_other_stream(torch.cuda.current_stream(res.dev))
+                self._snap = res.download()
+        return self._snap
+
+    def _resident_tracks(self, s):
+        d = self._download()
+        if self._res is None:
+            return []
+        kal = self._res.kalman
+        out = []
+        for r in range(int(d["trk_off"][s]), int(d["trk_off"][s + 1])):
+            bbox = d["bbox"][r].copy() if kal else d["bbox"][r].astype(np.float32)
+            out.append(ResidentTrack(int(d["track_id"][r]), bbox, int(d["label"][r]), _STATES[int(d["state"][r])], int(d["birth_age"][r]),
+                                     int(d["inactive_age"][r]), d["emb"][r].copy(),
+                                     ResidentKalman(d["kx"][r].copy(), d["kP"][r].reshape(8, 8).copy()) if kal else None))
+        return out
+
+    def _resident_matches(self, s, low):
+        if not self._has_rec[s] or (low and self.low_threshold is None):
+            return None
+        rec = self._download()["records"][s]
+        if not self._res.low_rec:
+            return read_stream_record(rec)[7]
+        out = read_stream_low_record(rec)
+        return out[-1] if low else out[7]
+
+    def snapshot(self, streams=None):
+        """lifecycle="device": the state of the given streams (default: all) as numpy arrays from ONE download: "offsets" int64 [n + 1] (the
+        rows of streams[i] are offsets[i] .. offsets[i + 1] of the arrays below), "track_ids" int64, "states" (TrackState values) / "birth_age"
+        / "inactive_age" int32, "labels" int64, "bboxes" (the reported boxes: float32, float64 with the filter) [R, 4], "embeddings" float32
+        [R, E], "table_boxes" float32 [R, 4], with the filter "kx" [R, 8] / "kP" [R, 64] float64, and "next_track_id" int64 [n]."""
+        if not self._resident:
+            raise ValueError("snapshot() reads the device state of lifecycle='device'; with lifecycle='host' the tracks are bank[s].tracks")
+        live = self._check_streams(streams)
+        d = self._download()
+        off = d["trk_off"]
+        rows = np.concatenate([np.arange(off[s], off[s + 1], dtype=np.int64) for s in live] + [np.zeros(0, np.int64)])
+        out = {"offsets": np.concatenate([[0], np.cumsum([int(off[s + 1] - off[s]) for s in live])]).astype(np.int64),
+               "next_track_id": d["next_track_id"][live].copy()}
+        if self._res is None:
+            return out
+        kal = self._res.kalman
+        out.update(track_ids=d["track_id"][rows], states=d["state"][rows], birth_age=d["birth_age"][rows], inactive_age=d["inactive_age"][rows],
+                   labels=d["label"][rows].astype(np.int64), bboxes=d["bbox"][rows] if kal else d["bbox"][rows].astype(np.float32),
+                   embeddings=d["emb"][rows], table_boxes=d["box"][rows])
+        if kal:
+            out.update(kx=d["kx"][rows], kP=d["kP"][rows])
+        return out
+
+    def check(self):
+        """lifecycle="device": download the streams' sticky status words; if any is set, clear them all and raise ValueError naming each
+        stream, its code (the association status of its first skipped step; "overflow": births were dropped at max_tracks) and the step
+        counter of its first event."""
+        if not self._resident or self._res is None:
+            return
+        res = self._res
+        with _on(res.dev):
+            cur = torch.cuda.current_stream(res.dev)
+            self._table.wait_for_other_stream(cur)
+            o = res.off["status"]
+            words = res.ctl[o:o + 8 * self.num_streams]
+            status = words.cpu().numpy().view(np.int32).reshape(-1, 2)
+            if not status[:, 0].any():
+                return
+            words.zero_()
+            self._table.stream = cur
+            self._snap = None
+        said = []
+        for s in np.flatnonzero(status[:, 0]).tolist():
+            code, step = int(status[s, 0]), int(status[s, 1])
+            what = [f"association status {code & 0xffff} (skipped)"] if code & 0xffff else []
+            what += ["overflow (births dropped at max_tracks)"] if code & STATUS_OVERFLOW else []
+            said.append(f"stream {s}: {' and '.join(what)}, first at step {step}")
+        raise ValueError("TrackerBank(lifecycle='device'): " + "; ".join(said))
+
+
 def build_tracker(config, model=None, num_streams=None):
     """tracker.py:349-353; with `num_streams`, a TrackerBank of that many streams with the same settings."""
     if isinstance(config, str):
         config = load_config(config)["tracker"]
     if num_streams is not None:
         return TrackerBank(num_streams, model=model, **config)
+    config = dict(config)
+    if config.pop("lifecycle", "host") != "host":
+        raise ValueError("lifecycle='device' is a TrackerBank mode (pass num_streams): one stream on one wave loses to a CPU core")
+    config.pop("max_tracks", None)
     return Tracker(model=model, **config)

@@ -1230,6 +1230,85 @@ int cnl_track_streams_gated_f32(const float* det_emb, const float* det_box, cons
                                 void* record, int64_t record_stride, const cnl_track_gate* gate, void* stream);
 
 /*
+ * The track life cycle of a step over S streams on the device (csrc/track_lifecycle.hip), opt-in: what the host does between the records of
+ * cnl_track_streams_f32 / _low_f32 / _gated_f32 and the table update (models/tracker.py:164-196, 305-347), so that a step is a fixed sequence
+ * of launches without a synchronisation.  The entries above are unchanged and are given the CAPACITIES: every stream owns at most max_tracks
+ * rows, the pooled tables and every per-row array below have C = S * max_tracks rows, R = C, T_max = max_tracks, T_new = C, and their records
+ * (with_detections = 0), trk_off, trk_eligible, index lists and cnl_track_gate.trk_label are the device memory named here.
+ *
+ * Per-row state (cnl_track_rows, C rows; rows trk_off[s] .. trk_off[s+1] are stream s's, rows from trk_off[S] on are padding and zero):
+ * track_id int64; state int32 (1 UNCONFIRMED, 2 ACTIVE, 3 INACTIVE); birth_age, inactive_age, label int32; box f64 [C,4], the REPORTED box;
+ * trk_off int32 [S+1].  old_rows is read, new_rows written (ping-pong, never aliased).  next_track_id int64 [S] is updated in place.
+ *
+ * cnl_track_lifecycle_i32, queued behind the assign launch, two kernels:
+ *  1. per stream s (one single-wave workgroup each), with i = slot_of[s] (int32 [S]: the slot of this step's detections, -1 no part):
+ *     s == reset_stream (by value; -1: none): the stream is left with no rows and next_track_id[s] = 0, whatever its slot.
+ *     -1, or a record whose status is not 0 (a SKIPPED stream — the stated deviation from the host path, which redoes such a stream on the host
+ *         and raises scipy's error: here nothing can be read): the rows are carried, nothing ages, nothing predicts (flags 0).  A record whose
+ *         k or section offsets do not fit record_stride (not one the association entry wrote with these sizes) is skipped likewise, code 4.
+ *     else, from the stream's record: a stage-1/2 match (row, track) updates the track from detection POSITION `row` of slot i (the reference's
+ *         quirk: not det_index[row]), a stage-3 match (low row x, track) from detection low_index[x] with keep_emb = 1; every other track is
+ *         unmatched.  matched: UNCONFIRMED -> birth_age + 1, ACTIVE once birth_age >= min_birth_age; INACTIVE -> ACTIVE, inactive_age = 0.
+ *         unmatched: UNCONFIRMED -> deleted; ACTIVE -> INACTIVE, inactive_age = 0; INACTIVE -> inactive_age + 1, deleted once inactive_age >=
+ *         max_inactive_age.  The new rows are the surviving old rows in order, then one birth per unmatched detection row q (ascending) from
+ *         detection det_index[q]: id = next_track_id[s]++, UNCONFIRMED, ages 0, the detection's label (read by label_kind as the record's label
+ *         section is).  Capacity: only the first max_tracks - survivors births happen; the others are dropped and consume no id.
+ *     status int32 [S][2], sticky (the caller clears it): word 0 = the first skipped step's association status in bits 0..15, bit 16 = births
+ *     were dropped; word 1 = the `step` of the first event.
+ *  2. the prefix sum of the streams' new counts -> new_rows.trk_off; the per-row state in pooled order; src_trk / src_det (global: slot * k + d)
+ *     / keep_emb / flags (1 for the rows of a stream that took part, else 0) for cnl_track_apply_keep_f32 and cnl_track_kalman_f64 over C rows;
+ *     trk_eligible[r] = the new row is ACTIVE (the next step's stage 3).  A padding row r carries itself: src_trk = r, src_det = -1, flag 0.
+ * cnl_track_lifecycle_emit_f64, queued behind the table update and the filter, one kernel: new_rows.box[r] = a born / matched row's detection
+ * box (kalman_box[r], the filter launch's out_box, when kalman_box is set), a carried row's old_rows.box[src_trk[r]]; and for each slot i < S_live
+ * the ACTIVE rows of stream live[i] in row order: out_box [S_live, max_tracks, 4] (f32, or f64 with out_box_f64), out_track_id / out_label
+ * [S_live, max_tracks] int64, out_count [S_live] int32; entries at and beyond the count are zero.
+ * No allocation, no synchronisation, no atomics; the same bits on every run.  workspace: cnl_track_lifecycle_workspace_bytes, 8-byte aligned.
+ * CNL_E_BAD_ARG before any HIP call: a null or misaligned pointer (int64 / f64 arrays, record, record_stride and workspace 8 bytes, the others
+ * their element's), aliased old / new rows, a workspace too small, S / S_live / k / max_tracks out of range, a bad label_kind; CNL_E_UNSUPPORTED:
+ * max_tracks > 4096 (the assignment's limit), S > 4096, S_live * k >= 2^31.
+ */
+typedef struct cnl_track_rows {
+    int64_t* track_id;
+    int32_t* state;
+    int32_t* birth_age;
+    int32_t* inactive_age;
+    int32_t* label;
+    double* box;
+    int32_t* trk_off;
+} cnl_track_rows;
+typedef struct cnl_track_lifecycle {
+    cnl_track_rows old_rows, new_rows;
+    const void* record;         /* the association entry's records, device memory */
+    int64_t record_stride;
+    const int32_t* live;        /* [S_live] slot -> stream, as given to the association entry */
+    const int32_t* slot_of;     /* [S] stream -> slot, -1, -2 */
+    const void* det_label;      /* this step's detections, as given to the association entry */
+    const float* det_box;
+    int64_t* next_track_id;
+    int32_t* status;
+    int32_t* src_trk;           /* [C] each: the lists of the table update and the filter */
+    int32_t* src_det;
+    int32_t* flags;
+    uint8_t* keep_emb;
+    uint8_t* trk_eligible;
+    const double* kalman_box;   /* emit: out_box of the filter launch [C,4]; null without a filter */
+    void* out_box;              /* emit: the step's outputs */
+    int64_t* out_track_id;
+    int64_t* out_label;
+    int32_t* out_count;
+    void* workspace;
+    int64_t workspace_bytes;
+    int32_t S, S_live, k, max_tracks;
+    int32_t label_kind, low_record;     /* low_record: the records have the _low layout */
+    int32_t min_birth_age, max_inactive_age;
+    int32_t step, out_box_f64;
+    int32_t reset_stream, reserved;     /* reset_stream: a stream to forget in this call, -1 none */
+} cnl_track_lifecycle;
+int64_t cnl_track_lifecycle_workspace_bytes(int32_t S, int32_t max_tracks);
+int cnl_track_lifecycle_i32(const cnl_track_lifecycle* p, void* stream);
+int cnl_track_lifecycle_emit_f64(const cnl_track_lifecycle* p, void* stream);
+
+/*
  * Wire formats: COCO boxes are xywh — torchvision box_convert(boxes, "xyxy", "xywh") of
  * CenterNet.validation_step (models/centernet.py:207): out[i] = (x1, y1, x2 - x1, y2 - y1); n boxes of 4 floats, may be in place.
  * boxes and out are 16-byte aligned (a box is moved as one 16-byte word; CNL_E_BAD_ARG otherwise).
