@@ -109,6 +109,17 @@ class TrackLifecycle(Structure):
                                        "out_box_f64", "reset_stream", "reserved")]
 
 
+class MotionFrame(Structure):
+    """cnl_motion_frame: one frame record of cnl_camera_motion_u8 (40 bytes)."""
+    _fields_ = [("src", c_void_p), ("cur", c_void_p), ("prev", c_void_p), ("h", c_int32), ("w", c_int32), ("row_stride", c_int32), ("reserved", c_int32)]
+
+
+class CameraMotion(Structure):
+    """cnl_camera_motion: the operands and the rule of one cnl_camera_motion_u8 call (112 bytes)."""
+    _fields_ = [(n, c_void_p) for n in ("frames", "boxes", "count", "shift", "used", "vectors", "sad", "status")] + \
+               [(n, c_int32) for n in ("L", "k", "step", "downscale", "gy", "gx", "block", "radius", "min_texture", "max_sad", "min_blocks", "reserved")]
+
+
 class LossParams(Structure):
     """cnl_loss_params: the rule of one cnl_detection_loss_f64 call (72 bytes; cnl_sizeof_params(4))."""
     _fields_ = [("stride", c_double), ("target_param", c_double), ("hm_alpha", c_double), ("hm_beta", c_double),
@@ -145,6 +156,7 @@ class PixelOp(Structure):
 
 assert ctypes.sizeof(LetterboxFrame) == 40 and ctypes.sizeof(AugmentPlacement) == 96 and ctypes.sizeof(WarpPlacement) == 192
 assert ctypes.sizeof(PixelOp) == 400
+assert ctypes.sizeof(MotionFrame) == 40 and ctypes.sizeof(CameraMotion) == 112
 
 _REID_COMMON = [c_void_p, c_int64, c_int64, c_int64, c_int64, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int32,
                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, POINTER(ReidLossParams)]
@@ -297,6 +309,8 @@ _SIGNATURES = {
     "cnl_track_lifecycle_workspace_bytes": (ctypes.c_int64, [c_int32, c_int32]),
     "cnl_track_lifecycle_i32": (ctypes.c_int, [ctypes.POINTER(TrackLifecycle), c_void_p]),
     "cnl_track_lifecycle_emit_f64": (ctypes.c_int, [ctypes.POINTER(TrackLifecycle), c_void_p]),
+    "cnl_track_shift_f64": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
+    "cnl_camera_motion_u8": (ctypes.c_int, [ctypes.POINTER(CameraMotion), c_int32, c_void_p]),
     "cnl_relu_grad_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32]),
     "cnl_relu_grad_terms": (c_int64, [c_int32, c_int32, c_int32, c_int32]),
     "cnl_relu_grad_f32": (ctypes.c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p,

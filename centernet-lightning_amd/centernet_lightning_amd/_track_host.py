@@ -611,6 +611,7 @@ class TrackTable:
 _LIFECYCLE_MODES = ("host", "device")
 _STATES = (None, TrackState.UNCONFIRMED, TrackState.ACTIVE, TrackState.INACTIVE, TrackState.TO_DELETE)      # the device's state words
 STATUS_OVERFLOW = 1 << 16       # bit of a stream's sticky status word: births were dropped at max_tracks (cnl_track_lifecycle_i32)
+STATUS_BAD_SHIFT = 1 << 17      # ... a non-finite camera_motion shift was skipped (cnl_track_shift_f64)
 
 
 class ResidentKalman:
@@ -862,6 +863,13 @@ class TrackerSettings:
         self.kalman_skipped = int(np.count_nonzero(status))
 
     _gated = property(lambda self: self.class_aware or self.motion_gate is not None)
+
+    @staticmethod
+    def _refuse_camera_motion(kwargs, who):
+        """camera_motion= shifts the resident bank's tables on the device; every other mode keeps its track boxes in host records."""
+        if kwargs.pop("camera_motion", None) is not None:
+            raise ValueError(f"camera_motion= with {who}: TrackerBank(lifecycle='device') is required (here the track boxes live in host records, "
+                             "and a device shift would cost the synchronisation the option exists to avoid)")
 
     def _check_gate_thresholds(self, *thresholds):
         """With a gate on, a threshold at or above the gated pairs' cost would accept them."""

@@ -51,7 +51,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._track_host import (_BOX_MODES, _LIFECYCLE_MODES, _REID_METRICS, _STATES, _STATUS_TOO_LARGE, STATUS_OVERFLOW, BoxKalman,  # noqa: F401
+from ._track_host import (_BOX_MODES, _LIFECYCLE_MODES, _REID_METRICS, _STATES, _STATUS_TOO_LARGE, STATUS_BAD_SHIFT, STATUS_OVERFLOW, BoxKalman,  # noqa: F401
                           ResidentKalman, ResidentState, ResidentTrack, Track, TrackerSettings, TrackState, _grown,
                           _Mapped, _on, check_kept_count, frame_layout, frame_low_layout, gate_costs, launch_frame, launch_frame_gated, launch_frame_low,
                           life_cycle, low_stage,
@@ -84,6 +84,7 @@ class Tracker(TrackerSettings):
         """Run the model on a batch of consecutive frames and update the tracks frame by frame (tracker.py:84-121).
         Returns {"bboxes": [...], "track_ids": [...]} with one list per frame (active tracks only).
         (kalman="device": two stream synchronisations per frame instead of one, see `update`.)"""
+        self._refuse_camera_motion(kwargs, "Tracker")
         det = self._detect(images, kwargs)
         out = {"bboxes": [], "track_ids": []}
         for i in range(images.shape[0]):
@@ -103,6 +104,7 @@ class Tracker(TrackerSettings):
         torch tensors; the arrays are moved to the HIP device, where the association costs are computed.
         With use_kalman=True, kalman="device" the filter runs in one launch behind the table update, and the call ends with a SECOND stream
         synchronisation (the first makes the frame record readable), so that the filtered boxes are in `Track.bbox` when it returns."""
+        self._refuse_camera_motion(kwargs, "Tracker")
         dev = self.device
         d_box, d_score, d_emb, d_label, host, label_kind = normalise_detections(dev, bboxes, labels, scores, embeddings)
         detection_threshold, reid_threshold, box_threshold, low_threshold, low_box_threshold = self._thresholds(kwargs)
@@ -378,13 +380,16 @@ class TrackerBank(TrackerSettings):
     def step_batch(self, images: torch.Tensor, streams=None, **kwargs):
         """Run the model on one frame from each participating stream (images[i] is the next frame of stream streams[i]; default: stream i)
         and advance those streams.  Returns {"bboxes": [...], "track_ids": [...]} with one list per image (active tracks only).
-        (kalman="device": two stream synchronisations per step instead of one, see `update_batch`.)"""
+        (kalman="device": two stream synchronisations per step instead of one, see `update_batch`.)
+        camera_motion (lifecycle="device" only): see `update_batch`; the boxes here are normalised, so a pixel shift is scaled first:
+        `camera_motion=cm.update(frames)["shift"] * torch.tensor([1 / width, 1 / height], device=dev)`."""
         live = self._check_streams(streams)
+        camera_motion = self._camera_motion(kwargs, len(live))
         if images.dim() != 4 or images.shape[0] != len(live):
             raise ValueError(f"images {tuple(images.shape)}: expected [{len(live)}, 3, H, W], one frame per participating stream")
         det = self._detect(images, kwargs)
         if self._resident:
-            out = self._step_device(det["bboxes"], det["labels"], det["scores"], det["embeddings"], live, kwargs)
+            out = self._step_device(det["bboxes"], det["labels"], det["scores"], det["embeddings"], live, kwargs, camera_motion)
             for s in live:
                 self._frames[s] += 1
             return out
@@ -435,10 +440,28 @@ class TrackerBank(TrackerSettings):
         len(streams), default every stream).  As `Tracker.update`, it does not advance `frame`.  With use_kalman=True, kalman="device" the
         step ends with a SECOND stream synchronisation, behind the filter launch (see `Tracker.update`); a stream that takes no part keeps
         its filter state unpredicted, as on the host path.
-        lifecycle="device": returns the step's device tensors (see the constructor); None on the host path."""
+        lifecycle="device": returns the step's device tensors (see the constructor); None on the host path.
+        camera_motion (lifecycle="device" only; None, the default, is the step without it, launch for launch): a float32 [L, 2] tensor on the
+        bank's device, the global image shift (dx, dy) of each participating stream since its previous frame, in the units of `bboxes`
+        (`CameraMotion.update(frames)["shift"]` for boxes in frame pixels).  One launch in front of the association (cnl_track_shift_f64) adds
+        (dx, dy, dx, dy) to every position the stream's rows hold — the box table, the reported boxes and, with kalman="device", the positions
+        of the filter state — so that IoU costs and the motion gate see the tracks where the camera moved them.  A non-finite shift skips its
+        stream and `check()` reports it.  Every other mode raises ValueError: there the boxes live in host records."""
+        live = self._check_streams(streams)
+        camera_motion = self._camera_motion(kwargs, len(live))
         if self._resident:
-            return self._step_device(bboxes, labels, scores, embeddings, self._check_streams(streams), kwargs)
-        self._step(bboxes, labels, scores, embeddings, self._check_streams(streams), kwargs)
+            return self._step_device(bboxes, labels, scores, embeddings, live, kwargs, camera_motion)
+        self._step(bboxes, labels, scores, embeddings, live, kwargs)
+
+    def _camera_motion(self, kwargs, L):
+        """Takes `camera_motion` out of a step's keywords -> the shift tensor or None, checked as far as the host can without a device."""
+        if not self._resident:
+            return self._refuse_camera_motion(kwargs, f"lifecycle={self.lifecycle!r}" + (", kalman='host'" if self.use_kalman and self.kalman == "host" else ""))
+        shift = kwargs.pop("camera_motion", None)
+        if shift is not None and not (isinstance(shift, torch.Tensor) and shift.dtype == torch.float32 and tuple(shift.shape) == (L, 2)):
+            got = f"{shift.dtype} {tuple(shift.shape)}" if isinstance(shift, torch.Tensor) else type(shift).__name__
+            raise ValueError(f"camera_motion: expected a float32 [{L}, 2] tensor (dx, dy per participating stream), got {got}")
+        return shift
 
     def _step(self, bboxes, labels, scores, embeddings, live, kwargs):
         dev = self.device
@@ -617,9 +640,10 @@ class TrackerBank(TrackerSettings):
         self._snap = None
         self._step_no += 1
 
-    def _step_device(self, bboxes, labels, scores, embeddings, live, kwargs):
+    def _step_device(self, bboxes, labels, scores, embeddings, live, kwargs, camera_motion=None):
         S, L, M = self.num_streams, len(live), self.max_tracks
-        for name, t in (("bboxes", bboxes), ("labels", labels), ("scores", scores), ("embeddings", embeddings)):
+        for name, t in (("bboxes", bboxes), ("labels", labels), ("scores", scores), ("embeddings", embeddings)) + \
+                ((("camera_motion", camera_motion),) if camera_motion is not None else ()):
             if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device == self.device):
                 raise ValueError(f"lifecycle='device': {name} must be a tensor on the bank's device, got {type(t).__name__}"
                                  f"{' on ' + str(t.device) if isinstance(t, torch.Tensor) else ''} (host arrays are refused: the mode exists to "
@@ -646,6 +670,11 @@ class TrackerBank(TrackerSettings):
                 raise ValueError("lifecycle='device': low_threshold cannot be switched on or off per call (the records are laid out by the first step)")
             lv = res.live_list(tuple(live))
             b, C = res.cur, res.C
+            if camera_motion is not None:       # the tracks go where the camera moved them, in front of the association that reads them
+                shift = camera_motion.contiguous()
+                _lib.check(lib.cnl_track_shift_f64(res.box[b].data_ptr(), res.ptr("box", b), res.kx[b].data_ptr() if res.kalman else None,
+                                                   res.ptr("trk_off", b), lv.data_ptr(), shift.data_ptr(), res.ptr("status"), S, L, M,
+                                                   self._step_no & 0x7fffffff, ctypes.c_void_p(cur.cuda_stream)), "cnl_track_shift_f64")
             operands = (d_emb.data_ptr(), d_box.data_ptr(), d_score.data_ptr(), d_label.data_ptr() if label_kind else None, label_kind, S, L,
                         lv.data_ptr(), k, E, float(detection_threshold), float(reid_threshold), float(box_threshold))
             tables = (res.emb[b].data_ptr(), res.box[b].data_ptr(), res.ptr("trk_off", b))
@@ -734,7 +763,7 @@ class TrackerBank(TrackerSettings):
 
     def check(self):
         """lifecycle="device": download the streams' sticky status words; if any is set, clear them all and raise ValueError naming each
-        stream, its code (the association status of its first skipped step; "overflow": births were dropped at max_tracks) and the step
+        stream, its code (the association status of its first skipped step; "overflow": births were dropped at max_tracks; a non-finite camera_motion shift that was skipped) and the step
         counter of its first event."""
         if not self._resident or self._res is None:
             return
@@ -755,6 +784,7 @@ class TrackerBank(TrackerSettings):
             code, step = int(status[s, 0]), int(status[s, 1])
             what = [f"association status {code & 0xffff} (skipped)"] if code & 0xffff else []
             what += ["overflow (births dropped at max_tracks)"] if code & STATUS_OVERFLOW else []
+            what += ["a non-finite camera_motion shift (skipped)"] if code & STATUS_BAD_SHIFT else []
             said.append(f"stream {s}: {' and '.join(what)}, first at step {step}")
         raise ValueError("TrackerBank(lifecycle='device'): " + "; ".join(said))
 

@@ -285,6 +285,35 @@ __global__ __launch_bounds__(64) void emit_kernel(const Args a) {
     if (lane == 0) a.out_count[i] = count;
 }
 
+// camera-motion compensation: one single-wave workgroup per slot adds the slot's shift to every position its stream's rows hold
+constexpr int BAD_SHIFT = 1 << 17;
+__global__ __launch_bounds__(64) void shift_kernel(float* __restrict__ trk_box, double* __restrict__ box, double* __restrict__ kx,
+                                                    const int* __restrict__ trk_off, const int* __restrict__ live, const float* __restrict__ shift,
+                                                    int* __restrict__ status, int S, int max_tracks, int step) {
+    const int i = blockIdx.x, lane = threadIdx.x;
+    const int s = live[i];
+    if (s < 0 || s >= S) return;
+    const float dx = shift[2 * i], dy = shift[2 * i + 1];
+    if (!(isfinite(dx) && isfinite(dy))) {      // the stream is skipped; sticky, as the life cycle's codes
+        if (lane == 0) {
+            int* word = status + 2 * s;
+            const int have = word[0];
+            if (have == 0) word[1] = step;
+            word[0] = have | BAD_SHIFT;
+        }
+        return;
+    }
+    const int t0 = trk_off[s], t1 = trk_off[s + 1];
+    if (t0 < 0 || t1 < t0 || (long)t1 > (long)S * max_tracks) return;
+    // item q: coordinate q & 3 of row t0 + (q >> 2); x for even coordinates, y for odd ones
+    for (long q = (long)t0 * 4 + lane; q < (long)t1 * 4; q += 64) {
+        const float df = (q & 1) ? dy : dx;
+        trk_box[q] += df;
+        box[q] += (double)df;
+        if (kx) kx[(q >> 2) * 8 + (q & 3)] += (double)df;
+    }
+}
+
 static bool rows_ok(const cnl_track_rows& r) {
     return r.track_id && r.state && r.birth_age && r.inactive_age && r.label && r.box && r.trk_off &&
            (((uintptr_t)r.track_id | (uintptr_t)r.box) & 7) == 0 &&
@@ -320,6 +349,20 @@ using namespace cnl_lifecycle;
 extern "C" int64_t cnl_track_lifecycle_workspace_bytes(int32_t S, int32_t max_tracks) {
     if (S <= 0 || max_tracks <= 0) return 0;
     return stage_bytes(S, max_tracks);
+}
+
+extern "C" int cnl_track_shift_f64(float* trk_box, double* box, double* kx, const int32_t* trk_off, const int32_t* live, const float* shift,
+                                   int32_t* status, int32_t S, int32_t S_live, int32_t max_tracks, int32_t step, void* stream) {
+    const char* name = "cnl_track_shift_f64";
+    CNL_REQUIRE(trk_box && box && trk_off && live && shift && status, CNL_E_BAD_ARG, "%s: null pointer", name);
+    CNL_REQUIRE(S > 0 && S <= MAX_STREAMS && S_live > 0 && S_live <= S && max_tracks > 0 && max_tracks <= MAX_TRACKS, CNL_E_BAD_ARG,
+                "%s: bad S / S_live / max_tracks (%d / %d / %d)", name, S, S_live, max_tracks);
+    CNL_REQUIRE((((uintptr_t)trk_box | (uintptr_t)trk_off | (uintptr_t)live | (uintptr_t)shift | (uintptr_t)status) & 3) == 0 &&
+                (((uintptr_t)box | (uintptr_t)kx) & 7) == 0, CNL_E_BAD_ARG,
+                "%s: trk_box, trk_off, live, shift and status must be 4-byte aligned, box and kx 8-byte aligned", name);
+    hipLaunchKernelGGL(shift_kernel, dim3((unsigned)S_live), dim3(64), 0, (hipStream_t)stream, trk_box, box, kx, trk_off, live, shift, status, S, max_tracks,
+                       step);
+    return cnl::check_launch("track shift_kernel");
 }
 
 extern "C" int cnl_track_lifecycle_i32(const cnl_track_lifecycle* p, void* stream) {

@@ -1309,6 +1309,74 @@ int cnl_track_lifecycle_i32(const cnl_track_lifecycle* p, void* stream);
 int cnl_track_lifecycle_emit_f64(const cnl_track_lifecycle* p, void* stream);
 
 /*
+ * Camera-motion compensation, part 2 (csrc/track_lifecycle.hip): the global image shift of a step applied to the resident bank, ONE launch in
+ * front of the step's association launch.  For each slot i < S_live with s = live[i] and (dx, dy) = shift[2i], shift[2i+1] (float32, in the units
+ * of the boxes the bank is given), every row r of trk_off[s] .. trk_off[s+1] — all states — gets (dx, dy, dx, dy) added to trk_box[4r ..] (one
+ * fp32 add each), to box[4r ..], the float64 reported box a carried row hands to the next emit (one float64 add of (double)dx / dy each), and,
+ * when kx is not null, to kx[8r .. 8r+3], the positions of the filter state (likewise).  P, the velocities, embeddings, ages and ids are not
+ * touched; rows of other streams are not touched.  A shift with a non-finite component SKIPS its stream and sets bit 17 of the stream's sticky
+ * status word (status[2s], with status[2s+1] = step if the word was 0: the words of cnl_track_lifecycle_i32).  Offsets that do not lie in
+ * 0 <= trk_off[s] <= trk_off[s+1] <= S * max_tracks, or a stream index outside 0 .. S-1, skip the slot.  `live` must not name a stream twice.
+ * CNL_E_BAD_ARG before any HIP call: a null pointer (kx may be null), S, S_live or max_tracks out of range, trk_box / shift / live / trk_off /
+ * status not 4-byte aligned, box / kx not 8-byte aligned.
+ */
+int cnl_track_shift_f64(float* trk_box, double* box, double* kx, const int32_t* trk_off, const int32_t* live, const float* shift, int32_t* status,
+                        int32_t S, int32_t S_live, int32_t max_tracks, int32_t step, void* stream);
+
+/*
+ * Camera-motion compensation, part 1 (csrc/camera_motion.hip): the global translation between each stream's previous and current frame, by
+ * block matching on a coarse luma plane.  Integer arithmetic throughout; tests/camera_motion_ref.py restates the rule in numpy and is held
+ * equal to it.  Three launches, chosen by `stages` (bit 0 coarse luma, bit 1 block search, bit 2 aggregate; 7 is the whole call):
+ *
+ * Frames: L records (device memory).  src is a packed frame of `step` = 3 or 4 bytes per pixel (R, G, B first; a fourth byte is ignored) or,
+ * with step = 1, a luma plane (the Y plane of an NV12 / I420 surface); h x w pixels, rows row_stride bytes apart, read in place and only read.
+ *   luma:    step 1: the byte.  step 3 / 4: Y = (77 R + 150 G + 29 B + 128) >> 8.
+ *   coarse:  d = downscale in {1, 2, 4, 8}; Hc = h / d, Wc = w / d (integer division: leftover rows and columns are dropped);
+ *            coarse[y][x] = (sum of the d x d lumas + (d * d) / 2) >> (2 log2 d)   ((d * d) / 2 is 0 at d = 1), one byte, written densely
+ *            (rows Wc bytes apart) to the record's `cur` plane.  `prev` is the plane the previous call wrote for the same stream at the same
+ *            frame size, or null: no previous frame (status bit 0), and nothing is searched.
+ *   blocks:  B = block in {8, 16}, R = radius in 1 .. 8, a grid of gy x gx blocks, each of 1 .. 16.  Along an axis of coarse length n with
+ *            m blocks, block i starts at R + (i * (n - 2R - B)) / (m - 1), or at R + (n - 2R - B) / 2 when m == 1.  When Hc < 2R + B or
+ *            Wc < 2R + B the frame is too small (status bit 2), and nothing is searched.
+ *   search:  the shift s = (sx, sy) means cur(p) = prev(p - s): the content moved by s.  For every s in [-R, R]^2,
+ *            SAD(s) = sum over the block of |cur[y0+y][x0+x] - prev[y0+y-sy][x0+x-sx]|; the winner has the smallest key
+ *            (SAD, |sy| + |sx|, sy, sx) in lexicographic order.
+ *   abstain: a block does not vote when it is flat: sum |cur - m| < min_texture * B * B with m = (sum cur + B * B / 2) / (B * B); or matches
+ *            badly: best SAD > max_sad * B * B; or its centre pixel (cx, cy) = ((x0 + B / 2) * d, (y0 + B / 2) * d) lies inside a live box:
+ *            x1 <= cx < x2 and y1 <= cy < y2 in float32 for some j < k with j < count[i] (count null: every j) whose four coordinates are
+ *            finite (boxes [L, k, 4] x1 y1 x2 y2 in frame pixels; null: no mask).
+ *   outputs of the search, per slot and block (row-major over the grid): vectors int16 (sx, sy) and sad int32 = the winner and its SAD;
+ *            (0, 0) and -1 for a block that abstained or was not searched.
+ *   aggregate: over the n blocks with sad >= 0: used = n; n < min_blocks: shift (0, 0) and status bit 1.  Otherwise sx* is the element at index
+ *            (n - 1) / 2 of the ascending sx values, sy* likewise and independently, and shift = ((float)(sx* * d), (float)(sy* * d)), in the
+ *            frame's own pixels.  status = bit 0 | bit 1 | bit 2 as above (an unsearched slot has n = 0, so bit 1 as well).
+ * No atomics, no floats before the final conversion, no synchronisation; every word has one writer.
+ * CNL_E_BAD_ARG before any HIP call: a null pointer (boxes and count may be null; count without boxes is refused), L < 1, k < 0 (k >= 1 with
+ * boxes), a parameter outside the ranges above, min_texture / max_sad outside 0 .. 255, min_blocks < 1, stages outside 1 .. 7, shift / used / sad
+ * / status / boxes / count not 4-byte aligned, vectors not 2-byte aligned, frames not 8-byte aligned.  CNL_E_UNSUPPORTED: L > 65535.
+ */
+typedef struct cnl_motion_frame {      /* 40 bytes */
+    const void* src;
+    void* cur;                          /* Hc * Wc bytes, written by stage bit 0 */
+    const void* prev;                   /* Hc * Wc bytes, or null */
+    int32_t h, w, row_stride, reserved;
+} cnl_motion_frame;
+typedef struct cnl_camera_motion {     /* 112 bytes */
+    const cnl_motion_frame* frames;     /* [L], device memory */
+    const float* boxes;                 /* [L, k, 4] or null */
+    const int32_t* count;               /* [L] or null */
+    float* shift;                       /* [L, 2] (dx, dy) */
+    int32_t* used;                      /* [L] */
+    int16_t* vectors;                   /* [L, gy * gx, 2] */
+    int32_t* sad;                       /* [L, gy * gx] */
+    int32_t* status;                    /* [L] */
+    int32_t L, k, step, downscale;
+    int32_t gy, gx, block, radius;
+    int32_t min_texture, max_sad, min_blocks, reserved;
+} cnl_camera_motion;
+int cnl_camera_motion_u8(const cnl_camera_motion* p, int32_t stages, void* stream);
+
+/*
  * Wire formats: COCO boxes are xywh — torchvision box_convert(boxes, "xyxy", "xywh") of
  * CenterNet.validation_step (models/centernet.py:207): out[i] = (x1, y1, x2 - x1, y2 - y1); n boxes of 4 floats, may be in place.
  * boxes and out are 16-byte aligned (a box is moved as one 16-byte word; CNL_E_BAD_ARG otherwise).
