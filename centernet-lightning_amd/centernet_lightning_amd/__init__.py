@@ -14,6 +14,7 @@ from .tiles import TileGeometry, merge_soft, merge_tiles, tile_grid, tile_uint8,
 from .yuv import rgb_to_yuv, split_planes, yuv_coefficients
 from .crops import crop_detections
 from .camera_motion import CameraMotion
+from .zones import Line, Zone, ZoneCounter
 from .overlay import DEFAULT_PALETTE, draw_detections
 from .flip import flip_merge, mirror_append_uint8
 from .coco_eval import CocoEvaluator
@@ -29,7 +30,7 @@ __all__ = ["CenterNet", "build_centernet", "load_config", "DetectionOutput", "Tr
            "collate_detections", "Collator", "all_gather_records", "pack_detections", "unpack_detections", "shard_range",
            "Tracker", "TrackerBank", "Track", "TrackState", "ResidentTrack", "build_tracker", "match_with_threshold", "formats", "TraceableCenterNet", "export_torchscript", "export_onnx",
            "letterbox_geometry", "LetterboxGeometry", "TileGeometry", "tile_grid", "tile_uint8", "merge_tiles",
-           "letterbox_yuv420", "tile_yuv420", "yuv_coefficients", "split_planes", "crop_detections", "CameraMotion",
+           "letterbox_yuv420", "tile_yuv420", "yuv_coefficients", "split_planes", "crop_detections", "CameraMotion", "ZoneCounter", "Zone", "Line",
            "draw_detections", "DEFAULT_PALETTE", "rgb_to_yuv", "flip_merge", "mirror_append_uint8", "CocoEvaluator",
            "MotEvaluator", "evaluate_mot_tracking_sequence", "LossMeter", "detection_loss", "render_targets", "DetectionLoss",
            "detection_loss_grad", "reid_loss", "reid_loss_grad", "ReIDLoss", "TrackingLoss",

@@ -120,6 +120,13 @@ class CameraMotion(Structure):
                [(n, c_int32) for n in ("L", "k", "step", "downscale", "gy", "gx", "block", "radius", "min_texture", "max_sad", "min_blocks", "reserved")]
 
 
+class TrackZones(Structure):
+    """cnl_track_zones: the operands and the rule of one cnl_track_zones_f64 call (168 bytes)."""
+    _fields_ = [(n, c_void_p) for n in ("boxes", "track_ids", "labels", "count", "live", "geometry", "state", "status", "inside", "dwell", "occupancy",
+                                        "zone_counts", "line_counts", "events", "event_count")] + \
+               [(n, c_int32) for n in ("S", "L", "M", "max_tracks", "Z", "Ln", "max_events", "max_absent", "anchor", "boxes_f64", "bank", "step")]
+
+
 class LossParams(Structure):
     """cnl_loss_params: the rule of one cnl_detection_loss_f64 call (72 bytes; cnl_sizeof_params(4))."""
     _fields_ = [("stride", c_double), ("target_param", c_double), ("hm_alpha", c_double), ("hm_beta", c_double),
@@ -157,6 +164,7 @@ class PixelOp(Structure):
 assert ctypes.sizeof(LetterboxFrame) == 40 and ctypes.sizeof(AugmentPlacement) == 96 and ctypes.sizeof(WarpPlacement) == 192
 assert ctypes.sizeof(PixelOp) == 400
 assert ctypes.sizeof(MotionFrame) == 40 and ctypes.sizeof(CameraMotion) == 112
+assert ctypes.sizeof(TrackZones) == 168
 
 _REID_COMMON = [c_void_p, c_int64, c_int64, c_int64, c_int64, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int32,
                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, POINTER(ReidLossParams)]
@@ -311,6 +319,8 @@ _SIGNATURES = {
     "cnl_track_lifecycle_emit_f64": (ctypes.c_int, [ctypes.POINTER(TrackLifecycle), c_void_p]),
     "cnl_track_shift_f64": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "cnl_camera_motion_u8": (ctypes.c_int, [ctypes.POINTER(CameraMotion), c_int32, c_void_p]),
+    "cnl_track_zones_state_bytes": (ctypes.c_int64, [c_int32, c_int32, c_int32, c_int32]),
+    "cnl_track_zones_f64": (ctypes.c_int, [ctypes.POINTER(TrackZones), c_void_p]),
     "cnl_relu_grad_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32]),
     "cnl_relu_grad_terms": (c_int64, [c_int32, c_int32, c_int32, c_int32]),
     "cnl_relu_grad_f32": (ctypes.c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p,

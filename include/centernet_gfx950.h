@@ -1377,6 +1377,79 @@ typedef struct cnl_camera_motion {     /* 112 bytes */
 int cnl_camera_motion_u8(const cnl_camera_motion* p, int32_t stages, void* stream);
 
 /*
+ * Zone occupancy, line crossings and dwell events from the outputs of a device life-cycle step (csrc/track_zones.hip): ONE launch behind
+ * cnl_track_lifecycle_emit_f64, no synchronisation.  tests/zones_ref.py restates the rule in numpy and is held equal to it bit for bit: all
+ * geometry is float64 on the widened inputs, one rounding per operation, no contraction.
+ *
+ * Inputs, for L slots of M rows: boxes [L, M, 4] x1 y1 x2 y2 (float32, or float64 with boxes_f64), track_ids / labels [L, M] int64, count [L]
+ * int32 (clamped to 0 .. M).  live int32 [S]: live[i], i < L, is slot i's stream; live[L ..] are the streams that take no part.  `live` names
+ * every stream once; a slot whose stream index lies outside 0 .. S-1 is skipped.
+ * Geometry, S records of 8 + 336 Z + 104 Ln bytes, device memory, only read: int32 n_zones, n_lines; Z zone records { int32 n_vertices (0: a
+ * padding zone, nothing is inside it), dwell_alert, n_labels (0: every label), reserved; int64 labels[8]; double v[16][2] }; Ln line records
+ * { double ax, ay, bx, by; int32 n_labels, reserved; int64 labels[8] } of which the first n_lines count.
+ *
+ *  1. anchor: anchor = 0 (bottom centre): ((x1 + x2) * 0.5, y2); 1 (centre): ((x1 + x2) * 0.5, (y1 + y2) * 0.5).  A row at or beyond count, or
+ *     with a non-finite anchor, is NOT PRESENT this step; the latter sets status bit 0.
+ *  2. zone membership, even-odd, no division: for every edge (xi, yi) -> (xj, yj), j the next vertex cyclically, with (yi > py) != (yj > py):
+ *     t = (xj - xi) * (py - yi) - (px - xi) * (yj - yi); toggle when yj > yi ? t > 0 : t < 0.  A track whose label is not among the zone's
+ *     labels is outside it.
+ *  3. line crossing of the segment p0 (the remembered anchor) -> p1 (this step's): cross(u, v) = u.x * v.y - u.y * v.x; d0 = cross(B - A,
+ *     p0 - A) > 0, d1 likewise for p1; none if d0 == d1.  e0 = cross(p1 - p0, A - p0) > 0, e1 likewise for B; none if e0 == e1.  Otherwise
+ *     forward (kind 3) if d1 — the track entered the side where cross > 0, on a y-down screen the right-hand side of A -> B —, backward (kind
+ *     4) if not.  The line itself belongs to the side cross <= 0: a touch from that side and back counts nothing (from the other side: one
+ *     backward and one forward crossing, net zero); a crossing through the shared endpoint of a polyline A-B, B-C counts once.  A track
+ *     with no remembered anchor, or with a filtered label, crosses nothing.
+ *  4. identity: per stream a list of at most E = 2 * max_tracks entries { id, anchor, inside mask, Z dwell counts, absent age }.  A present row
+ *     takes the state of the FIRST entry with its id; none: it is new.  (Ids are distinct within a stream's step, as the bank's are; were
+ *     they not, every such row takes that first entry.)  An entry no present row took is absent: age + 1; it is in no occupancy, its dwell
+ *     stands, it makes no event; when age > max_absent it is forgotten with one exit event per zone it was inside.  When it returns, lines
+ *     are tested from its remembered anchor and its dwell continues.  The new list: the present rows in row order (age 0), then the remembered
+ *     absent entries in their previous order; entries beyond E are dropped without events: status bit 1.
+ *  5. per present row and zone z: inside -> dwell = (was inside ? previous dwell : 0) + 1, else 0.  Events (track_id, kind, index, value):
+ *     kind 1 enter zone (value 1: the track is new to the counter, else 0), 2 exit zone (value: the dwell it had), 3 / 4 forward / backward
+ *     crossing of line `index` (value 0), 5 dwell reached exactly dwell_alert[z] > 0 (value: the dwell).  Order: the present rows in row
+ *     order; per row the zones ascending (exit or enter, then the alert), then the lines ascending; then the expired entries in previous-list
+ *     order, zones ascending.  Events beyond max_events are not stored: status bit 2; event_count and the counters still count them.
+ *
+ * Outputs: inside int32 [L, M] (bit z: the anchor is in zone z; 0 for a row that is not present); dwell int32 [L, M, Z]; occupancy int32
+ * [L, Z]; zone_counts int64 [L, Z, 2] cumulative (enters, exits) and line_counts int64 [L, Ln, 2] cumulative (forward, backward) of the
+ * stream; events int64 [L, max_events, 4], zero rows behind the stored ones; event_count int32 [L], the true number.
+ * status int32 [S, 2], sticky (the caller clears it): word 0 the bits above, word 1 the `step` of the first event.
+ *
+ * State: cnl_track_zones_state_bytes(S, max_tracks, Z, Ln) bytes (0 for sizes outside the limits), zeroed by the caller, 8-byte aligned: two
+ * banks [2][S] of one stream's block { int64 zone_counts[Z][2], line_counts[Ln][2]; int32 n_entries, 0; int64 id[E]; double anchor[E][2];
+ * int32 inside[E], age[E], dwell[E][Z] }.  A call reads bank `bank` and writes the other one — a stream that takes no part is copied —, so the
+ * caller alternates `bank`.  Zeroing a stream's block of the current bank forgets the stream.
+ * One workgroup per slot; no float atomics, integer LDS adds of ballot popcounts: the same bits on every run.
+ * CNL_E_BAD_ARG before any HIP call: a null struct or pointer (dwell / occupancy / zone_counts may be null with Z = 0, line_counts with Ln =
+ * 0), S outside 1 .. 65535, L outside 1 .. S, max_tracks outside 1 .. 4096, M outside 1 .. max_tracks, Z or Ln outside 0 .. 16, max_events
+ * outside 1 .. 65536, max_absent < 0, anchor / boxes_f64 / bank not 0 or 1, a misaligned pointer (8 bytes: int64 / float64 arrays, geometry,
+ * state; 4 bytes: the others).
+ */
+typedef struct cnl_track_zones {       /* 168 bytes */
+    const void* boxes;
+    const int64_t* track_ids;
+    const int64_t* labels;
+    const int32_t* count;
+    const int32_t* live;
+    const void* geometry;
+    void* state;
+    int32_t* status;
+    int32_t* inside;
+    int32_t* dwell;
+    int32_t* occupancy;
+    int64_t* zone_counts;
+    int64_t* line_counts;
+    int64_t* events;
+    int32_t* event_count;
+    int32_t S, L, M, max_tracks;
+    int32_t Z, Ln, max_events, max_absent;
+    int32_t anchor, boxes_f64, bank, step;
+} cnl_track_zones;
+int64_t cnl_track_zones_state_bytes(int32_t S, int32_t max_tracks, int32_t Z, int32_t Ln);
+int cnl_track_zones_f64(const cnl_track_zones* p, void* stream);
+
+/*
  * Wire formats: COCO boxes are xywh — torchvision box_convert(boxes, "xyxy", "xywh") of
  * CenterNet.validation_step (models/centernet.py:207): out[i] = (x1, y1, x2 - x1, y2 - y1); n boxes of 4 floats, may be in place.
  * boxes and out are 16-byte aligned (a box is moved as one 16-byte word; CNL_E_BAD_ARG otherwise).
